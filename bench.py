@@ -1,6 +1,6 @@
 """ViT-SOM training-step benchmark (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one full optimisation step of the hot path on one synthetic batch already resident
@@ -197,6 +197,41 @@ def bmu_roofline(ops, B, world, bmu_ms, bmu_calls):
                          "frac": round(nbytes / t_s / 1e9 / HBM_PEAK_GBS, 4)}}
 
 
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: a tensor above this many elements contributes a fixed sample of this size
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(model, loss):
+    """What a caller of the timed path holds after its last step, as host arrays: the loss (and its two terms), the
+    parameters after the optimizer step and the gradients it applied.  `params` / `grads` concatenate every trainable
+    tensor in named_parameters() order, flattened; a tensor of more than DUMP_SAMPLE elements (the [K, L] prototypes)
+    contributes DUMP_SAMPLE of its elements, at sorted indices drawn from a generator seeded with 0."""
+    import numpy as np
+    parts, pv, gv = model._last, [], []
+    for name, _ in model._named_trainable():
+        p, g = model.arena.p(name).reshape(-1), model.arena.g(name).reshape(-1)
+        if p.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(p.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            idx = idx.to(p.device)
+            p, g = p[idx], g[idx]
+        pv.append(p.cpu())
+        gv.append(g.cpu())
+    return {"loss": np.float64(float(loss)), "recon_loss": np.float64(float(parts["main"])),
+            "som_loss": np.float64(float(parts["som"])),
+            "params": torch.cat(pv).numpy(), "grads": torch.cat(gv).numpy()}
+
+
+def dump_outputs(out_dir, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(args, script=None, argv=None) -> int:
     """One child process per GPU (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in its environment), rendezvous on
     127.0.0.1.  Rank 0 inherits stdout, so its JSON line is this command's output."""
@@ -244,7 +279,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=512, help="per-GPU batch (BASELINE c3: 512)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0): loss, recon_loss, som_loss, "
+                         "params (after the optimizer step), grads -- see step_outputs()")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: this process becomes the launcher -- it starts one fresh child per
@@ -304,6 +344,8 @@ def main():
         loss = step()
     barrier()
     dt = time.perf_counter() - t0
+    # before the BMU timing below runs further steps over the same parameters
+    outputs = step_outputs(model, loss) if args.dump_outputs and rank == 0 else None
     # The BMU distance kernel inside the step, by HIP events on the stream it is launched on.  The timed region above runs
     # the product path -- the step's launches re-issued from C by the launch tape (model.py) -- where the host cannot place
     # events around one kernel; so the same steps go on for a few more iterations through the host-driven path (same
@@ -359,6 +401,8 @@ def main():
         if cpu_res is not None:
             out["cpu_baseline"] = cpu_res
         print(json.dumps(out), flush=True)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
     if world > 1:
         torch.distributed.destroy_process_group()
 
