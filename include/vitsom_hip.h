@@ -289,7 +289,10 @@ int vsom_comm_destroy(void);
  *   vsom_tape_cut        close the current segment, open the next; returns the index of the closed one
  *   vsom_tape_pause      1: execute but do not keep what follows (calls whose arguments change per step), 0: resume
  *   vsom_tape_end        stop recording; returns the number of segments
- *   vsom_tape_replay     re-issue one segment's operations in order (no per-launch host work beyond hipLaunchKernel)
+ *   vsom_tape_replay     re-issue one segment's operations in order (per launch: hipLaunchKernel + hipGetLastError).  Each
+ *                        operation's status is checked (launch, event record / wait, RCCL; an all-reduce with no live
+ *                        communicator is refused before RCCL is called): the replay stops at the first failure and returns
+ *                        its status, the error string naming the segment, the operation's index and what it is
  *   vsom_tape_segment_ops / vsom_tape_recording (0 no, 1 recording, 2 paused) / vsom_tape_destroy
  * Pointers are frozen into the tape: the caller replays only while every buffer the recorded step touched is alive and in
  * place (the host mirror stages each batch into fixed input buffers and ties the tape to its activation buffers).

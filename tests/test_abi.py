@@ -81,6 +81,14 @@ def test_round3_entries_host_side():
     assert lib.vsom_comm_destroy() == 0
     # launch tape: cut / end / replay without a recording are refused or no-ops, never a crash
     assert lib.vsom_tape_recording() == 0
+    assert lib.vsom_tape_cut() == -1 and "not recording" in last_error()
+    assert lib.vsom_tape_end() == -1 and "not recording" in last_error()
+    tid = lib.vsom_tape_begin()                     # an empty tape: one segment, no operation
+    assert tid > 0 and lib.vsom_tape_recording() == 1
+    assert lib.vsom_tape_end() == 1 and lib.vsom_tape_recording() == 0
+    assert lib.vsom_tape_segment_ops(tid, 0) == 0
+    assert lib.vsom_tape_destroy(tid) == 0
+    assert lib.vsom_tape_replay(tid, 0) == -1 and "no such tape" in last_error()
 
 
 def test_hook_signature_sees_every_switch():

@@ -161,6 +161,7 @@ def test_vsom_comm_rccl_one_rank_bucketed_exchange_keeps_the_trajectory():
     import vit_som_amd
     from oracle.gen_golden import make_config
     from vit_som_amd import ops
+    from vit_som_amd._lib import VsomError
     from vit_som_amd.tuning import hooks
     hooks.set(launch_tape=False)            # this test counts the exchange calls the HOST issues (the taped form: next test)
     cfg = make_config(3, 32, 4, 192, 6, 3, 96, 2, (12, 12), 0, 64)
@@ -200,12 +201,12 @@ def test_vsom_comm_rccl_one_rank_bucketed_exchange_keeps_the_trajectory():
         finally:
             if use_comm:
                 ops.comm_allreduce_sum = orig
-        return [float(v) for v in losses], m.arena.params.clone(), calls, m.arena.numel
+        return [float(v) for v in losses], m.arena.params.clone(), calls, m.arena.numel, m
 
     try:
-        l0, p0, _, _ = run(False)
+        l0, p0, _, _, _ = run(False)
         try:
-            l1, p1, calls, numel = run(True)
+            l1, p1, calls, numel, _ = run(True)
         finally:
             ops.comm_destroy()
         assert ops.comm_info() == (0, -1)
@@ -216,7 +217,14 @@ def test_vsom_comm_rccl_one_rank_bucketed_exchange_keeps_the_trajectory():
         # other launches, the remainder by allreduce_gradients(); same trajectory
         hooks.set(launch_tape=True)
         try:
-            l2, p2, calls2, _ = run(True)
+            l2, p2, calls2, _, m2 = run(True)
+            # a replayed all-reduce checks that the communicator it was recorded with is still there: with none, the
+            # replay stops there and reports it (before RCCL or the GPU sees the call) instead of leaving un-reduced
+            # gradients behind a success status
+            assert m2.vit._acts[64].__dict__.get("tape") is not None
+            ops.comm_destroy()
+            with pytest.raises(VsomError, match="vsom_comm_allreduce_sum.*no communicator"):
+                m2.train_step_fused(x, y)
         finally:
             ops.comm_destroy()
         assert l0 == l2 and torch.equal(p0, p2)

@@ -723,6 +723,58 @@ def test_launch_tape_replays_the_step_bit_for_bit(mode, B):
     assert torch.equal(g0, g1) and torch.equal(p0, p1)
 
 
+def test_launch_tape_is_recorded_again_after_a_move_or_on_another_stream():
+    """A tape replays only onto the storage and the launch stream it was recorded with.  After m.cpu(); m.cuda() (new
+    arenas, weight transposes and frozen parameters; the activation buffers and their tape survive) and for a step run
+    under another current stream, the step is recorded again instead of replaying the old tape; parameters, gradients and
+    losses stay bit-identical to the host-driven run of the same sequence."""
+    import vit_som_amd
+    from oracle.gen_golden import make_config
+    from vit_som_amd.tuning import hooks
+    B = 64
+    cfg = make_config(3, 32, 4, 192, 3, 3, 96, 2, (8, 8), 0, B, gamma=0.02, Tmax=4.0, Tmin=0.1)
+    g = torch.Generator().manual_seed(4)
+    xs = [torch.randn(B, 3, 32, 32, generator=g).to(DEV) for _ in range(8)]
+    y = torch.zeros(B, dtype=torch.int64, device=DEV)
+    other = torch.cuda.Stream()
+
+    def run(tape_on):
+        hooks.set(launch_tape=tape_on)
+        try:
+            torch.manual_seed(0)
+            m = vit_som_amd.ViTSOM(copy.deepcopy(cfg), device=DEV)
+            m.set_schedule(4000, 400)
+            m._it = 40
+            (opt,), _ = m.configure_optimizers()
+            out, ids = [], []
+            for i in range(8):
+                if i == 4:
+                    m.cpu()
+                    m.cuda()
+                st = other if i == 6 else torch.cuda.current_stream()
+                st.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(st):
+                    loss = m.train_step_fused(xs[i], y)
+                    out.append((float(loss), float(m._last["main"]), float(m._last["som"])))
+                    opt.step()
+                torch.cuda.current_stream().wait_stream(st)
+                tape = m.vit._acts[B].__dict__.get("tape")
+                ids.append(tape.id if tape is not None else 0)
+            torch.cuda.synchronize()
+            return out, m.arena.params.clone(), m.arena.grads.clone(), ids
+        finally:
+            hooks.reset()
+
+    o0, p0, g0, ids0 = run(False)
+    o1, p1, g1, ids1 = run(True)
+    assert ids0 == [0] * 8
+    assert ids1[:2] == [0, 0] and ids1[2] == ids1[3] > 0, ids1              # recorded at the third step, then replayed
+    assert ids1[4] not in (0, ids1[3]) and ids1[5] == ids1[4], ids1         # moved: recorded again, then replayed
+    assert ids1[6] not in (0, ids1[5]) and ids1[7] not in (0, ids1[6]), ids1   # another stream, and back
+    assert o0 == o1
+    assert torch.equal(g0, g1) and torch.equal(p0, p1)
+
+
 def test_bmu_plane_images_follow_the_prototypes():
     """The cosine BMU pass on pre-split plane images (B >= 192): the prototypes' image is rewritten by the optimizer step,
     the step results equal the in-loop-split path's (losses to fp32 rounding of the row norms, same BMUs), and every other

@@ -104,7 +104,10 @@ int vsom_comm_allreduce_sum(float* buf, long n, vsom_stream_t stream) {
     if (n == 0) return VSOM_OK;
     const int rc = rccl_status(g_rccl.AllReduce(buf, buf, (size_t)n, ncclFloat32, ncclSum, g_comm, stream), "ncclAllReduce");
     if (rc == VSOM_OK && g_tape_rec)                  // a recorded step re-issues its collectives too (same order on every rank)
-        tape_push([=]() { (void)g_rccl.AllReduce(buf, buf, (size_t)n, ncclFloat32, ncclSum, g_comm, stream); });
+        tape_push({[=]() {
+            VSOM_REQUIRE(g_comm != nullptr, VSOM_EINVAL, "comm_allreduce_sum: no communicator (destroyed since the recording)");
+            return rccl_status(g_rccl.AllReduce(buf, buf, (size_t)n, ncclFloat32, ncclSum, g_comm, stream), "ncclAllReduce");
+        }, "vsom_comm_allreduce_sum"});
     return rc;
 }
 

@@ -39,17 +39,23 @@ inline int hip_status(hipError_t e, const char* what) {
 // LDS size, stream and the by-value arguments, all inside one closure -- so that vsom_tape_replay can re-issue a whole
 // training step's launches from C in one call (the host mirror's Python + ctypes path costs ~9 us per launch, 4 ms per
 // step: host-bound below ~256 images per GPU).
+// A recorded operation returns its status (error text set on failure); `what` names it in vsom_tape_replay's error.
+struct TapeOp {
+    std::function<int()> run;
+    const char* what;
+};
 struct TapeRec;
 extern thread_local TapeRec* g_tape_rec;                    // non-null while this thread records (and is not paused)
-void tape_push(std::function<void()>&& op);
+void tape_push(TapeOp&& op);
 
+// The launch itself runs unchanged (the caller's VSOM_LAUNCH_CHECK sees its status); the recorded op checks it on replay.
 template <class F>
-inline void launch_or_record(F&& f) {
+inline void launch_or_record(F&& f, const char* what) {
     f();
-    if (g_tape_rec) tape_push(std::function<void()>(std::forward<F>(f)));
+    if (g_tape_rec) tape_push({[f = std::forward<F>(f)]() { f(); return hip_status(hipGetLastError(), "kernel launch"); }, what});
 }
 #define VSOM_LAUNCH(kernel, grid, block, lds, stream, ...)                                       \
-    ::vsom::launch_or_record([=]() { hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__); })
+    ::vsom::launch_or_record([=]() { hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__); }, #kernel)
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }

@@ -1,9 +1,10 @@
 // Launch tape: record the kernel launches (and stream / event edges) of a training step once, while they run, and re-issue
 // them from C afterwards -- one call per segment instead of one Python + ctypes round trip per launch.
 //
-// What a tape holds: closures, in issue order.  A closure is one hipLaunchKernelGGL with its by-value arguments frozen
-// (VSOM_LAUNCH, common.h), one event record or one stream wait (vsom_event_record / vsom_stream_wait_event: library-owned
-// events, so that the edges between the step's HIP streams are part of the tape), or one RCCL all-reduce (comm.hip).
+// What a tape holds: ops (TapeOp, common.h), in issue order.  An op is one hipLaunchKernelGGL with its by-value arguments
+// frozen (VSOM_LAUNCH), one event record or one stream wait (vsom_event_record / vsom_stream_wait_event: library-owned
+// events, so that the edges between the step's HIP streams are part of the tape), or one RCCL all-reduce (comm.hip).  Every
+// op returns its status; a replay stops at the first one that fails.
 // What it cannot hold: anything whose arguments change from step to step.  Those few calls (the neighbourhood kernel with
 // the temperature, the loss combination, AdamW with lr / step) stay with the host, which cuts the tape into segments around
 // them (vsom_tape_cut / vsom_tape_pause) and replays segment, call, segment, ...  Inputs are staged into fixed buffers by the host.
@@ -17,14 +18,14 @@
 namespace vsom {
 
 struct TapeRec {
-    std::vector<std::vector<std::function<void()>>> segments;
+    std::vector<std::vector<TapeOp>> segments;
     bool paused = false;
 };
 
 thread_local TapeRec* g_tape_rec = nullptr;          // what VSOM_LAUNCH appends to (null: not recording, or paused)
 static thread_local TapeRec* g_tape_cur = nullptr;   // the tape being recorded on this thread (also while paused)
 
-void tape_push(std::function<void()>&& op) { g_tape_rec->segments.back().push_back(std::move(op)); }
+void tape_push(TapeOp&& op) { g_tape_rec->segments.back().push_back(std::move(op)); }
 
 namespace {
 std::mutex g_mu;
@@ -85,8 +86,17 @@ int vsom_tape_replay(int tape, int segment) {
     TapeRec* t = tape_of(tape);
     VSOM_REQUIRE(t && t != g_tape_cur, VSOM_EINVAL, "tape_replay: no such tape (or it is still being recorded)");
     VSOM_REQUIRE(segment >= 0 && segment < (int)t->segments.size(), VSOM_EINVAL, "tape_replay: no segment %d", segment);
-    for (const auto& op : t->segments[segment]) op();
-    return hip_status(hipGetLastError(), "tape_replay");
+    const std::vector<TapeOp>& ops = t->segments[segment];
+    for (size_t i = 0; i < ops.size(); ++i) {
+        const int rc = ops[i].run();
+        if (rc != VSOM_OK) {
+            char why[512];
+            snprintf(why, sizeof(why), "%s", vsom_last_error_string());
+            set_error("tape_replay: segment %d, op %d (%s): %s", segment, (int)i, ops[i].what, why);
+            return rc;
+        }
+    }
+    return VSOM_OK;
 }
 
 int vsom_tape_destroy(int tape) {
@@ -100,12 +110,10 @@ int vsom_tape_destroy(int tape) {
 // ---- library-owned events: the edges between the step's streams, recordable on a tape
 static int event_of(int ev, hipEvent_t* out) {
     VSOM_REQUIRE(ev >= 0 && ev < MAX_EVENTS, VSOM_EINVAL, "event id %d outside [0, %d)", ev, MAX_EVENTS);
+    std::lock_guard<std::mutex> lk(g_mu);
     if (!g_events[ev]) {
-        std::lock_guard<std::mutex> lk(g_mu);
-        if (!g_events[ev]) {
-            const int rc = hip_status(hipEventCreateWithFlags(&g_events[ev], hipEventDisableTiming), "hipEventCreateWithFlags");
-            if (rc) return rc;
-        }
+        const int rc = hip_status(hipEventCreateWithFlags(&g_events[ev], hipEventDisableTiming), "hipEventCreateWithFlags");
+        if (rc) return rc;
     }
     *out = g_events[ev];
     return VSOM_OK;
@@ -116,7 +124,8 @@ int vsom_event_record(int ev, vsom_stream_t stream) {
     int rc = event_of(ev, &e);
     if (rc) return rc;
     rc = hip_status(hipEventRecord(e, stream), "hipEventRecord");
-    if (rc == VSOM_OK && g_tape_rec) tape_push([=]() { (void)hipEventRecord(e, stream); });
+    if (rc == VSOM_OK && g_tape_rec)
+        tape_push({[=]() { return hip_status(hipEventRecord(e, stream), "hipEventRecord"); }, "vsom_event_record"});
     return rc;
 }
 
@@ -125,7 +134,9 @@ int vsom_stream_wait_event(vsom_stream_t stream, int ev) {
     int rc = event_of(ev, &e);
     if (rc) return rc;
     rc = hip_status(hipStreamWaitEvent(stream, e, 0), "hipStreamWaitEvent");
-    if (rc == VSOM_OK && g_tape_rec) tape_push([=]() { (void)hipStreamWaitEvent(stream, e, 0); });
+    if (rc == VSOM_OK && g_tape_rec)
+        tape_push({[=]() { return hip_status(hipStreamWaitEvent(stream, e, 0), "hipStreamWaitEvent"); },
+                   "vsom_stream_wait_event"});
     return rc;
 }
 

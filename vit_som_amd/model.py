@@ -15,6 +15,7 @@ data-parallel exchange (one RCCL all-reduce over the gradient arena).  There is 
 """
 import math
 import os
+import weakref
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -1016,14 +1017,9 @@ class _StepLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, model, x, y, gamma_t, T):
         ctx.model = model
-        ctx.taped = hasattr(model, "_tape_usable") and model._tape_usable(x)
-        if ctx.taped:
-            out, ctx.backward_done = model._taped_forward(x, y, gamma_t, T)
-            out = out.clone()
-        else:
-            out = model._forward_losses(x, y, gamma_t, T, want_grad=True).clone()
+        out, ctx.run_backward = model._step(x, y, gamma_t, T)
         ctx.forward_id = model._forward_id
-        return out
+        return out.clone()
 
     @staticmethod
     def backward(ctx, gout):
@@ -1032,23 +1028,106 @@ class _StepLoss(torch.autograd.Function):
             raise RuntimeError("ViTSOM: backward() called twice for one training_step (or after a later forward): the "
                                "step's buffers and gradient seeds are single-use; gradient accumulation is not supported")
         m._seeds_consumed = True
-        if ctx.taped and m._ctx[1].__dict__.get("tape") is not None:
-            m._taped_backward(gout)        # segment 2 scales the seeds by gout, segment 3 is the backward
-        else:
-            m._scale_seeds(gout)           # 1.0 under a plain loss.backward()
-            m._backward()
+        ctx.run_backward(gout)             # the seeds scaled by gout (1.0 under a plain loss.backward()), then the backward
         m._expose_grads()
         return None, None, None, None, None, None
 
 
 class _StepTape:
-    """Handle of a recorded step (vsom_tape_*): destroyed with the activation buffers it points into."""
+    """A training step recorded on a launch tape (vsom_tape_*) while it runs; later steps re-issue its ~420 launches from C.
+    Segments: 0 = forward up to the distances, 1 = main loss, 2 = loss-seed scaling (autograd bridge only), 3 = the whole
+    backward.  The host issues the neighbourhood kernel and the loss combination in the holes between 0 | 1 | 2, with each
+    step's temperature and gamma.  The third step of a batch size is recorded; inputs are staged into fixed buffers.
 
-    def __init__(self, tid, nseg, key, started, comm_dirty, side, som_bufs):
+    The tape points into: the ViT activations `a`, which own it; the SOM buffers `s`; the arenas, the weight transposes and
+    the frozen parameters, which only _apply / _pack move or rebuild, always with a new arena; the prototypes' plane image;
+    ops.scratch blocks, grow-only with retired blocks kept alive, so they need no check.  `valid` compares the others by
+    identity -- weak references, never id(), which CPython reuses -- and the switches, exchange and launch stream of the
+    recording.  A tape that fails it is closed and the step recorded again."""
+
+    @staticmethod
+    def _key(m):
+        return (ops.get_gemm_mode(), ops.get_attention_fused(), hooks.signature(), m.world_size, m._use_vsom_comm, ops.stream())
+
+    @classmethod
+    @torch.no_grad()
+    def step(cls, m, x, y, gamma_t: float, T: float):
+        """A training step's forward through the tape of its batch size -> (total, backward), like _ArenaOwner._step."""
+        if not (hooks.launch_tape and x.is_cuda and (m.world_size == 1 or m._use_vsom_comm) and ops.tape_recording() == 0):
+            return _ArenaOwner._step(m, x, y, gamma_t, T)
+        x = m.vit._check_input(x)
+        a = m.vit._buffers_for(x.shape[0], x.device)
+        if not hasattr(a, "x_in"):
+            a.x_in = torch.empty(a.B, m.vit.in_chans, m.vit.img_size, m.vit.img_size, dtype=torch.float32, device=a.device)
+            a.y_in = torch.zeros(a.B, dtype=torch.int64, device=a.device)
+            a.gout_in = torch.ones(1, dtype=torch.float32, device=a.device)
+            a.steps_seen = 0
+        xs, ys = a.x_in.copy_(x), a.y_in
+        if m.classification:
+            ys.copy_(y.view(-1))
+        tape = a.__dict__.get("tape")
+        if tape is not None and not tape.valid(m, a):
+            tape.close()
+            tape = a.tape = None
+        if hooks.adamw_planes and m.som_layer._planes_shape_ok(a.B):
+            m.som_layer._w_planes()                   # outside the tape: launches only when the optimizer-kept image is stale
+        if tape is None:
+            a.steps_seen += 1
+            if a.steps_seen <= 2:                     # host-driven: scratch buffers and lazily built tables settle first
+                return _ArenaOwner._step(m, xs, ys, gamma_t, T)
+            tid = ops.tape_begin()
+            try:
+                total = m._forward_losses(xs, ys, gamma_t, T, want_grad=True)      # segments 0 | hole | 1 | hole | 2 ...
+                a.gout_in.fill_(1.0)
+                m._scale_seeds(a.gout_in)                                          # ... segment 2 (x 1.0: exact no-op)
+                ops.tape_cut()
+                m._backward()                                                      # segment 3
+            except BaseException:
+                ops.tape_end()
+                ops.tape_destroy(tid)
+                raise
+            tape = a.tape = cls(tid, ops.tape_end(), m, a)
+            # the recording ran the backward (seed 1); the autograd bridge replays it with its own seed
+            return total, lambda gout=None: gout is not None and tape.backward(m, gout)
+        # the host-side state a host-driven step leaves behind, then segment | hole | segment | hole
+        s = tape.som_bufs
+        a.version += 1
+        m._ctx = (xs, a, s)
+        m._forward_id, m._seeds_consumed = m._forward_id + 1, False
+        total = tape.forward(lambda: m._call_neigh(s, gamma_t, T, a.B, True),
+                             lambda: m._call_parts(a, s, gamma_t, T, a.B, xs.numel(), True))
+        return total, lambda gout=None: tape.backward(m, gout)
+
+    def __init__(self, tid, nseg, m, a):
         if nseg != 4:
             ops.tape_destroy(tid)
             raise RuntimeError(f"launch tape: expected 4 segments, recorded {nseg}")
-        self.id, self.key, self.started, self.comm_dirty, self.side, self.som_bufs = tid, key, started, comm_dirty, side, som_bufs
+        w = m.som_layer._wplanes
+        self.id, self.key, self.gout_in, self.som_bufs = tid, self._key(m), a.gout_in, m._ctx[2]
+        self.arena, self.planes = weakref.ref(m.arena), (lambda: None) if w is None else weakref.ref(w)
+        self.started, self.comm_dirty, self.side = list(m._started), m._comm_dirty, m.vit._side
+
+    def valid(self, m, a) -> bool:
+        return (self.key == self._key(m) and self.arena() is m.arena and self.planes() is m.som_layer._wplanes
+                and self.som_bufs is m.som_layer._bufs.get(a.B))
+
+    def forward(self, neigh, parts):
+        """Segments 0 and 1, each followed by its host-issued call; returns what `parts` returns (the total loss)."""
+        ops.tape_replay(self.id, 0)
+        neigh()
+        ops.tape_replay(self.id, 1)
+        return parts()
+
+    @torch.no_grad()
+    def backward(self, m, gout=None):
+        """Segment 3 (segment 2 first when a loss seed comes in), then the host-side state the recorded backward left."""
+        m._grads_reduced = False
+        m._exchange_reset()
+        if gout is not None:
+            self.gout_in.copy_(gout.detach().reshape(1))
+            ops.tape_replay(self.id, 2)
+        ops.tape_replay(self.id, 3)
+        m._started, m._comm_dirty, m.vit._side = list(self.started), self.comm_dirty, self.side
 
     def close(self):
         if self.id:
@@ -1110,6 +1189,14 @@ class _ArenaOwner:
 
     def _after_pack(self):
         pass
+
+    def _step(self, x, y, gamma_t: float, T: float):
+        """Forward + losses of a training step -> (total, backward); backward(gout=None) fills the gradient arena."""
+        def backward(gout=None):
+            if gout is not None:
+                self._scale_seeds(gout)
+            self._backward()
+        return self._forward_losses(x, y, gamma_t, T, want_grad=True), backward
 
     def _named_trainable(self):
         return [(n, p) for n, p in self.named_parameters() if p.requires_grad]
@@ -1666,80 +1753,8 @@ class ViTSOM(_ArenaOwner, _Base):
         self.som_layer.update_temperature(self._it)                     # vit_som.py:84 (iteration BEFORE increment)
         return self._gamma_t(), float(self.som_layer.current_temperature)
 
-    # -- launch tape: the step's ~420 launches recorded once (while they run) and re-issued from C -------------------
-    # Segments: 0 = forward up to the distances, 1 = main loss, 2 = loss-seed scaling (autograd bridge only), 3 = the whole
-    # backward; the neighbourhood kernel and the loss combination sit in the holes between 0 | 1 | 2 and are issued from here
-    # with this step's temperature and gamma.  Inputs are staged into fixed buffers; every other buffer of the step is
-    # persistent per batch size, so the tape lives and dies with the activation buffers (`a`).
-    def _tape_key(self):
-        return (ops.get_gemm_mode(), ops.get_attention_fused(), hooks.signature(),
-                self.world_size, self._use_vsom_comm, id(self.arena), id(self.som_layer._wplanes))
-
-    def _tape_usable(self, x) -> bool:
-        return bool(hooks.launch_tape and x.is_cuda and (self.world_size == 1 or self._use_vsom_comm) and ops.tape_recording() == 0)
-
-    def _stage_inputs(self, x, y, a: _Acts):
-        if not hasattr(a, "x_in"):
-            a.x_in = torch.empty(a.B, self.vit.in_chans, self.vit.img_size, self.vit.img_size, dtype=torch.float32, device=a.device)
-            a.y_in = torch.zeros(a.B, dtype=torch.int64, device=a.device)
-            a.gout_in = torch.ones(1, dtype=torch.float32, device=a.device)
-            a.steps_seen = 0
-        a.x_in.copy_(x)
-        if self.classification:
-            a.y_in.copy_(y.view(-1))
-        return a.x_in, a.y_in
-
-    @torch.no_grad()
-    def _taped_forward(self, x, y, gamma_t: float, T: float):
-        """Forward + losses (+ the backward too while the tape is being recorded).  Returns (total, backward_done)."""
-        x = self.vit._check_input(x)
-        a = self.vit._buffers_for(x.shape[0], x.device)
-        xs, ys = self._stage_inputs(x, y, a)
-        tape = a.__dict__.get("tape")
-        # the tape holds raw pointers: it is valid only for the buffers (ViT activations `a`, SOM buffers `s`, arenas) and the
-        # switches it was recorded with
-        if tape is not None and (tape.key != self._tape_key() or tape.som_bufs is not self.som_layer._bufs.get(a.B)):
-            tape.close()
-            tape = a.tape = None
-        if hooks.adamw_planes and self.som_layer._planes_shape_ok(a.B):
-            self.som_layer._w_planes()                # outside the tape: launches only when the optimizer-kept image is stale
-        if tape is None:
-            a.steps_seen += 1
-            if a.steps_seen <= 2:                     # host-driven: scratch buffers and lazily built tables settle first
-                return self._forward_losses(xs, ys, gamma_t, T, want_grad=True), False
-            tid = ops.tape_begin()
-            try:
-                total = self._forward_losses(xs, ys, gamma_t, T, want_grad=True)          # segments 0 | hole | 1 | hole | 2 ...
-                a.gout_in.fill_(1.0)
-                self._scale_seeds(a.gout_in)                                              # ... segment 2 (x 1.0: exact no-op)
-                ops.tape_cut()
-                self._backward()                                                          # segment 3
-            finally:
-                nseg = ops.tape_end()
-            a.tape = _StepTape(tid, nseg, self._tape_key(), list(self._started), self._comm_dirty, self.vit._side, self._ctx[2])
-            return total, True
-        # replay: the host-side state a host-driven step leaves behind, then segment | hole | segment | hole
-        s = tape.som_bufs
-        a.version += 1
-        self._ctx = (xs, a, s)
-        self._forward_id, self._seeds_consumed = self._forward_id + 1, False
-        ops.tape_replay(tape.id, 0)
-        self._call_neigh(s, gamma_t, T, a.B, True)
-        ops.tape_replay(tape.id, 1)
-        return self._call_parts(a, s, gamma_t, T, a.B, xs.numel(), True), False
-
-    @torch.no_grad()
-    def _taped_backward(self, gout=None):
-        """The backward of the last taped forward (segment 3; segment 2 first when a loss seed other than 1 comes in)."""
-        _, a, _ = self._ctx
-        tape = a.tape
-        self._grads_reduced = False
-        self._exchange_reset()
-        if gout is not None:
-            a.gout_in.copy_(gout.detach().reshape(1))
-            ops.tape_replay(tape.id, 2)
-        ops.tape_replay(tape.id, 3)
-        self._started, self._comm_dirty, self.vit._side = list(tape.started), tape.comm_dirty, tape.side
+    def _step(self, x, y, gamma_t: float, T: float):
+        return _StepTape.step(self, x, y, gamma_t, T)
 
     def training_step(self, batch, batch_idx):
         """vit_som.py:80-105.  Returns a scalar tensor; ``.backward()`` runs the HIP backward."""
@@ -1761,16 +1776,8 @@ class ViTSOM(_ArenaOwner, _Base):
         arena (the caller then runs optimizer.step()).  Returns the loss tensor."""
         self._estimated_steps()
         gamma_t, T = self._schedules_for_step()
-        if self._tape_usable(x):
-            total, backward_done = self._taped_forward(x, y, gamma_t, T)
-            if not backward_done:
-                if self._ctx[1].__dict__.get("tape") is not None:
-                    self._taped_backward()
-                else:
-                    self._backward()
-        else:
-            total = self._forward_losses(x, y, gamma_t, T, want_grad=True)
-            self._backward()
+        total, backward = self._step(x, y, gamma_t, T)
+        backward()
         self._advance()
         return total
 

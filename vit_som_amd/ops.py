@@ -635,7 +635,10 @@ def tape_begin() -> int:
 
 
 def tape_cut() -> int:
-    return int(lib.vsom_tape_cut())
+    seg = int(lib.vsom_tape_cut())
+    if seg < 0:
+        check(seg, "vsom_tape_cut")
+    return seg
 
 
 def tape_end() -> int:
@@ -654,7 +657,7 @@ class tape_hole:
     def __enter__(self):
         self.active = tape_recording() == 1
         if self.active:
-            lib.vsom_tape_cut()
+            tape_cut()
             check(lib.vsom_tape_pause(1), "vsom_tape_pause")
 
     def __exit__(self, *exc):

@@ -28,7 +28,7 @@ class _Hooks:
         return self
 
     def signature(self):
-        """All switches as a tuple: what a recorded launch sequence was recorded under (model.py _tape_key)."""
+        """All switches as a tuple: what a recorded launch sequence was recorded under (model.py _StepTape)."""
         return tuple((k, getattr(self, k)) for k in sorted(vars(_Hooks)) if not k.startswith("_") and not callable(getattr(_Hooks, k)))
 
     def reset(self):
