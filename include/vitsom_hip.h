@@ -318,6 +318,40 @@ int vsom_contingency(const int64_t* a, const int64_t* b, long n, int na, int nb,
 /* out[r] = first argmax_c X[r,c] -- torch.argmax(cls_logits, dim=1), evaluation.py:119 */
 int vsom_argmax_rows(const float* X, long ldx, int rows, int cols, int64_t* out, vsom_stream_t stream);
 
+/* k-means of evaluate_kmeans (evaluation.py:54-91): the data-touching steps of sklearn.cluster.KMeans
+ * (sklearn/cluster/_kmeans.py, algorithm="lloyd", dense fp32, unit sample weights).  X is [N, D] with row stride ldx;
+ * centres are [k, D] contiguous; labels int64.  Every sum has a fixed order (no floating-point atomics): results are
+ * bitwise reproducible.  One workspace of vsom_kmeans_workspace_bytes(N, D, k) bytes serves every entry below
+ * (host arithmetic only; 0 for a non-positive size). */
+size_t vsom_kmeans_workspace_bytes(long N, int D, int k);
+/* One Lloyd E-step and the partial M-step in one launch (_k_means_lloyd.pyx lloyd_iter_chunked_dense; each row is read
+ * twice, the second time for the M-step shortly after the first):
+ * labels[i] = first argmin_j |x_i - c_j|^2 (fp32 sum of squared differences; ties -> lowest j), mind[i] = that
+ * distance, and into the workspace: per-workgroup cluster sums / counts and the number of i with
+ * labels[i] != prev_labels[i] (prev_labels may alias labels).  k <= 1024. */
+int vsom_kmeans_assign(const float* X, long ldx, long N, int D, const float* centers, int k, int64_t* labels,
+                       const int64_t* prev_labels, float* mind, void* ws, size_t ws_bytes, vsom_stream_t stream);
+/* After vsom_kmeans_assign with the same (N, D, k, ws): the per-workgroup partials reduced in fixed order into
+ * counts[k] and centers_new = sums * (1 / counts) (_average_centers: an empty cluster takes the row of the first
+ * argmax of counts, averaged if that cluster comes before it and its raw sum if after, as sklearn's in-place loop), and
+ * status[4] (fp64) = {labels changed, center_shift_tot = sum |new - old|^2 (_kmeans_single_lloyd),
+ * empty clusters, inertia = sum_i mind[i] (_inertia)}. */
+int vsom_kmeans_update(const float* centers_old, float* centers_new, long N, int D, int k, const float* mind,
+                       int64_t* counts, double* status, void* ws, size_t ws_bytes, vsom_stream_t stream);
+/* _relocate_empty_clusters_dense after vsom_kmeans_update found empty clusters: moves[2m] = an empty cluster,
+ * moves[2m+1] = the far sample the host chose for it (argpartition of mind), applied in order to the reduced sums
+ * and counts; then centers_new, status[1] (shift) and status[2] (clusters still empty) again. */
+int vsom_kmeans_relocate(const float* X, long ldx, long N, int D, int k, const int64_t* labels, const int64_t* moves,
+                         int n_moves, const float* centers_old, float* centers_new, int64_t* counts, double* status,
+                         void* ws, size_t ws_bytes, vsom_stream_t stream);
+/* _kmeans_plusplus' candidate step: dist[t][i] = min(closest[i], |x_i - x_{candidates[t]}|^2) (closest may be NULL:
+ * no minimum) and pots[t] = sum_i dist[t][i] (fp64, fixed order), for t < n_candidates <= 64. */
+int vsom_kmeanspp_dist(const float* X, long ldx, long N, int D, const int64_t* candidates, int n_candidates,
+                       const float* closest, float* dist, double* pots, vsom_stream_t stream);
+/* _tolerance: out[0] = mean over columns of var(X, axis=0) (fp64); workspace as for (N, D, k). */
+int vsom_kmeans_colvar(const float* X, long ldx, long N, int D, int k, double* out, void* ws, size_t ws_bytes,
+                       vsom_stream_t stream);
+
 /* SOMLayer.som_loss(weights, distances) = mean(weights * distances) for ARBITRARY weights (som_layer.py:137-142):
    loss_sum <- sum_ik weights[i,k] dist[i,k]; with coef/row_dot/col_dot given, also the backward coefficients of
    grad_scale * that sum w.r.t. the distances' inputs (what vsom_som_bwd consumes) -- with weights = an upstream

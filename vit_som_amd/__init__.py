@@ -5,3 +5,4 @@ from . import ops  # noqa: F401
 from .model import FusedAdamW, SOMLayer, ViTAutoencoder, ViTSOM, param_groups_lrd  # noqa: F401,E402
 from .desom import DESOM, Autoencoder  # noqa: F401,E402
 from . import evaluation  # noqa: F401,E402
+from .kmeans import KMeans, kmeans_plusplus  # noqa: F401,E402

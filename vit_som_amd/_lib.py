@@ -107,6 +107,14 @@ SIGNATURES = {
                                   C.c_int, C.c_float, C.c_int, c_stream]),
     "vsom_contingency": (C.c_int, [c_fp, c_fp, C.c_long, C.c_int, C.c_int, c_fp, c_fp, c_stream]),
     "vsom_argmax_rows": (C.c_int, [c_fp, C.c_long, C.c_int, C.c_int, c_fp, c_stream]),
+    "vsom_kmeans_workspace_bytes": (C.c_size_t, [C.c_long, C.c_int, C.c_int]),
+    "vsom_kmeans_assign": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_size_t,
+                                     c_stream]),
+    "vsom_kmeans_update": (C.c_int, [c_fp, c_fp, C.c_long, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_size_t, c_stream]),
+    "vsom_kmeans_relocate": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, C.c_int, c_fp, c_fp, C.c_int, c_fp, c_fp, c_fp,
+                                       c_fp, c_fp, C.c_size_t, c_stream]),
+    "vsom_kmeanspp_dist": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, C.c_int, c_fp, c_fp, c_fp, c_stream]),
+    "vsom_kmeans_colvar": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, C.c_int, c_fp, c_fp, C.c_size_t, c_stream]),
     "vsom_fill": (C.c_int, [c_fp, C.c_long, C.c_float, c_stream]),
     "vsom_scaled_mul": (C.c_int, [c_fp, c_fp, c_fp, C.c_long, c_fp, C.c_float, c_stream]),
     "vsom_som_weighted_loss": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_float, c_fp, c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_int,

@@ -1,11 +1,12 @@
 """On-device evaluation mirroring the reference's tools/evaluation.py entry points
-(evaluate_clustering :18-52, evaluate_classification :93-128, calculate_purity :130-151).
+(evaluate_clustering :18-52, evaluate_kmeans :54-91, evaluate_classification :93-128, calculate_purity :130-151).
 
 The model forward runs on the HIP kernels (encoder + SOM only: `ViTSOM.predict`); BMU / label
 pairs are folded into a contingency table ON DEVICE batch by batch (`vsom_contingency`, integer
 atomics), so the only device->host traffic of a whole evaluation pass is that table.  Purity, NMI
 (sklearn's arithmetic-mean normalisation) and the macro precision / recall / F1 are O(classes^2)
-host arithmetic on the table.
+host arithmetic on the table.  evaluate_kmeans keeps the model outputs in one device buffer and clusters them with
+the HIP k-means (kmeans.py).
 """
 import time
 
@@ -13,6 +14,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .kmeans import KMeans
 
 
 class _Table:
@@ -124,6 +126,63 @@ def evaluate_clustering(model, config, dataloader, num_labels=None):
     purity, nmi = purity_from_table(w), nmi_from_table(w)
     inference_time = time.time() - start
     print(f"Purity: {purity:.3f}, NMI: {nmi:.3f}, Inference Time: {inference_time:.3f}")
+    return purity, nmi, inference_time
+
+
+def _gather_rows(t, world_size):
+    """Every rank's rows, concatenated in rank order (ranks may hold different row counts)."""
+    import torch.distributed as dist
+    n = torch.tensor([t.shape[0]], dtype=torch.int64, device=t.device)
+    sizes = [torch.zeros_like(n) for _ in range(world_size)]
+    dist.all_gather(sizes, n)
+    sizes = [int(s) for s in sizes]
+    pad = torch.zeros((max(sizes),) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    pad[:t.shape[0]] = t
+    parts = [torch.empty_like(pad) for _ in range(world_size)]
+    dist.all_gather(parts, pad)
+    return torch.cat([p[:s] for p, s in zip(parts, sizes)])
+
+
+def evaluate_kmeans(model, config, dataloader, num_labels=None):
+    """evaluation.py:54-91 -> (purity, nmi, inference_time) of KMeans(n_clusters=len(unique(labels)), random_state=0,
+    n_init=10) on the model's outputs.  The features are what the reference clusters: for vit_som the SECOND output of
+    ViTSOM.forward, i.e. recon_img flattened to C*H*W (the reference calls it x_encoded, vit_som.py:67-78), for desom
+    the encoder latent x_encoded (desom.py:50-54).  Features and labels stay on the device; the fit is the HIP k-means
+    (kmeans.py).  Labels must lie in [0, num_labels) (default max(data.num_classes, 256)).  With model.world_size > 1
+    every rank gathers the whole set and runs the same deterministic fit, so all ranks report the whole set's metrics."""
+    model.eval()
+    d = config["data"]
+    C, S = d["num_channels"], d["input_size"]
+    arch = config["hyperparameters"]["model_arch"]
+    dev = model.arena.device
+    L = int(num_labels) if num_labels else max(int(d.get("num_classes", 0)), 256)
+    feats, labels, start = [], [], time.time()
+    with torch.no_grad():                                  # evaluation.py:67
+        for x, y in dataloader:
+            x = x.to(dev, non_blocking=True)
+            y = y.to(dev, non_blocking=True)
+            if arch == "vit_som":
+                _, f, *_ = model(x.reshape(-1, C, S, S))
+            elif arch == "desom":
+                _, f, *_ = model(x.reshape(x.shape[0], -1))
+            else:
+                raise ValueError(f"evaluate_kmeans: unknown model_arch {arch!r}")
+            feats.append(f.reshape(f.shape[0], -1))
+            labels.append(y.reshape(-1).long())
+    X, y = torch.cat(feats), torch.cat(labels)
+    world = _world(model)
+    if world > 1:
+        X, y = _gather_rows(X, world), _gather_rows(y, world)
+    hist = _Table(1, L, dev)                               # len(np.unique(y_trues)), labels range-checked
+    hist.add(torch.zeros_like(y), y)
+    n_clusters = int((hist.numpy() > 0).sum())
+    km = KMeans(n_clusters=n_clusters, random_state=0, n_init=10)
+    table = _Table(n_clusters, L, dev)
+    table.add(km.fit_predict(X), y)
+    w = table.numpy()
+    purity, nmi = purity_from_table(w), nmi_from_table(w)
+    inference_time = time.time() - start
+    print(f"Purity (KMeans): {purity:.3f}, NMI (KMeans): {nmi:.3f}, Inference Time: {inference_time:.3f}")
     return purity, nmi, inference_time
 
 

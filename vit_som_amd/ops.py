@@ -587,6 +587,63 @@ def argmax_rows(x, out):
     return out
 
 
+# ---------------------------------------------------------------- k-means (evaluate_kmeans)
+def kmeans_workspace_bytes(N: int, D: int, k: int) -> int:
+    return lib.vsom_kmeans_workspace_bytes(N, D, k)
+
+
+def _kmeans_x(X):
+    _f32(X, "X")
+    assert X.dim() == 2, "X must be [N, D]"
+    return X.shape[0], X.shape[1], _rows(X)
+
+
+def kmeans_assign(X, centers, labels, prev_labels, mind, ws):
+    """One Lloyd E-step + partial M-step: labels / mind written, cluster partials into ws."""
+    N, D, ldx = _kmeans_x(X)
+    _f32(centers, "centers"); _f32(mind, "mind")
+    assert centers.is_contiguous() and centers.shape[1] == D and labels.dtype == torch.int64 and prev_labels.dtype == torch.int64
+    assert labels.numel() == N and prev_labels.numel() == N and mind.numel() == N
+    check(lib.vsom_kmeans_assign(ptr(X), ldx, N, D, ptr(centers), centers.shape[0], ptr(labels), ptr(prev_labels), ptr(mind),
+                                 ptr(ws), ws.numel() * ws.element_size(), stream()), "vsom_kmeans_assign")
+
+
+def kmeans_update(centers_old, centers_new, N, mind, counts, status, ws):
+    """centers_new, counts [k] int64 and status [4] fp64 = (changed, center_shift_tot, empty, inertia)."""
+    k, D = centers_old.shape
+    assert centers_new.is_contiguous() and centers_old.is_contiguous() and counts.dtype == torch.int64 and status.dtype == torch.float64
+    check(lib.vsom_kmeans_update(ptr(centers_old), ptr(centers_new), N, D, k, ptr(mind), ptr(counts), ptr(status), ptr(ws),
+                                 ws.numel() * ws.element_size(), stream()), "vsom_kmeans_update")
+
+
+def kmeans_relocate(X, labels, moves, centers_old, centers_new, counts, status, ws):
+    """Apply the empty-cluster moves (int64 [m, 2] device tensor of (cluster, sample)) in order, then the centres again."""
+    N, D, ldx = _kmeans_x(X)
+    k = centers_old.shape[0]
+    assert moves.dtype == torch.int64 and moves.is_contiguous() and moves.is_cuda
+    check(lib.vsom_kmeans_relocate(ptr(X), ldx, N, D, k, ptr(labels), ptr(moves), moves.shape[0], ptr(centers_old),
+                                   ptr(centers_new), ptr(counts), ptr(status), ptr(ws), ws.numel() * ws.element_size(),
+                                   stream()), "vsom_kmeans_relocate")
+
+
+def kmeanspp_dist(X, candidates, closest, dist, pots):
+    """dist [T, N] = min(closest, squared distance to each candidate row); pots [T] fp64 = row sums of dist."""
+    N, D, ldx = _kmeans_x(X)
+    T = candidates.numel()
+    assert candidates.dtype == torch.int64 and candidates.is_cuda and dist.shape == (T, N) and dist.is_contiguous()
+    assert pots.dtype == torch.float64 and pots.numel() >= T
+    check(lib.vsom_kmeanspp_dist(ptr(X), ldx, N, D, ptr(candidates), T, ptr(closest), ptr(dist), ptr(pots), stream()),
+          "vsom_kmeanspp_dist")
+
+
+def kmeans_colvar(X, k, out, ws):
+    """out[0] = mean(var(X, axis=0)) in fp64."""
+    N, D, ldx = _kmeans_x(X)
+    assert out.dtype == torch.float64
+    check(lib.vsom_kmeans_colvar(ptr(X), ldx, N, D, k, ptr(out), ptr(ws), ws.numel() * ws.element_size(), stream()),
+          "vsom_kmeans_colvar")
+
+
 # ---------------------------------------------------------------- data-parallel exchange (RCCL)
 COMM_ID_BYTES = 128
 
