@@ -193,7 +193,7 @@ def test_steps_are_deterministic():
 
 def test_stream_level_concurrency_is_bitwise_identical():
     """Weight-gradient GEMMs and the SOM backward run on side streams, and the forward runs as two
-    half-batch chains on two streams (model.py).  Arithmetic and summation order are unchanged, so 8
+    half-batch chains on two streams (model.py, vit.py).  Arithmetic and summation order are unchanged, so 8
     training steps at CIFAR layer shapes must end in bit-identical parameters with every combination
     of the switches -- any missed ordering edge would show up here."""
     import vit_som_amd

@@ -14,8 +14,11 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from ._base import _HAVE_PL, _Acts, _Base
 from .arena import ParamArena
-from .model import _HAVE_PL, FusedAdamW, SOMLayer, _Acts, _ArenaOwner, _Base, _StepLoss
+from .optim import FusedAdamW
+from .som import SOMLayer
+from .step import _ArenaOwner, _StepLoss
 
 
 class Autoencoder(nn.Module):

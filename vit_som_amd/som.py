@@ -1,0 +1,278 @@
+"""SOMLayer (models/som_layer.py:8-152) on the HIP kernels, with the autograd functions of its distances and loss."""
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import ops
+from ._base import _Acts, _Base
+from ._lib import Event, on_stream
+from .tuning import hooks
+
+
+class _SomDistancesFn(torch.autograd.Function):
+    """SOMLayer.forward under autograd (som_layer.py:83-89, 111-125): distances differentiable w.r.t. the input rows
+    and the prototypes; the BMU indices are returned alongside (non-differentiable, argmin)."""
+
+    @staticmethod
+    def forward(ctx, x, W, layer):
+        with torch.no_grad():
+            s = layer._buffers_for(x.shape[0], x.device)
+            layer._distances_into(x, s)
+            dist, bmu = s.dist.clone(), s.bmu.clone()
+            ctx.save_for_backward(x, W, dist, s.inx.clone(), s.inw.clone())
+        ctx.mode = layer._dist_mode
+        ctx.mark_non_differentiable(bmu)
+        return dist, bmu
+
+    @staticmethod
+    def backward(ctx, g_dist, _g_bmu):
+        x, W, dist, inx, inw = ctx.saved_tensors
+        B, K = dist.shape
+        with torch.no_grad():
+            f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dist.device)   # noqa: E731
+            coef, row_dot, col_dot, tmp = f(B, K), f(B), f(K), f(1)
+            # backward coefficients of sum(g * dist): the upstream gradient plays the role of the weights
+            ops.som_weighted_loss(dist, g_dist.float().contiguous(), tmp, inv_nx=inx, inv_nw=inw, grad_scale=1.0, coef=coef,
+                                  row_dot=row_dot, col_dot=col_dot, distance=ctx.mode)
+            gW, gX = torch.empty_like(W), torch.empty_like(x)
+            if ctx.mode == ops.DIST_MANHATTAN:
+                ops.som_bwd_manhattan(x, W, coef, gW, gX, accumulate_gx=False)
+            else:
+                ops.som_bwd(x, W, coef, row_dot, col_dot, gW, gX, accumulate_gx=False)
+        return gX, gW, None
+
+
+class _SomLossFn(torch.autograd.Function):
+    """mean(weights * distances) (som_layer.py:137-142) with gradients to both arguments."""
+
+    @staticmethod
+    def forward(ctx, weights, distances):
+        ctx.save_for_backward(weights, distances)
+        tmp = torch.empty(1, dtype=torch.float32, device=distances.device)
+        ops.som_weighted_loss(distances, weights, tmp)
+        out = torch.empty((), dtype=torch.float32, device=distances.device)
+        ops.scaled_mul(out.view(1), tmp, factor=1.0 / distances.numel())
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        weights, distances = ctx.saved_tensors
+        g = gout.detach().reshape(1).float().contiguous()
+        inv = 1.0 / distances.numel()
+        gw = ops.scaled_mul(torch.empty_like(weights), distances, scale_dev=g, factor=inv) if ctx.needs_input_grad[0] else None
+        gd = ops.scaled_mul(torch.empty_like(distances), weights, scale_dev=g, factor=inv) if ctx.needs_input_grad[1] else None
+        return gw, gd
+
+
+# ------------------------------------------------------------------------------------ SOM layer
+class SOMLayer(_Base):
+    """models/som_layer.py:8-152 on the HIP kernels (cosine / euclidean / manhattan distance; square /
+    hexa topology; clients: ViTSOM and DESOM)."""
+
+    def __init__(self, config):
+        super().__init__()
+        hp = config["hyperparameters"]
+        self.model_arch = hp["model_arch"]
+        som_hp, data_hp = hp["som"], config["data"]
+        vit_hp = hp["vit"] if self.model_arch == "vit_som" else None
+        self.total_epochs, self.batch_size = hp["total_epochs"], hp["batch_size"]
+        self.map_size = som_hp["map_size"]
+        self.Tmax, self.Tmin = som_hp["Tmax"], som_hp["Tmin"]
+        self.topology, self.distance_fcn = som_hp["topology"], som_hp["distance_fcn"]
+        self.n_prototypes = int(np.prod(self.map_size))
+        modes = {"cosine": ops.DIST_COSINE, "euclidean": ops.DIST_EUCLIDEAN, "manhattan": ops.DIST_MANHATTAN}
+        if self.distance_fcn not in modes:                              # som_layer.py:111-125 raises the same way
+            raise ValueError(f"Unsupported distance function: {self.distance_fcn}")
+        self._dist_mode = modes[self.distance_fcn]
+        if self.model_arch == "vit_som":                                       # som_layer.py:35-40
+            self.use_reduced = som_hp["use_reduced"]
+            latent_dim = vit_hp["emb_dim"]
+            if not self.use_reduced:
+                latent_dim *= (data_hp["input_size"] // vit_hp["patch_size"]) ** 2
+        else:                                                                  # DESOM: the autoencoder's code
+            self.use_reduced = False
+            latent_dim = hp["ae"]["encoder_dims"][-1]
+        self.latent_dim = latent_dim
+        self.current_temperature = self.Tmax
+        proto = torch.rand(self.n_prototypes, latent_dim)                      # som_layer.py:44-56
+        if self.distance_fcn == "cosine":
+            proto = torch.nn.functional.normalize(proto, p=2, dim=1)
+        self.prototypes = nn.Parameter(proto)
+        self.create_grid_positions()
+        self._world_size = 1
+        self._n_train: Optional[int] = None
+        self._bufs: Dict[int, _Acts] = {}
+        # pre-split plane image of the prototypes for the BMU contraction (ops.bmu_planes_*): valid while its stamp
+        # equals _w_stamp().  FusedAdamW rewrites it in the pass that updates the prototypes; anything else that
+        # changes them is seen through torch's version counter, the storage address or _raw_updates.
+        self._wplanes: Optional[torch.Tensor] = None
+        self._wplanes_stamp = None
+        self._raw_updates = 0           # updates of the prototypes that bypass torch (raw-pointer kernels)
+        self._planes_used = False       # a forward took the planes path: the optimizer keeps the image current
+
+    # ---- plane image of the prototypes ---------------------------------------------------
+    def _w_stamp(self):
+        W = self.prototypes
+        return (W.data_ptr(), W._version, self._raw_updates, tuple(W.shape))
+
+    def invalidate_planes(self):
+        """Call after changing the prototypes behind torch's back (writes through ``.data`` or a raw pointer)."""
+        self._wplanes_stamp = None
+
+    def _planes_shape_ok(self, B: int) -> bool:
+        W = self.prototypes
+        return bool(hooks.bmu_planes and self._dist_mode == ops.DIST_COSINE and W.is_cuda and ops.get_gemm_mode() != ops.GEMM_F32
+                    and ops.bmu_planes_supported(B, W.shape[0], W.shape[1]))
+
+    def _w_planes(self) -> torch.Tensor:
+        """The prototypes' plane buffer, re-split here if it does not describe them any more."""
+        W = self.prototypes
+        if self._wplanes is None or self._wplanes.device != W.device or self._wplanes.numel() != ops.lib.vsom_bmu_planes_bytes(*W.shape):
+            self._wplanes = ops.bmu_planes_alloc(W.shape[0], W.shape[1], W.device)
+            self._wplanes_stamp = None
+        if self._wplanes_stamp != self._w_stamp():
+            ops.bmu_planes_from(W.detach(), self._wplanes)
+            self._wplanes_stamp = self._w_stamp()
+        return self._wplanes
+
+    def _w_planes_async(self, side_stream, force: bool):
+        """Bring the prototypes' image up to date on `side_stream`, behind everything the launch stream holds so far
+        (the optimizer step that wrote the prototypes, the last contraction that read the image) -- when it is stale,
+        or always with `force` (a recorded training step must contain the launch whatever the state it was recorded
+        in).  Returns the event the consumer has to wait for, or None when nothing was launched."""
+        W = self.prototypes
+        if self._wplanes is None or self._wplanes.device != W.device or self._wplanes.numel() != ops.lib.vsom_bmu_planes_bytes(*W.shape):
+            self._wplanes = ops.bmu_planes_alloc(W.shape[0], W.shape[1], W.device)
+            self._wplanes_stamp = None
+        if not force and self._wplanes_stamp == self._w_stamp():
+            return None
+        Event.pooled().record().wait(side_stream)
+        with on_stream(side_stream):
+            ops.bmu_planes_from(W.detach(), self._wplanes)
+        self._wplanes_stamp = self._w_stamp()
+        return Event.pooled().record(side_stream)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        self.invalidate_planes()
+
+    def create_grid_positions(self):                                   # som_layer.py:60-81
+        if self.topology == "square":
+            gy, gx = torch.meshgrid(torch.arange(self.map_size[0]), torch.arange(self.map_size[1]), indexing="ij")
+            positions = torch.stack([gy, gx], dim=-1).view(-1, 2).float()
+        elif self.topology == "hexa":
+            rows, cols = self.map_size
+            positions = torch.zeros(self.n_prototypes, 2)
+            for i in range(self.n_prototypes):
+                row, col = i // cols, i % cols
+                positions[i, 0] = col + (0.5 if row % 2 == 1 else 0.0)
+                positions[i, 1] = row * np.sqrt(3) / 2
+        else:
+            raise ValueError(f"Unsupported topology: {self.topology}")
+        self.register_buffer("grid_positions", positions)
+
+    def _buffers_for(self, B: int, device) -> _Acts:
+        s = self._bufs.get(B)
+        if s is not None and s.device == device:
+            return s
+        K = self.n_prototypes
+        f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=device)   # noqa: E731
+        s = _Acts()
+        s.device = device
+        s.inx, s.inw = f(B), f(K)
+        s.dist, s.bmu = f(B, K), torch.empty(B, dtype=torch.int64, device=device)
+        s.reranked = torch.zeros(1, dtype=torch.int32, device=device)      # rows whose BMU needed the exact re-rank (cumulative)
+        s.coef, s.row_dot, s.col_dot = f(B, K), f(B), f(K)
+        s.loss_sum = f(1)
+        # like the ViT's activation buffers: at most two batch sizes stay allocated (training and validation batches alternate)
+        self._bufs = dict(list(self._bufs.items())[-1:] + [(B, s)])
+        return s
+
+    # reference API -----------------------------------------------------------------------
+    @torch.no_grad()
+    def compute_distances(self, x):                                    # som_layer.py:111-125
+        if x.dim() > 2:
+            x = x.flatten(start_dim=1)
+        s = self._buffers_for(x.shape[0], x.device)
+        self._distances_into(x, s)
+        return s.dist.clone()
+
+    def _distances_into(self, x2d, s: _Acts):
+        if self._dist_mode == ops.DIST_COSINE:
+            W = self.prototypes
+            if (ops.get_gemm_mode() != ops.GEMM_F32 and W.shape[0] <= 2048 and W.shape[1] % 4 == 0
+                    and x2d.stride(0) % 4 == 0 and x2d.data_ptr() % 16 == 0):
+                # norms + reduced-precision contraction + exact re-rank in one pass over X and W
+                if self._planes_shape_ok(x2d.shape[0]):
+                    # ... on pre-split operands: the prototypes' image is kept by the optimizer, the samples' written here
+                    self._planes_used = True
+                    if getattr(s, "xplanes", None) is None:
+                        s.xplanes = ops.bmu_planes_alloc(x2d.shape[0], x2d.shape[1], x2d.device)
+                    wplanes = self._w_planes()
+                    ops.bmu_planes_from(x2d, s.xplanes)
+                    ops.bmu_cosine_x3_planes_fwd(x2d, W, s.xplanes, wplanes, s.dist, s.bmu, s.inx, s.inw, s.reranked)
+                else:
+                    ops.bmu_cosine_x3_fwd(x2d, W, s.dist, s.bmu, s.inx, s.inw, s.reranked)
+            else:
+                ops.row_inv_norm(x2d, s.inx)
+                ops.row_inv_norm(W, s.inw)
+                ops.bmu_cosine_fwd(x2d, W, s.inx, s.inw, s.dist, s.bmu)
+        elif self._dist_mode == ops.DIST_MANHATTAN:
+            ops.bmu_manhattan_fwd(x2d, self.prototypes, s.dist, s.bmu)
+        else:                                   # euclidean: inx / inw hold the squared norms
+            ops.row_sqnorm(x2d, s.inx)
+            ops.row_sqnorm(self.prototypes, s.inw)
+            ops.bmu_euclid_fwd(x2d, self.prototypes, s.inx, s.inw, s.dist, s.bmu)
+
+    def forward(self, x):                                              # som_layer.py:83-89
+        """-> (distances [B,K], bmu_indices [B] int64).  With autograd enabled the distances are differentiable
+        w.r.t. `x` and the prototypes (``_SomDistancesFn``); the fused training step does not go through here."""
+        if x.dim() > 2:
+            x = x.flatten(start_dim=1)
+        x = x.float()
+        if x.stride(-1) != 1:
+            x = x.contiguous()
+        if torch.is_grad_enabled() and (x.requires_grad or self.prototypes.requires_grad):
+            return _SomDistancesFn.apply(x, self.prototypes, self)
+        with torch.no_grad():
+            s = self._buffers_for(x.shape[0], x.device)
+            self._distances_into(x, s)
+            return s.dist.clone(), s.bmu.clone()
+
+    def total_iterations(self) -> float:
+        n = self._n_train
+        if n is None:
+            tr = getattr(self, "_trainer_ref", None)
+            if tr is None:
+                raise RuntimeError("SOMLayer: call ViTSOM.set_schedule(n_train, estimated_stepping_batches) "
+                                   "or attach a trainer before training_step")
+            n = len(tr.train_dataloader.dataset)
+        # single-process semantics on the GLOBAL batch (the reference divides by the per-rank
+        # batch size only, som_layer.py:131 -- SURVEY.md section 5, defect (b))
+        return (n / (self.batch_size * self._world_size)) * self.total_epochs
+
+    def update_temperature(self, iteration):                           # som_layer.py:127-132
+        it = float(iteration)
+        self.current_temperature = self.Tmax * (self.Tmin / self.Tmax) ** (it / (self.total_iterations() - 1))
+
+    def index_to_position(self, indices):                              # som_layer.py:134-135
+        return torch.stack((indices // self.map_size[1], indices % self.map_size[1]), dim=1).float()
+
+    @torch.no_grad()
+    def compute_weights(self, bmu_indices):                            # som_layer.py:144-152
+        B, K = bmu_indices.shape[0], self.n_prototypes
+        dev = bmu_indices.device
+        h = torch.empty(B, K, dtype=torch.float32, device=dev)
+        zero_d = torch.zeros(B, K, dtype=torch.float32, device=dev)
+        tmp = torch.empty(1, dtype=torch.float32, device=dev)
+        ops.som_neigh_loss(zero_d, bmu_indices.contiguous(), self.grid_positions, float(self.current_temperature), tmp, h=h,
+                           distance=self._dist_mode)
+        return h
+
+    def som_loss(self, weights, distances):                            # som_layer.py:137-142
+        """mean(weights * distances) for ANY weights tensor, differentiable in both arguments."""
+        if weights.shape != distances.shape:
+            raise ValueError(f"som_loss: weights {tuple(weights.shape)} and distances {tuple(distances.shape)} differ")
+        return _SomLossFn.apply(weights.float().contiguous(), distances.float().contiguous())

@@ -12,13 +12,13 @@ class _Hooks:
     fwd_split_blocks = None     # how many encoder blocks run as two chains (None = all)
     overlap_allreduce = True    # N > 1: issue the all-reduce pieces inside the backward pass
     bucket_blocks = 3           # encoder blocks per early all-reduce piece
-    bmu_planes = True           # cosine BMU pass on pre-split plane images where the shape allows (model.py SOMLayer._distances_into)
+    bmu_planes = True           # cosine BMU pass on pre-split plane images where the shape allows (som.py SOMLayer._distances_into)
     adamw_planes = False        # True: FusedAdamW writes the prototypes' plane image in its own pass (+27 us on the critical path);
                                 # False: the training forward re-splits them on the SOM stream under the encoder (hidden)
     ln_reduce_batched = True    # the LayerNorm backwards' dgamma / dbeta reductions in one launch per exchange piece instead of 30 (ops.LayerNormJobs)
     bmu_overlap = False         # True: the BMU pass on the SOM stream under the decoder forward (model.py _run_forward): -0.02..-0.04 ms per
                                 # step, but the contraction then shares the chip (72 instead of 58-63 us per launch) -- off: it runs alone
-    launch_tape = True          # train_step_fused / training_step re-issue the recorded launches of a step from C (model.py)
+    launch_tape = True          # train_step_fused / training_step re-issue the recorded launches of a step from C (step.py)
 
     def set(self, **kw):
         for k, v in kw.items():
@@ -28,7 +28,7 @@ class _Hooks:
         return self
 
     def signature(self):
-        """All switches as a tuple: what a recorded launch sequence was recorded under (model.py _StepTape)."""
+        """All switches as a tuple: what a recorded launch sequence was recorded under (step.py _StepTape)."""
         return tuple((k, getattr(self, k)) for k in sorted(vars(_Hooks)) if not k.startswith("_") and not callable(getattr(_Hooks, k)))
 
     def reset(self):
