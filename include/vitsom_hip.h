@@ -168,6 +168,19 @@ int vsom_attention_probs(const float* qkv, const float* lse, float* probs, int B
    two-piece split of the gradient GEMMs (gradients within 8e-6 relative of fp64); 3 = form 1 with fp32 products always */
 int vsom_set_attention_fused(int fused);
 
+/* Single-query attention: ONE query row per (image, head) against the image's N keys -- the CLS row of a classifier's
+ * last encoder block (classifier.py).  q[B,E] and kv[B*N,2E] (K then V) keep the qkv Linear's head interleave
+ * (E = H*hd, head h in columns [h*hd, (h+1)*hd)); o[B,E] = softmax(q k^T * hd^-0.5) v, lse[B,H] = log-sum-exp of the
+ * scaled scores.  hd in {8, 16, 32, 64}, any N >= 1; fp32 throughout; every output element written; no atomics
+ * (bitwise reproducible).  q / kv / o 16-byte aligned. */
+int vsom_attention_q1_fwd(const float* q, const float* kv, float* o, float* lse, int B, int N, int H, int hd,
+                          vsom_stream_t stream);
+/* dq[B,E] and dkv[B*N,2E] from dout[B,E] (autograd of the above); each (image, head) owns its rows of dkv. */
+int vsom_attention_q1_bwd(const float* dout, const float* o, const float* lse, const float* q, const float* kv, float* dq,
+                          float* dkv, int B, int N, int H, int hd, vsom_stream_t stream);
+/* dst[r, 0:cols] += src[r, 0:cols] for r < rows (row strides lds / ldd in floats): the CLS rows' residual gradient. */
+int vsom_rows_add(const float* src, long lds, float* dst, long ldd, int rows, int cols, vsom_stream_t stream);
+
 /* ------------------------------------------------------------------ SOM layer */
 /* inv_norm[r] = 1 / max(||X[r,:]||_2, eps)   -- F.normalize(p=2, eps=1e-12), som_layer.py:120-121 */
 int vsom_row_inv_norm(const float* X, long ldx, int rows, int cols, float eps, float* inv_norm,

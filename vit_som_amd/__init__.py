@@ -3,7 +3,8 @@
 
 Layers, lowest first: ``_lib`` / ``ops`` (the C-ABI), ``arena``, ``tuning`` and ``_base``; ``vit``
 (ViTAutoencoder) and ``som`` (SOMLayer); ``optim`` (FusedAdamW) and ``step`` (the fused step's
-machinery shared by every arena-owning model); ``model`` (ViTSOM) and ``desom`` (DESOM), two peers."""
+machinery shared by every arena-owning model); ``model`` (ViTSOM) and ``desom`` (DESOM), two peers;
+``classifier`` (ViTClassifier, the plain ViT baseline)."""
 from . import _lib  # noqa: F401  (fails loudly when libvitsom_hip.so is absent)
 from . import ops  # noqa: F401
 from .vit import ViTAutoencoder  # noqa: F401,E402
@@ -11,5 +12,6 @@ from .som import SOMLayer  # noqa: F401,E402
 from .optim import FusedAdamW, param_groups_lrd  # noqa: F401,E402
 from .model import ViTSOM  # noqa: F401,E402
 from .desom import DESOM, Autoencoder  # noqa: F401,E402
+from .classifier import ViTClassifier  # noqa: F401,E402
 from . import evaluation  # noqa: F401,E402
 from .kmeans import KMeans, kmeans_plusplus  # noqa: F401,E402

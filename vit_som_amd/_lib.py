@@ -50,6 +50,9 @@ SIGNATURES = {
     "vsom_attention_bwd": (C.c_int, [c_fp] * 6 + [C.c_int] * 4 + [c_stream]),
     "vsom_set_attention_fused": (C.c_int, [C.c_int]),
     "vsom_attention_probs": (C.c_int, [c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
+    "vsom_attention_q1_fwd": (C.c_int, [c_fp] * 4 + [C.c_int] * 4 + [c_stream]),
+    "vsom_attention_q1_bwd": (C.c_int, [c_fp] * 7 + [C.c_int] * 4 + [c_stream]),
+    "vsom_rows_add": (C.c_int, [c_fp, C.c_long, c_fp, C.c_long, C.c_int, C.c_int, c_stream]),
     "vsom_tape_begin": (C.c_int, []),
     "vsom_tape_cut": (C.c_int, []),
     "vsom_tape_pause": (C.c_int, [C.c_int]),

@@ -297,6 +297,32 @@ def attention_probs(qkv, lse, probs, B, N, H, hd):
     return probs
 
 
+def attention_q1_fwd(q, kv, out, lse, B, N, H, hd):
+    """Single-query attention (the CLS row): q[B,E], kv[B*N,2E] (K then V) -> out[B,E], lse[B,H]."""
+    assert all(t.is_contiguous() for t in (q, kv, out, lse))
+    _f32(q, "q"); _f32(kv, "kv"); _f32(out, "out"); _f32(lse, "lse")
+    check(lib.vsom_attention_q1_fwd(ptr(q), ptr(kv), ptr(out), ptr(lse), B, N, H, hd, stream()), "vsom_attention_q1_fwd")
+    return out
+
+
+def attention_q1_bwd(dout, out, lse, q, kv, dq, dkv, B, N, H, hd):
+    """dq[B,E], dkv[B*N,2E] of attention_q1_fwd; every element written."""
+    assert all(t.is_contiguous() for t in (dout, out, lse, q, kv, dq, dkv))
+    _f32(dout, "dout"); _f32(q, "q"); _f32(kv, "kv"); _f32(dq, "dq"); _f32(dkv, "dkv")
+    check(lib.vsom_attention_q1_bwd(ptr(dout), ptr(out), ptr(lse), ptr(q), ptr(kv), ptr(dq), ptr(dkv), B, N, H, hd, stream()),
+          "vsom_attention_q1_bwd")
+    return dq, dkv
+
+
+def rows_add(src, dst):
+    """dst += src over [rows, cols] views with any row stride (e.g. the CLS rows of a [B*N, E] buffer)."""
+    rows, cols = src.shape
+    _f32(src, "src"); _f32(dst, "dst")
+    assert dst.shape == (rows, cols)
+    check(lib.vsom_rows_add(ptr(src), _rows(src), ptr(dst), _rows(dst), rows, cols, stream()), "vsom_rows_add")
+    return dst
+
+
 # ---------------------------------------------------------------- SOM
 def row_inv_norm(x, out, eps=1e-12):
     rows, cols = x.shape

@@ -179,7 +179,7 @@ def _vsom_comm_selftest(world_size: int, device) -> bool:
 class _ArenaOwner:
     """What every model on this path shares: trainable tensors packed into flat arenas
     (arena.py), gradients exposed as views, and the data-parallel exchange over the gradient
-    arena.  Subclasses provide ``som_layer`` and may override the two hooks."""
+    arena.  Subclasses may provide ``som_layer`` and override the two hooks."""
 
     arena: Optional[ParamArena] = None
     world_size, rank = 1, 0
@@ -249,7 +249,9 @@ class _ArenaOwner:
         """backend: "rccl" = the library's own communicator (vsom_comm_*; the default on the GPU unless torch.distributed
         runs on gloo), "torch" = torch.distributed's all_reduce (gloo on CPU tensors, or its "nccl" = RCCL)."""
         self.world_size, self.rank = int(world_size), int(rank)
-        self.som_layer._world_size = int(world_size)
+        som = getattr(self, "som_layer", None)          # ViTClassifier has none
+        if som is not None:
+            som._world_size = int(world_size)
         self._backend_defaulted = backend is None
         if backend is None:
             backend = "torch"

@@ -11,6 +11,9 @@ in-memory set of the configured shape.  One process per GPU: under torchrun (WOR
 rank takes an interleaved shard of each loader and gradients are summed by one RCCL all-reduce.
 
     python -m vit_som_amd.train --config configs/vit_som/vit_som_cifar-10.yaml [--runs 5] [--epochs N]
+
+A config with hyperparameters.model_arch == "vit" (the reference's configs/vit/*.yaml) trains the ViT baseline,
+ViTClassifier, as experiments/benchmarking/train_vit.py does.
 """
 import argparse
 import copy
@@ -23,6 +26,7 @@ import torch
 import yaml
 
 from .evaluation import evaluate_classification, evaluate_clustering
+from .classifier import ViTClassifier
 from .model import ViTSOM
 
 
@@ -96,8 +100,10 @@ def synthetic_loaders(config, rank=0, world_size=1, n_train=2048, n_val=256, n_t
             TensorLoader(xv, yv, bs, rank=rank, world_size=world_size), TensorLoader(xs, ys, bs, rank=rank, world_size=world_size))
 
 
-def fit(model, config, train_loader, val_loader, ckpt_dir, dataset_name, use_validation, max_epochs=None, log=print):
-    """The Lightning fit loop the reference relies on (train_vit_som.py:86-93), written out."""
+def fit(model, config, train_loader, val_loader, ckpt_dir, dataset_name, use_validation, max_epochs=None, log=print,
+        ckpt_prefix="vit_som"):
+    """The Lightning fit loop the reference relies on (train_vit_som.py:86-93), written out.  The best checkpoint is
+    <ckpt_dir>/<ckpt_prefix>_<dataset_name>_best.ckpt (train_vit.py:84 names it vit_<dataset>_best)."""
     hp = config["hyperparameters"]
     epochs = int(max_epochs if max_epochs is not None else hp["total_epochs"])
     dev = model.arena.device
@@ -131,7 +137,8 @@ def fit(model, config, train_loader, val_loader, ckpt_dir, dataset_name, use_val
             rec["val/total_loss"] = float(vloss / max(vb, 1))
             if model.rank == 0 and rec["val/accuracy"] > best_acc:        # ModelCheckpoint(monitor='val/accuracy', mode='max')
                 best_acc = rec["val/accuracy"]
-                best_path = model.save_checkpoint(os.path.join(ckpt_dir, f"vit_som_{dataset_name}_best.ckpt"), opt, sched, epoch)
+                best_path = model.save_checkpoint(os.path.join(ckpt_dir, f"{ckpt_prefix}_{dataset_name}_best.ckpt"), opt, sched,
+                                                  epoch)
         history.append(rec)
         log(" ".join(f"{k}={v:.5g}" if isinstance(v, float) else f"{k}={v}" for k, v in rec.items()))
     if not use_validation and model.rank == 0:                            # ModelCheckpoint(save_last=True)
@@ -139,9 +146,62 @@ def fit(model, config, train_loader, val_loader, ckpt_dir, dataset_name, use_val
     return {"history": history, "best_model_path": best_path, "last_model_path": last_path, "optimizer": opt}
 
 
-def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir="experiments/states/vit_som",
-         log=print):
-    """train_vit_som.py:27-130."""
+def _init_process(world, rank, local_rank):
+    torch.cuda.set_device(local_rank % max(torch.cuda.device_count(), 1))
+    if world > 1 and not torch.distributed.is_initialized():
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        torch.distributed.init_process_group(os.environ.get("VSOM_DIST_BACKEND", "nccl"), rank=rank, world_size=world)
+    torch.manual_seed(0)                                                  # pl.seed_everything(0)
+    np.random.seed(0)
+
+
+def main_vit(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir="experiments/states/vit",
+             log=print):
+    """experiments/benchmarking/train_vit.py: the ViT baseline (ViTClassifier).  Each run trains with the best
+    val/accuracy checkpointed, reloads that checkpoint and reports the test loader's classification metrics."""
+    data_hp = config["data"]
+    dataset_name = data_hp["dataset"]
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    _init_process(world, rank, int(os.environ.get("LOCAL_RANK", "0")))
+    all_metrics = {k: [] for k in ("accuracy", "precision", "recall", "f1", "run_duration", "inference_time")}
+    for run in range(n_runs):
+        log(f"Starting run {run + 1} for {dataset_name}...")
+        start = time.time()
+        if rank == 0:
+            clear_directory(model_states_dir)
+        train_loader, val_loader, test_loader = make_loaders(config, rank, world)
+        log("Training ViT Classifier...")
+        model = ViTClassifier(copy.deepcopy(config))
+        model.set_distributed(world, rank)
+        model.broadcast_parameters()
+        fit(model, config, train_loader, val_loader, model_states_dir, dataset_name, True, max_epochs, log, ckpt_prefix="vit")
+        model.on_train_end()
+        torch.cuda.synchronize()
+        run_duration = time.time() - start
+        log(f"Run {run + 1} duration: {run_duration:.2f} seconds")
+        # rank 0 wrote the best checkpoint (ModelCheckpoint(monitor='val/accuracy', mode='max')); every rank reloads it
+        path = os.path.join(model_states_dir, f"vit_{dataset_name}_best.ckpt")
+        if world > 1:
+            torch.distributed.barrier()
+        best_model = ViTClassifier.load_from_checkpoint(path, config=config)
+        best_model.set_distributed(world, rank, backend="torch")
+        acc, prec, rec, f1, inf_t = evaluate_classification(best_model, config, test_loader)
+        for k, v in (("accuracy", acc), ("precision", prec), ("recall", rec), ("f1", f1), ("run_duration", run_duration),
+                     ("inference_time", inf_t)):
+            all_metrics[k].append(v)
+    if n_runs > 1:
+        _report(all_metrics, n_runs, dataset_name, log)
+    return all_metrics
+
+
+def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print):
+    """train_vit_som.py:27-130; a config with hyperparameters.model_arch == "vit" runs main_vit (train_vit.py) instead.
+    model_states_dir defaults to experiments/states/vit_som (experiments/states/vit for the ViT baseline)."""
+    if config["hyperparameters"].get("model_arch") == "vit":
+        return main_vit(config, n_runs=n_runs, max_epochs=max_epochs, make_loaders=make_loaders,
+                        model_states_dir=model_states_dir or "experiments/states/vit", log=log)
+    if model_states_dir is None:
+        model_states_dir = "experiments/states/vit_som"
     hp, data_hp = config["hyperparameters"], config["data"]
     use_validation = data_hp["num_classes"] > 0
     dataset_name = data_hp["dataset"]
@@ -191,7 +251,7 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser(description="ViT-SOM training driver (MI355X)")
+    ap = argparse.ArgumentParser(description="ViT-SOM / ViT training driver (MI355X)")
     ap.add_argument("--config", type=str, required=True)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--epochs", type=int, default=None)

@@ -19,6 +19,7 @@ class _Hooks:
     bmu_overlap = False         # True: the BMU pass on the SOM stream under the decoder forward (model.py _run_forward): -0.02..-0.04 ms per
                                 # step, but the contraction then shares the chip (72 instead of 58-63 us per launch) -- off: it runs alone
     launch_tape = True          # train_step_fused / training_step re-issue the recorded launches of a step from C (step.py)
+    cls_prune = True            # ViTClassifier: the last encoder block on the CLS rows only (classifier.py); False: in full
 
     def set(self, **kw):
         for k, v in kw.items():

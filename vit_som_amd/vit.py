@@ -204,6 +204,12 @@ class ViTAutoencoder(nn.Module):
         return L.x2
 
     def _encode(self, x: torch.Tensor, a: _Acts):
+        cur = self._encode_trunk(x, a, len(self.blocks))
+        ops.layernorm_fwd(cur, self.norm.weight, self.norm.bias, a.xe, a.mean_e, a.rstd_e, self.eps)
+        return a.xe
+
+    def _encode_trunk(self, x: torch.Tensor, a: _Acts, depth: int):
+        """Patch embedding and encoder blocks [0, depth) -> the output of block depth - 1 ([T, E]; the tokens when 0)."""
         E = self.embed_dim
         p = self.patch_embed.patch_size[0]
         a.version += 1
@@ -240,7 +246,7 @@ class ViTAutoencoder(nn.Module):
             # 11.68 ms per step; round 1 kept it to half because the f32-MFMA BMU pass ran slower right after a dense
             # forward -- the bf16 BMU pass does not).
             nsplit = len(self.blocks) if hooks.fwd_split_blocks is None else int(hooks.fwd_split_blocks)
-            nsplit = max(0, min(nsplit, len(self.blocks)))
+            nsplit = max(0, min(nsplit, depth))
             # enqueue the two chains alternately, block by block: the host feeds both streams at the same pace (all
             # of chain 0 first left the second stream idle for the ~0.7 ms the host needs to enqueue six blocks)
             c0, c1 = a.tok0[:Th], a.tok0[Th:]
@@ -250,13 +256,12 @@ class ViTAutoencoder(nn.Module):
                     c1 = self._block_fwd(self.blocks[i], cuts[1][i], c1, Bh, a.N)
             self._event().record(side).wait()
             cur = a.enc[nsplit - 1].x2 if nsplit > 0 else a.tok0
-            for blk, L in zip(self.blocks[nsplit:], a.enc[nsplit:]):
+            for blk, L in zip(self.blocks[nsplit:depth], a.enc[nsplit:depth]):
                 cur = self._block_fwd(blk, L, cur, a.B, a.N)
         else:
-            for blk, L in zip(self.blocks, a.enc):
+            for blk, L in zip(self.blocks[:depth], a.enc[:depth]):
                 cur = self._block_fwd(blk, L, cur, a.B, a.N)
-        ops.layernorm_fwd(cur, self.norm.weight, self.norm.bias, a.xe, a.mean_e, a.rstd_e, self.eps)
-        return a.xe
+        return cur
 
     def _decode(self, a: _Acts):
         ops.linear_residual_fwd(a.xe, self.decoder_embed.weight, self.decoder_embed.bias, self.decoder_pos_embed[0],
@@ -463,17 +468,21 @@ class ViTAutoencoder(nn.Module):
             before_dxe()
         self._dx(WT, gout, self.decoder_embed.weight, a.d_xe, accumulate=before_dxe is not None)
 
-    def _encoder_bwd(self, a: _Acts, G, WT=None, on_block=None):
+    def _encoder_bwd(self, a: _Acts, G, WT=None, on_block=None, depth=None):
         """a.d_xe holds dL/d(xe); writes every encoder gradient.  on_block(i) is called once block i's
-        backward (main chain and weight-gradient side work) has been enqueued."""
+        backward (main chain and weight-gradient side work) has been enqueued.  With `depth` given, the caller has
+        already run the final norm and blocks [depth, D) and left dL/d(output of block depth - 1) in the first
+        [T, E] gradient buffer (self._views(a, E)[0]); only blocks [0, depth) and the patch embedding run."""
         self._side_join(keep=0)            # the decoder's blocks may still be reading the shared buffers
         E = self.embed_dim
         ring = self._views(a, E)
         gA = ring[0]
-        x_last = a.enc[-1].x2 if a.enc else a.tok0
-        self._ln_bwd(a.d_xe, x_last, a.mean_e, a.rstd_e, self.norm.weight, None, gA, G("norm.weight"), G("norm.bias"))
+        if depth is None:
+            depth = len(self.blocks)
+            x_last = a.enc[-1].x2 if a.enc else a.tok0
+            self._ln_bwd(a.d_xe, x_last, a.mean_e, a.rstd_e, self.norm.weight, None, gA, G("norm.weight"), G("norm.bias"))
         gout, pos = gA, 0
-        for j, i in enumerate(reversed(range(len(self.blocks)))):
+        for j, i in enumerate(reversed(range(depth))):
             x_in = a.enc[i - 1].x2 if i > 0 else a.tok0
             bufs = [ring[(pos + 1) % 5], ring[(pos + 2) % 5]]
             gout = self._block_bwd(self.blocks[i], a.enc[i], x_in, gout, a, G, f"blocks.{i}", bufs, WT, j & 1)
