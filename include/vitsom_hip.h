@@ -148,6 +148,23 @@ int vsom_layernorm_bwd_partial(const float* dY, const float* X, const float* mea
                                size_t part_bytes, vsom_stream_t stream);
 int vsom_layernorm_bwd_finish_many(const int64_t* jobs_dev, int first, int count, int max_cols, vsom_stream_t stream);
 
+/* The input-gradient GEMM of vsom_linear_bwd_input_t (dY[M,N], Wt[K,N]) with the LayerNorm backward of its product in
+ * the epilogue: dX = (resid ? resid : 0) + LN'(dY Wt^T) over rows of width K, in one launch -- the product never reaches
+ * memory.  dX is bit for bit what vsom_linear_bwd_input_t into a scratch buffer followed by vsom_layernorm_bwd writes;
+ * dgamma / dbeta come from per-row-tile partials (rounding differs from vsom_layernorm_bwd, the reduction is as
+ * deterministic).  _partial leaves the partials in `part` for vsom_layernorm_bwd_finish_many (same job format, nblk =
+ * part_bytes_query / (8 K)).  Supported (vsom_linear_bwd_input_ln_supported != 0): the split-bf16 GEMM modes, K = 192 or
+ * 96, enough row tiles for the column reducer; otherwise VSOM_EUNSUPPORTED and the caller takes the two-launch path.
+ * Pointers 16-byte aligned, lddy % 4 == 0, X / resid / dX dense [M, K]. */
+int vsom_linear_bwd_input_ln_supported(int M, int N, int K);
+size_t vsom_linear_bwd_input_ln_partial_bytes(int M, int K);
+int vsom_linear_bwd_input_ln(const float* dY, long lddy, const float* Wt, int M, int N, int K, const float* X,
+                             const float* mean, const float* rstd, const float* gamma, const float* resid, float* dX,
+                             float* dgamma, float* dbeta, void* ws, size_t ws_bytes, vsom_stream_t stream);
+int vsom_linear_bwd_input_ln_partial(const float* dY, long lddy, const float* Wt, int M, int N, int K, const float* X,
+                                     const float* mean, const float* rstd, const float* gamma, const float* resid,
+                                     float* dX, void* part, size_t part_bytes, vsom_stream_t stream);
+
 /* ------------------------------------------------------------------ multi-head attention */
 /* out[B,N,H*hd] = softmax(q k^T * hd^-0.5) v, qkv laid out [B,N,3,H,hd] (the qkv Linear's
  * output, vit.py:30-37; dropout p=0).  lse[B,H,N] = log-sum-exp of the scaled scores (saved for

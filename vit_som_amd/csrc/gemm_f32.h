@@ -33,6 +33,7 @@ enum Epi : int {
     EPI_GELU_BWD = 5,   // v = acc * R[m*ldr + n] (R = gelu'(pre) saved by the forward) (+ C if accumulate)
     EPI_SLAB = 6,       // split-k partial: slab[z][m*N + n] = acc; optional column sums of A
     EPI_BIAS_RELU = 7,  // pre = acc + bias[n]; C = (pre > 0) as 1.0/0.0 (the derivative); C2 = max(pre, 0)
+    EPI_LN_BWD = 8,     // LayerNorm backward of the tile's full rows (gemm_x6.h): C = dX, ln_part[tile] = dgamma / dbeta partials
 };
 
 struct GemmP {
@@ -56,6 +57,9 @@ struct GemmP {
     int a_vec, b_vec;            // 16-byte vector loads legal for A / B
     unsigned a_bytes, b_bytes;   // extent of A / B for the bounds-checked buffer loads (FAST path)
     int products;                // split-bf16 engine: 6 (exact three-piece split; default when 0) or 3 (two-piece split)
+    // EPI_LN_BWD: acc = dY of a LayerNorm over the N columns; C (ldc = N) = its dX
+    const float* ln_x; const float* ln_mean; const float* ln_rstd; const float* ln_gamma; const float* ln_resid;
+    float* ln_part;              // [row tile][2][N]
 };
 
 template <int R_>

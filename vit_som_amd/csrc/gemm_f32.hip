@@ -236,6 +236,47 @@ static TnPlan bwd_weight_plan(int M, int N, int K) {
 }
 static long pad4(long n) { return (n + 3) & ~3L; }
 
+// ---- input-gradient GEMM + LayerNorm backward (EPI_LN_BWD): one column tile spanning the LayerNorm's width (the A row
+// panel is read once instead of three / one and a half times), 64 x 192 (2 x 2 waves of 32 x 96) for the encoder and
+// 128 x 96 (4 waves of 32 x 96) for the decoder.  128 x 192 (4 waves of 32 x 192) needs more than 256 registers per lane
+// with the epilogue: one workgroup per CU, or spills.
+static bool ln_fused_width(int K) { return K == 192 || K == 96; }
+static int ln_fused_tiles(int M, int K) { return cdiv(M, K == 192 ? 64 : 128); }
+
+static int linear_bwd_input_ln_launch(const float* dY, long lddy, const float* Wt, int M, int N, int K, const float* X,
+                                      const float* mean, const float* rstd, const float* gamma, const float* resid,
+                                      float* dX, float* part, size_t part_bytes, hipStream_t stream) {
+    VSOM_REQUIRE(dY && Wt && X && mean && rstd && gamma && dX, VSOM_EINVAL, "linear_bwd_input_ln: null pointer");
+    VSOM_REQUIRE(M > 0 && N > 0 && lddy >= N, VSOM_EINVAL, "linear_bwd_input_ln: bad shape M=%d N=%d lddy=%ld", M, N, lddy);
+    VSOM_REQUIRE(vsom_linear_bwd_input_ln_supported(M, N, K), VSOM_EUNSUPPORTED,
+                 "linear_bwd_input_ln: unsupported (M=%d N=%d K=%d, gemm mode %d)", M, N, K, gemm_mode());
+    VSOM_REQUIRE(aligned16(dY) && aligned16(Wt) && aligned16(X) && aligned16(gamma) && aligned16(dX) &&
+                 (!resid || aligned16(resid)) && lddy % 4 == 0 && N % 4 == 0, VSOM_EALIGN,
+                 "linear_bwd_input_ln: operands must be 16-byte aligned (lddy, N multiples of 4)");
+    VSOM_REQUIRE(part && aligned16(part) && part_bytes >= vsom_linear_bwd_input_ln_partial_bytes(M, K), VSOM_EWORKSPACE,
+                 "linear_bwd_input_ln: partial buffer too small or misaligned");
+    const long ab = operand_bytes(M, lddy, N), bb = operand_bytes(K, N, N);
+    VSOM_REQUIRE(ab < 0xFFFF0000L && (long)M * K * 4 < 0xFFFF0000L, VSOM_EUNSUPPORTED, "linear_bwd_input_ln: operand larger than 4 GB");
+    GemmP g = {};
+    g.A = dY; g.lda = lddy; g.B = Wt; g.ldb = N; g.C = dX; g.ldc = K;
+    g.M = M; g.N = K; g.K = N; g.alpha = 1.f;
+    g.ktiles_per_split = cdiv(N, 32);
+    g.a_vec = g.b_vec = 1;
+    g.a_bytes = (unsigned)ab; g.b_bytes = (unsigned)bb;
+    g.products = gemm_grad_products();
+    g.ln_x = X; g.ln_mean = mean; g.ln_rstd = rstd; g.ln_gamma = gamma; g.ln_resid = resid; g.ln_part = part;
+    const dim3 grid(ln_fused_tiles(M, K)), block(256);
+    const bool x3 = g.products == 3;
+    if (K == 192) {
+        if (x3) VSOM_LAUNCH((gemm_x6_ln_kernel<3, 2, 2, 2>), grid, block, 0, stream, g);
+        else VSOM_LAUNCH((gemm_x6_ln_kernel<3, 2, 2, 3>), grid, block, 0, stream, g);
+    } else {
+        if (x3) VSOM_LAUNCH((gemm_x6_ln_kernel<3, 4, 1, 2>), grid, block, 0, stream, g);
+        else VSOM_LAUNCH((gemm_x6_ln_kernel<3, 4, 1, 3>), grid, block, 0, stream, g);
+    }
+    VSOM_LAUNCH_CHECK("gemm_x6_ln_kernel");
+}
+
 
 // dW[N,K] = sum_m dY[row(m), n] X[m, k] (+ db = column sums of dY rows); row(m) = optional map
 int linear_bwd_weight_impl(const float* dY, long lddy, const float* X, long ldx, float* dW, float* db, int M, int N,
@@ -376,6 +417,34 @@ int vsom_linear_bwd_input_t(const float* dY, long lddy, const float* Wt, float* 
         return launch_gemm(true, true, EPI_GELU_BWD, g, 1, stream);
     }
     return launch_gemm(true, true, EPI_NONE, g, 1, stream);
+}
+
+int vsom_linear_bwd_input_ln_supported(int M, int N, int K) {
+    // the column reduction of the one-call form must be the wide single-pass reducer that finish_many runs (>= 32 slabs)
+    return M > 0 && N > 0 && split_engine() && ln_fused_width(K) && ln_fused_tiles(M, K) >= 32;
+}
+
+size_t vsom_linear_bwd_input_ln_partial_bytes(int M, int K) {
+    if (M <= 0 || !ln_fused_width(K)) return 0;
+    return (size_t)ln_fused_tiles(M, K) * 2 * (size_t)K * sizeof(float);
+}
+
+int vsom_linear_bwd_input_ln(const float* dY, long lddy, const float* Wt, int M, int N, int K, const float* X,
+                             const float* mean, const float* rstd, const float* gamma, const float* resid, float* dX,
+                             float* dgamma, float* dbeta, void* ws, size_t ws_bytes, vsom_stream_t stream) {
+    VSOM_REQUIRE(dgamma && dbeta, VSOM_EINVAL, "linear_bwd_input_ln: null pointer");
+    float* part = static_cast<float*>(ws);
+    const int rc = linear_bwd_input_ln_launch(dY, lddy, Wt, M, N, K, X, mean, rstd, gamma, resid, dX, part, ws_bytes, stream);
+    if (rc) return rc;
+    // same reducer, arguments and order as vsom_layernorm_bwd_finish_many on this job
+    return reduce_slabs2_internal(part, 2L * K, ln_fused_tiles(M, K), dgamma, K, dbeta, K, K, stream);
+}
+
+int vsom_linear_bwd_input_ln_partial(const float* dY, long lddy, const float* Wt, int M, int N, int K, const float* X,
+                                     const float* mean, const float* rstd, const float* gamma, const float* resid,
+                                     float* dX, void* part, size_t part_bytes, vsom_stream_t stream) {
+    return linear_bwd_input_ln_launch(dY, lddy, Wt, M, N, K, X, mean, rstd, gamma, resid, dX, static_cast<float*>(part),
+                                      part_bytes, stream);
 }
 
 int vsom_set_gemm_mode(int mode) {

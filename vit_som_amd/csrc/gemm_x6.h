@@ -26,10 +26,12 @@
 // fp32 MFMA's, so the epilogues are shared.
 #pragma once
 #include "gemm_f32.h"
+#include "layernorm_bwd.h"
 
 namespace vsom {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef unsigned v4u32 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned x6_bits(float x) { return __builtin_bit_cast(unsigned, x); }
 __device__ __forceinline__ float x6_float(unsigned x) { return __builtin_bit_cast(float, x); }
@@ -114,9 +116,110 @@ __device__ __forceinline__ void x6_store_ks(const X6Blk& b, char* planes, int pl
     }
 }
 
+// ---- EPI_LN_BWD: the LayerNorm backward of whole output rows (one column tile, BN = the LayerNorm's width).  After the k-loop
+// the operand LDS is dead: the accumulators pass through it 8 rows per wave row at a time (register v of a 32x32 accumulator
+// holds row (v & 3) + 8 (v >> 2) + 4 h, so pass q = registers 4q..4q+3 = rows 8q..8q+7), restaged into the layout of
+// layernorm_bwd_v4_kernel (16 lanes per row, float4 chunk sub + 16 j), and ln_bwd_row runs on them: dX carries the bits of
+// the GEMM + layernorm_bwd pair.  The dY tile never reaches memory.  Each tile writes one dgamma / dbeta partial
+// part[tile][2][N]: column sums over its rows in a fixed order (per lane in pass order, then the 16 row groups in order).
+template <int WN, int WAVES_M, int WAVES_N, int LDS_BYTES>
+__device__ __forceinline__ void x6_ln_bwd_epilogue(const GemmP& g, const f32x16 (&acc)[1][WN], char* lds, int bm0, int wm0,
+                                                   int wn0, int r, int h, int tile) {
+    constexpr int BN = WAVES_N * WN * 32;
+    constexpr int cols = BN;                 // the host launches this epilogue with N == BN only
+    constexpr int NCH = (BN + 63) / 64;
+    constexpr int LROW = BN + 8;             // floats per staged row: the two lane halves (rows 4 apart) 32 banks apart
+    constexpr int PROWS = WAVES_M * 8;       // rows per pass
+    constexpr int ITER = PROWS / 16;         // 16 row groups of 16 lanes
+    static_assert(PROWS % 16 == 0 && PROWS * LROW * 4 <= LDS_BYTES && 16 * 2 * BN * 4 <= LDS_BYTES, "LN epilogue does not fit");
+    float* st = reinterpret_cast<float*>(lds);
+    const int t = threadIdx.x, sub = t & 15, rg = t >> 4;
+    const float inv_n = 1.0f / (float)cols;
+    // bounds-checked buffer accesses (32-bit offsets; rows past M read 0 and drop their stores -- d = 0 there)
+    const unsigned rbytes = (unsigned)g.M * cols * 4u;
+    const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.ln_x), 0, (int)rbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.ln_resid), 0, (int)rbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsD = __builtin_amdgcn_make_buffer_rsrc(g.C, 0, (int)rbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsM = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.ln_mean), 0, g.M * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.ln_rstd), 0, g.M * 4, 0x00020000);
+    const bool has_resid = g.ln_resid != nullptr;
+    f32x4 gam[NCH], dg[NCH], db[NCH];
+    bool cv[NCH];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        cv[j] = 4 * (sub + 16 * j) < cols;
+        gam[j] = cv[j] ? reinterpret_cast<const f32x4*>(g.ln_gamma)[sub + 16 * j] : f32x4{0.f, 0.f, 0.f, 0.f};
+        dg[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        db[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const int wr = wm0 >> 5;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        // every global load of the pass before its first store (see gemm_epilogue)
+        bool ok[ITER];
+        unsigned off[ITER][NCH];
+        float mu[ITER], rs[ITER];
+        f32x4 xv[ITER][NCH], rr[ITER][NCH];
+#pragma unroll
+        for (int i = 0; i < ITER; ++i) {
+            const int lr = 16 * i + rg;
+            const int row = bm0 + (lr >> 3) * 32 + 8 * q + (lr & 7);
+            ok[i] = row < g.M;
+#pragma unroll
+            for (int j = 0; j < NCH; ++j)       // OOB itself, never OOB + something: that wraps round into row 0
+                off[i][j] = (ok[i] && cv[j]) ? (unsigned)row * (cols * 4u) + 16u * (sub + 16 * j) : OOB;
+            const unsigned roff = ok[i] ? (unsigned)row * 4u : OOB;
+            mu[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsM, (int)roff, 0, 0));
+            rs[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsS, (int)roff, 0, 0));
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) {
+                xv[i][j] = bload4(rsX, off[i][j]);
+                rr[i][j] = has_resid ? bload4(rsR, off[i][j]) : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+        __syncthreads();                      // q = 0: the last k-tile's operand reads; q > 0: the previous pass's reads
+#pragma unroll
+        for (int j = 0; j < WN; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) st[(wr * 8 + e + 4 * h) * LROW + wn0 + j * 32 + r] = acc[0][j][4 * q + e];
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < ITER; ++i) {
+            const int lr = 16 * i + rg;
+            f32x4 d[NCH], o[NCH];
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) {
+                d[j] = (cv[j] && ok[i]) ? *reinterpret_cast<const f32x4*>(st + lr * LROW + 4 * (sub + 16 * j)) : f32x4{0.f, 0.f, 0.f, 0.f};
+                if (!cv[j]) xv[i][j] = f32x4{mu[i], mu[i], mu[i], mu[i]};
+            }
+            ln_bwd_row<NCH>(d, xv[i], mu[i], rs[i], gam, inv_n, o, dg, db);
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) {
+                if (has_resid) ln_bwd_add_resid(o[j], rr[i][j]);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32, o[j]), rsD, (int)off[i][j], 0, 0);
+            }
+        }
+    }
+    __syncthreads();
+    float* sh = st;                           // [16 row groups][dgamma | dbeta][cols]
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        if (!cv[j]) continue;
+        reinterpret_cast<f32x4*>(sh + (rg * 2 + 0) * cols)[sub + 16 * j] = dg[j];
+        reinterpret_cast<f32x4*>(sh + (rg * 2 + 1) * cols)[sub + 16 * j] = db[j];
+    }
+    __syncthreads();
+    for (int c = t; c < 2 * cols; c += 256) {
+        float s = 0.f;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) s += sh[q * 2 * cols + c];
+        g.ln_part[(long)tile * 2 * cols + c] = s;
+    }
+}
+
 // NPL = 3: exact three-piece split, six products; NPL = 2: two-piece round-to-nearest split, three products (x3_split above)
 template <bool A_KC, bool B_KC, int WM, int WN, int WAVES_M, int WAVES_N, int EPI, int NPL = 3>
-__global__ __launch_bounds__(256) void gemm_x6_kernel(const GemmP g) {
+__device__ __forceinline__ void gemm_x6_body(const GemmP& g) {
     constexpr int BM = WAVES_M * WM * 32;
     constexpr int BN = WAVES_N * WN * 32;
     constexpr int PA = BM * X6_RS, PB = BN * X6_RS;
@@ -163,7 +266,7 @@ __global__ __launch_bounds__(256) void gemm_x6_kernel(const GemmP g) {
     StageRegs<B_KC ? BN : 32> sb;
     OffKC<A_KC ? BM : 32> oa; OffKC<B_KC ? BN : 32> ob;
     constexpr int TA = 2 * BM, TB0 = 256 - 2 * BN;
-    static_assert(TA <= 256 && TB0 >= 0, "tile too large for the k-strided task map");
+    static_assert((A_KC || TA <= 256) && (B_KC || TB0 >= 0), "tile too large for the k-strided task map");
     const bool has_a = !A_KC && t < TA, has_b = !B_KC && t >= TB0;
     const int kga = t & 7, mqa = t >> 3, kgb = (t - TB0) & 7, mqb = (t - TB0) >> 3;
     X6Blk ba, bb;
@@ -255,7 +358,25 @@ __global__ __launch_bounds__(256) void gemm_x6_kernel(const GemmP g) {
             }
         }
     }
-    gemm_epilogue<WM, WN, EPI>(g, acc, bm0 + wm0, bn0 + wn0, r, h, z);
+    if constexpr (EPI == EPI_LN_BWD) {
+        static_assert(A_KC && B_KC && WM == 1, "EPI_LN_BWD: NT GEMM, one accumulator row per wave");
+        x6_ln_bwd_epilogue<WN, WAVES_M, WAVES_N, (int)sizeof(lds)>(g, acc, lds, bm0, wm0, wn0, r, h, tm);
+    } else {
+        gemm_epilogue<WM, WN, EPI>(g, acc, bm0 + wm0, bn0 + wn0, r, h, z);
+    }
+}
+
+template <bool A_KC, bool B_KC, int WM, int WN, int WAVES_M, int WAVES_N, int EPI, int NPL = 3>
+__global__ __launch_bounds__(256) void gemm_x6_kernel(const GemmP g) {
+    gemm_x6_body<A_KC, B_KC, WM, WN, WAVES_M, WAVES_N, EPI, NPL>(g);
+}
+
+// The input-gradient GEMM with the LayerNorm backward in its epilogue (EPI_LN_BWD, one column tile of BN = the LayerNorm's
+// width), its own kernel so that it can ask for at least two workgroups per CU: 64 x 192 takes 160 VGPRs (three per CU),
+// 128 x 96 180 (two).  (128 x 192 would need more than 256: one workgroup per CU, or spills.)
+template <int WN, int WAVES_M, int WAVES_N, int NPL>
+__global__ __launch_bounds__(256, 2) void gemm_x6_ln_kernel(const GemmP g) {
+    gemm_x6_body<true, true, 1, WN, WAVES_M, WAVES_N, EPI_LN_BWD, NPL>(g);
 }
 
 }  // namespace vsom

@@ -1,6 +1,7 @@
 // LayerNorm forward / backward: one wave per token row, row held in registers, 16 B-free
 // scalar-coalesced accesses (rows are 4..1024 floats; E = 192 -> 3 values per lane).
 #include "gemm_f32.h"
+#include "layernorm_bwd.h"
 
 namespace vsom {
 
@@ -110,10 +111,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
 // decoder's 96 -> NCH = 2 with half of the second chunk masked): 16 lanes per row, 4 rows per wave,
 // each lane holds NCH float4 chunks (chunk j of lane l = columns 4 (l + 16 j) ..) -- four times the
 // bytes in flight per wave of the scalar kernels above.
-__device__ __forceinline__ float group16_sum(float v) {
-    v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 1, 64);
-    return v;
-}
+// (group16_sum and the backward's per-row body: layernorm_bwd.h)
 
 template <int NCH>
 __global__ __launch_bounds__(256) void layernorm_fwd_v4_kernel(const float* __restrict__ X, const float* __restrict__ gamma,
@@ -179,40 +177,25 @@ __global__ __launch_bounds__(256) void layernorm_bwd_v4_kernel(const float* __re
         const bool ok = row < rows;
         const long base = (long)(ok ? row : 0) * cols;
         const float mu = mean[ok ? row : 0], rs = rstd[ok ? row : 0];
-        f32x4 xh[NCH], g[NCH];
-        float s1 = 0.f, s2 = 0.f;
+        f32x4 d[NCH], xv[NCH], o[NCH];
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
-            f32x4 d = f32x4{0.f, 0.f, 0.f, 0.f}, xv = f32x4{mu, mu, mu, mu};
+            d[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            xv[j] = f32x4{mu, mu, mu, mu};
             if (cv[j]) {
-                xv = reinterpret_cast<const f32x4*>(X + base)[sub + 16 * j];
-                if (ok) d = reinterpret_cast<const f32x4*>(dY + base)[sub + 16 * j];
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                xh[j][e] = (xv[e] - mu) * rs;
-                g[j][e] = d[e] * gam[j][e];
-                s1 += g[j][e];
-                s2 = fmaf(g[j][e], xh[j][e], s2);
-                dg[j][e] = fmaf(d[e], xh[j][e], dg[j][e]);
-                db[j][e] += d[e];
+                xv[j] = reinterpret_cast<const f32x4*>(X + base)[sub + 16 * j];
+                if (ok) d[j] = reinterpret_cast<const f32x4*>(dY + base)[sub + 16 * j];
             }
         }
-        s1 = group16_sum(s1) * inv_n;
-        s2 = group16_sum(s2) * inv_n;
+        ln_bwd_row<NCH>(d, xv, mu, rs, gam, inv_n, o, dg, db);
         if (ok) {
 #pragma unroll
             for (int j = 0; j < NCH; ++j) {
                 if (!cv[j]) continue;
-                f32x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = rs * (g[j][e] - s1 - xh[j][e] * s2);
                 if (resid) {
-                    const f32x4 rr = reinterpret_cast<const f32x4*>(resid + base)[sub + 16 * j];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] += rr[e];
+                    ln_bwd_add_resid(o[j], reinterpret_cast<const f32x4*>(resid + base)[sub + 16 * j]);
                 }
-                reinterpret_cast<f32x4*>(dX + base)[sub + 16 * j] = o;
+                reinterpret_cast<f32x4*>(dX + base)[sub + 16 * j] = o[j];
             }
         }
     }

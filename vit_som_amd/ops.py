@@ -260,6 +260,27 @@ class LayerNormJobs:
         self.n += 1
         return dx
 
+    def bwd_linear_fused(self, dy, Wt, x, mean, rstd, gamma, resid, dx, dgamma, dbeta):
+        """dX of the Linear whose input-gradient GEMM (dy, Wt) feeds this LayerNorm's dY, in one launch
+        (linear_bwd_input_ln_partial); one job of the table, like `bwd`."""
+        rows, cols = x.shape
+        key = (ptr(dgamma), ptr(dbeta), rows, cols, "fused")
+        i = self.n
+        if i < len(self.keys) and self.keys[i] != key:
+            del self.keys[i:], self.rows_host[i:], self.parts[i:]
+            self.table = None
+        if i == len(self.keys):
+            nbytes = lib.vsom_linear_bwd_input_ln_partial_bytes(rows, cols)
+            part = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self.keys.append(key); self.parts.append(part)
+            self.rows_host.append([ptr(part), ptr(dgamma), ptr(dbeta), ((nbytes // (8 * cols)) << 32) | cols])
+            self.max_cols = max(self.max_cols, cols)
+            self.table = None
+        part = self.parts[i]
+        linear_bwd_input_ln_partial(dy, Wt, x, mean, rstd, gamma, resid, dx, part)
+        self.n += 1
+        return dx
+
     def flush(self):
         if self.n == self.flushed:
             return
@@ -272,6 +293,38 @@ class LayerNormJobs:
 
 def layernorm_bwd_deferrable(rows: int, cols: int) -> bool:
     return bool(lib.vsom_layernorm_bwd_deferrable(int(rows), int(cols)))
+
+
+# ---------------------------------------------------------------- input-gradient GEMM + LayerNorm backward
+def linear_bwd_input_ln_supported(rows: int, n: int, cols: int) -> bool:
+    """Whether linear_bwd_input_ln takes dY[rows, n] -> LayerNorm width `cols` in the current GEMM mode."""
+    return bool(lib.vsom_linear_bwd_input_ln_supported(int(rows), int(n), int(cols)))
+
+
+def _ln_fused_args(dy, Wt, x, mean, rstd, gamma, resid, dx):
+    M, N = dy.shape
+    K = Wt.shape[0]
+    for n_, t in (("dy", dy), ("Wt", Wt), ("x", x), ("dx", dx)):
+        _f32(t, n_)
+    assert Wt.shape[1] == N and Wt.is_contiguous() and x.shape == (M, K) == dx.shape and x.is_contiguous() and dx.is_contiguous()
+    assert resid is None or (resid.is_contiguous() and resid.shape == (M, K))
+    return (ptr(dy), _rows(dy), ptr(Wt), M, N, K, ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(resid), ptr(dx))
+
+
+def linear_bwd_input_ln(dy, Wt, x, mean, rstd, gamma, resid, dx, dgamma, dbeta):
+    """dx = resid + LayerNorm_bwd(dy Wt^T) with dgamma / dbeta, in one GEMM launch plus the column reduction: bit for bit
+    linear_bwd_input_t into scratch followed by layernorm_bwd for dx; dgamma / dbeta to rounding."""
+    args = _ln_fused_args(dy, Wt, x, mean, rstd, gamma, resid, dx)
+    ws = scratch(lib.vsom_linear_bwd_input_ln_partial_bytes(x.shape[0], x.shape[1]), x.device)
+    check(lib.vsom_linear_bwd_input_ln(*args, ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream()), "vsom_linear_bwd_input_ln")
+    return dx
+
+
+def linear_bwd_input_ln_partial(dy, Wt, x, mean, rstd, gamma, resid, dx, part):
+    """The same leaving the dgamma / dbeta partials in `part` for layernorm_bwd_finish_many (LayerNormJobs)."""
+    args = _ln_fused_args(dy, Wt, x, mean, rstd, gamma, resid, dx)
+    check(lib.vsom_linear_bwd_input_ln_partial(*args, ptr(part), part.numel(), stream()), "vsom_linear_bwd_input_ln_partial")
+    return dx
 
 
 # ---------------------------------------------------------------- attention

@@ -20,6 +20,8 @@ class _Hooks:
                                 # step, but the contraction then shares the chip (72 instead of 58-63 us per launch) -- off: it runs alone
     launch_tape = True          # train_step_fused / training_step re-issue the recorded launches of a step from C (step.py)
     cls_prune = True            # ViTClassifier: the last encoder block on the CLS rows only (classifier.py); False: in full
+    ln_bwd_fused = True         # the block LayerNorm backwards (norm2, norm1) in the epilogue of the input-gradient GEMM that feeds
+                                # them (vit.py _block_bwd, ops.linear_bwd_input_ln); False: GEMM into scratch + layernorm_bwd
 
     def set(self, **kw):
         for k, v in kw.items():

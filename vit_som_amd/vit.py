@@ -417,6 +417,19 @@ class ViTAutoencoder(nn.Module):
             return jobs.bwd(dy, x, mean, rstd, gamma, resid, dx, dgamma, dbeta)
         return ops.layernorm_bwd(dy, x, mean, rstd, gamma, resid, dx, dgamma, dbeta)
 
+    def _dx_ln(self, WT, dy, weight, da, x, mean, rstd, gamma, resid, dx, dgamma, dbeta):
+        """dX of a Linear, then the backward of the LayerNorm whose output fed it: one launch (the LayerNorm backward in
+        the GEMM's epilogue, the product never stored) where the transposed weight copy, the shape and the GEMM mode allow
+        it (hooks.ln_bwd_fused), else the GEMM into the scratch `da` and _ln_bwd.  Same dX bits either way."""
+        wt = WT(weight) if (WT is not None and hooks.ln_bwd_fused) else None
+        if wt is not None and ops.linear_bwd_input_ln_supported(dy.shape[0], dy.shape[1], x.shape[1]):
+            jobs = self.__dict__.get("_ln_jobs")
+            if jobs is not None:
+                return jobs.bwd_linear_fused(dy, wt, x, mean, rstd, gamma, resid, dx, dgamma, dbeta)
+            return ops.linear_bwd_input_ln(dy, wt, x, mean, rstd, gamma, resid, dx, dgamma, dbeta)
+        self._dx(WT, dy, weight, da)
+        return self._ln_bwd(da, x, mean, rstd, gamma, resid, dx, dgamma, dbeta)
+
     def _block_bwd(self, blk: Block, L: _Acts, x_in, gout, a: _Acts, G, prefix: str, bufs, WT=None, parity: int = 0):
         """gout: gradient w.r.t. the block output [T,dim]; returns gradient w.r.t. x_in (in bufs)."""
         T, dim, hid = a.T, blk.dim, blk.hidden
@@ -428,16 +441,14 @@ class ViTAutoencoder(nn.Module):
         self._dw(gout, L.hact, G(f"{prefix}.mlp.2.weight"), G(f"{prefix}.mlp.2.bias"))
         self._dx(WT, gout, blk.mlp["2"].weight, dh, gelu_grad=L.hpre)
         self._dw(dh, L.a2, G(f"{prefix}.mlp.0.weight"), G(f"{prefix}.mlp.0.bias"))
-        self._dx(WT, dh, blk.mlp["0"].weight, da)
-        self._ln_bwd(da, L.x1, L.mean2, L.rstd2, blk.norm2.weight, gout, g1, G(f"{prefix}.norm2.weight"),
-                          G(f"{prefix}.norm2.bias"))
+        self._dx_ln(WT, dh, blk.mlp["0"].weight, da, L.x1, L.mean2, L.rstd2, blk.norm2.weight, gout, g1,
+                    G(f"{prefix}.norm2.weight"), G(f"{prefix}.norm2.bias"))
         self._dw(g1, L.ao, G(f"{prefix}.attn.proj.weight"), G(f"{prefix}.attn.proj.bias"))
         self._dx(WT, g1, blk.attn.proj.weight, da)
         ops.attention_bwd(L.qkv, L.ao, da, L.lse, dqkv, a.delta, a.B, a.N, blk.heads, dim // blk.heads)
         self._dw(dqkv, L.a1, G(f"{prefix}.attn.qkv.weight"), G(f"{prefix}.attn.qkv.bias"))
-        self._dx(WT, dqkv, blk.attn.qkv.weight, da)
-        self._ln_bwd(da, x_in, L.mean1, L.rstd1, blk.norm1.weight, g1, g0, G(f"{prefix}.norm1.weight"),
-                          G(f"{prefix}.norm1.bias"))
+        self._dx_ln(WT, dqkv, blk.attn.qkv.weight, da, x_in, L.mean1, L.rstd1, blk.norm1.weight, g1, g0,
+                    G(f"{prefix}.norm1.weight"), G(f"{prefix}.norm1.bias"))
         self._side_mark()
         return g0
 
