@@ -3,8 +3,9 @@
 
 Layers, lowest first: ``_lib`` / ``ops`` (the C-ABI), ``arena``, ``tuning`` and ``_base``; ``vit``
 (ViTAutoencoder) and ``som`` (SOMLayer); ``optim`` (FusedAdamW) and ``step`` (the fused step's
-machinery shared by every arena-owning model); ``model`` (ViTSOM) and ``desom`` (DESOM), two peers;
-``classifier`` (ViTClassifier, the plain ViT baseline)."""
+machinery shared by every arena-owning model); ``vit_owner`` (what the two ViT models share);
+``model`` (ViTSOM), ``classifier`` (ViTClassifier, the plain ViT baseline) and ``desom`` (DESOM),
+three peers."""
 from . import _lib  # noqa: F401  (fails loudly when libvitsom_hip.so is absent)
 from . import ops  # noqa: F401
 from .vit import ViTAutoencoder  # noqa: F401,E402

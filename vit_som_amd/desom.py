@@ -18,7 +18,7 @@ from ._base import _HAVE_PL, _Acts, _Base
 from .arena import ParamArena
 from .optim import FusedAdamW
 from .som import SOMLayer
-from .step import _ArenaOwner, _StepLoss
+from .step import _ArenaOwner
 
 
 class Autoencoder(nn.Module):
@@ -75,9 +75,7 @@ class DESOM(_ArenaOwner, _Base):
         self._it = 0
         self._last: Dict[str, torch.Tensor] = {}
         self._bufs: Optional[_Acts] = None
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        self._pack(torch.device(device))
+        self._pack(self._default_device(device))
 
     # FusedAdamW protocol (the reference's Adam has no weight decay: _default_weight_decay stays 0)
     def _decoder_param_names(self):
@@ -256,9 +254,7 @@ class DESOM(_ArenaOwner, _Base):
         """desom.py:58-74.  Returns a scalar tensor; ``.backward()`` runs the HIP backward."""
         x, y = batch
         self.update()
-        if self._anchor is None:
-            self._anchor = torch.zeros((), device=self.arena.device, requires_grad=True)
-        return _StepLoss.apply(self._anchor, self, x, y, self.gamma, float(self.som_layer.current_temperature))
+        return self._step_loss(x, y, self.gamma, float(self.som_layer.current_temperature))
 
     def train_step_fused(self, x, y):
         """Same step without the autograd bridge (the caller then runs optimizer.step())."""

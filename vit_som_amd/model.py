@@ -10,113 +10,41 @@ names, positional return tuples / dtypes and ``state_dict`` keys:
   SOMLayer        models/som_layer.py:8-152  forward / compute_distances / update_temperature /
                                              compute_weights / som_loss / index_to_position (som.py)
 
-FusedAdamW and param_groups_lrd live in optim.py; the fused step's autograd bridge, launch tape
-and arena owner, shared with DESOM, in step.py.  All arithmetic runs in libvitsom_hip.so
-(hand-written gfx950 kernels) through ``ops``; these files only own memory (flat parameter
-arenas, activation buffers), ordering, schedules and the data-parallel exchange (one RCCL
-all-reduce over the gradient arena).  There is no CPU path.
+What ViTSOM shares with ViTClassifier (the ViT, its W^T copies, streams, encoder buckets, the
+backward's frame, optimizer and checkpoints) lives in vit_owner.py; FusedAdamW and
+param_groups_lrd in optim.py; the fused step's autograd bridge, launch tape and arena owner,
+shared with DESOM, in step.py.  All arithmetic runs in libvitsom_hip.so (hand-written gfx950
+kernels) through ``ops``; these files only own memory (flat parameter arenas, activation
+buffers), ordering, schedules and the data-parallel exchange (one RCCL all-reduce over the
+gradient arena).  There is no CPU path.
 """
-import math
-import os
-from typing import Dict, Optional
-
 import torch
 
 from . import ops
-from ._base import _HAVE_PL, _Acts, _Base
-from ._lib import Event, on_stream, stream_wait_stream
-from .arena import ParamArena
-from .optim import FusedAdamW, param_groups_lrd
+from ._base import _HAVE_PL, _Acts
+from ._lib import Event, on_stream
 from .som import SOMLayer
-from .step import _ArenaOwner, _StepLoss, _StepTape
+from .step import _StepTape
 from .tuning import hooks
-from .vit import ViTAutoencoder, _Affine
-
-_LOSS_RING = 16     # the loss terms of a step stay readable until this many further steps have run
-_STEP_STREAMS: Dict[int, tuple] = {}        # device index -> (side stream, SOM stream), shared by every model of the process
+from .vit_owner import _ViTOwner
 
 
 # ------------------------------------------------------------------------------------ ViT-SOM
-class ViTSOM(_ArenaOwner, _Base):
+class ViTSOM(_ViTOwner):
     """Vision Transformer Self-Organizing Map (models/vit_som.py:17-187), MI355X-native."""
 
     def __init__(self, config, device=None):
-        super().__init__()
-        # NOTE: unlike vit_som.py:23 this does NOT lower torch's global float32 matmul precision:
-        # every contraction here is exact fp32 on MFMA (SURVEY.md fact 5).
-        self.config = config
-        if _HAVE_PL:
-            self.save_hyperparameters(config)
-        hp, data_hp = config["hyperparameters"], config["data"]
-        vit_hp, opt_hp, som_hp = hp["vit"], hp["optimizer"], hp["som"]
+        super().__init__(config)
+        hp = config["hyperparameters"]
         self.gamma = hp["gamma"]
-        self.use_reduced = som_hp["use_reduced"]
-        self.classification = data_hp["num_classes"] > 0
-        self.vit = ViTAutoencoder(
-            img_size=data_hp["input_size"], patch_size=vit_hp["patch_size"], in_chans=data_hp["num_channels"],
-            embed_dim=vit_hp["emb_dim"], depth=vit_hp["depth"], num_heads=vit_hp["heads"],
-            decoder_embed_dim=vit_hp["dec_emb_dim"], decoder_depth=vit_hp["dec_depth"],
-            decoder_num_heads=vit_hp["heads"], mlp_ratio=vit_hp["mlp_ratio"], eps=1e-6)
+        self.use_reduced = hp["som"]["use_reduced"]
+        self.classification = config["data"]["num_classes"] > 0
         self.som_layer = SOMLayer(config)
         if self.classification:
-            self.cls_head = _Affine((data_hp["num_classes"], vit_hp["emb_dim"]), (data_hp["num_classes"],))
-            with torch.no_grad():
-                self.cls_head.weight.normal_(std=0.02)
-                bound = 1.0 / math.sqrt(vit_hp["emb_dim"])
-                self.cls_head.bias.uniform_(-bound, bound)
-        self.smoothing = float(opt_hp["smoothing"])
+            self._add_cls_head()
+        self.smoothing = float(hp["optimizer"]["smoothing"])
         self.register_buffer("iteration", torch.tensor(0))
-        self._it = 0
-        self._n_train: Optional[int] = None
-        self._est_steps: Optional[int] = None
-        self.world_size, self.rank = 1, 0
-        self._grads_reduced = False
-        self._forward_id, self._seeds_consumed = 0, False
-        self._last: Dict[str, torch.Tensor] = {}
-        self.arena: Optional[ParamArena] = None
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        self._pack(torch.device(device))
-
-    # -- arenas -------------------------------------------------------------------------------
-    def _default_weight_decay(self, name: str, p) -> float:
-        if name.startswith("vit."):
-            return 0.0 if p.ndim == 1 else 0.05
-        return 0.01
-
-    def _after_pack(self):
-        self._build_weight_transposes()
-
-    def _decoder_param_names(self):
-        return [n for n, _ in self._named_trainable() if n.startswith("vit.decoder_")]
-
-    def _build_weight_transposes(self):
-        """Transposed copies W^T of the ViT Linear weights whose input gradient is needed, so that
-        dX = dY W runs on the forward's kernel family (both operands contiguous along the reduction).
-        One flat buffer + a device table; refreshed by ONE batched transpose per backward pass."""
-        arena, dev = self.arena, self.arena.device
-        rows, views, off = [], {}, 0
-        for n, p in self._named_trainable():
-            if not (n.startswith("vit.") and p.ndim == 2 and n.endswith(".weight")) or "patch_embed" in n:
-                continue
-            N, K = p.shape
-            if N % 4 or K % 4:
-                continue
-            src = (arena.p(n).data_ptr() - arena.params.data_ptr()) // 4
-            rows.append((src, off, N, K))
-            views[arena.p(n).data_ptr()] = (off, K, N)
-            off += -(-N * K // 64) * 64
-        self._wt_flat = torch.empty(max(off, 1), dtype=torch.float32, device=dev)
-        self._wt_table = torch.tensor(rows, dtype=torch.int64, device=dev).view(-1, 4) if rows else None
-        self._wt_views = {k: self._wt_flat[o:o + a * b].view(a, b) for k, (o, a, b) in views.items()}
-        self._wt_max = (max(r[2] for r in rows), max(r[3] for r in rows)) if rows else (1, 1)
-
-    def _refresh_weight_transposes(self):
-        if self._wt_table is not None and self._wt_flat.is_cuda:
-            ops.transpose_many(self.arena.params, self._wt_flat, self._wt_table, *self._wt_max)
-
-    def _WT(self, weight):
-        return self._wt_views.get(weight.data_ptr())
+        self._pack(self._default_device(device))
 
     # -- schedules ----------------------------------------------------------------------------
     def set_schedule(self, n_train: int, estimated_stepping_batches: int):
@@ -138,22 +66,12 @@ class ViTSOM(_ArenaOwner, _Base):
         ramp_up_end_step = self._estimated_steps() // 2
         return self.config["hyperparameters"]["gamma"] * min(1.0, self._it / ramp_up_end_step)
 
-    def _log(self, *a, **k):
-        """self.log / self.log_dict when a Lightning trainer is attached (vit_som.py:95-101); a no-op otherwise.
-        Errors raised by Lightning's logger propagate."""
-        if _HAVE_PL and getattr(self, "_trainer", None) is not None:
-            self.log_dict(*a, **k) if isinstance(a[0], dict) else self.log(*a, **k)
-
     # -- fused forward + losses ---------------------------------------------------------------
     def _som_input(self, a: _Acts):
         E, N, B = self.vit.embed_dim, a.N, a.B
         if self.use_reduced:
             return torch.as_strided(a.xe, (B, E), (N * E, 1), a.xe.storage_offset())
         return torch.as_strided(a.xe, (B, (N - 1) * E), (N * E, 1), a.xe.storage_offset() + E)
-
-    def _cls_view(self, buf: torch.Tensor, a: _Acts):
-        E = self.vit.embed_dim
-        return torch.as_strided(buf, (a.B, E), (a.N * E, 1), buf.storage_offset())
 
     @torch.no_grad()
     def _run_forward(self, x, need_decoder: bool, fresh_w: bool = False):
@@ -224,22 +142,14 @@ class ViTSOM(_ArenaOwner, _Base):
     def _call_parts(self, a: _Acts, s: _Acts, gamma_t: float, T: float, B: int, numel_x: int, want_grad: bool):
         # total = main + gamma_t * som (and the two terms by themselves, for logging) from the two device-side sums, in one
         # tiny kernel that also advances the `iteration` buffer of a training step (vit_som.py:104): no ATen kernel in
-        # the step.  The three values land in their own slot of a small ring, so `_last` and the returned loss stay
-        # valid for the next _LOSS_RING - 1 steps (plain tensors: .get / `in` / iteration / ** all see them).
+        # the step.  The three values land in their own slot of the loss ring.
         K = self.som_layer.n_prototypes
         main_scale = 1.0 / B if self.classification else 1.0 / numel_x
-        a.loss_slot = (a.loss_slot + 1) % _LOSS_RING
-        parts = a.loss_ring[a.loss_slot]
+        parts = self._next_loss_slot(a)
         ops.loss_parts(parts, a.main_sum, main_scale, s.loss_sum, gamma_t / (B * K), 1.0 / (B * K),
                        counter=self.iteration if want_grad else None)
         self._last = {"total": parts[0], "main": parts[1], "som": parts[2], "gamma_t": gamma_t, "T": T}
         return parts[0]
-
-    def _loss_buffers(self, a: _Acts, dev):
-        if not hasattr(a, "main_sum"):
-            a.main_sum = torch.empty(1, dtype=torch.float32, device=dev)
-            a.loss_ring = torch.zeros(_LOSS_RING, 4, dtype=torch.float32, device=dev)
-            a.loss_slot = 0
 
     @torch.no_grad()
     def _forward_losses(self, x, y, gamma_t: float, T: float, want_grad: bool):
@@ -267,20 +177,6 @@ class ViTSOM(_ArenaOwner, _Base):
             total = self._call_parts(a, s, gamma_t, T, B, x.numel(), want_grad)
         return total
 
-    def _ensure_streams(self, device):
-        """The two extra HIP streams of the step (kept to two: a process has few hardware queues)."""
-        if getattr(self, "_side_stream", None) is None or self._side_stream.device != device:
-            # one pair per device for the whole process: which hardware queue a stream lands on depends on how many
-            # streams the process has created, and two of a model's streams on one queue serialise (measured: the 3rd, 5th
-            # ... model of a process ran its step 1.4x slower at batch 128)
-            key = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
-            pair = _STEP_STREAMS.get(key)
-            if pair is None:
-                pair = _STEP_STREAMS[key] = (torch.cuda.Stream(device=device), torch.cuda.Stream(device=device))
-            self._side_stream = pair[0]      # weight-gradient GEMMs; second forward chain
-            self._som_stream = pair[1]       # SOM backward + early all-reduce; the prototypes' plane image in the forward
-        self.vit.__dict__["_lent_stream"] = self._side_stream
-
     @torch.no_grad()
     def _scale_seeds(self, gout):
         """Multiply the loss-side gradient seeds by the scalar `gout` (a 0-dim device tensor)."""
@@ -289,60 +185,25 @@ class ViTSOM(_ArenaOwner, _Base):
         for buf in ((s.coef, s.row_dot, s.col_dot) + ((a.dlogits,) if self.classification else (a.dpred,))):
             ops.scale_by(buf, gout)
 
-    def _exchange_buckets(self):
-        """Arena slices reduced early, in the order the backward finishes them: name -> (lo, hi)."""
-        b = self.__dict__.get("_bucket_cache")
-        if b is not None and b[0] is self.arena:
-            return b[1]
-        names = [n for n, _ in self._named_trainable()]
+    def _head_buckets(self):
+        """The prototypes, then (clustering only: in classification mode its gradients are zero) the decoder."""
         out = {"som": (self.arena.offsets["som_layer.prototypes"][0], self.arena.numel)}
-        dec = [n for n in names if n.startswith("vit.decoder_")]
+        dec = self._decoder_param_names()
         if dec and not self.classification:
             out["decoder"] = self._arena_span(dec[0], dec[-1])
-        D = len(self.vit.blocks)
-        step = max(1, int(hooks.bucket_blocks))
-        hi_name = "vit.norm.bias"
-        for i in range(D - step, 0, -step):                 # blocks [i, i + step) (+ the final norm for the top bucket)
-            out[f"enc{i}"] = self._arena_span(f"vit.blocks.{i}.norm1.weight", hi_name)
-            hi_name = f"vit.blocks.{i - 1}.mlp.2.bias"
-        self.__dict__["_bucket_cache"] = (self.arena, out)
         return out
 
-    @torch.no_grad()
-    def _backward(self):
-        """All backward kernels; overwrites the whole gradient arena (no accumulation)."""
-        x, a, s = self._ctx
-        self._grads_reduced = False
-        self._exchange_reset()
-        if x.is_cuda and hooks.side_stream:
-            self._ensure_streams(x.device)
-            self.vit._side = self._side_stream
-        else:
-            self.vit._side = None
-        Gv = self._G("vit.")
-        self._refresh_weight_transposes()
-        # the LayerNorm backwards leave their dgamma / dbeta reductions to one launch per exchange piece (or one in all)
-        jobs = None
-        if x.is_cuda and hooks.ln_reduce_batched:
-            jobs = a.__dict__.get("ln_jobs")
-            if jobs is None:
-                jobs = a.ln_jobs = ops.LayerNormJobs(x.device)
-            jobs.begin()
-        self.vit.__dict__["_ln_jobs"] = jobs
-        try:
-            self._backward_body(x, a, s, Gv, jobs)
-        finally:
-            self.vit.__dict__["_ln_jobs"] = None
+    def _head_params(self):
+        return list(self.som_layer.parameters()) + (list(self.cls_head.parameters()) if self.classification else [])
 
-    def _backward_body(self, x, a, s, Gv, jobs):
+    def _head_backward(self, a, s, Gv, reduce):
+        """The SOM, decoder and cls_head backwards; leaves dL/d(xe) in a.d_xe for the whole encoder."""
         X = self._som_input(a)
         E, N = self.vit.embed_dim, a.N
         if self.use_reduced:
             gX = torch.as_strided(a.d_xe, (a.B, E), (N * E, 1), a.d_xe.storage_offset())
         else:
             gX = torch.as_strided(a.d_xe, (a.B, (N - 1) * E), (N * E, 1), a.d_xe.storage_offset() + E)
-        buckets = self._exchange_buckets() if self._overlap_enabled() else {}
-        main = torch.cuda.current_stream() if x.is_cuda else None
 
         def som_backward(gx_out, accumulate):
             if self.som_layer._dist_mode == ops.DIST_MANHATTAN:
@@ -352,31 +213,19 @@ class ViTSOM(_ArenaOwner, _Base):
                 ops.som_bwd(X, self.som_layer.prototypes, s.coef, s.row_dot, s.col_dot,
                             self._grad_views["som_layer.prototypes"], gx_out, accumulate_gx=accumulate)
 
-        def streams_now():
-            return [st for st in (main, self.vit._side) if st is not None]
-
-        def flush():
-            if jobs is not None:
-                jobs.flush()
-
         side = self._som_stream if self.vit._side is not None else None
         if self.classification or side is None:
             if self.classification:
                 ops.fill(a.d_xe, 0.0)
-                # decoder is unused by the classification loss: its gradients are exactly zero
-                for n in self._decoder_param_names():
-                    ops.fill(self._grad_views[n], 0.0)
+                self._zero_decoder_grads()
                 ops.linear_bwd_weight(a.dlogits, self._cls_view(a.xe, a), self._grad_views["cls_head.weight"],
                                       self._grad_views["cls_head.bias"])
                 ops.linear_bwd_input(a.dlogits, self.cls_head.weight, self._cls_view(a.d_xe, a), accumulate=True)
             else:
                 self.vit._decoder_bwd(a, Gv, self._WT)
-                if "decoder" in buckets:
-                    flush()
-                    self._reduce_early(*buckets["decoder"], streams=streams_now())
+                reduce("decoder")
             som_backward(gX, True)
-            if "som" in buckets:
-                self._reduce_early(*buckets["som"], streams=streams_now())
+            reduce("som")
         else:
             # The SOM backward depends only on the forward (coef, X, W), so it runs on a stream of its
             # own under the decoder backward and writes its input gradient straight into (the zeroed)
@@ -387,8 +236,7 @@ class ViTSOM(_ArenaOwner, _Base):
             with on_stream(side):
                 ops.fill(a.d_xe, 0.0)
                 som_backward(gX, False)
-            if "som" in buckets:
-                self._reduce_early(*buckets["som"], streams=[side])
+            reduce("som", [side])
             # a dedicated event: its wait is deferred to the end of the decoder backward, by which time a pooled
             # (round-robin) event could have been re-recorded for something else (deep decoders)
             som_done = self.__dict__.get("_som_done_ev")
@@ -396,23 +244,9 @@ class ViTSOM(_ArenaOwner, _Base):
                 som_done = self.__dict__["_som_done_ev"] = Event()
             som_done.record(side)
             self.vit._decoder_bwd(a, Gv, self._WT, before_dxe=lambda: som_done.wait())
-            if "decoder" in buckets:
-                flush()
-                self._reduce_early(*buckets["decoder"], streams=streams_now())
+            reduce("decoder")
+        return None
 
-        def on_block(i):
-            b = buckets.get(f"enc{i}")
-            if b is not None:
-                flush()
-                self._reduce_early(*b, streams=streams_now())
-
-        self.vit._encoder_bwd(a, Gv, self._WT, on_block if buckets else None)
-        flush()
-        if self.vit._side is not None:
-            stream_wait_stream(None, self.vit._side)     # every gradient is final from here on
-            self.vit.__dict__.setdefault("_side_pending", []).clear()
-
-    # -- data-parallel exchange ----------------------------------------------------------------
     # -- reference API ---------------------------------------------------------------------------
     def _schedules_for_step(self):
         self.som_layer.update_temperature(self._it)                     # vit_som.py:84 (iteration BEFORE increment)
@@ -426,9 +260,7 @@ class ViTSOM(_ArenaOwner, _Base):
         x, y = batch
         self._estimated_steps()
         gamma_t, T = self._schedules_for_step()
-        if self._anchor is None:
-            self._anchor = torch.zeros((), device=self.arena.device, requires_grad=True)
-        total = _StepLoss.apply(self._anchor, self, x, y, gamma_t, T)
+        total = self._step_loss(x, y, gamma_t, T)
         self._advance()
         if _HAVE_PL and getattr(self, "_trainer", None) is not None:          # vit_som.py:91,95-102
             main = "train/cls_loss" if self.classification else "train/recon_loss"
@@ -463,65 +295,6 @@ class ViTSOM(_ArenaOwner, _Base):
                 logs["val/accuracy"] = self._last["acc"]
             self._log(logs)
         return total.clone()
-
-    def configure_optimizers(self):
-        """vit_som.py:127-163: AdamW/Adam (lr * batch_size / 256), reference param groups, per-epoch
-        LambdaLR with the warm-up / cosine multiplier floored at min_lr."""
-        hp = self.config["hyperparameters"]
-        opt_hp = hp["optimizer"]
-        groups = param_groups_lrd(self.vit, weight_decay=opt_hp["weight_decay"], layer_decay=opt_hp["layer_decay"])
-        other = list(self.som_layer.parameters())
-        if self.classification:
-            other.extend(list(self.cls_head.parameters()))
-        groups.append({"params": other})
-        if opt_hp["type"] not in ("adamw", "adam"):
-            raise ValueError(f"unsupported optimizer type {opt_hp['type']!r}")
-        optimizer = FusedAdamW(self, groups, lr=opt_hp["lr"] * hp["batch_size"] / 256,
-                               betas=(opt_hp["beta_1"], opt_hp["beta_2"]), adamw=(opt_hp["type"] == "adamw"))
-        if opt_hp["scheduler"] != "cosine_annealing":
-            raise ValueError(f"unsupported scheduler {opt_hp['scheduler']!r}")
-        lr_func = lambda epoch: max(opt_hp["min_lr"], min((epoch + 1) / (opt_hp["warmup_epochs"] + 1e-8),   # noqa: E731
-                                                           0.5 * (math.cos(epoch / hp["total_epochs"] * math.pi) + 1)))
-        scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lr_lambda=lr_func)
-        return [optimizer], [scheduler]
-
-    # -- checkpoints: Lightning's .ckpt layout (SURVEY 8(f) N3) --------------------------------------
-    def save_checkpoint(self, path, optimizer=None, scheduler=None, epoch=0, global_step=None):
-        """Write a file with the keys a Lightning ModelCheckpoint writes (train_vit_som.py:81-84):
-        state_dict (reference key names), hyper_parameters (= the config dict, vit_som.py:26),
-        optimizer_states / lr_schedulers, epoch, global_step."""
-        ckpt = {
-            "epoch": int(epoch), "global_step": int(self._it if global_step is None else global_step),
-            "pytorch-lightning_version": "2.2.1", "hparams_name": "config",
-            "state_dict": {k: v.detach().cpu().clone() for k, v in self.state_dict().items()},
-            "hyper_parameters": self.config,
-            "optimizer_states": [optimizer.state_dict()] if optimizer is not None else [],
-            "lr_schedulers": [scheduler.state_dict()] if scheduler is not None else [],
-        }
-        for st in ckpt["optimizer_states"]:
-            for s in st["state"].values():
-                for k2 in ("exp_avg", "exp_avg_sq"):
-                    s[k2] = s[k2].cpu()
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        torch.save(ckpt, path)
-        return path
-
-    @classmethod
-    def load_from_checkpoint(cls, checkpoint_path, config=None, device=None, map_location=None):
-        """ViTSOM.load_from_checkpoint(path, config=config) (train_vit_som.py:111).  Only loaders
-        that execute nothing from the file are used (torch.load(weights_only=True))."""
-        ckpt = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
-        if config is None:
-            config = ckpt.get("hyper_parameters")
-            if config is None:
-                raise ValueError("checkpoint carries no hyper_parameters; pass config=")
-        model = cls(config, device=device)
-        model.load_state_dict(ckpt["state_dict"])
-        model._loaded_checkpoint = ckpt
-        return model
-
-    def on_train_end(self):                                             # vit_som.py:165-172
-        print(f"Peak GPU memory usage: {torch.cuda.max_memory_allocated() / 1e9:.4f} GB")
 
     def get_latent_representation(self, x):
         """vit_som.py:174-187 (the reference unpacks 4 of 3 values; this returns what it meant)."""

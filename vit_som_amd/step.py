@@ -192,6 +192,19 @@ class _ArenaOwner:
     def _after_pack(self):
         pass
 
+    @staticmethod
+    def _default_device(device=None) -> torch.device:
+        """`device`, else the current GPU when there is one, else the CPU."""
+        if device is not None:
+            return torch.device(device)
+        return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+
+    def _step_loss(self, x, y, gamma_t: float, T: float):
+        """A training step through the autograd bridge: its loss as a scalar whose .backward() runs the HIP backward."""
+        if self._anchor is None:
+            self._anchor = torch.zeros((), device=self.arena.device, requires_grad=True)
+        return _StepLoss.apply(self._anchor, self, x, y, gamma_t, T)
+
     def _step(self, x, y, gamma_t: float, T: float):
         """Forward + losses of a training step -> (total, backward); backward(gout=None) fills the gradient arena."""
         def backward(gout=None):
