@@ -10,7 +10,8 @@ the build container by ``oracle/gen_golden.py`` (reference modules imported unmo
 /root/reference) and committed as arrays under ``tests/golden/*.npz``
 (``tests/test_oracle_golden.py``).  The only third-party arithmetic on the path that is NOT in
 /root/reference is timm's ``PatchEmbed`` (version unpinned by the reference); it is restated
-here as ``Conv2d(k=s=p) -> flatten(2).transpose(1,2)`` per its published behaviour and that
+here as ``Conv2d(k=s=p) -> flatten(2).transpose(1,2)`` per its published behaviour (computed as
+the equivalent patchify + matmul) and that
 single boundary is "parity unpinned" (see DESIGN.md).
 
 Every function cites the reference file:line it follows (paths relative to /root/reference).
@@ -241,9 +242,14 @@ def unpatchify(x: torch.Tensor, p: int) -> torch.Tensor:
 
 def patch_embed(P: Params, x: torch.Tensor, p: int) -> torch.Tensor:
     """timm PatchEmbed as used at vit.py:76,207: Conv2d(C,E,k=p,s=p,bias) -> flatten(2) ->
-    transpose(1,2).  (third-party, unpinned: restated from published behaviour)"""
-    y = F.conv2d(x, P["vit.patch_embed.proj.weight"], P["vit.patch_embed.proj.bias"], stride=p)
-    return y.flatten(2).transpose(1, 2)
+    transpose(1,2).  (third-party, unpinned: restated from published behaviour)
+
+    A convolution with kernel == stride is a matmul of the patches with the flattened kernel; written that way (the
+    kernel's [E, C, p, p] reordered to patchify's (p, q, c) column order) it runs in any dtype on any device -- float64
+    on the GPU included, which the convolution libraries do not all provide."""
+    W = P["vit.patch_embed.proj.weight"]
+    Wf = W.permute(0, 2, 3, 1).reshape(W.shape[0], -1)
+    return F.linear(patchify(x, p), Wf, P["vit.patch_embed.proj.bias"])
 
 
 def vit_forward(P: Params, x: torch.Tensor, d: Dims):
@@ -365,11 +371,16 @@ def gamma_ramp(gamma: float, iteration: int, estimated_stepping_batches: int) ->
     return gamma * min(1.0, iteration / ramp_up_end_step)
 
 
-def training_loss(P: Params, x, y, d: Dims, iteration: int, n_train: int, est_steps: int):
-    """ViTSOM.training_step, vit_som.py:80-105.  Returns (total, dict of parts)."""
-    cls, recon, logits, dist, bmu = forward(P, x, d)
+def training_loss(P: Params, x, y, d: Dims, iteration: int, n_train: int, est_steps: int, bmu=None):
+    """ViTSOM.training_step, vit_som.py:80-105.  Returns (total, dict of parts).
+
+    bmu: optional [B] indices the neighbourhood is built from instead of the oracle's own argmin -- a caller comparing
+    a step with this oracle passes the step's BMU, so that an fp32 near-tie resolved the other way does not change what
+    is compared.  parts["bmu"] is always the oracle's own argmin (the BMU policy is checked on it separately)."""
+    cls, recon, logits, dist, own_bmu = forward(P, x, d)
     T = temperature(iteration, d.Tmax, d.Tmin, n_train, d.batch_size, d.total_epochs)   # :84
-    h = neighbourhood(bmu, P["som_layer.grid_positions"], T)                            # :85
+    h_bmu = own_bmu if bmu is None else torch.as_tensor(bmu).to(device=dist.device, dtype=torch.int64)
+    h = neighbourhood(h_bmu, P["som_layer.grid_positions"], T)                          # :85
     ls = som_loss(h, dist)                                                              # :86
     g = gamma_ramp(d.gamma, iteration, est_steps)
     if d.classification:
@@ -377,7 +388,7 @@ def training_loss(P: Params, x, y, d: Dims, iteration: int, n_train: int, est_st
     else:
         main = F.l1_loss(recon, x)                                                      # :100
     total = main + g * ls
-    return total, {"main": main, "som": ls, "gamma_t": g, "T": T, "bmu": bmu, "dist": dist,
+    return total, {"main": main, "som": ls, "gamma_t": g, "T": T, "bmu": own_bmu, "dist": dist,
                    "cls": cls, "recon": recon, "logits": logits, "h": h}
 
 
@@ -394,12 +405,12 @@ def validation_loss(P: Params, x, y, d: Dims, T: float):
     return main + d.gamma * ls, {"main": main, "som": ls, "acc": acc, "bmu": bmu}
 
 
-def loss_and_grads(P: Params, x, y, d: Dims, iteration: int, n_train: int, est_steps: int):
+def loss_and_grads(P: Params, x, y, d: Dims, iteration: int, n_train: int, est_steps: int, bmu=None):
     """Autograd of training_loss w.r.t. every trainable parameter (what Lightning's
     loss.backward() produces).  Parameters unused by the loss (the decoder in
-    classification mode) get a zero gradient here."""
+    classification mode) get a zero gradient here.  bmu: see training_loss."""
     Q = {k: (v.detach().clone().requires_grad_(True) if k not in FROZEN else v) for k, v in P.items()}
-    total, parts = training_loss(Q, x, y, d, iteration, n_train, est_steps)
+    total, parts = training_loss(Q, x, y, d, iteration, n_train, est_steps, bmu=bmu)
     keys = trainable_keys(Q)
     grads = torch.autograd.grad(total, [Q[k] for k in keys], allow_unused=True)
     G = {k: (g if g is not None else torch.zeros_like(Q[k])) for k, g in zip(keys, grads)}

@@ -129,25 +129,24 @@ def test_cifar_shapes_against_oracle(num_classes, map_size):
             P[k] = P[k] + 0.05 * torch.randn(P[k].shape, generator=g)
     x, y = O.synthetic_batch(d, B, seed=1)
     it, n_train, est = 40, 50000, 200
-    total, parts, G = O.loss_and_grads(P, x, y, d, it, n_train, est)
     m = build(cfg, P)
     m._it = it
     m.set_schedule(n_train, est)
     cls, recon, logits, dist, bmu = m(x.to(DEV))
+    loss = m.training_step((x.to(DEV), y.to(DEV)), 0)
+    loss.backward()
+    # the reference's neighbourhood from the step's own BMU: an fp32 near-tie resolved the other way (allowed by bmu_ok)
+    # must not take a gradient out of the comparison
+    total, parts, G = O.loss_and_grads(P, x, y, d, it, n_train, est, bmu=m._ctx[2].bmu.cpu())
     assert torch.allclose(cls.cpu(), parts["cls"], atol=1e-4)
     assert torch.allclose(dist.cpu(), parts["dist"], atol=1e-5)
     assert bmu_ok(bmu.cpu(), parts["dist"].double())
     assert torch.allclose(recon.cpu(), parts["recon"], atol=1e-4)
     if num_classes:
         assert torch.allclose(logits.cpu(), parts["logits"], atol=1e-4)
-    loss = m.training_step((x.to(DEV), y.to(DEV)), 0)
     assert abs(float(loss) - float(total)) < 1e-4
-    loss.backward()
-    same_bmu = torch.equal(bmu.cpu(), parts["bmu"])
     for n, p in m.named_parameters():
         if p.requires_grad:
-            if not same_bmu and n == "som_layer.prototypes":
-                continue
             e = rel_err(p.grad.cpu(), G[n])
             assert e < 1e-4 or float((p.grad.cpu() - G[n]).abs().max()) < 1e-9, (n, e)
 
@@ -162,21 +161,20 @@ def test_mnist_shapes_against_oracle():
     P = O.init_params(cfg, seed=4)
     x, y = O.synthetic_batch(d, B, seed=2)
     it, n_train, est = 25, 60000, 100
-    total, parts, G = O.loss_and_grads(P, x, y, d, it, n_train, est)
     m = build(cfg, P)
     m._it = it
     m.set_schedule(n_train, est)
     loss = m.training_step((x.to(DEV), y.to(DEV)), 0)
-    assert abs(float(loss) - float(total)) < 1e-4
     s = m._ctx[2]
+    total, parts, G = O.loss_and_grads(P, x, y, d, it, n_train, est, bmu=s.bmu.cpu())
+    assert abs(float(loss) - float(total)) < 1e-4
     assert torch.allclose(s.dist.cpu(), parts["dist"], atol=1e-5)
     assert bmu_ok(s.bmu.cpu(), parts["dist"].double())
     loss.backward()
-    if torch.equal(s.bmu.cpu(), parts["bmu"]):
-        for n, p in m.named_parameters():
-            if p.requires_grad:
-                e = rel_err(p.grad.cpu(), G[n])
-                assert e < 2e-4 or float((p.grad.cpu() - G[n]).abs().max()) < 1e-9, (n, e)
+    for n, p in m.named_parameters():
+        if p.requires_grad:
+            e = rel_err(p.grad.cpu(), G[n])
+            assert e < 2e-4 or float((p.grad.cpu() - G[n]).abs().max()) < 1e-9, (n, e)
 
 
 def test_steps_are_deterministic():
@@ -268,23 +266,22 @@ def _shape_case(cfg, B, seed, it=30, n_train=100000, est=400, grad_tol=2e-4):
     d = O.Dims(cfg)
     P = O.init_params(cfg, seed=seed)
     x, y = O.synthetic_batch(d, B, seed=seed + 1)
-    total, parts, G = O.loss_and_grads(P, x, y, d, it, n_train, est)
     m = build(cfg, P)
     m._it = it
     m.set_schedule(n_train, est)
     loss = m.training_step((x.to(DEV), y.to(DEV)), 0)
     s = m._ctx[2]
+    total, parts, G = O.loss_and_grads(P, x, y, d, it, n_train, est, bmu=s.bmu.cpu())
     assert abs(float(loss) - float(total)) < 1e-4
     assert torch.allclose(s.dist.cpu(), parts["dist"], atol=2e-5)
     assert bmu_ok(s.bmu.cpu(), parts["dist"].double())
     if m.classification:
         assert torch.allclose(m._ctx[1].logits.cpu(), parts["logits"], atol=1e-4)
     loss.backward()
-    if torch.equal(s.bmu.cpu(), parts["bmu"]):
-        for n, p in m.named_parameters():
-            if p.requires_grad:
-                e = rel_err(p.grad.cpu(), G[n])
-                assert e < grad_tol or float((p.grad.cpu() - G[n]).abs().max()) < 1e-9, (n, e)
+    for n, p in m.named_parameters():
+        if p.requires_grad:
+            e = rel_err(p.grad.cpu(), G[n])
+            assert e < grad_tol or float((p.grad.cpu() - G[n]).abs().max()) < 1e-9, (n, e)
     return m
 
 

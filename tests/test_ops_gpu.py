@@ -7,7 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import rel_err
+from helpers import rel_err, tile_rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -96,8 +96,23 @@ def test_linear_residual_fwd(ops, gemm_mode, M, N, K, rmod):
     assert rel_err(out.cpu(), ref) < GEMM_TOL
 
 
-@pytest.mark.parametrize("M,N,K", [(130, 576, 192), (257, 192, 768), (33, 10, 24), (70, 12, 4), (300, 768, 192)])
+BWD_INPUT_SHAPES = [(130, 576, 192), (257, 192, 768), (33, 10, 24), (70, 12, 4), (300, 768, 192)]
+
+
+@pytest.mark.parametrize("M,N,K", BWD_INPUT_SHAPES)
 def test_linear_bwd_input(ops, M, N, K):
+    """vsom_linear_bwd_input in the default GEMM mode (the other modes: test_linear_bwd_input_other_modes)."""
+    _check_linear_bwd_input(ops, M, N, K)
+
+
+@pytest.mark.parametrize("gemm_mode", ["split_bf16", "f32"], indirect=True)
+@pytest.mark.parametrize("M,N,K", BWD_INPUT_SHAPES)
+def test_linear_bwd_input_other_modes(ops, gemm_mode, M, N, K):
+    """The same in the remaining GEMM modes: GEMM_F32 runs the f32 <A_KC, !B_KC> kernel."""
+    _check_linear_bwd_input(ops, M, N, K)
+
+
+def _check_linear_bwd_input(ops, M, N, K):
     dy, W = rnd(M, N, seed=1), rnd(N, K, seed=2, scale=0.1)
     ref = dy.double() @ W.double()
     dx = torch.empty(M, K, device=DEV)
@@ -111,6 +126,30 @@ def test_linear_bwd_input(ops, M, N, K):
     dx3 = torch.empty(M, K, device=DEV)
     ops.linear_bwd_input(dev(dy), dev(W), dx3, gelu_grad=dev(gg))
     assert rel_err(dx3.cpu(), ref * gg.double()) < GEMM_TOL
+
+
+@pytest.mark.parametrize("M,N,K,R", [(64, 10, 192, 65), (128, 100, 192, 65), (37, 576, 192, 3), (20, 192, 96, 257)])
+def test_linear_bwd_input_strided_accumulate(ops, gemm_mode, M, N, K, R):
+    """dX (+)= dY W on row-strided views (lddy > N, lddx > K), as the CLS rows of a [B*R, E] buffer are updated
+    (vit_owner._cls_view): the B rows accumulate, the R - 1 rows between them keep their bits."""
+    dy_full = rnd(M * R, N, seed=1)
+    W = rnd(N, K, seed=2, scale=0.1)
+    dyd = torch.as_strided(dev(dy_full), (M, N), (R * N, 1))
+    dy = dy_full.view(M, R * N)[:, :N]
+    ref = dy.double() @ W.double()
+    base = rnd(M * R, K, seed=5)
+    dx_full = dev(base).clone()
+    dxd = torch.as_strided(dx_full, (M, K), (R * K, 1))
+    ops.linear_bwd_input(dyd, dev(W), dxd, accumulate=True)
+    got = dx_full.cpu().view(M, R, K)
+    assert rel_err(got[:, 0], ref + base.view(M, R, K)[:, 0].double()) < GEMM_TOL
+    assert torch.equal(got[:, 1:], base.view(M, R, K)[:, 1:])
+    # and overwriting (accumulate=False) through the same views
+    dx_full = dev(base).clone()
+    ops.linear_bwd_input(dyd, dev(W), torch.as_strided(dx_full, (M, K), (R * K, 1)))
+    got = dx_full.cpu().view(M, R, K)
+    assert rel_err(got[:, 0], ref) < GEMM_TOL
+    assert torch.equal(got[:, 1:], base.view(M, R, K)[:, 1:])
 
 
 @pytest.mark.parametrize("M,N,K", [(130, 576, 192), (257, 192, 768), (33, 12, 24), (70, 12, 4), (300, 768, 192), (4160, 768, 192)])
@@ -196,27 +235,35 @@ def test_linear_bwd_weight(ops, gemm_mode, M, N, K):
     assert torch.equal(dW, dW2) and torch.equal(db, db2)
 
 
-@pytest.mark.parametrize("B,C,S,p,E", [(6, 3, 32, 4, 192), (4, 1, 28, 2, 16), (3, 3, 8, 4, 24)])
+@pytest.mark.parametrize("B,C,S,p,E", [(6, 3, 32, 4, 192), (4, 1, 28, 2, 16), (3, 3, 8, 4, 24),
+                                       # the weight gradient with the CLS-skipping row map on the x6 tile kernel:
+                                       # E % 192 == 0 and C*p*p % 64 == 0 (config 1), both multiples of 96 (config 2);
+                                       # 25 patches per image, not a multiple of 32: the generic kernel with the map
+                                       (4, 3, 64, 8, 192), (4, 3, 64, 8, 96), (3, 3, 40, 8, 192)])
 def test_patch_embed(ops, O, gemm_mode, B, C, S, p, E):
     n = (S // p) ** 2
     img = rnd(B, C, S, S, seed=1)
     W, b = rnd(E, C, p, p, seed=2, scale=0.2), rnd(E, seed=3)
     cls, pos = rnd(1, 1, E, seed=4), O.sincos_pos_embed(E, S // p)
-    P = {"vit.patch_embed.proj.weight": W, "vit.patch_embed.proj.bias": b}
-    ref = torch.cat(((cls + pos[:, :1]).expand(B, -1, -1), O.patch_embed(P, img, p) + pos[:, 1:]), dim=1)
+    # reference in fp64, forward and backward
+    Wl, bl, cl = (t.double().requires_grad_(True) for t in (W, b, cls))
+    Pl = {"vit.patch_embed.proj.weight": Wl, "vit.patch_embed.proj.bias": bl}
+    pos64 = pos.double()
+    out = torch.cat(((cl + pos64[:, :1]).expand(B, -1, -1), O.patch_embed(Pl, img.double(), p) + pos64[:, 1:]), dim=1)
     tokens = torch.empty(B, n + 1, E, device=DEV)
     xp = torch.empty(B * n, C * p * p, device=DEV)
     ops.patch_embed_fwd(dev(img), dev(W.reshape(E, -1).contiguous()), dev(b), dev(pos[0]), dev(cls.reshape(E)), tokens, xp, p)
-    assert torch.allclose(tokens.cpu(), ref, atol=2e-6)
+    e = float((tokens.cpu().double() - out.detach()).abs().max())
+    assert rel_err(tokens.cpu(), out.detach()) < GEMM_TOL
+    # fp32 accumulation over C*p*p products: 2e-6 up to 48; at 192 (|tokens| up to ~12) 5.6e-6 measured in every mode
+    assert e < (2e-6 if C * p * p <= 48 else 1e-5), e
     # backward
     dt = rnd(B, n + 1, E, seed=5)
-    Wl = W.clone().requires_grad_(True); bl = b.clone().requires_grad_(True); cl = cls.clone().requires_grad_(True)
-    Pl = {"vit.patch_embed.proj.weight": Wl, "vit.patch_embed.proj.bias": bl}
-    out = torch.cat(((cl + pos[:, :1]).expand(B, -1, -1), O.patch_embed(Pl, img, p) + pos[:, 1:]), dim=1)
-    out.backward(dt)
+    out.backward(dt.double())
     dW, db, dc = torch.empty(E, C * p * p, device=DEV), torch.empty(E, device=DEV), torch.empty(E, device=DEV)
     ops.patch_embed_bwd(dev(dt), xp, dW, db, dc, B, C, S, p, E)
-    assert rel_err(dW.cpu(), Wl.grad.reshape(E, -1)) < 1e-5
+    assert rel_err(dW.cpu(), Wl.grad.reshape(E, -1)) < 1e-5, rel_err(dW.cpu(), Wl.grad.reshape(E, -1))
+    assert tile_rel_err(dW.cpu(), Wl.grad.reshape(E, -1)) < 2e-5, tile_rel_err(dW.cpu(), Wl.grad.reshape(E, -1))
     assert rel_err(db.cpu(), bl.grad) < 1e-5
     assert rel_err(dc.cpu(), cl.grad.reshape(E)) < 1e-5
 
