@@ -104,6 +104,11 @@ int vsom_transpose_many(const float* src_base, float* dst_base, const long long*
 #define VSOM_GEMM_SPLIT_BF16_GRAD3 2
 int vsom_set_gemm_mode(int mode);
 int vsom_get_gemm_mode(void);
+/* test / measurement hook for the weight-gradient GEMMs of VSOM_GEMM_SPLIT_BF16_GRAD3 mode whose output sides both
+   divide by 192: 0 = the 192 x 64 tiles, 1 = 192 x 192 tiles at the split count of the 192 x 64 plan (bitwise the same
+   dW and db; the GPU suite checks), 2 = 192 x 192 tiles with their own split count (default).  The workspace query
+   follows the setting. */
+int vsom_set_wgrad_tiles(int mode);
 
 /* dW[N,K] = dY[M,N]^T * X[M,K] ;  db[N] = column sums of dY (db may be NULL)
  * -- autograd of nn.Linear w.r.t. weight/bias.  The reduction over the M token rows is split

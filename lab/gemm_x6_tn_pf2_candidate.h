@@ -1,3 +1,9 @@
+// Lab (round 5, not built): the weight-gradient kernel of csrc/gemm_x6_tn.h with a PF template parameter -- PF = 2 keeps
+// two k-tiles of global loads in flight in two register stages over ONE LDS stage (56 KB), body unrolled by two so the
+// stages swap roles without copies.  Measured as gemm_x6_tn_kernel<3, 1, 2, 6, 2, 2> (192 x 192 tiles, 12 waves) in place
+// of the library's header: bitwise equal to the 192 x 64 kernel at its split count; alone 149.8 vs 150.6 us for the four
+// encoder dW GEMMs with PF = 1; in the step 8.84 vs 8.77 ms (worse): profiles/r05_wgrad_lab.txt.  Superseded by the
+// two-LDS-stage form (STAGES = 2 in gemm_x6_tn.h).
 // Split-bf16 weight-gradient GEMM:  dW[n,k] = sum_t dY[row(t), n] X[t, k]  (+ db[n] = sum_t dY[row(t), n]).
 //
 // Both operands are strided along the reduction index t (the token rows).  The fp32 tiles are loaded
@@ -10,10 +16,10 @@
 // t-rows of a transposed read then tile the 256-byte bank row (conflict-free).
 //
 // Tiles 192 x 64 or 96 x 96 (outputs x 32 t per step; 4 / 3 waves), one k-tile of global loads in flight under the
-// MFMAs, two workgroups per CU (41 / 61 KB LDS for two / three planes).  Wide form for the three-product mode: 192 x 192
-// tiles (12 waves of 96 x 32), so every operand byte is streamed from L2 into LDS half as often; two LDS stages
-// (112 KB, one workgroup per CU) and one barrier per k-tile.  Each output element sums the same k-tiles in the same MFMA
-// order whatever the tile shape, so at equal ktiles_per_split the slabs are bitwise those of the narrow form.
+// MFMAs, two workgroups per CU (61 KB LDS).  Wide form for the three-product mode: 192 x 192 tiles, every operand
+// byte streamed from L2 into LDS half as often; one workgroup per CU (56 KB LDS, one stage) and PF = 2 k-tiles of
+// global loads in flight in registers.  Each output element sums the same k-tiles in the same MFMA order whatever
+// the tile shape, so at equal ktiles_per_split the slabs are bitwise those of the narrow form.
 // The reduction over t is split over workgroups;
 // partial tiles go to fp32 slabs summed by reduce_slabs in fixed order (bitwise reproducible).
 // The bias gradient rides along: the dY tile passes through this thread's registers anyway, so the
@@ -47,15 +53,14 @@ __device__ __forceinline__ s16x4 tn_trread(const char* p) {
 // NPL = 3: the exact three-piece split, six products (fp32-accurate: |error| < 2^-22 per product).  NPL = 2: the two-piece
 // round-to-nearest split, three products (|error| <= 3 * 2^-16 per product worst case, ~4e-6 relative on a weight gradient
 // summed over the token rows): half the matrix-core work, two LDS planes instead of three.
-template <int WM, int WN, int WAVES_M, int WAVES_N, int NPL, int STAGES = 1>
+template <int WM, int WN, int WAVES_M, int WAVES_N, int NPL, int PF = 1>
 __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_x6_tn_kernel(const TnP g) {
     constexpr int BM = WAVES_M * WM * 32, BN = WAVES_N * WN * 32, NT = WAVES_M * WAVES_N * 64;
     constexpr int SA = tn_stride(BM), SB = tn_stride(BN), PA = 32 * SA, PB = 32 * SB;
     constexpr int FA = (32 * BM / 4 + NT - 1) / NT, FB = (32 * BN / 4 + NT - 1) / NT;
     static_assert(NPL * (PA + PB) >= NT * FA * 16, "LDS too small for the bias partials");
-    static_assert(STAGES == 1 || STAGES == 2, "one or two LDS stages");
-    constexpr int ST = NPL * (PA + PB);             // bytes of one LDS stage
-    __shared__ __attribute__((aligned(16))) char lds[STAGES * ST];
+    static_assert(PF == 1 || PF == 2, "one or two k-tiles of loads in flight");
+    __shared__ __attribute__((aligned(16))) char lds[NPL * (PA + PB)];
     char* As = lds; char* Bs = lds + NPL * PA;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm0 = (wave / WAVES_N) * WM * 32, wn0 = (wave % WAVES_N) * WN * 32;
@@ -80,7 +85,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_x6_tn_kernel(cons
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.dY), 0, (int)g.a_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.X), 0, (int)g.b_bytes, 0x00020000);
     // staging: float4 number idx = i*NT + t of the [32 t][C/4] tile; a thread keeps the same column quad in every k-tile
-    f32x4 sa[FA], sb[FB];
+    f32x4 sa[FA], sb[FB], sa2[PF == 2 ? FA : 1], sb2[PF == 2 ? FB : 1];
     unsigned ga[FA], gb[FB];
     int la[FA], lb[FB];
 #pragma unroll
@@ -102,35 +107,35 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_x6_tn_kernel(cons
 #pragma unroll
     for (int i = 0; i < FA; ++i) cs[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    auto gload = [&](int kt) {
+    auto gload = [&](f32x4(&va)[FA], f32x4(&vb)[FB], int kt) {
         // rows past the end of dY / X lie beyond the descriptor: the loads return zeros
         const long t0 = (long)kt << 5;
         const long ra = g.a_seg ? (t0 / g.a_seg) * g.a_stride + g.a_off + t0 % g.a_seg : t0;
         const unsigned sa_off = (unsigned)(ra * g.ldy * 4), sb_off = (unsigned)(t0 * g.ldx * 4);
 #pragma unroll
-        for (int i = 0; i < FA; ++i) sa[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, ga[i], sa_off, 0));
+        for (int i = 0; i < FA; ++i) va[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, ga[i], sa_off, 0));
 #pragma unroll
-        for (int i = 0; i < FB; ++i) sb[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, gb[i], sb_off, 0));
+        for (int i = 0; i < FB; ++i) vb[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, gb[i], sb_off, 0));
     };
-    auto lstore = [&](int so) {          // so: byte offset of the LDS stage
+    auto lstore = [&](const f32x4(&va)[FA], const f32x4(&vb)[FB]) {
 #pragma unroll
         for (int i = 0; i < FA; ++i) {
             if (la[i] < 0) continue;
-            if (want_colsum) cs[i] += sa[i];
+            if (want_colsum) cs[i] += va[i];
             uint2 p1, p2, p3;
-            if constexpr (NPL == 3) x6_split(sa[i], p1, p2, p3); else x3_split(sa[i], p1, p2);
-            *reinterpret_cast<uint2*>(As + so + la[i]) = p1;
-            *reinterpret_cast<uint2*>(As + so + PA + la[i]) = p2;
-            if constexpr (NPL == 3) *reinterpret_cast<uint2*>(As + so + 2 * PA + la[i]) = p3;
+            if constexpr (NPL == 3) x6_split(va[i], p1, p2, p3); else x3_split(va[i], p1, p2);
+            *reinterpret_cast<uint2*>(As + la[i]) = p1;
+            *reinterpret_cast<uint2*>(As + PA + la[i]) = p2;
+            if constexpr (NPL == 3) *reinterpret_cast<uint2*>(As + 2 * PA + la[i]) = p3;
         }
 #pragma unroll
         for (int i = 0; i < FB; ++i) {
             if (lb[i] < 0) continue;
             uint2 p1, p2, p3;
-            if constexpr (NPL == 3) x6_split(sb[i], p1, p2, p3); else x3_split(sb[i], p1, p2);
-            *reinterpret_cast<uint2*>(Bs + so + lb[i]) = p1;
-            *reinterpret_cast<uint2*>(Bs + so + PB + lb[i]) = p2;
-            if constexpr (NPL == 3) *reinterpret_cast<uint2*>(Bs + so + 2 * PB + lb[i]) = p3;
+            if constexpr (NPL == 3) x6_split(vb[i], p1, p2, p3); else x3_split(vb[i], p1, p2);
+            *reinterpret_cast<uint2*>(Bs + lb[i]) = p1;
+            *reinterpret_cast<uint2*>(Bs + PB + lb[i]) = p2;
+            if constexpr (NPL == 3) *reinterpret_cast<uint2*>(Bs + 2 * PB + lb[i]) = p3;
         }
     };
     // transposed fragment reads: lane l -> 16-lane group G = l >> 4 (columns 16 (G & 1) .., t rows 8 (G >> 1) ..),
@@ -148,18 +153,18 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_x6_tn_kernel(cons
         const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         return __builtin_bit_cast(bf16x8, v);
     };
-    auto mfma_tile = [&](int so) {
+    auto mfma_tile = [&]() {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 a[WM][NPL], b[WN][NPL];
 #pragma unroll
             for (int i = 0; i < WM; ++i)
 #pragma unroll
-                for (int pl = 0; pl < NPL; ++pl) a[i][pl] = frag(As + so + pl * PA, fa[i], SA, ks);
+                for (int pl = 0; pl < NPL; ++pl) a[i][pl] = frag(As + pl * PA, fa[i], SA, ks);
 #pragma unroll
             for (int j = 0; j < WN; ++j)
 #pragma unroll
-                for (int pl = 0; pl < NPL; ++pl) b[j][pl] = frag(Bs + so + pl * PB, fbo[j], SB, ks);
+                for (int pl = 0; pl < NPL; ++pl) b[j][pl] = frag(Bs + pl * PB, fbo[j], SB, ks);
 #pragma unroll
             for (int i = 0; i < WM; ++i)
 #pragma unroll
@@ -177,42 +182,57 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_x6_tn_kernel(cons
                 }
         }
     };
-    if constexpr (STAGES == 1) {
+    if constexpr (PF == 1) {
         if (kt_begin < kt_end) {
-            gload(kt_begin);
-            lstore(0);
+            gload(sa, sb, kt_begin);
+            lstore(sa, sb);
         }
         __syncthreads();
         for (int kt = kt_begin; kt + 1 < kt_end; ++kt) {          // branch-free body, last k-tile peeled (see gemm_x6.h)
-            gload(kt + 1);
+            gload(sa, sb, kt + 1);
             __builtin_amdgcn_sched_barrier(0);
-            mfma_tile(0);
+            mfma_tile();
             __builtin_amdgcn_sched_barrier(0);
             __syncthreads();
-            lstore(0);
+            lstore(sa, sb);
             __syncthreads();
         }
-        if (kt_begin < kt_end) mfma_tile(0);
+        if (kt_begin < kt_end) mfma_tile();
     } else {
-        // two LDS stages, one barrier per k-tile: k-tile kt + 1 goes to the other stage while kt is multiplied; the stage
-        // written here was last read before the previous barrier
+        // two register stages: k-tile kt in LDS, kt + 1 and kt + 2 in flight.  The body is unrolled by two so the stages
+        // swap roles without copies; a load past the range re-reads its last k-tile (never stored), which keeps the body
+        // branch-free so the compiler waits for exactly the older stage.
+        const int kt_last = kt_end - 1;
         if (kt_begin < kt_end) {
-            gload(kt_begin);
-            lstore(0);
-            if (kt_begin + 1 < kt_end) gload(kt_begin + 1);
+            gload(sa, sb, kt_begin);
+            gload(sa2, sb2, kt_begin + 1 < kt_end ? kt_begin + 1 : kt_last);
+            lstore(sa, sb);
         }
         __syncthreads();
-        int so = 0;
-        for (int kt = kt_begin; kt + 1 < kt_end; ++kt) {
-            lstore(ST - so);
-            gload(kt + 2 < kt_end ? kt + 2 : kt + 1);             // past the range: re-read (never stored), branch-free
+        int kt = kt_begin;
+        for (; kt + 2 < kt_end; kt += 2) {
+            gload(sa, sb, kt + 2);
             __builtin_amdgcn_sched_barrier(0);
-            mfma_tile(so);
+            mfma_tile();                                           // k-tile kt
             __builtin_amdgcn_sched_barrier(0);
             __syncthreads();
-            so = ST - so;
+            lstore(sa2, sb2);                                      // kt + 1
+            __syncthreads();
+            gload(sa2, sb2, kt + 3 < kt_end ? kt + 3 : kt_last);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_tile();                                           // kt + 1
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();
+            lstore(sa, sb);                                        // kt + 2
+            __syncthreads();
         }
-        if (kt_begin < kt_end) mfma_tile(so);
+        if (kt + 1 < kt_end) {
+            mfma_tile();
+            __syncthreads();
+            lstore(sa2, sb2);
+            __syncthreads();
+        }
+        if (kt_begin < kt_end) mfma_tile();
     }
 
     if (want_colsum) {

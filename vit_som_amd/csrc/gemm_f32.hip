@@ -179,16 +179,20 @@ int reduce_slabs_internal(const float* slabs, long stride, int nslabs, float* ou
 // L).  Workgroups are resident 3 per CU (register budget of the 128x64 tile), so a launch runs in
 // ceil(tiles*s / slots) rounds of ceil(ktiles/s) k-tiles each; pick the s that minimises
 // rounds x (k-tiles per workgroup + fixed per-workgroup cost) + the slab-reduction cost.
-int choose_splits(int tiles, int ktiles, int max_splits, bool prefer_xcd_multiple) {
-    static int slots = 0;
-    if (!slots) {
-        int dev = 0, cus = 256;
+static int device_cus() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0, n = 256;
         if (hipGetDevice(&dev) == hipSuccess) {
             hipDeviceProp_t p;
-            if (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) cus = p.multiProcessorCount;
+            if (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) n = p.multiProcessorCount;
         }
-        slots = 3 * cus;
+        cus = n;
     }
+    return cus;
+}
+int choose_splits(int tiles, int ktiles, int max_splits, bool prefer_xcd_multiple) {
+    const int slots = 3 * device_cus();
     if (max_splits > ktiles) max_splits = ktiles;
     if (max_splits < 1) max_splits = 1;
     // measured relative MFMA efficiency with 1 / 2 / 3 co-resident workgroups per CU
@@ -211,9 +215,18 @@ int choose_splits(int tiles, int ktiles, int max_splits, bool prefer_xcd_multipl
     return best_s;
 }
 // Weight-gradient plan: tile configuration of gemm_x6_tn_kernel (0 = none fits: the generic k-strided
-// kernel) and the number of reduction splits -- a function of the shape only, so that the workspace
-// query and the launch agree.
+// kernel; 1 = 192 x 64, 2 = 96 x 96, 3 = 192 x 192) and the number of reduction splits -- a function of the shape
+// and the switches only, so that the workspace query and the launch agree.
 struct TnPlan { int cfg; int splits; };
+// test / measurement hook (vsom_set_wgrad_tiles): 0 = the 192 x 64 tiles only, 1 = 192 x 192 tiles at the split count
+// of the 192 x 64 plan (bitwise the same dW and db), 2 = 192 x 192 tiles with their own split count (default)
+static std::atomic<int> g_wgrad_tiles{2};
+static int splits_for(int tiles, int ktiles, int target) {
+    int s = (target + tiles / 2) / tiles;
+    if (s > ktiles) s = ktiles;
+    if (s < 1) s = 1;
+    return cdiv(ktiles, cdiv(ktiles, s));
+}
 static TnPlan bwd_weight_plan(int M, int N, int K) {
     TnPlan p;
     p.cfg = (N % 192 == 0 && K % 64 == 0) ? 1 : (N % 96 == 0 && K % 96 == 0) ? 2 : 0;
@@ -227,11 +240,15 @@ static TnPlan bwd_weight_plan(int M, int N, int K) {
     // shares the chip with the backward chain, fewer and longer reduction ranges win -- and more so since the gradient GEMMs
     // run three products (round 3, lab builds A/B on one box: 768 / 512 / 384 / 320 / 256 / 192 workgroups ->
     // +0.17 / 0 / -0.08...-0.10 / 0 / +0.15 / +0.45 ms per step; rounding the count to a multiple of 8: no difference)
-    int s = (384 + tiles / 2) / tiles;
-    if (s > ktiles) s = ktiles;
-    if (s < 1) s = 1;
-    const int per = cdiv(ktiles, s);
-    p.splits = cdiv(ktiles, per);
+    p.splits = splits_for(tiles, ktiles, 384);
+    const int wide = g_wgrad_tiles.load(std::memory_order_relaxed);
+    if (wide && gemm_grad_products() == 3 && N % 192 == 0 && K % 192 == 0) {
+        p.cfg = 3;
+        // 192 x 192: one 112 KB workgroup per CU.  Workgroups for three quarters of the CUs: inside the step the rest serve
+        // the backward chain (round 5, in-step A/B on one box: 256 / 192 / 160 / 128 workgroups -> -0.22 / -0.31 / -0.25 /
+        // -0.13 ms per step against the 192 x 64 plan; alone 256 is fastest)
+        if (wide == 2) p.splits = splits_for((N / 192) * (K / 192), ktiles, 3 * device_cus() / 4);
+    }
     return p;
 }
 static long pad4(long n) { return (n + 3) & ~3L; }
@@ -306,7 +323,9 @@ int linear_bwd_weight_impl(const float* dY, long lddy, const float* X, long ldx,
         t.slab_bias = db ? slab + wlen : nullptr; t.slab_bias_stride = wlen + blen;
         t.a_bytes = (unsigned)ab; t.b_bytes = (unsigned)bb;
         const bool x3 = gemm_grad_products() == 3;
-        if (plan.cfg == 1) {
+        if (plan.cfg == 3) {
+            VSOM_LAUNCH((gemm_x6_tn_kernel<3, 1, 2, 6, 2, 2>), dim3((N / 192) * (K / 192) * splits), dim3(768), 0, stream, t);
+        } else if (plan.cfg == 1) {
             if (x3) VSOM_LAUNCH((gemm_x6_tn_kernel<3, 1, 2, 2, 2>), dim3((N / 192) * (K / 64) * splits), dim3(256), 0, stream, t);
             else VSOM_LAUNCH((gemm_x6_tn_kernel<3, 1, 2, 2, 3>), dim3((N / 192) * (K / 64) * splits), dim3(256), 0, stream, t);
         } else {
@@ -454,6 +473,12 @@ int vsom_set_gemm_mode(int mode) {
     return VSOM_OK;
 }
 int vsom_get_gemm_mode(void) { return gemm_mode(); }
+
+int vsom_set_wgrad_tiles(int mode) {
+    VSOM_REQUIRE(mode >= 0 && mode <= 2, VSOM_EINVAL, "set_wgrad_tiles: unknown mode %d", mode);
+    g_wgrad_tiles.store(mode, std::memory_order_relaxed);
+    return VSOM_OK;
+}
 
 size_t vsom_linear_bwd_weight_workspace_bytes(int M, int N, int K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;

@@ -172,6 +172,22 @@ def get_gemm_mode() -> int:
     return int(lib.vsom_get_gemm_mode())
 
 
+def set_wgrad_tiles(mode):
+    """Test / measurement hook (include/vitsom_hip.h, vsom_set_wgrad_tiles): 0 = 192 x 64 weight-gradient tiles, 1 = 192 x 192
+    tiles at the 192 x 64 plan's split count (bitwise the same result), 2 = 192 x 192 tiles with their own plan (default)."""
+    global _wgrad_tiles
+    check(lib.vsom_set_wgrad_tiles(int(mode)), "vsom_set_wgrad_tiles")
+    _wgrad_tiles = int(mode)
+
+
+_wgrad_tiles = 2
+
+
+def get_wgrad_tiles() -> int:
+    """The value last set through set_wgrad_tiles (the library's default otherwise)."""
+    return _wgrad_tiles
+
+
 def linear_bwd_weight(dy, x, dW, db):
     M, N = dy.shape
     K = x.shape[1]
