@@ -109,6 +109,10 @@ int vsom_get_gemm_mode(void);
    dW and db; the GPU suite checks), 2 = 192 x 192 tiles with their own split count (default).  The workspace query
    follows the setting. */
 int vsom_set_wgrad_tiles(int mode);
+/* test / measurement hook for vsom_linear_bwd_input_ln{,_partial} at K = 192 in VSOM_GEMM_SPLIT_BF16_GRAD3 mode:
+   0 = 64 x 192 tiles, 1 = 192 x 192 tiles (default).  dX and the partials are bitwise the same (the GPU suite checks);
+   the partial layout and its size query do not depend on the setting.  Other values: VSOM_EINVAL. */
+int vsom_set_ln_tiles(int mode);
 
 /* dW[N,K] = dY[M,N]^T * X[M,K] ;  db[N] = column sums of dY (db may be NULL)
  * -- autograd of nn.Linear w.r.t. weight/bias.  The reduction over the M token rows is split

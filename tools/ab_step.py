@@ -1,6 +1,6 @@
 """A/B timing of the whole training step inside ONE process (box-to-box and clock drift cancel):
 alternates one test hook (vit_som_amd/tuning.py) between blocks of steps.  usage: ab_step.py hook=a,b [steps] [rounds]
-e.g. ab_step.py fwd_split_blocks=0,6,12   ab_step.py side_stream=0,1   ab_step.py attn_fused=0,1   ab_step.py wgrad_tiles=0,2"""
+e.g. ab_step.py fwd_split_blocks=0,6,12   ab_step.py side_stream=0,1   ab_step.py attn_fused=0,1   ab_step.py wgrad_tiles=0,2   ab_step.py ln_tiles=0,1"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -14,6 +14,8 @@ def apply(key, v):
         ops.set_attention_fused(int(v))
     elif key == "wgrad_tiles":                       # 0 192 x 64 weight-gradient tiles, 1 192 x 192 at their split count, 2 (default) 192 x 192
         ops.set_wgrad_tiles(int(v))
+    elif key == "ln_tiles":                          # 0 64 x 192 LayerNorm-fused dX tiles, 1 (default) 192 x 192
+        ops.set_ln_tiles(int(v))
     elif key == "gemm_mode":                         # 0 f32 MFMA, 1 six products everywhere, 2 (default) three in the gradient GEMMs
         ops.set_gemm_mode(int(v))
     else:

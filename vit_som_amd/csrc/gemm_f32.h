@@ -62,8 +62,8 @@ struct GemmP {
     float* ln_part;              // [row tile][2][N]
 };
 
-template <int R_>
-struct StageRegs { f32x4 v[R_ / 32]; };
+template <int R_, int NT = 256>
+struct StageRegs { f32x4 v[R_ * 8 / NT]; };
 
 constexpr unsigned OOB = 0xFFFFFFF0u;      // byte offset past any buffer: raw buffer loads return 0
 
@@ -80,24 +80,25 @@ __device__ __forceinline__ f32x4 bload4s(__amdgpu_buffer_rsrc_t rsrc, unsigned v
 // FAST path: 16-byte hardware-bounds-checked buffer loads.  Each thread's byte offsets into the
 // operand are computed ONCE per output tile (OOB when its row / column is outside the matrix);
 // inside the k-loop a load costs one add and one select.
-// k-contiguous tile: ROWS x 32, thread t loads float4 at (row = p*32 + t/8, k = (t%8)*4)
-template <int ROWS>
-struct OffKC { unsigned off[ROWS / 32]; };
-template <int ROWS>
-__device__ __forceinline__ void init_kc(OffKC<ROWS>& o, long ld, int row0, int nrows, int t) {
+// k-contiguous tile: ROWS x 32, thread t of NT loads float4 at (row = p*(NT/8) + t/8, k = (t%8)*4)
+template <int ROWS, int NT = 256>
+struct OffKC { unsigned off[ROWS * 8 / NT]; };
+template <int ROWS, int NT = 256>
+__device__ __forceinline__ void init_kc(OffKC<ROWS, NT>& o, long ld, int row0, int nrows, int t) {
+    static_assert(ROWS % (NT / 8) == 0, "k-contiguous tile rows must be a multiple of NT / 8");
 #pragma unroll
-    for (int p = 0; p < ROWS / 32; ++p) {
-        const int row = row0 + p * 32 + (t >> 3);
+    for (int p = 0; p < ROWS * 8 / NT; ++p) {
+        const int row = row0 + p * (NT / 8) + (t >> 3);
         o.off[p] = (row < nrows) ? (unsigned)(((long)row * ld + ((t & 7) << 2)) << 2) : OOB;
     }
 }
-template <int ROWS>
-__device__ __forceinline__ void load_kc_fast(StageRegs<ROWS>& s, __amdgpu_buffer_rsrc_t rsrc, const OffKC<ROWS>& o,
+template <int ROWS, int NT = 256>
+__device__ __forceinline__ void load_kc_fast(StageRegs<ROWS, NT>& s, __amdgpu_buffer_rsrc_t rsrc, const OffKC<ROWS, NT>& o,
                                              int k0, int K, int t) {
     const bool kok = k0 + ((t & 7) << 2) < K;
     const unsigned kbytes = (unsigned)k0 << 2;
 #pragma unroll
-    for (int p = 0; p < ROWS / 32; ++p) s.v[p] = bload4(rsrc, (kok && o.off[p] != OOB) ? o.off[p] + kbytes : OOB);
+    for (int p = 0; p < ROWS * 8 / NT; ++p) s.v[p] = bload4(rsrc, (kok && o.off[p] != OOB) ? o.off[p] + kbytes : OOB);
 }
 // k-strided tile: 32 x COLS, thread t loads float4 at (k = p*KPP + t/(COLS/4), col = (t%(COLS/4))*4)
 template <int COLS>

@@ -259,6 +259,9 @@ static long pad4(long n) { return (n + 3) & ~3L; }
 // with the epilogue: one workgroup per CU, or spills.
 static bool ln_fused_width(int K) { return K == 192 || K == 96; }
 static int ln_fused_tiles(int M, int K) { return cdiv(M, K == 192 ? 64 : 128); }
+// test / measurement hook (vsom_set_ln_tiles): 0 = the 64 x 192 tiles only, 1 = 192 x 192 tiles (gemm_x6_ln_wide_kernel) for
+// the encoder width in the three-product mode (default).  Both write the same dX and per-64-row partials, bit for bit.
+static std::atomic<int> g_ln_tiles{1};
 
 static int linear_bwd_input_ln_launch(const float* dY, long lddy, const float* Wt, int M, int N, int K, const float* X,
                                       const float* mean, const float* rstd, const float* gamma, const float* resid,
@@ -282,8 +285,14 @@ static int linear_bwd_input_ln_launch(const float* dY, long lddy, const float* W
     g.a_bytes = (unsigned)ab; g.b_bytes = (unsigned)bb;
     g.products = gemm_grad_products();
     g.ln_x = X; g.ln_mean = mean; g.ln_rstd = rstd; g.ln_gamma = gamma; g.ln_resid = resid; g.ln_part = part;
-    const dim3 grid(ln_fused_tiles(M, K)), block(256);
     const bool x3 = g.products == 3;
+    if (K == 192 && x3 && g_ln_tiles.load(std::memory_order_relaxed) == 1) {
+        // 192 x 192: the transposed weight is staged and split once per 192 rows (round 6); the partials keep
+        // the 64-row layout, so the workspace and finish_many do not change
+        VSOM_LAUNCH((gemm_x6_ln_wide_kernel<3, 6, 2, 2>), dim3(cdiv(M, 192)), dim3(768), 0, stream, g);
+        VSOM_LAUNCH_CHECK("gemm_x6_ln_wide_kernel");
+    }
+    const dim3 grid(ln_fused_tiles(M, K)), block(256);
     if (K == 192) {
         if (x3) VSOM_LAUNCH((gemm_x6_ln_kernel<3, 2, 2, 2>), grid, block, 0, stream, g);
         else VSOM_LAUNCH((gemm_x6_ln_kernel<3, 2, 2, 3>), grid, block, 0, stream, g);
@@ -473,6 +482,12 @@ int vsom_set_gemm_mode(int mode) {
     return VSOM_OK;
 }
 int vsom_get_gemm_mode(void) { return gemm_mode(); }
+
+int vsom_set_ln_tiles(int mode) {
+    VSOM_REQUIRE(mode == 0 || mode == 1, VSOM_EINVAL, "set_ln_tiles: unknown mode %d", mode);
+    g_ln_tiles.store(mode, std::memory_order_relaxed);
+    return VSOM_OK;
+}
 
 int vsom_set_wgrad_tiles(int mode) {
     VSOM_REQUIRE(mode >= 0 && mode <= 2, VSOM_EINVAL, "set_wgrad_tiles: unknown mode %d", mode);

@@ -75,14 +75,14 @@ __device__ __forceinline__ int x6_chunk_off(int row, int chunk) { return row * X
 // byte offset of the 8-byte piece kq (4 consecutive k, kq = 0..7) of row `row`
 __device__ __forceinline__ int x6_piece_off(int row, int kq) { return x6_chunk_off(row, kq >> 1) + ((kq & 1) << 3); }
 
-template <int ROWS, int NPL = 3>
-__device__ __forceinline__ void x6_store(const StageRegs<ROWS>& s, char* planes, int t) {
+template <int ROWS, int NPL = 3, int NT = 256>
+__device__ __forceinline__ void x6_store(const StageRegs<ROWS, NT>& s, char* planes, int t) {
     constexpr int PL = ROWS * X6_RS;
 #pragma unroll
-    for (int p = 0; p < ROWS / 32; ++p) {
+    for (int p = 0; p < ROWS * 8 / NT; ++p) {
         uint2 p1, p2, p3;
         if constexpr (NPL == 3) x6_split(s.v[p], p1, p2, p3); else x3_split(s.v[p], p1, p2);
-        char* dst = planes + x6_piece_off(p * 32 + (t >> 3), t & 7);
+        char* dst = planes + x6_piece_off(p * (NT / 8) + (t >> 3), t & 7);
         *reinterpret_cast<uint2*>(dst) = p1;
         *reinterpret_cast<uint2*>(dst + PL) = p2;
         if constexpr (NPL == 3) *reinterpret_cast<uint2*>(dst + 2 * PL) = p3;
@@ -122,9 +122,11 @@ __device__ __forceinline__ void x6_store_ks(const X6Blk& b, char* planes, int pl
 // layernorm_bwd_v4_kernel (16 lanes per row, float4 chunk sub + 16 j), and ln_bwd_row runs on them: dX carries the bits of
 // the GEMM + layernorm_bwd pair.  The dY tile never reaches memory.  Each tile writes one dgamma / dbeta partial
 // part[tile][2][N]: column sums over its rows in a fixed order (per lane in pass order, then the 16 row groups in order).
+// The 192-row form runs this once per 64-row group of 256 threads (t = thread index inside the group, lds = the group's
+// own LDS region, bm0 = its first row, tile = its 64-row block index); a group wholly past M writes nothing.
 template <int WN, int WAVES_M, int WAVES_N, int LDS_BYTES>
 __device__ __forceinline__ void x6_ln_bwd_epilogue(const GemmP& g, const f32x16 (&acc)[1][WN], char* lds, int bm0, int wm0,
-                                                   int wn0, int r, int h, int tile) {
+                                                   int wn0, int r, int h, int tile, int t) {
     constexpr int BN = WAVES_N * WN * 32;
     constexpr int cols = BN;                 // the host launches this epilogue with N == BN only
     constexpr int NCH = (BN + 63) / 64;
@@ -133,7 +135,7 @@ __device__ __forceinline__ void x6_ln_bwd_epilogue(const GemmP& g, const f32x16 
     constexpr int ITER = PROWS / 16;         // 16 row groups of 16 lanes
     static_assert(PROWS % 16 == 0 && PROWS * LROW * 4 <= LDS_BYTES && 16 * 2 * BN * 4 <= LDS_BYTES, "LN epilogue does not fit");
     float* st = reinterpret_cast<float*>(lds);
-    const int t = threadIdx.x, sub = t & 15, rg = t >> 4;
+    const int sub = t & 15, rg = t >> 4;
     const float inv_n = 1.0f / (float)cols;
     // bounds-checked buffer accesses (32-bit offsets; rows past M read 0 and drop their stores -- d = 0 there)
     const unsigned rbytes = (unsigned)g.M * cols * 4u;
@@ -209,6 +211,7 @@ __device__ __forceinline__ void x6_ln_bwd_epilogue(const GemmP& g, const f32x16 
         reinterpret_cast<f32x4*>(sh + (rg * 2 + 1) * cols)[sub + 16 * j] = db[j];
     }
     __syncthreads();
+    if (bm0 >= g.M) return;                   // no barrier below
     for (int c = t; c < 2 * cols; c += 256) {
         float s = 0.f;
 #pragma unroll
@@ -217,13 +220,22 @@ __device__ __forceinline__ void x6_ln_bwd_epilogue(const GemmP& g, const f32x16 
     }
 }
 
-// NPL = 3: exact three-piece split, six products; NPL = 2: two-piece round-to-nearest split, three products (x3_split above)
-template <bool A_KC, bool B_KC, int WM, int WN, int WAVES_M, int WAVES_N, int EPI, int NPL = 3>
+// NPL = 3: exact three-piece split, six products; NPL = 2: two-piece round-to-nearest split, three products (x3_split above).
+// NT threads (WAVES_M * WAVES_N waves; k-strided operands need 256); STAGES = 2: two LDS operand stages, one barrier per
+// k-tile (as gemm_x6_tn.h).  The per-element k order and MFMA order do not depend on NT, STAGES or the tile height.
+template <bool A_KC, bool B_KC, int WM, int WN, int WAVES_M, int WAVES_N, int EPI, int NPL = 3, int NT = 256, int STAGES = 1>
 __device__ __forceinline__ void gemm_x6_body(const GemmP& g) {
     constexpr int BM = WAVES_M * WM * 32;
     constexpr int BN = WAVES_N * WN * 32;
     constexpr int PA = BM * X6_RS, PB = BN * X6_RS;
-    __shared__ __attribute__((aligned(16))) char lds[NPL * (PA + PB)];
+    constexpr int ST = NPL * (PA + PB);                         // bytes of one operand stage
+    static_assert(NT == WAVES_M * WAVES_N * 64 && (NT == 256 || (A_KC && B_KC)), "thread count");
+    static_assert(STAGES == 1 || STAGES == 2, "one or two LDS stages");
+    // EPI_LN_BWD: one LDS region per 64-row group of 256 threads, carved from the dead operand stages
+    constexpr int RG = NT / 256;
+    constexpr int LN_NEED = EPI == EPI_LN_BWD ? 16 * 2 * BN * 4 : 0;
+    constexpr int LDS_BYTES = STAGES * ST > RG * LN_NEED ? STAGES * ST : RG * LN_NEED;
+    __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
     char* As = lds;
     char* Bs = lds + NPL * PA;
 
@@ -260,11 +272,11 @@ __device__ __forceinline__ void gemm_x6_body(const GemmP& g) {
 
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.A), 0, (int)g.a_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.B), 0, (int)g.b_bytes, 0x00020000);
-    // per-operand staging state: k-contiguous operands use StageRegs / OffKC (all 256 threads),
+    // per-operand staging state: k-contiguous operands use StageRegs / OffKC (all NT threads),
     // k-strided ones the 4x4 task map (A tasks on threads [0, 2 BM), B tasks on [256 - 2 BN, 256))
-    StageRegs<A_KC ? BM : 32> sa;
-    StageRegs<B_KC ? BN : 32> sb;
-    OffKC<A_KC ? BM : 32> oa; OffKC<B_KC ? BN : 32> ob;
+    StageRegs<A_KC ? BM : 32, NT> sa;
+    StageRegs<B_KC ? BN : 32, NT> sb;
+    OffKC<A_KC ? BM : 32, NT> oa; OffKC<B_KC ? BN : 32, NT> ob;
     constexpr int TA = 2 * BM, TB0 = 256 - 2 * BN;
     static_assert((A_KC || TA <= 256) && (B_KC || TB0 >= 0), "tile too large for the k-strided task map");
     const bool has_a = !A_KC && t < TA, has_b = !B_KC && t >= TB0;
@@ -273,37 +285,31 @@ __device__ __forceinline__ void gemm_x6_body(const GemmP& g) {
     unsigned cola = OOB, colb = OOB;
     float cs[4] = {0.f, 0.f, 0.f, 0.f};          // EPI_SLAB bias partial: column sums of A over this thread's k rows
     const bool want_colsum = (EPI == EPI_SLAB) && !A_KC && g.slab_bias != nullptr && bn0 == 0;
-    if constexpr (A_KC) init_kc<BM>(oa, g.lda, bm0, g.M, t);
+    if constexpr (A_KC) init_kc<BM, NT>(oa, g.lda, bm0, g.M, t);
     else if (has_a && bm0 + 4 * mqa < g.M) cola = (unsigned)(bm0 + 4 * mqa) << 2;
-    if constexpr (B_KC) init_kc<BN>(ob, g.ldb, bn0, g.N, t);
+    if constexpr (B_KC) init_kc<BN, NT>(ob, g.ldb, bn0, g.N, t);
     else if (has_b && bn0 + 4 * mqb < g.N) colb = (unsigned)(bn0 + 4 * mqb) << 2;
     auto gload = [&](int kt) {
-        if constexpr (A_KC) load_kc_fast<BM>(sa, rsA, oa, kt << 5, g.K, t);
+        if constexpr (A_KC) load_kc_fast<BM, NT>(sa, rsA, oa, kt << 5, g.K, t);
         else if (has_a) x6_load_ks(ba, rsA, cola, (unsigned)g.lda << 2, kt << 5, g.K, kga, g.a_seg, g.a_stride, g.a_off);
-        if constexpr (B_KC) load_kc_fast<BN>(sb, rsB, ob, kt << 5, g.K, t);
+        if constexpr (B_KC) load_kc_fast<BN, NT>(sb, rsB, ob, kt << 5, g.K, t);
         else if (has_b) x6_load_ks(bb, rsB, colb, (unsigned)g.ldb << 2, kt << 5, g.K, kgb, 0, 0, 0);
     };
-    auto lstore = [&]() {
+    auto lstore = [&](int so) {         // so: byte offset of the LDS stage
         if constexpr (A_KC) {
-            x6_store<BM, NPL>(sa, As, t);
+            x6_store<BM, NPL, NT>(sa, As + so, t);
         } else if (has_a) {
             if (want_colsum) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) cs[e] += (ba.v[0][e] + ba.v[1][e]) + (ba.v[2][e] + ba.v[3][e]);
             }
-            x6_store_ks<NPL>(ba, As, PA, mqa, kga);
+            x6_store_ks<NPL>(ba, As + so, PA, mqa, kga);
         }
-        if constexpr (B_KC) x6_store<BN, NPL>(sb, Bs, t);
-        else if (has_b) x6_store_ks<NPL>(bb, Bs, PB, mqb, kgb);
+        if constexpr (B_KC) x6_store<BN, NPL, NT>(sb, Bs + so, t);
+        else if (has_b) x6_store_ks<NPL>(bb, Bs + so, PB, mqb, kgb);
     };
 
-    if (kt_begin < kt_end) {
-        gload(kt_begin);
-        lstore();
-    }
-    __syncthreads();
-
-    auto mfma_tile = [&]() {
+    auto mfma_tile = [&](int so) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 a[WM][NPL], b[WN][NPL];
@@ -311,12 +317,12 @@ __device__ __forceinline__ void gemm_x6_body(const GemmP& g) {
             for (int i = 0; i < WM; ++i)
 #pragma unroll
                 for (int pl = 0; pl < NPL; ++pl)
-                    a[i][pl] = *reinterpret_cast<const bf16x8*>(As + pl * PA + x6_chunk_off(wm0 + i * 32 + r, 2 * ks + h));
+                    a[i][pl] = *reinterpret_cast<const bf16x8*>(As + so + pl * PA + x6_chunk_off(wm0 + i * 32 + r, 2 * ks + h));
 #pragma unroll
             for (int j = 0; j < WN; ++j)
 #pragma unroll
                 for (int pl = 0; pl < NPL; ++pl)
-                    b[j][pl] = *reinterpret_cast<const bf16x8*>(Bs + pl * PB + x6_chunk_off(wn0 + j * 32 + r, 2 * ks + h));
+                    b[j][pl] = *reinterpret_cast<const bf16x8*>(Bs + so + pl * PB + x6_chunk_off(wn0 + j * 32 + r, 2 * ks + h));
 #pragma unroll
             for (int i = 0; i < WM; ++i)
 #pragma unroll
@@ -337,16 +343,43 @@ __device__ __forceinline__ void gemm_x6_body(const GemmP& g) {
     // The steady-state loop body is branch-free (the last k-tile is peeled): with a conditional
     // prefetch inside, hipcc carries the accumulators through VGPRs and copies all of them
     // AGPR -> VGPR -> AGPR on every iteration.
-    for (int kt = kt_begin; kt + 1 < kt_end; ++kt) {
-        gload(kt + 1);
-        __builtin_amdgcn_sched_barrier(0);      // loads first, then the whole MFMA phase, and only then the split
-        mfma_tile();                            // (left alone, hipcc interleaves load -> vmcnt(0) -> split into the MFMAs)
-        __builtin_amdgcn_sched_barrier(0);
+    if constexpr (STAGES == 1) {
+        if (kt_begin < kt_end) {
+            gload(kt_begin);
+            lstore(0);
+        }
         __syncthreads();
-        lstore();
+        for (int kt = kt_begin; kt + 1 < kt_end; ++kt) {
+            gload(kt + 1);
+            __builtin_amdgcn_sched_barrier(0);      // loads first, then the whole MFMA phase, and only then the split
+            mfma_tile(0);                           // (left alone, hipcc interleaves load -> vmcnt(0) -> split into the MFMAs)
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();
+            lstore(0);
+            __syncthreads();
+        }
+        if (kt_begin < kt_end) mfma_tile(0);
+    } else {
+        // k-tile kt + 1 goes to the other stage while kt is multiplied; the stage written here was last read before the
+        // previous barrier
+        if (kt_begin < kt_end) {
+            gload(kt_begin);
+            lstore(0);
+            if (kt_begin + 1 < kt_end) gload(kt_begin + 1);
+        }
         __syncthreads();
+        int so = 0;
+        for (int kt = kt_begin; kt + 1 < kt_end; ++kt) {
+            lstore(ST - so);
+            gload(kt + 2 < kt_end ? kt + 2 : kt + 1);             // past the range: re-read (never stored), branch-free
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_tile(so);
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();
+            so = ST - so;
+        }
+        if (kt_begin < kt_end) mfma_tile(so);
     }
-    if (kt_begin < kt_end) mfma_tile();
     if constexpr (EPI == EPI_SLAB && !A_KC) {
         if (want_colsum && has_a) {              // the 8 k-groups of a column quad are 8 consecutive lanes
 #pragma unroll
@@ -359,8 +392,12 @@ __device__ __forceinline__ void gemm_x6_body(const GemmP& g) {
         }
     }
     if constexpr (EPI == EPI_LN_BWD) {
-        static_assert(A_KC && B_KC && WM == 1, "EPI_LN_BWD: NT GEMM, one accumulator row per wave");
-        x6_ln_bwd_epilogue<WN, WAVES_M, WAVES_N, (int)sizeof(lds)>(g, acc, lds, bm0, wm0, wn0, r, h, tm);
+        static_assert(A_KC && B_KC && WM == 1 && WAVES_M % RG == 0, "EPI_LN_BWD: NT GEMM, one accumulator row per wave");
+        // row group gi = threads [256 gi, 256 gi + 256) = wave rows [gi WAVES_M / RG, (gi + 1) WAVES_M / RG)
+        constexpr int GM = WAVES_M / RG * 32, RGS = (LDS_BYTES / RG) & ~15;
+        const int gi = t >> 8;
+        x6_ln_bwd_epilogue<WN, WAVES_M / RG, WAVES_N, RGS>(g, acc, lds + gi * RGS, bm0 + gi * GM, wm0 - gi * GM, wn0, r, h,
+                                                           tm * RG + gi, t & 255);
     } else {
         gemm_epilogue<WM, WN, EPI>(g, acc, bm0 + wm0, bn0 + wn0, r, h, z);
     }
@@ -377,6 +414,15 @@ __global__ __launch_bounds__(256) void gemm_x6_kernel(const GemmP g) {
 template <int WN, int WAVES_M, int WAVES_N, int NPL>
 __global__ __launch_bounds__(256, 2) void gemm_x6_ln_kernel(const GemmP g) {
     gemm_x6_body<true, true, 1, WN, WAVES_M, WAVES_N, EPI_LN_BWD, NPL>(g);
+}
+
+// Wide form for the encoder in the three-product mode: 192 x 192 tiles of 12 waves (three 64-row groups of 2 x 2 waves of
+// 32 x 96, one workgroup per CU, two operand stages), so the transposed weight is staged and split once per 192 rows
+// instead of once per 64.  Each row group runs the epilogue above on its own LDS region and writes the partial of its
+// 64-row block: dX and the partials are bitwise those of gemm_x6_ln_kernel<3, 2, 2, NPL>.
+template <int WN, int WAVES_M, int WAVES_N, int NPL>
+__global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_x6_ln_wide_kernel(const GemmP g) {
+    gemm_x6_body<true, true, 1, WN, WAVES_M, WAVES_N, EPI_LN_BWD, NPL, WAVES_M * WAVES_N * 64, 2>(g);
 }
 
 }  // namespace vsom

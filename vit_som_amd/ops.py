@@ -188,6 +188,22 @@ def get_wgrad_tiles() -> int:
     return _wgrad_tiles
 
 
+def set_ln_tiles(mode):
+    """Test / measurement hook (include/vitsom_hip.h, vsom_set_ln_tiles) of the LayerNorm-fused input-gradient GEMM at the
+    encoder width: 0 = 64 x 192 tiles, 1 = 192 x 192 tiles (default; bitwise the same dX and partials)."""
+    global _ln_tiles
+    check(lib.vsom_set_ln_tiles(int(mode)), "vsom_set_ln_tiles")
+    _ln_tiles = int(mode)
+
+
+_ln_tiles = 1
+
+
+def get_ln_tiles() -> int:
+    """The value last set through set_ln_tiles (the library's default otherwise)."""
+    return _ln_tiles
+
+
 def linear_bwd_weight(dy, x, dW, db):
     M, N = dy.shape
     K = x.shape[1]

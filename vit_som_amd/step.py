@@ -52,7 +52,7 @@ class _StepTape:
 
     @staticmethod
     def _key(m):
-        return (ops.get_gemm_mode(), ops.get_attention_fused(), ops.get_wgrad_tiles(), hooks.signature(), m.world_size, m._use_vsom_comm, ops.stream())
+        return (ops.get_gemm_mode(), ops.get_attention_fused(), ops.get_wgrad_tiles(), ops.get_ln_tiles(), hooks.signature(), m.world_size, m._use_vsom_comm, ops.stream())
 
     @classmethod
     @torch.no_grad()
