@@ -38,28 +38,10 @@ struct BmuP {
     unsigned x_bytes, w_bytes;
 };
 
-// k-contiguous fp32 tile ROWS x 32 staged by NT threads: thread t loads float4 (row = p * (NT / 8) + t / 8, k = (t % 8) * 4)
-template <int ROWS, int NT> struct X3Stage { f32x4 v[ROWS / (NT / 8)]; };
-template <int ROWS, int NT> struct X3Off { unsigned off[ROWS / (NT / 8)]; };
-template <int ROWS, int NT>
-__device__ __forceinline__ void x3_init(X3Off<ROWS, NT>& o, long ld, int row0, int nrows, int t) {
-#pragma unroll
-    for (int p = 0; p < ROWS / (NT / 8); ++p) {
-        const int row = row0 + p * (NT / 8) + (t >> 3);
-        o.off[p] = (row < nrows) ? (unsigned)(((long)row * ld + ((t & 7) << 2)) << 2) : OOB;
-    }
-}
-template <int ROWS, int NT>
-__device__ __forceinline__ void x3_load(X3Stage<ROWS, NT>& s, __amdgpu_buffer_rsrc_t rsrc, const X3Off<ROWS, NT>& o, int k0, int K, int t) {
-    const bool kok = k0 + ((t & 7) << 2) < K;
-    const unsigned kbytes = (unsigned)k0 << 2;
-#pragma unroll
-    for (int p = 0; p < ROWS / (NT / 8); ++p) s.v[p] = bload4(rsrc, (kok && o.off[p] != OOB) ? o.off[p] + kbytes : OOB);
-}
-
-// tile (WAVES_M WM 32) x (WAVES_N WN 32) x 32; LDS: 2 planes x (BM + BN) rows x 64 B (swizzled image of gemm_x6.h).  The split costs ~18 VALU per
-// float4 against 3 (not 6) MFMAs per 16-deep step, so the tile has to be LARGE to keep the loop off the VALU issue
-// limit: 7.5 VALU per MFMA at 128 x 128 (measured 89 us, issue-bound), 3.5 at 256 x 192.
+// tile (WAVES_M WM 32) x (WAVES_N WN 32) x 32; LDS: 2 planes x (BM + BN) rows x 64 B (swizzled image of gemm_x6.h), the
+// staging, k-loop and products of gemm_x6.h.  The split costs ~18 VALU per float4 against 3 (not 6) MFMAs per
+// 16-deep step, so the tile has to be LARGE to keep the loop off the VALU issue limit: 7.5 VALU per MFMA at 128 x 128
+// (measured 89 us, issue-bound), 3.5 at 256 x 192.
 template <int WM, int WN, int WAVES_M, int WAVES_N>
 __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void bmu_x3_kernel(const BmuP g) {
     constexpr int BM = WAVES_M * WM * 32, BN = WAVES_N * WN * 32, NT = WAVES_M * WAVES_N * 64, RPP = NT / 8;
@@ -90,22 +72,22 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void bmu_x3_kernel(const Bm
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.X), 0, (int)g.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.W), 0, (int)g.w_bytes, 0x00020000);
     // (a second staging register set -- two k-tiles of loads in flight -- measured slower: 95 vs 87 us at 128 x 128)
-    X3Stage<BM, NT> sa0; X3Stage<BN, NT> sb0;
-    X3Off<BM, NT> oa; X3Off<BN, NT> ob;
-    x3_init<BM, NT>(oa, g.ldx, bm0, g.B, t);
-    x3_init<BN, NT>(ob, g.L, bn0, g.K, t);
-    const bool want_x = tn == 0, want_w = tm == 0;            // squared-norm partials: one column / row of tiles
+    StageRegs<BM, NT> sa; StageRegs<BN, NT> sb;
+    OffKC<BM, NT> oa; OffKC<BN, NT> ob;
+    init_kc<BM, NT>(oa, g.ldx, bm0, g.B, t);
+    init_kc<BN, NT>(ob, g.L, bn0, g.K, t);
+    const bool want_x = tn == 0, want_w = tm == 0;      // squared-norm partials: one column / row of tiles
     float ssa[BM / RPP], ssb[BN / RPP];
 #pragma unroll
     for (int p = 0; p < BM / RPP; ++p) ssa[p] = 0.f;
 #pragma unroll
     for (int p = 0; p < BN / RPP; ++p) ssb[p] = 0.f;
 
-    auto gload = [&](X3Stage<BM, NT>& sa, X3Stage<BN, NT>& sb, int kt) {       // kt beyond the range: k >= L -> zeros (never stored)
-        x3_load<BM, NT>(sa, rsA, oa, kt << 5, g.L, t);
-        x3_load<BN, NT>(sb, rsB, ob, kt << 5, g.L, t);
+    auto gload = [&](int kt) {             // kt beyond the range: k >= L -> zeros (never stored)
+        load_kc_fast<BM, NT>(sa, rsA, oa, kt << 5, g.L, t);
+        load_kc_fast<BN, NT>(sb, rsB, ob, kt << 5, g.L, t);
     };
-    auto lstore = [&](const X3Stage<BM, NT>& sa, const X3Stage<BN, NT>& sb) {
+    auto lstore = [&](int) {
 #pragma unroll
         for (int p = 0; p < BM / RPP; ++p) {
             const f32x4 v = sa.v[p];
@@ -127,7 +109,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void bmu_x3_kernel(const Bm
             *reinterpret_cast<uint2*>(dst + PB) = p2;
         }
     };
-    auto mfma_tile = [&]() {
+    auto mfma_tile = [&](int) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 a[WM][2], b[WN][2];
@@ -144,30 +126,10 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void bmu_x3_kernel(const Bm
 #pragma unroll
             for (int i = 0; i < WM; ++i)
 #pragma unroll
-                for (int j = 0; j < WN; ++j) {
-                    f32x16 c = acc[i][j];
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][0], c, 0, 0, 0);   // 2^-9 terms
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][0], c, 0, 0, 0);   // leading term
-                    acc[i][j] = c;
-                }
+                for (int j = 0; j < WN; ++j) x6_products<2>(acc[i][j], a[i], b[j]);
         }
     };
-    if (kt_begin < kt_end) {
-        gload(sa0, sb0, kt_begin);
-        lstore(sa0, sb0);
-    }
-    __syncthreads();
-    for (int kt = kt_begin; kt + 1 < kt_end; ++kt) {       // branch-free body, last k-tile peeled (gemm_x6.h)
-        gload(sa0, sb0, kt + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_tile();
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();
-        lstore(sa0, sb0);
-        __syncthreads();
-    }
-    if (kt_begin < kt_end) mfma_tile();
+    X6_KLOOP(1, 2 * (PA + PB), kt_begin, kt_end, gload, lstore, mfma_tile);
 
     // squared-norm partials: the 8 threads of a row are 8 consecutive lanes
     if (want_x) {
@@ -417,7 +379,7 @@ __global__ __launch_bounds__(256) void bmu_x3_finalize_kernel(const float* __res
 //     buffer_load_dwordx4 ... lds (1 KB pieces, no VGPRs, no VALU) -> ds_read_b128 (lane-linear, conflict-free) -> MFMA
 // over a ring of four 16-deep stages (28 KB each), DMA three stages ahead with counted vmcnt, ONE barrier per stage, the
 // fragments of stage s + 1 read under the MFMAs of stage s (register double buffer), everything that is not an MFMA issued
-// between the three MFMA groups of a stage.  Same products, same order, same reduction split as bmu_x3_kernel<2,3,4,2>:
+// between the three MFMA groups of a stage.  Same products, same order (x6_products<2>), same reduction split as bmu_x3_kernel<2,3,4,2>:
 // the slabs are bit-identical (lab/bmu_planes_lab.hip checks that), so distances and BMUs are too, up to the last bit of
 // the row norms (their partial sums are cut at other places).
 constexpr int PL_CHUNK = 64;                       // k per workgroup of the image writer (4 stages)
@@ -598,7 +560,7 @@ __global__ __launch_bounds__(512) void bmu_x3_planes_kernel(const BmuPlP g) {
 
     const unsigned a_in_stage = (unsigned)(wmi * WM * 2048 + lane * 16), b_in_stage = (unsigned)(PL_RA * 2048 + wni * WN * 2048 + lane * 16);
     PlFrags f0, f1;
-    // product P of the three (a2 b1, a1 b2, a1 b1 -- smallest first, the order of bmu_x3_kernel) for the six tiles of the wave
+    // product P of the three (a2 b1, a1 b2, a1 b1 -- smallest first, the order of x6_products<2>) for the six tiles of the wave
     auto mfma_group = [&](const PlFrags& f, auto P) {
         constexpr int PA_ = P.value == 0 ? 1 : 0, PB_ = P.value == 1 ? 1 : 0;
 #pragma unroll

@@ -24,6 +24,8 @@
 // MFMA: lane (r = l & 31, h = l >> 5) supplies A[row r][k = 8h + j] and B[k = 8h + j][col r],
 // j = 0..7 -- one 16-byte LDS read per plane per 16-k step; the accumulator layout equals the
 // fp32 MFMA's, so the epilogues are shared.
+// One definition each, used by gemm_x6_body, gemm_x6_tn_kernel (gemm_x6_tn.h) and bmu_x3_kernel (bmu_x3.hip): the MFMA
+// order (x6_products) and the k-loop with its LDS stages and sched_barriers (X6_KLOOP).
 #pragma once
 #include "gemm_f32.h"
 #include "layernorm_bwd.h"
@@ -115,6 +117,77 @@ __device__ __forceinline__ void x6_store_ks(const X6Blk& b, char* planes, int pl
         if constexpr (NPL == 3) *reinterpret_cast<uint2*>(dst + 2 * plane_bytes) = p3;
     }
 }
+
+// The MFMA order of the split-bf16 engine, written only here: acc += a * b over the NPL planes, smallest terms first
+// (NPL = 3: the six products with i + j <= 4; NPL = 2: a2 b1 + a1 b2 + a1 b1).  The wide tile forms (gemm_x6_ln_wide_kernel,
+// gemm_x6_tn_kernel<..., STAGES = 2>) are bitwise their narrow forms and bmu_x3_planes_kernel's slabs bitwise
+// bmu_x3_kernel's only because every kernel sums each output element in this order.
+template <int NPL>
+__device__ __forceinline__ void x6_products(f32x16& acc, const bf16x8 (&a)[NPL], const bf16x8 (&b)[NPL]) {
+    f32x16 c = acc;
+    if constexpr (NPL == 3) {
+        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);   // 2^-16 terms
+        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
+    }
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);       // 2^-8 (2^-9) terms
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);       // leading term
+    acc = c;
+}
+
+// The k-loop of the split-bf16 kernels over k-tiles [kt_begin, kt_end): gload(kt) loads k-tile kt into the staging
+// registers, lstore(so) splits them into the LDS stage at byte offset so, mfma_tile(so) multiplies that stage.
+// STAGES = 1: one LDS stage (so = 0), two barriers per k-tile; the next k-tile's loads are in flight under the MFMAs.
+// STAGES = 2: two stages ST bytes apart, one barrier per k-tile: k-tile kt + 1 goes to the other stage while kt is
+// multiplied; the stage written was last read before the previous barrier.  Past the range the last k-tile is re-read
+// (never stored), so the body stays branch-free.
+// The steady-state body is branch-free and the last k-tile is peeled: with a conditional prefetch inside, hipcc carries the
+// accumulators through VGPRs and copies all of them AGPR -> VGPR -> AGPR on every iteration.  The sched_barriers keep the
+// loads first, then the whole MFMA phase, and only then the split (left alone, hipcc interleaves load -> vmcnt(0) -> split
+// into the MFMAs).
+// A macro, not a function template taking the three lambdas: hipcc optimises such a function on its own before inlining
+// it, and the kernels then come out rescheduled (gemm_x6_body's, the two-stage ones with other instruction counts).  As
+// a macro the loop is the kernel's own code and every kernel compiles to the instructions of its former hand-written loop.
+#define X6_KLOOP(STAGES, ST, kt_begin, kt_end, gload, lstore, mfma_tile)                                                    \
+    do {                                                                                                                    \
+        static_assert((STAGES) == 1 || (STAGES) == 2, "one or two LDS stages");                                            \
+        if constexpr ((STAGES) == 1) {                                                                                      \
+            if ((kt_begin) < (kt_end)) {                                                                                    \
+                gload(kt_begin);                                                                                            \
+                lstore(0);                                                                                                  \
+            }                                                                                                               \
+            __syncthreads();                                                                                                \
+            for (int kt_ = (kt_begin); kt_ + 1 < (kt_end); ++kt_) {                                                         \
+                gload(kt_ + 1);                                                                                             \
+                __builtin_amdgcn_sched_barrier(0);                                                                          \
+                mfma_tile(0);                                                                                               \
+                __builtin_amdgcn_sched_barrier(0);                                                                          \
+                __syncthreads();                                                                                            \
+                lstore(0);                                                                                                  \
+                __syncthreads();                                                                                            \
+            }                                                                                                               \
+            if ((kt_begin) < (kt_end)) mfma_tile(0);                                                                        \
+        } else {                                                                                                            \
+            if ((kt_begin) < (kt_end)) {                                                                                    \
+                gload(kt_begin);                                                                                            \
+                lstore(0);                                                                                                  \
+                if ((kt_begin) + 1 < (kt_end)) gload((kt_begin) + 1);                                                       \
+            }                                                                                                               \
+            __syncthreads();                                                                                                \
+            int so_ = 0;                                                                                                    \
+            for (int kt_ = (kt_begin); kt_ + 1 < (kt_end); ++kt_) {                                                         \
+                lstore((ST) - so_);                                                                                         \
+                gload(kt_ + 2 < (kt_end) ? kt_ + 2 : kt_ + 1);                                                              \
+                __builtin_amdgcn_sched_barrier(0);                                                                          \
+                mfma_tile(so_);                                                                                             \
+                __builtin_amdgcn_sched_barrier(0);                                                                          \
+                __syncthreads();                                                                                            \
+                so_ = (ST) - so_;                                                                                           \
+            }                                                                                                               \
+            if ((kt_begin) < (kt_end)) mfma_tile(so_);                                                                      \
+        }                                                                                                                   \
+    } while (0)
 
 // ---- EPI_LN_BWD: the LayerNorm backward of whole output rows (one column tile, BN = the LayerNorm's width).  After the k-loop
 // the operand LDS is dead: the accumulators pass through it 8 rows per wave row at a time (register v of a 32x32 accumulator
@@ -221,8 +294,8 @@ __device__ __forceinline__ void x6_ln_bwd_epilogue(const GemmP& g, const f32x16 
 }
 
 // NPL = 3: exact three-piece split, six products; NPL = 2: two-piece round-to-nearest split, three products (x3_split above).
-// NT threads (WAVES_M * WAVES_N waves; k-strided operands need 256); STAGES = 2: two LDS operand stages, one barrier per
-// k-tile (as gemm_x6_tn.h).  The per-element k order and MFMA order do not depend on NT, STAGES or the tile height.
+// NT threads (WAVES_M * WAVES_N waves; k-strided operands need 256); STAGES: LDS operand stages of X6_KLOOP.  The
+// per-element k order and MFMA order (x6_products) do not depend on NT, STAGES or the tile height.
 template <bool A_KC, bool B_KC, int WM, int WN, int WAVES_M, int WAVES_N, int EPI, int NPL = 3, int NT = 256, int STAGES = 1>
 __device__ __forceinline__ void gemm_x6_body(const GemmP& g) {
     constexpr int BM = WAVES_M * WM * 32;
@@ -230,7 +303,6 @@ __device__ __forceinline__ void gemm_x6_body(const GemmP& g) {
     constexpr int PA = BM * X6_RS, PB = BN * X6_RS;
     constexpr int ST = NPL * (PA + PB);                         // bytes of one operand stage
     static_assert(NT == WAVES_M * WAVES_N * 64 && (NT == 256 || (A_KC && B_KC)), "thread count");
-    static_assert(STAGES == 1 || STAGES == 2, "one or two LDS stages");
     // EPI_LN_BWD: one LDS region per 64-row group of 256 threads, carved from the dead operand stages
     constexpr int RG = NT / 256;
     constexpr int LN_NEED = EPI == EPI_LN_BWD ? 16 * 2 * BN * 4 : 0;
@@ -326,60 +398,10 @@ __device__ __forceinline__ void gemm_x6_body(const GemmP& g) {
 #pragma unroll
             for (int i = 0; i < WM; ++i)
 #pragma unroll
-                for (int j = 0; j < WN; ++j) {
-                    f32x16 c = acc[i][j];
-                    if constexpr (NPL == 3) {
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][2], b[j][0], c, 0, 0, 0);   // 2^-16 terms
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][2], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][1], c, 0, 0, 0);
-                    }
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][0], c, 0, 0, 0);   // 2^-8 (2^-9) terms
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][0], c, 0, 0, 0);   // leading term
-                    acc[i][j] = c;
-                }
+                for (int j = 0; j < WN; ++j) x6_products<NPL>(acc[i][j], a[i], b[j]);
         }
     };
-    // The steady-state loop body is branch-free (the last k-tile is peeled): with a conditional
-    // prefetch inside, hipcc carries the accumulators through VGPRs and copies all of them
-    // AGPR -> VGPR -> AGPR on every iteration.
-    if constexpr (STAGES == 1) {
-        if (kt_begin < kt_end) {
-            gload(kt_begin);
-            lstore(0);
-        }
-        __syncthreads();
-        for (int kt = kt_begin; kt + 1 < kt_end; ++kt) {
-            gload(kt + 1);
-            __builtin_amdgcn_sched_barrier(0);      // loads first, then the whole MFMA phase, and only then the split
-            mfma_tile(0);                           // (left alone, hipcc interleaves load -> vmcnt(0) -> split into the MFMAs)
-            __builtin_amdgcn_sched_barrier(0);
-            __syncthreads();
-            lstore(0);
-            __syncthreads();
-        }
-        if (kt_begin < kt_end) mfma_tile(0);
-    } else {
-        // k-tile kt + 1 goes to the other stage while kt is multiplied; the stage written here was last read before the
-        // previous barrier
-        if (kt_begin < kt_end) {
-            gload(kt_begin);
-            lstore(0);
-            if (kt_begin + 1 < kt_end) gload(kt_begin + 1);
-        }
-        __syncthreads();
-        int so = 0;
-        for (int kt = kt_begin; kt + 1 < kt_end; ++kt) {
-            lstore(ST - so);
-            gload(kt + 2 < kt_end ? kt + 2 : kt + 1);             // past the range: re-read (never stored), branch-free
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_tile(so);
-            __builtin_amdgcn_sched_barrier(0);
-            __syncthreads();
-            so = ST - so;
-        }
-        if (kt_begin < kt_end) mfma_tile(so);
-    }
+    X6_KLOOP(STAGES, ST, kt_begin, kt_end, gload, lstore, mfma_tile);
     if constexpr (EPI == EPI_SLAB && !A_KC) {
         if (want_colsum && has_a) {              // the 8 k-groups of a column quad are 8 consecutive lanes
 #pragma unroll

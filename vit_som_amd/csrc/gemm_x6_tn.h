@@ -12,8 +12,11 @@
 // Tiles 192 x 64 or 96 x 96 (outputs x 32 t per step; 4 / 3 waves), one k-tile of global loads in flight under the
 // MFMAs, two workgroups per CU (41 / 61 KB LDS for two / three planes).  Wide form for the three-product mode: 192 x 192
 // tiles (12 waves of 96 x 32), so every operand byte is streamed from L2 into LDS half as often; two LDS stages
-// (112 KB, one workgroup per CU) and one barrier per k-tile.  Each output element sums the same k-tiles in the same MFMA
-// order whatever the tile shape, so at equal ktiles_per_split the slabs are bitwise those of the narrow form.
+// (112 KB, one workgroup per CU) and one barrier per k-tile.  The k-loop (X6_KLOOP) and the MFMA order (x6_products) are
+// gemm_x6.h's; what is this kernel's own is the [t][column] LDS image, its transposed fragment reads, the bias column sums
+// and the slab layout.  Each output element sums the same
+// k-tiles in the same MFMA order whatever the tile shape, so at equal ktiles_per_split the slabs are bitwise those of the
+// narrow form.
 // The reduction over t is split over workgroups;
 // partial tiles go to fp32 slabs summed by reduce_slabs in fixed order (bitwise reproducible).
 // The bias gradient rides along: the dY tile passes through this thread's registers anyway, so the
@@ -53,14 +56,13 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_x6_tn_kernel(cons
     constexpr int SA = tn_stride(BM), SB = tn_stride(BN), PA = 32 * SA, PB = 32 * SB;
     constexpr int FA = (32 * BM / 4 + NT - 1) / NT, FB = (32 * BN / 4 + NT - 1) / NT;
     static_assert(NPL * (PA + PB) >= NT * FA * 16, "LDS too small for the bias partials");
-    static_assert(STAGES == 1 || STAGES == 2, "one or two LDS stages");
     constexpr int ST = NPL * (PA + PB);             // bytes of one LDS stage
     __shared__ __attribute__((aligned(16))) char lds[STAGES * ST];
     char* As = lds; char* Bs = lds + NPL * PA;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm0 = (wave / WAVES_N) * WM * 32, wn0 = (wave % WAVES_N) * WN * 32;
-    const int tiles_n = g.KI / BN, tiles_m = g.NO / BM, ntiles = tiles_m * tiles_n;
     // split-major, XCD-contiguous: every XCD owns a slice of the token rows and reads it once
+    const int tiles_n = g.KI / BN, tiles_m = g.NO / BM, ntiles = tiles_m * tiles_n;
     const int lid = xcd_remap(blockIdx.x, gridDim.x);
     const int z = lid / ntiles, rem = lid - z * ntiles;
     const int bm0 = (rem / tiles_n) * BM, bn0 = (rem % tiles_n) * BN;
@@ -163,57 +165,10 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void gemm_x6_tn_kernel(cons
 #pragma unroll
             for (int i = 0; i < WM; ++i)
 #pragma unroll
-                for (int j = 0; j < WN; ++j) {
-                    f32x16 c = acc[i][j];
-                    if constexpr (NPL == 3) {
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][2], b[j][0], c, 0, 0, 0);   // 2^-16 terms
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][2], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][1], c, 0, 0, 0);
-                    }
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][0], c, 0, 0, 0);   // 2^-8 (2^-9) terms
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][0], c, 0, 0, 0);   // leading term
-                    acc[i][j] = c;
-                }
+                for (int j = 0; j < WN; ++j) x6_products<NPL>(acc[i][j], a[i], b[j]);
         }
     };
-    if constexpr (STAGES == 1) {
-        if (kt_begin < kt_end) {
-            gload(kt_begin);
-            lstore(0);
-        }
-        __syncthreads();
-        for (int kt = kt_begin; kt + 1 < kt_end; ++kt) {          // branch-free body, last k-tile peeled (see gemm_x6.h)
-            gload(kt + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_tile(0);
-            __builtin_amdgcn_sched_barrier(0);
-            __syncthreads();
-            lstore(0);
-            __syncthreads();
-        }
-        if (kt_begin < kt_end) mfma_tile(0);
-    } else {
-        // two LDS stages, one barrier per k-tile: k-tile kt + 1 goes to the other stage while kt is multiplied; the stage
-        // written here was last read before the previous barrier
-        if (kt_begin < kt_end) {
-            gload(kt_begin);
-            lstore(0);
-            if (kt_begin + 1 < kt_end) gload(kt_begin + 1);
-        }
-        __syncthreads();
-        int so = 0;
-        for (int kt = kt_begin; kt + 1 < kt_end; ++kt) {
-            lstore(ST - so);
-            gload(kt + 2 < kt_end ? kt + 2 : kt + 1);             // past the range: re-read (never stored), branch-free
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_tile(so);
-            __builtin_amdgcn_sched_barrier(0);
-            __syncthreads();
-            so = ST - so;
-        }
-        if (kt_begin < kt_end) mfma_tile(so);
-    }
+    X6_KLOOP(STAGES, ST, kt_begin, kt_end, gload, lstore, mfma_tile);
 
     if (want_colsum) {
         // fixed-order combine: every thread parks its FA column-quad partials, then thread c < BM sums the 32
