@@ -391,6 +391,39 @@ int vsom_kmeanspp_dist(const float* X, long ldx, long N, int D, const int64_t* c
 int vsom_kmeans_colvar(const float* X, long ldx, long N, int D, int k, double* out, void* ws, size_t ws_bytes,
                        vsom_stream_t stream);
 
+/* UMAP of visualize_umap_progression (evaluation.py:267-323; vit_som_amd/umap.py states the algorithm).  No
+ * floating-point atomics, every sum in one fixed order: a fit is bitwise reproducible.
+ * Exact k nearest neighbours of every row of X [N, D] (row stride ldx) among all rows: knn_idx int64 [N, k] and
+ * knn_dist f32 [N, k] ascending by (distance, index), row i itself first with distance 0 (its duplicates follow).
+ * metric VSOM_DIST_EUCLIDEAN: the true distance sqrt(max(|x|^2 + |y|^2 - 2 <x,y>, 0)); VSOM_DIST_COSINE:
+ * 1 - <x,y> / (|x| |y|) clamped at 0, 0 when both rows are zero and 1 when exactly one is.  <x,y> is an f32 matrix-core
+ * contraction; the squared norms are summed in its order, so identical rows are at distance exactly 0.
+ * 1 <= k <= 64, k < N.  Workspace: vsom_umap_knn_workspace_bytes(N, k) (host arithmetic; 0 for a non-positive size). */
+size_t vsom_umap_knn_workspace_bytes(long N, int k);
+int vsom_umap_knn(const float* X, long ldx, long N, int D, int k, int metric, int64_t* knn_idx, float* knn_dist, void* ws,
+                  size_t ws_bytes, vsom_stream_t stream);
+/* Negative sample p of edge `edge` in epoch `epoch` (host arithmetic, the function vsom_umap_epoch evaluates):
+ *   splitmix64(z) = z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *                   z ^ z >> 31                                                    (all mod 2^64)
+ *   sample = splitmix64(splitmix64(seed ^ edge) ^ (epoch << 32 | p)) mod N         (epoch, p < 2^32)
+ * -1 for a negative argument or N < 1. */
+long vsom_umap_neg_sample(uint64_t seed, int epoch, long edge, long p, long N);
+/* One layout epoch n = `epoch` of optimize_layout_euclidean (move_other) with synchronous updates.  The graph is a
+ * symmetric CSR (indptr int64 [N+1], indices int64); per edge e = (v, u) fp64 epochs_per_sample, epoch_of_next_sample,
+ * epochs_per_negative_sample, epoch_of_next_negative_sample (the two "next" arrays are updated in place).  Y_in / Y_out
+ * [N, dim] f32 (must not alias).  For every vertex v, in CSR order over its edges with next_e <= n:
+ *   attraction  d2 = |y_v - y_u|^2, c = -2ab d2^(b-1) / (a d2^b + 1) (0 if d2 == 0), term = clip(c (y_v - y_u), -4, 4)
+ *               per component, added twice (the reverse edge's "move other" update of v is the same term);
+ *   next_e += epochs_per_sample_e; n_neg = floor((n - next_neg_e) / epochs_per_negative_sample_e);
+ *   repulsion   for p < n_neg: s = vsom_umap_neg_sample(seed, n, e, p, N), d2 = |y_v - y_s|^2,
+ *               c = 2 gamma b / ((0.001 + d2)(a d2^b + 1)), term = clip(c (y_v - y_s), -4, 4); skipped when d2 == 0;
+ *   next_neg_e += n_neg * epochs_per_negative_sample_e;
+ * then Y_out[v] = y_v + alpha * (the terms summed in that order).  Every term reads Y_in.  1 <= dim <= 4. */
+int vsom_umap_epoch(const int64_t* indptr, const int64_t* indices, const double* epochs_per_sample,
+                    double* epoch_of_next_sample, const double* epochs_per_negative_sample,
+                    double* epoch_of_next_negative_sample, const float* Y_in, float* Y_out, long N, int dim, float a,
+                    float b, float gamma, float alpha, int epoch, uint64_t seed, vsom_stream_t stream);
+
 /* SOMLayer.som_loss(weights, distances) = mean(weights * distances) for ARBITRARY weights (som_layer.py:137-142):
    loss_sum <- sum_ik weights[i,k] dist[i,k]; with coef/row_dot/col_dot given, also the backward coefficients of
    grad_scale * that sum w.r.t. the distances' inputs (what vsom_som_bwd consumes) -- with weights = an upstream

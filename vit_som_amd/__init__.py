@@ -16,3 +16,4 @@ from .desom import DESOM, Autoencoder  # noqa: F401,E402
 from .classifier import ViTClassifier  # noqa: F401,E402
 from . import evaluation  # noqa: F401,E402
 from .kmeans import KMeans, kmeans_plusplus  # noqa: F401,E402
+from .umap import UMAP  # noqa: F401,E402

@@ -6,8 +6,10 @@ pairs are folded into a contingency table ON DEVICE batch by batch (`vsom_contin
 atomics), so the only device->host traffic of a whole evaluation pass is that table.  Purity, NMI
 (sklearn's arithmetic-mean normalisation) and the macro precision / recall / F1 are O(classes^2)
 host arithmetic on the table.  evaluate_kmeans keeps the model outputs in one device buffer and clusters them with
-the HIP k-means (kmeans.py).
+the HIP k-means (kmeans.py); visualize_umap_progression (:267-323) embeds the latent representations with the HIP
+UMAP (umap.py).
 """
+import os
 import time
 
 import numpy as np
@@ -15,6 +17,7 @@ import torch
 
 from . import ops
 from .kmeans import KMeans
+from .umap import UMAP
 
 
 class _Table:
@@ -184,6 +187,53 @@ def evaluate_kmeans(model, config, dataloader, num_labels=None):
     inference_time = time.time() - start
     print(f"Purity (KMeans): {purity:.3f}, NMI (KMeans): {nmi:.3f}, Inference Time: {inference_time:.3f}")
     return purity, nmi, inference_time
+
+
+def visualize_umap_progression(model, config, dataloader, epoch=0, output_dir="experiments/plots/vit_som/umap"):
+    """evaluation.py:267-323: UMAP(n_neighbors=15, min_dist=0.1, metric='cosine', random_state=42) of
+    model.get_latent_representation(x) over the whole set, fitted on the device (umap.py), drawn as the reference's
+    scatter plot into output_dir/som_umap_epoch_{epoch}.png (rank 0 only; skipped with a warning when matplotlib is
+    missing).  With model.world_size > 1 every rank gathers all rows and runs the same deterministic fit.  Returns
+    (embedding [N, 2] float32, labels [N]) as host arrays (the reference returns None)."""
+    model.eval()
+    d = config["data"]
+    C, S = d["num_channels"], d["input_size"]
+    dev = model.arena.device
+    lat, labels = [], []
+    with torch.no_grad():
+        for x, y in dataloader:
+            x = x.to(dev, non_blocking=True).reshape(-1, C, S, S)
+            y = y.to(dev, non_blocking=True)
+            z = model.get_latent_representation(x)
+            lat.append(z.reshape(z.shape[0], -1).float().clone())     # the model's buffers are reused by the next batch
+            labels.append(y.reshape(-1).long())
+    X, y = torch.cat(lat), torch.cat(labels)
+    world = _world(model)
+    if world > 1:
+        X, y = _gather_rows(X, world), _gather_rows(y, world)
+    reducer = UMAP(n_neighbors=15, min_dist=0.1, metric="cosine", random_state=42)
+    embedding = reducer.fit_transform(X.contiguous()).cpu().numpy()
+    all_labels = y.cpu().numpy()
+    if int(getattr(model, "rank", 0)) == 0:
+        try:
+            import matplotlib.pyplot as plt
+        except ImportError:
+            import warnings
+            warnings.warn("visualize_umap_progression: matplotlib is not installed; no plot written")
+            return embedding, all_labels
+        os.makedirs(output_dir, exist_ok=True)
+        plt.figure(figsize=(10, 8), dpi=300)
+        plt.axis("off")
+        scatter = plt.scatter(embedding[:, 0], embedding[:, 1], c=all_labels, cmap="tab10", s=3, alpha=0.7,
+                              edgecolor="none", rasterized=True)
+        cbar = plt.colorbar(scatter, ticks=range(10), drawedges=True)
+        cbar.set_ticklabels([str(i) for i in range(10)])
+        cbar.ax.tick_params(labelsize=10, width=0.5)
+        cbar.outline.set_linewidth(0.5)
+        plt.savefig(os.path.join(output_dir, f"som_umap_epoch_{epoch}.png"), bbox_inches="tight", pad_inches=0,
+                    transparent=False, dpi=400)
+        plt.close()
+    return embedding, all_labels
 
 
 def evaluate_classification(model, config, dataloader):

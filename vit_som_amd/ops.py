@@ -755,6 +755,43 @@ def kmeans_colvar(X, k, out, ws):
           "vsom_kmeans_colvar")
 
 
+# ---------------------------------------------------------------- UMAP (visualize_umap_progression)
+UMAP_MAX_K = 64                                                  # csrc/umap.hip: one list entry per lane
+
+
+def umap_knn(X, k, metric, knn_idx, knn_dist):
+    """knn_idx int64 [N, k] / knn_dist f32 [N, k]: the exact k nearest rows of X (row itself first), ascending by
+    (distance, index); metric DIST_EUCLIDEAN or DIST_COSINE."""
+    N, D, ldx = _kmeans_x(X)
+    assert knn_idx.dtype == torch.int64 and knn_idx.is_contiguous() and knn_idx.shape == (N, k)
+    _f32(knn_dist, "knn_dist")
+    assert knn_dist.is_contiguous() and knn_dist.shape == (N, k)
+    ws = scratch(lib.vsom_umap_knn_workspace_bytes(N, k), X.device)
+    check(lib.vsom_umap_knn(ptr(X), ldx, N, D, int(k), int(metric), ptr(knn_idx), ptr(knn_dist), ptr(ws), ws.numel(),
+                            stream()), "vsom_umap_knn")
+    return knn_idx, knn_dist
+
+
+def umap_neg_sample(seed, epoch, edge, p, N) -> int:
+    """The negative sample vsom_umap_epoch draws (host arithmetic)."""
+    return int(lib.vsom_umap_neg_sample(int(seed), int(epoch), int(edge), int(p), int(N)))
+
+
+def umap_epoch(indptr, indices, eps, next_s, eps_neg, next_neg, Y_in, Y_out, a, b, gamma, alpha, epoch, seed):
+    """One synchronous layout epoch: Y_out from Y_in; next_s / next_neg (fp64 per edge) updated in place."""
+    N, dim = Y_in.shape
+    _f32(Y_in, "Y_in"); _f32(Y_out, "Y_out")
+    assert Y_in.is_contiguous() and Y_out.is_contiguous() and Y_out.shape == (N, dim)
+    assert indptr.dtype == indices.dtype == torch.int64 and indptr.numel() == N + 1
+    nnz = indices.numel()
+    for t in (eps, next_s, eps_neg, next_neg):
+        assert t.dtype == torch.float64 and t.is_contiguous() and t.numel() == nnz and t.is_cuda
+    check(lib.vsom_umap_epoch(ptr(indptr), ptr(indices), ptr(eps), ptr(next_s), ptr(eps_neg), ptr(next_neg), ptr(Y_in),
+                              ptr(Y_out), N, dim, float(a), float(b), float(gamma), float(alpha), int(epoch), int(seed),
+                              stream()), "vsom_umap_epoch")
+    return Y_out
+
+
 # ---------------------------------------------------------------- data-parallel exchange (RCCL)
 COMM_ID_BYTES = 128
 
