@@ -357,6 +357,28 @@ int vsom_contingency(const int64_t* a, const int64_t* b, long n, int na, int nb,
 /* out[r] = first argmax_c X[r,c] -- torch.argmax(cls_logits, dim=1), evaluation.py:119 */
 int vsom_argmax_rows(const float* X, long ldx, int rows, int cols, int64_t* out, vsom_stream_t stream);
 
+/* Decoder output -> pictures, for visualize_decoded_prototypes (evaluation.py:153-222).  pred is what decoder_pred
+ * wrote for `chunk` images: [chunk * (n + 1), p*p*C] contiguous, a CLS row in front of each image's n = g*g patch rows.
+ * Image i of the chunk is prototype k0 + i of K.  The CLS row is dropped and unpatchify's index map (vit.py:141-153,
+ * nhwpqc -> nchpwq) applied; S = g * p.  Either or both outputs (the other NULL):
+ *   images  f32 [K, C, S, S]: images[k0 + i] = the unpatchified values, bit for bit;
+ *   canvas  uint8 RGB [rows*S + (rows-1)*gap, cols*S + (cols-1)*gap, 3], rows * cols == K: prototype k at cell
+ *           divmod(k, cols) (axes.flatten() order), level floor(255 t + 0.5) with t as imshow forms it:
+ *           C == 3: clip(v, 0, 1) per channel; C == 1: (v - min) / (max - min) over that image, on all three channels,
+ *           0 for a constant image.  Each image also writes the 255 strip to its right and below it (none at the
+ *           last column / row), so K images fill the whole canvas.
+ * Other channel counts: VSOM_EUNSUPPORTED. */
+int vsom_proto_mosaic(const float* pred, int chunk, int n, int p, int C, float* images, unsigned char* canvas, int k0,
+                      int K, int rows, int cols, int gap, vsom_stream_t stream);
+/* The label of the LAST sample that lands on each map cell (evaluation.py:254-258 `heatmap[divmod(bmu)] = label` in
+ * sample order), order-independent: cells[bmu[i]] = max(cells[bmu[i]], (first_ordinal + i + 1) << 32 | label[i]) for
+ * i < n (integer atomic max; zero `cells` [K] before the first batch; a cell never hit stays 0 and decodes to label 0).
+ * first_ordinal = the number of samples in the batches before this one; ordinals stay below 2^31, so the words are
+ * positive as int64 too and tables of several ranks combine with one MAX all-reduce.  A bmu outside [0, K) or a
+ * label outside [0, 2^31) is counted in out_of_range[0] and not written. */
+int vsom_last_label(const int64_t* bmu, const int64_t* label, long n, long first_ordinal, int K,
+                    unsigned long long* cells, int* out_of_range, vsom_stream_t stream);
+
 /* k-means of evaluate_kmeans (evaluation.py:54-91): the data-touching steps of sklearn.cluster.KMeans
  * (sklearn/cluster/_kmeans.py, algorithm="lloyd", dense fp32, unit sample weights).  X is [N, D] with row stride ldx;
  * centres are [k, D] contiguous; labels int64.  Every sum has a fixed order (no floating-point atomics): results are

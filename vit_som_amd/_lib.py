@@ -116,6 +116,9 @@ SIGNATURES = {
                                   C.c_int, C.c_float, C.c_int, c_stream]),
     "vsom_contingency": (C.c_int, [c_fp, c_fp, C.c_long, C.c_int, C.c_int, c_fp, c_fp, c_stream]),
     "vsom_argmax_rows": (C.c_int, [c_fp, C.c_long, C.c_int, C.c_int, c_fp, c_stream]),
+    "vsom_proto_mosaic": (C.c_int, [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, c_stream]),
+    "vsom_last_label": (C.c_int, [c_fp, c_fp, C.c_long, C.c_long, C.c_int, c_fp, c_fp, c_stream]),
     "vsom_kmeans_workspace_bytes": (C.c_size_t, [C.c_long, C.c_int, C.c_int]),
     "vsom_kmeans_assign": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_size_t,
                                      c_stream]),

@@ -7,7 +7,9 @@ atomics), so the only device->host traffic of a whole evaluation pass is that ta
 (sklearn's arithmetic-mean normalisation) and the macro precision / recall / F1 are O(classes^2)
 host arithmetic on the table.  evaluate_kmeans keeps the model outputs in one device buffer and clusters them with
 the HIP k-means (kmeans.py); visualize_umap_progression (:267-323) embeds the latent representations with the HIP
-UMAP (umap.py).
+UMAP (umap.py).  The two pictures of the map itself: visualize_decoded_prototypes / decode_prototype (:153-222) push the
+prototypes through the ViT decoder in batches and assemble the mosaic on the device (`vsom_proto_mosaic`);
+visualize_label_heatmap (:224-265) folds (BMU, label) pairs into a last-label-per-cell table (`vsom_last_label`).
 """
 import os
 import time
@@ -234,6 +236,145 @@ def visualize_umap_progression(model, config, dataloader, epoch=0, output_dir="e
                     transparent=False, dpi=400)
         plt.close()
     return embedding, all_labels
+
+
+def _pyplot(who):
+    """matplotlib.pyplot, or None with a warning when matplotlib is not installed (no plot is written then)."""
+    try:
+        import matplotlib.pyplot as plt
+        return plt
+    except ImportError:
+        import warnings
+        warnings.warn(f"{who}: matplotlib is not installed; no plot written")
+        return None
+
+
+def _epoch(model):
+    return getattr(model, "current_epoch", 0)
+
+
+def decode_prototype(vit, prototype, num_patches, embed_dim, device):
+    """evaluation.py:209-222 (same signature) -> recon_img [1, C, S, S] on the device: the prototype behind a zero CLS row
+    through the decoder, unpatchified.  Runs in the ViT's decoder-only buffers (ViTAutoencoder.decode_prototypes)."""
+    proto = prototype.to(device).reshape(1, num_patches * embed_dim)
+    images, _ = vit.decode_prototypes(proto, chunk=1, want_canvas=False)
+    return images
+
+
+def decoded_prototype_canvas(model, config, chunk=512, gap=1):
+    """The computing half of visualize_decoded_prototypes: every prototype decoded, `chunk` per decoder pass, and laid
+    out on the map grid on the device.  Returns (images [K, C, S, S] float32, canvas uint8 [H, W, 3]) as host arrays;
+    prototype k sits at cell divmod(k, cols), cells `gap` white pixels apart.  Writes no file."""
+    d, vit_hp = config["data"], config["hyperparameters"]["vit"]
+    prototypes = model.som_layer.prototypes.detach()
+    num_patches = (d["input_size"] // vit_hp["patch_size"]) ** 2
+    if prototypes.shape[1] != num_patches * vit_hp["emb_dim"]:
+        raise ValueError("Prototype dimensions mismatch for decoding.")
+    images, canvas = model.vit.decode_prototypes(prototypes, model.som_layer.map_size, chunk=chunk, gap=gap)
+    return images.cpu().numpy(), canvas.cpu().numpy()
+
+
+def draw_decoded_prototypes(canvas, output_dir, model_arch, epoch):
+    """One imshow of the mosaic, axis off -> {output_dir}/{model_arch}_epoch_{epoch}_decoded_prototypes.png (host only).
+    Returns the path, or None when matplotlib is missing."""
+    plt = _pyplot("visualize_decoded_prototypes")
+    if plt is None:
+        return None
+    os.makedirs(output_dir, exist_ok=True)
+    fig = plt.figure(figsize=(10, 10 * canvas.shape[0] / canvas.shape[1]))
+    plt.imshow(canvas, interpolation="nearest")
+    plt.axis("off")
+    path = os.path.join(output_dir, f"{model_arch}_epoch_{epoch}_decoded_prototypes.png")
+    plt.savefig(path, bbox_inches="tight")
+    plt.close(fig)
+    return path
+
+
+def visualize_decoded_prototypes(model, config, output_dir="experiments/plots", return_decoded=False, chunk=512, gap=1):
+    """evaluation.py:153-207: the SOM prototypes decoded into image space and drawn on the map grid.  The reference runs
+    one decoder pass and one Axes per prototype; here the prototypes go through the decoder `chunk` at a time and the
+    picture is ONE image assembled on the device (decoded_prototype_canvas), drawn by rank 0.  Returns the
+    [K, C, S, S] array when return_decoded, else None."""
+    model.eval()
+    hp = config["hyperparameters"]
+    model_arch = hp["model_arch"]
+    if model_arch != "vit_som" or hp.get("som", {}).get("use_reduced", False):
+        print("Visualization supported only for vit_som with use_reduced=False.")
+        return None
+    images, canvas = decoded_prototype_canvas(model, config, chunk=chunk, gap=gap)
+    if int(getattr(model, "rank", 0)) == 0:
+        if draw_decoded_prototypes(canvas, output_dir, model_arch, _epoch(model)) is not None:
+            print(f"Saved decoded prototypes visualization to {output_dir}")
+    return images if return_decoded else None
+
+
+def draw_label_heatmap(heatmap, output_dir, model_arch, epoch):
+    """The reference's sns.heatmap(annot=True, fmt="d", cmap="viridis") in plain matplotlib ->
+    {output_dir}/{model_arch}_epoch_{epoch}_label_heatmap.png (host only).  Returns the path, or None without matplotlib."""
+    plt = _pyplot("visualize_label_heatmap")
+    if plt is None:
+        return None
+    os.makedirs(output_dir, exist_ok=True)
+    fig = plt.figure(figsize=(10, 8))
+    im = plt.imshow(heatmap, cmap="viridis", aspect="auto")
+    plt.colorbar(im)
+    mid = 0.5 * (float(heatmap.min()) + float(heatmap.max()))
+    size = max(3.0, min(10.0, 200.0 / max(heatmap.shape)))
+    for (r, c), v in np.ndenumerate(heatmap):
+        plt.text(c, r, str(int(v)), ha="center", va="center", fontsize=size, color="white" if v <= mid else "black")
+    plt.xticks(range(heatmap.shape[1]))
+    plt.yticks(range(heatmap.shape[0]))
+    path = os.path.join(output_dir, f"{model_arch}_epoch_{epoch}_label_heatmap.png")
+    plt.savefig(path)
+    plt.close(fig)
+    return path
+
+
+def visualize_label_heatmap(model, config, dataloader, output_dir="experiments/plots"):
+    """evaluation.py:224-265: the ground-truth label that lands on each map cell, as an annotated heat-map.  Where several
+    samples hit a cell the LAST one in loader order wins, as in the reference's loop; the fold runs on the device
+    (`vsom_last_label`: an atomic max over (sample ordinal, label) words), one launch per batch and no host
+    synchronisation in the loop.  With model.world_size > 1 every rank folds its shard, ordinals are shifted so that rank
+    r's samples follow rank r - 1's, and one MAX all-reduce combines the tables.  Returns the int64 [rows, cols] array
+    of the whole set (the reference returns None); a cell no sample hit holds 0."""
+    model.eval()
+    d = config["data"]
+    C, S = d["num_channels"], d["input_size"]
+    model_arch = config["hyperparameters"]["model_arch"]
+    if model_arch not in ("vit_som", "desom"):
+        raise ValueError(f"visualize_label_heatmap: unknown model_arch {model_arch!r}")
+    rows, cols = model.som_layer.map_size
+    dev = model.arena.device
+    cells = torch.zeros(rows * cols, dtype=torch.int64, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    seen = 0
+    for x, y in dataloader:
+        x = x.to(dev, non_blocking=True)
+        y = y.to(dev, non_blocking=True).reshape(-1).long().contiguous()
+        x = x.reshape(-1, C, S, S) if model_arch == "vit_som" else x.reshape(x.shape[0], -1)
+        bmu, _ = model.predict(x)
+        ops.last_label(bmu.contiguous().view(-1), y, seen, cells, bad)
+        seen += y.numel()
+    world = _world(model)
+    if world > 1:
+        import torch.distributed as dist
+        counts = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(world)]
+        dist.all_gather(counts, torch.tensor([seen], dtype=torch.int64, device=dev))
+        before = sum(int(c) for c in counts[:int(getattr(model, "rank", 0))])
+        if sum(int(c) for c in counts) >= 2 ** 31:
+            raise ValueError("visualize_label_heatmap: more than 2^31 - 1 samples")
+        cells = torch.where(cells != 0, cells + (before << 32), cells)
+        dist.all_reduce(cells, op=dist.ReduceOp.MAX)
+        bad = bad.long()
+        dist.all_reduce(bad)
+    nbad = int(bad.item())
+    if nbad:
+        raise ValueError(f"{nbad} BMU indices fell outside the {rows} x {cols} map or labels outside [0, 2^31)")
+    heatmap = (cells & 0xFFFFFFFF).view(rows, cols).cpu().numpy()
+    if int(getattr(model, "rank", 0)) == 0:
+        if draw_label_heatmap(heatmap, output_dir, model_arch, _epoch(model)) is not None:
+            print(f"Saved label heatmap visualization to {output_dir}")
+    return heatmap
 
 
 def evaluate_classification(model, config, dataloader):

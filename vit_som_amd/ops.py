@@ -698,6 +698,33 @@ def argmax_rows(x, out):
     return out
 
 
+def proto_mosaic(pred, n, p, C, k0, map_size, images=None, canvas=None, gap=1):
+    """Decoder output `pred` [chunk * (n + 1), p*p*C] -> images[k0 : k0 + chunk] ([K, C, S, S] float32) and / or the cells
+    k0 .. k0 + chunk - 1 of the uint8 RGB `canvas` of the rows x cols map (see vsom_proto_mosaic)."""
+    _f32(pred, "pred")
+    rows, cols = int(map_size[0]), int(map_size[1])
+    K, pd = rows * cols, p * p * C
+    assert pred.is_contiguous() and pred.dim() == 2 and pred.shape[1] == pd and pred.shape[0] % (n + 1) == 0
+    chunk, S = pred.shape[0] // (n + 1), int(round(n ** 0.5)) * p
+    if images is not None:
+        _f32(images, "images")
+        assert images.is_contiguous() and tuple(images.shape) == (K, C, S, S)
+    if canvas is not None:
+        assert canvas.is_cuda and canvas.dtype == torch.uint8 and canvas.is_contiguous()
+        assert tuple(canvas.shape) ==(rows * S + (rows - 1) * gap, cols * S + (cols - 1) * gap, 3)
+    check(lib.vsom_proto_mosaic(ptr(pred), chunk, int(n), int(p), int(C), ptr(images), ptr(canvas), int(k0), K, rows, cols,
+                                int(gap), stream()), "vsom_proto_mosaic")
+
+
+def last_label(bmu, label, first_ordinal, cells, bad):
+    """cells[bmu[i]] = max(cells[bmu[i]], (first_ordinal + i + 1) << 32 | label[i]) (cells: [K] int64, zeroed by the caller)."""
+    assert bmu.dtype == torch.int64 and label.dtype == torch.int64 and cells.dtype == torch.int64 and bad.dtype == torch.int32
+    assert bmu.is_cuda and bmu.is_contiguous() and label.is_contiguous() and cells.is_contiguous() and bmu.numel() == label.numel()
+    check(lib.vsom_last_label(ptr(bmu), ptr(label), bmu.numel(), int(first_ordinal), cells.numel(), ptr(cells), ptr(bad),
+                              stream()), "vsom_last_label")
+    return cells
+
+
 # ---------------------------------------------------------------- k-means (evaluate_kmeans)
 def kmeans_workspace_bytes(N: int, D: int, k: int) -> int:
     return lib.vsom_kmeans_workspace_bytes(N, D, k)

@@ -183,6 +183,7 @@ class _ArenaOwner:
 
     arena: Optional[ParamArena] = None
     world_size, rank = 1, 0
+    current_epoch = 0                            # Lightning's attribute; train.fit sets it (the plots' file names carry it)
     _grads_reduced = False
     _forward_id, _seeds_consumed = 0, False      # one backward per forward of the fused step (_StepLoss)
 

@@ -112,6 +112,7 @@ def fit(model, config, train_loader, val_loader, ckpt_dir, dataset_name, use_val
     (opt,), (sched,) = model.configure_optimizers()
     best_acc, best_path, last_path, history = -1.0, None, None, []
     for epoch in range(epochs):
+        model.current_epoch = epoch
         model.train()
         tot, nb = 0.0, 0
         for x, y in train_loader:

@@ -147,6 +147,40 @@ class ViTAutoencoder(nn.Module):
         return torch.einsum("nhwpqc->nchpwq", x).reshape(x.shape[0], c, h * p, w * p)
 
     # -- buffers ------------------------------------------------------------------------------
+    @staticmethod
+    def _layer_acts(f, B: int, N: int, dim: int, heads: int, hidden: int) -> _Acts:
+        """The forward tensors of one block for B images of N tokens."""
+        T = B * N
+        L = _Acts()
+        L.a1, L.mean1, L.rstd1 = f(T, dim), f(T), f(T)
+        L.qkv, L.ao, L.lse = f(T, 3 * dim), f(T, dim), f(B, heads, N)
+        L.x1, L.a2, L.mean2, L.rstd2 = f(T, dim), f(T, dim), f(T), f(T)
+        L.hpre, L.hact, L.x2 = f(T, hidden), f(T, hidden), f(T, dim)
+        return L
+
+    def _decoder_buffers_for(self, B: int, device) -> _Acts:
+        """What _decode needs for B token sequences and nothing else: the input tokens (xe), dec0, the decoder blocks'
+        forward tensors, dn and pred -- no encoder layer, no backward temporary (about a tenth of _buffers_for(B)).
+        One set is kept, apart from self._acts: decoding prototypes between epochs neither evicts nor touches the
+        training batch's buffers."""
+        d = self.__dict__.get("_dec_only")
+        if d is not None and d.B == B and d.device == device:
+            return d
+        E, DE = self.embed_dim, self.decoder_embed_dim
+        N = self.patch_embed.num_patches + 1
+        T = B * N
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)   # noqa: E731
+        self.__dict__["_dec_only"] = None                                     # the old set goes before the new one comes
+        d = _Acts()
+        d.device, d.B, d.N, d.T = device, B, N, T
+        d.xe = torch.zeros(T, E, dtype=torch.float32, device=device)          # the CLS rows stay zero (decode_prototype)
+        d.dec0 = f(T, DE)
+        d.dec = [self._layer_acts(f, B, N, DE, self.decoder_num_heads, b.hidden) for b in self.decoder_blocks]
+        d.dn, d.mean_d, d.rstd_d = f(T, DE), f(T), f(T)
+        d.pred = f(T, self.patch_embed.patch_size[0] ** 2 * self.in_chans)
+        self.__dict__["_dec_only"] = d
+        return d
+
     def _buffers_for(self, B: int, device) -> _Acts:
         a = self._acts.get(B)
         if a is not None and a.device == device:
@@ -161,14 +195,7 @@ class ViTAutoencoder(nn.Module):
         a.device, a.B, a.N, a.T = device, B, N, T
         a.xp = f(B * n, pd)
         a.tok0 = f(T, E)
-
-        def layer(dim, heads, hidden):
-            L = _Acts()
-            L.a1, L.mean1, L.rstd1 = f(T, dim), f(T), f(T)
-            L.qkv, L.ao, L.lse = f(T, 3 * dim), f(T, dim), f(B, heads, N)
-            L.x1, L.a2, L.mean2, L.rstd2 = f(T, dim), f(T, dim), f(T), f(T)
-            L.hpre, L.hact, L.x2 = f(T, hidden), f(T, hidden), f(T, dim)
-            return L
+        layer = lambda dim, heads, hidden: self._layer_acts(f, B, N, dim, heads, hidden)   # noqa: E731
         a.enc = [layer(E, self.num_heads, b.hidden) for b in self.blocks]
         a.xe, a.mean_e, a.rstd_e = f(T, E), f(T), f(T)
         a.dec0 = f(T, DE)
@@ -186,7 +213,7 @@ class ViTAutoencoder(nn.Module):
         a.dpred = f(T, pd)
         a.d_xe = f(T, E)
         a.version = 0            # bumped whenever the activation buffers are rewritten (staleness guard of the autograd bridges)
-        # at most two batch sizes stay allocated (the training batch and, e.g., decode_prototype's batch of one)
+        # at most two batch sizes stay allocated (the training batch and, e.g., an evaluation batch; decode_prototypes has its own decoder-only set)
         keep = list(self._acts.items())[-1:]
         self._acts = dict(keep + [(B, a)])
         return a
@@ -361,6 +388,41 @@ class ViTAutoencoder(nn.Module):
         a.xe.view(a.B, a.N, self.embed_dim).copy_(x)
         self._decode(a)
         return a
+
+    @torch.no_grad()
+    def decode_prototypes(self, prototypes, map_size=None, chunk: int = 512, gap: int = 1, want_canvas: bool = True):
+        """tools/evaluation.py:209-222 for a whole map at once: every row of `prototypes` [K, n*E] behind a zero CLS
+        row -> forward_decoder -> unpatchify, `chunk` prototypes per decoder pass, through the decoder-only buffers
+        (self._acts and the launch tapes tied to it are not touched; no autograd).  Returns (images [K, C, S, S] float32,
+        canvas): the uint8 RGB mosaic of the map_size = (rows, cols) grid with `gap` white pixels between cells
+        (ops.proto_mosaic), or None when not wanted.  Both are fresh device tensors."""
+        n, E = self.patch_embed.num_patches, self.embed_dim
+        if prototypes.dim() != 2 or prototypes.shape[1] != n * E:
+            raise ValueError(f"decode_prototypes: expected prototypes [K,{n * E}], got {tuple(prototypes.shape)}")
+        if not prototypes.is_cuda:
+            raise ValueError("decode_prototypes: prototypes must live on the MI355X (there is no CPU path)")
+        if ops.tape_recording():
+            raise RuntimeError("decode_prototypes: called while a launch tape is being recorded")
+        K, C, S, p = prototypes.shape[0], self.in_chans, self.img_size, self.patch_embed.patch_size[0]
+        rows, cols = (1, K) if map_size is None else (int(map_size[0]), int(map_size[1]))
+        if rows * cols != K or gap < 0:
+            raise ValueError(f"decode_prototypes: a {rows} x {cols} map with gap {gap} does not hold {K} prototypes")
+        dev = prototypes.device
+        B = max(1, min(int(chunk), K))
+        d = self._decoder_buffers_for(B, dev)
+        images = torch.empty(K, C, S, S, dtype=torch.float32, device=dev)
+        canvas = None
+        if want_canvas:
+            canvas = torch.empty(rows * S + (rows - 1) * gap, cols * S + (cols - 1) * gap, 3, dtype=torch.uint8, device=dev)
+        tokens = d.xe.view(B, n + 1, E)
+        for k0 in range(0, K, B):
+            m = min(B, K - k0)
+            # a short last chunk runs at the full row count (one GEMM plan per call); its spare rows hold the previous
+            # chunk's tokens and nobody reads their output
+            tokens[:m, 1:].copy_(prototypes[k0:k0 + m].detach().view(m, n, E))
+            self._decode(d)
+            ops.proto_mosaic(d.pred[:m * (n + 1)], n, p, C, k0, (rows, cols), images=images, canvas=canvas, gap=gap)
+        return images, canvas
 
     # -- backward -----------------------------------------------------------------------------
     @staticmethod
