@@ -492,6 +492,35 @@ int vsom_bmu_cosine_x3_planes_finalize(const float* X, long ldx, const float* W,
                                        const void* ws, size_t ws_bytes, float* dist, int64_t* bmu, float* inv_nx, float* inv_nw,
                                        int* reranked, int B, int K, int L, vsom_stream_t stream);
 
+/* ------------------------------------------------------------------ data: the input side of a step (augment.hip)
+ * A data set lives on the device as uint8 [N, C, H, W] (C 1 or 3, square, H <= 64).  vsom_augment_plan writes one row of
+ * VSOM_AUGMENT_PARAMS int32 per sample: {i1, j1, h1, w1,  i2, j2, h2, w2 (h2 = 0: no second crop),  flip,
+ * erase top, left, h, w (h = 0: none),  0, 0, 0}, drawn with Philox4x32-10 from (seed, epoch, index[b]) alone (index[b]
+ * clamped into [0, N), N = rows of the data set) -- counter
+ * (block, index, 0, epoch), key seed -- so a sample's augmentation does not depend on its place in a batch, the batch size or
+ * the rank count.  Boxes: the loop-free RandomResizedCrop draw of tools/utils.py:93-113 (area share U(scale0, scale1),
+ * aspect exp(U(log_ratio0, log_ratio1)), Python rounding, clamped to [1, size]), the second on the S x S result of the
+ * first; flip: one Bernoulli(flip_p); erase: timm RandomErasing's draw with probability erase_p (ten attempts of
+ * area U(0.02, 1/3) S^2, aspect exp(U(log 0.3, log 1/0.3)), accepted when h < S and w < S). */
+#define VSOM_AUGMENT_PARAMS 16
+int vsom_augment_plan(const int64_t* index, long N, int B, int H, int S, double scale0, double scale1, double log_ratio0,
+                      double log_ratio1, int two_stage, double scale2_0, double scale2_1, double log_ratio2_0,
+                      double log_ratio2_1, double flip_p, double erase_p, uint64_t seed, int epoch, int32_t* params,
+                      vsom_stream_t stream);
+/* out[b] (fp32 [B, C, S, S], 16-byte aligned) = the transform of data/data.py:287-313 applied to src[index[b]]:
+ * crop box 1 -> R x R with PIL's 8-bit antialiased bicubic (Image.crop(...).resize(..., BICUBIC) bit for bit: 22-bit
+ * fixed-point coefficients, horizontal pass first, 8-bit intermediate); with R == S optionally crop box 2 of that -> S x S
+ * again (the image stays in LDS); the S x S window at (off, off) of the result; horizontal flip; level / 255;
+ * (v - mean[c]) / std[c] (two true fp32 divides); inside the erase box a standard normal per element (Philox counter
+ * (element / 4, index, 1, epoch), Box-Muller in fp32).  params = NULL: the whole image, no flip, no erase -- the evaluation
+ * transform with R = int(S / 0.875), off = round((R - S) / 2), or identity geometry with R = S = H.  out_u8 (nullable,
+ * [B, C, S, S], 4-byte aligned) receives the 8-bit image before normalisation.  mean, std: C floats on the device.
+ * S <= 64, S <= R <= 73, H <= 4 S.  An index outside [0, N) is clamped into it, by both entries alike (N = rows of the
+ * data set), so plan, noise and pixels still belong to one row; a box outside its image is moved inside. */
+int vsom_augment_batch(const unsigned char* src, long N, int C, int H, int W, const int64_t* index, const int32_t* params,
+                       int B, int S, int R, int off, const float* mean, const float* std, uint64_t seed, int epoch,
+                       float* out, unsigned char* out_u8, vsom_stream_t stream);
+
 /* ------------------------------------------------------------------ small utilities */
 int vsom_fill(float* p, long n, float value, vsom_stream_t stream);
 /* out[0] = ca * a[0] + cb * b[0]: the step's total loss from its two device-side sums (vit_som.py:93,98); `counter`

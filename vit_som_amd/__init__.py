@@ -17,3 +17,4 @@ from .classifier import ViTClassifier  # noqa: F401,E402
 from . import evaluation  # noqa: F401,E402
 from .kmeans import KMeans, kmeans_plusplus  # noqa: F401,E402
 from .umap import UMAP  # noqa: F401,E402
+from .data import DeviceDataset, DeviceLoader, DeviceTransform  # noqa: F401,E402

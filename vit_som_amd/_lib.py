@@ -119,6 +119,10 @@ SIGNATURES = {
     "vsom_proto_mosaic": (C.c_int, [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, c_stream]),
     "vsom_last_label": (C.c_int, [c_fp, c_fp, C.c_long, C.c_long, C.c_int, c_fp, c_fp, c_stream]),
+    "vsom_augment_plan": (C.c_int, [c_fp, C.c_long, C.c_int, C.c_int, C.c_int] + [C.c_double] * 4 + [C.c_int] + [C.c_double] * 6
+                          + [C.c_uint64, C.c_int, c_fp, c_stream]),
+    "vsom_augment_batch": (C.c_int, [c_fp, C.c_long, C.c_int, C.c_int, C.c_int, c_fp, c_fp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     c_fp, c_fp, C.c_uint64, C.c_int, c_fp, c_fp, c_stream]),
     "vsom_kmeans_workspace_bytes": (C.c_size_t, [C.c_long, C.c_int, C.c_int]),
     "vsom_kmeans_assign": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_size_t,
                                      c_stream]),

@@ -725,6 +725,43 @@ def last_label(bmu, label, first_ordinal, cells, bad):
     return cells
 
 
+# ---------------------------------------------------------------- data pipeline (vit_som_amd.data)
+AUGMENT_PARAMS = 16
+
+
+def augment_plan(index, params, N, H, S, scale, log_ratio, scale2, log_ratio2, flip_p, erase_p, seed, epoch):
+    """params[b] <- the augmentation plan of row index[b] of a data set of N rows in `epoch` (see vsom_augment_plan);
+    scale2 = None: one crop."""
+    assert index.is_cuda and index.dtype == torch.int64 and index.is_contiguous() and index.dim() == 1
+    assert params.is_cuda and params.dtype == torch.int32 and params.is_contiguous()
+    assert params.dim() == 2 and params.shape[0] >= index.numel() and params.shape[1] == AUGMENT_PARAMS
+    two = scale2 is not None
+    s2, l2 = (scale2, log_ratio2) if two else ((0.0, 0.0), (0.0, 0.0))
+    check(lib.vsom_augment_plan(ptr(index), int(N), index.numel(), int(H), int(S), float(scale[0]), float(scale[1]), float(log_ratio[0]),
+                                float(log_ratio[1]), int(two), float(s2[0]), float(s2[1]), float(l2[0]), float(l2[1]),
+                                float(flip_p), float(erase_p), int(seed), int(epoch), ptr(params), stream()), "vsom_augment_plan")
+    return params
+
+
+def augment_batch(src, index, params, out, S, R, off, mean, std, seed, epoch, out_u8=None):
+    """out[b] <- the transformed row index[b] of the uint8 set `src` [N, C, H, W] (see vsom_augment_batch); params = None: the
+    whole image, no flip, no erase."""
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 4
+    assert index.is_cuda and index.dtype == torch.int64 and index.is_contiguous() and index.dim() == 1
+    N, C, H, W = src.shape
+    B = index.numel()
+    _f32(out, "out"), _f32(mean, "mean"), _f32(std, "std")
+    assert out.is_contiguous() and out.numel() >= B * C * S * S and mean.numel() == C and std.numel() == C
+    if params is not None:
+        assert params.is_cuda and params.dtype == torch.int32 and params.is_contiguous()
+        assert params.shape[0] >= B and params.shape[1] == AUGMENT_PARAMS
+    if out_u8 is not None:
+        assert out_u8.is_cuda and out_u8.dtype == torch.uint8 and out_u8.is_contiguous() and out_u8.numel() >= B * C * S * S
+    check(lib.vsom_augment_batch(ptr(src), N, C, H, W, ptr(index), ptr(params), B, int(S), int(R), int(off), ptr(mean), ptr(std),
+                                 int(seed), int(epoch), ptr(out), ptr(out_u8), stream()), "vsom_augment_batch")
+    return out
+
+
 # ---------------------------------------------------------------- k-means (evaluate_kmeans)
 def kmeans_workspace_bytes(N: int, D: int, k: int) -> int:
     return lib.vsom_kmeans_workspace_bytes(N, D, k)

@@ -7,8 +7,10 @@ reloaded last checkpoint on the train loader), mean (std) report.
 Data comes from a `make_loaders(config, rank, world_size)` callable returning
 (train_loader, val_loader, test_loader); the reference's data/data.py:get_dataloaders needs
 torchvision/timm and downloads (absent offline), so the default is a synthetic, class-structured
-in-memory set of the configured shape.  One process per GPU: under torchrun (WORLD_SIZE > 1) every
-rank takes an interleaved shard of each loader and gradients are summed by one RCCL all-reduce.
+in-memory set of the configured shape; `device_loaders` (--device-data, --data-npz PATH) keeps the
+images on the GPU as uint8 and applies the configs' crop / flip / erase augmentation there
+(vit_som_amd.data).  One process per GPU: under torchrun (WORLD_SIZE > 1) every rank takes an
+interleaved shard of each loader and gradients are summed by one RCCL all-reduce.
 
     python -m vit_som_amd.train --config configs/vit_som/vit_som_cifar-10.yaml [--runs 5] [--epochs N]
 
@@ -98,6 +100,43 @@ def synthetic_loaders(config, rank=0, world_size=1, n_train=2048, n_val=256, n_t
     (xt, yt), (xv, yv), (xs, ys) = make(n_train), make(n_val), make(n_test)
     return (TensorLoader(xt, yt, bs, shuffle=True, rank=rank, world_size=world_size, seed=seed, drop_last=True),
             TensorLoader(xv, yv, bs, rank=rank, world_size=world_size), TensorLoader(xs, ys, bs, rank=rank, world_size=world_size))
+
+
+def device_loaders(config, rank=0, world_size=1, n_train=2048, n_val=256, n_test=256, seed=0, npz=None, strict=False):
+    """A `make_loaders` whose input side runs on the device (vit_som_amd.data): the images live on the GPU as uint8, the train
+    loader applies the config's training transform (crops, flip, random erasing), val / test the evaluation transform.
+    Default data: synthetic_loaders' class-structured set, quantised to 8 bits (level = 255 clip(x / 4 + 1 / 2, 0, 1)).
+    `npz`: a local file with `images` / `labels` (and optionally `test_images` / `test_labels`; without them the last tenth
+    of the rows is held out) -- validation and test then share the held-out part."""
+    from .data import DeviceDataset, DeviceLoader, DeviceTransform
+    hp, d = config["hyperparameters"], config["data"]
+    C, S, bs = d["num_channels"], d["input_size"], hp["batch_size"]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if npz is not None:
+        with np.load(npz) as z:
+            xi, yi = torch.from_numpy(z["images"]), torch.from_numpy(z["labels"].astype(np.int64))
+            if "test_images" in z:
+                xh, yh = torch.from_numpy(z["test_images"]), torch.from_numpy(z["test_labels"].astype(np.int64))
+            else:
+                k = len(xi) - max(len(xi) // 10, 1)
+                (xi, xh), (yi, yh) = (xi[:k], xi[k:]), (yi[:k], yi[k:])
+        train_set = DeviceDataset(xi, yi, dev)
+        val_set = test_set = DeviceDataset(xh, yh, dev)
+    else:
+        ncls = max(int(d["num_classes"]), 1) if d["num_classes"] > 0 else 10
+        g = torch.Generator().manual_seed(seed)
+        templates = torch.randn(ncls, C, S, S, generator=g)
+
+        def make(n):
+            y = torch.randint(0, ncls, (n,), generator=g)
+            x = templates[y] + 0.5 * torch.randn(n, C, S, S, generator=g)
+            return DeviceDataset((x / 4 + 0.5).clamp_(0, 1).mul_(255).round_().to(torch.uint8), y, dev)
+        train_set, val_set, test_set = make(n_train), make(n_val), make(n_test)
+    t_train = DeviceTransform.from_config(config, True, strict=strict)
+    t_eval = DeviceTransform.from_config(config, False)
+    return (DeviceLoader(train_set, bs, t_train, shuffle=True, rank=rank, world_size=world_size, seed=seed, drop_last=True),
+            DeviceLoader(val_set, bs, t_eval, rank=rank, world_size=world_size),
+            DeviceLoader(test_set, bs, t_eval, rank=rank, world_size=world_size))
 
 
 def fit(model, config, train_loader, val_loader, ckpt_dir, dataset_name, use_validation, max_epochs=None, log=print,
@@ -256,5 +295,10 @@ if __name__ == "__main__":
     ap.add_argument("--config", type=str, required=True)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--epochs", type=int, default=None)
+    ap.add_argument("--device-data", action="store_true", help="keep the data on the GPU as uint8 and augment it there")
+    ap.add_argument("--data-npz", type=str, default=None, help="a local .npz with images / labels (implies --device-data)")
     a = ap.parse_args()
-    main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs)
+    loaders = synthetic_loaders
+    if a.device_data or a.data_npz:
+        loaders = lambda c, r, w: device_loaders(c, r, w, npz=a.data_npz)     # noqa: E731
+    main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs, make_loaders=loaders)
