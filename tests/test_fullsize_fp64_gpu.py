@@ -150,7 +150,7 @@ def _run_case(name):
     got = {n: m._grad_views[n].clone() for n in to_oracle}
     jobs = a.__dict__.get("ln_jobs")
     tape = a.__dict__.get("tape")
-    paths = dict(tape=(tape.id if tape is not None else 0, tape0), fwd_split=vit.__dict__.get("_fwd_side") is not None,
+    paths = dict(tape=(tape.id if tape is not None else 0, tape0), fwd_split=vit._fwd_side is not None,
                  jobs=(jobs.n, jobs.flushed, sum(1 for k in jobs.keys[:jobs.n] if k[-1] == "fused")) if jobs else None,
                  ln_supported=[ops.linear_bwd_input_ln_supported(a.T, 3 * d.E, d.E), ops.linear_bwd_input_ln_supported(a.T, d.hidden, d.E)])
     if kind == "som":

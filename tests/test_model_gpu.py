@@ -232,7 +232,7 @@ def _run_switch_combinations(cfg, finals, hooks, ops, vit_som_amd, flip_attentio
             y = torch.zeros(96, dtype=torch.int64, device=DEV)
             m.train_step_fused(x, y)
             opt.step()
-        assert (m.vit._side is not None) == (side == "1")
+        assert (m._sched.side is not None) == (side == "1")
         jobs = m.vit._acts[96].__dict__.get("ln_jobs")
         assert (jobs is not None and jobs.n == jobs.flushed == 2 * (4 + 2) + 2) == lnb      # every LayerNorm of the step went through the batch
         assert (m.vit.__dict__.get("_fwd_side") is not None) == (split == "1")

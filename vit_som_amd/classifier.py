@@ -83,11 +83,11 @@ class ViTClassifier(_ViTOwner):
         vit = self.model
         c.pruned = bool(hooks.cls_prune)
         if c.pruned:
-            cur = vit._encode_trunk(x, a, len(vit.blocks) - 1)
+            cur = vit._encode_trunk(x, a, len(vit.blocks) - 1, self._side_stream)
             self._last_block_fwd(cur, a, c)
             feat = c.xe
         else:
-            vit._encode(x, a)
+            vit._encode(x, a, self._side_stream)
             feat = self._cls_view(a.xe, a)
         ops.linear_fwd(feat, self.cls_head.weight, self.cls_head.bias, c.logits)
         return x, a, c
@@ -137,10 +137,10 @@ class ViTClassifier(_ViTOwner):
     def _head_params(self):
         return list(self.cls_head.parameters())
 
-    def _last_block_bwd(self, a: _Acts, c: _Acts, G):
+    def _last_block_bwd(self, a: _Acts, c: _Acts, sched):
         """Backward of the pruned last block from c.gx2 = dL/d(its CLS outputs); leaves dL/d(its input) [T, E] in the
         first gradient buffer of the ring, where ViTAutoencoder._encoder_bwd(depth=D-1) starts."""
-        vit = self.model
+        vit, G = self.model, sched.G
         D = len(vit.blocks)
         blk, L = vit.blocks[-1], a.enc[-1]
         E, B, N = vit.embed_dim, a.B, a.N
@@ -168,7 +168,7 @@ class ViTClassifier(_ViTOwner):
                           G(f"{pre}.norm1.bias"))
         ops.rows_add(c.gx1, self._cls_view(g0, a))          # the residual path reaches the CLS rows only
 
-    def _head_backward(self, a: _Acts, c: _Acts, Gv, reduce):
+    def _head_backward(self, a: _Acts, c: _Acts, sched, reduce):
         """The cls_head backward, then (pruned) the final LayerNorm and the last block on the CLS rows; returns the
         number of encoder blocks left to run."""
         vit = self.model
@@ -180,9 +180,9 @@ class ViTClassifier(_ViTOwner):
             ops.linear_bwd_weight(c.dlogits, c.xe, gw, gb)
             reduce("head", [main])
             ops.linear_bwd_input(c.dlogits, self.cls_head.weight, c.dxe)
-            ops.layernorm_bwd(c.dxe, c.x2, c.mean_e, c.rstd_e, vit.norm.weight, None, c.gx2, Gv("norm.weight"),
-                              Gv("norm.bias"))
-            self._last_block_bwd(a, c, Gv)
+            ops.layernorm_bwd(c.dxe, c.x2, c.mean_e, c.rstd_e, vit.norm.weight, None, c.gx2, sched.G("norm.weight"),
+                              sched.G("norm.bias"))
+            self._last_block_bwd(a, c, sched)
             reduce(f"enc{D - 1}")
             return D - 1
         ops.fill(a.d_xe, 0.0)

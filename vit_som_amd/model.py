@@ -44,6 +44,7 @@ class ViTSOM(_ViTOwner):
             self._add_cls_head()
         self.smoothing = float(hp["optimizer"]["smoothing"])
         self.register_buffer("iteration", torch.tensor(0))
+        self._som_done_ev = None    # the SOM backward's completion on its stream (_head_backward)
         self._pack(self._default_device(device))
 
     # -- schedules ----------------------------------------------------------------------------
@@ -82,7 +83,7 @@ class ViTSOM(_ViTOwner):
         self._ensure_streams(x.device)
         # the prototypes' plane image for the BMU pass: re-split on the SOM stream while the encoder runs
         w_ready = self.som_layer._w_planes_async(self._som_stream, fresh_w) if self.som_layer._planes_shape_ok(a.B) else None
-        self.vit._encode(x, a)
+        self.vit._encode(x, a, self._side_stream)
         s = self.som_layer._buffers_for(a.B, x.device)
         if need_decoder and hooks.bmu_overlap and hooks.side_stream:
             # The BMU pass and the decoder both start from the encoder output and do not meet before the losses: the pass
@@ -196,7 +197,7 @@ class ViTSOM(_ViTOwner):
     def _head_params(self):
         return list(self.som_layer.parameters()) + (list(self.cls_head.parameters()) if self.classification else [])
 
-    def _head_backward(self, a, s, Gv, reduce):
+    def _head_backward(self, a, s, sched, reduce):
         """The SOM, decoder and cls_head backwards; leaves dL/d(xe) in a.d_xe for the whole encoder."""
         X = self._som_input(a)
         E, N = self.vit.embed_dim, a.N
@@ -213,7 +214,7 @@ class ViTSOM(_ViTOwner):
                 ops.som_bwd(X, self.som_layer.prototypes, s.coef, s.row_dot, s.col_dot,
                             self._grad_views["som_layer.prototypes"], gx_out, accumulate_gx=accumulate)
 
-        side = self._som_stream if self.vit._side is not None else None
+        side = self._som_stream if sched.side is not None else None
         if self.classification or side is None:
             if self.classification:
                 ops.fill(a.d_xe, 0.0)
@@ -222,7 +223,7 @@ class ViTSOM(_ViTOwner):
                                       self._grad_views["cls_head.bias"])
                 ops.linear_bwd_input(a.dlogits, self.cls_head.weight, self._cls_view(a.d_xe, a), accumulate=True)
             else:
-                self.vit._decoder_bwd(a, Gv, self._WT)
+                self.vit._decoder_bwd(a, sched)
                 reduce("decoder")
             som_backward(gX, True)
             reduce("som")
@@ -232,18 +233,17 @@ class ViTSOM(_ViTOwner):
             # d_xe; the decoder's last GEMM waits for it and accumulates on top.  The prototype
             # all-reduce is issued behind it: it starts the moment gW is final, before the decoder
             # backward has finished.
-            self.vit._event().record().wait(side)
+            sched._event().record().wait(side)
             with on_stream(side):
                 ops.fill(a.d_xe, 0.0)
                 som_backward(gX, False)
             reduce("som", [side])
             # a dedicated event: its wait is deferred to the end of the decoder backward, by which time a pooled
             # (round-robin) event could have been re-recorded for something else (deep decoders)
-            som_done = self.__dict__.get("_som_done_ev")
-            if som_done is None:
-                som_done = self.__dict__["_som_done_ev"] = Event()
-            som_done.record(side)
-            self.vit._decoder_bwd(a, Gv, self._WT, before_dxe=lambda: som_done.wait())
+            if self._som_done_ev is None:
+                self._som_done_ev = Event()
+            som_done = self._som_done_ev.record(side)
+            self.vit._decoder_bwd(a, sched, before_dxe=lambda: som_done.wait())
             reduce("decoder")
         return None
 

@@ -4,6 +4,7 @@ Every wrapper validates device / dtype / inner-stride, passes raw device pointer
 and torch's current HIP stream, and raises ``VsomError`` on a non-zero status.  Nothing here
 computes: there is no eager fallback.
 """
+from contextlib import contextmanager
 from typing import Optional
 
 import torch
@@ -39,6 +40,20 @@ def timer_ms(name: str):
 def reset_timer(name: str):
     if name in _timers:
         _timers[name] = []
+
+
+@contextmanager
+def _timed(name: str):
+    """An event pair around the launches of the block, on the stream they go to, when timer `name` is enabled."""
+    rec = _timers.get(name)
+    if rec is None:
+        yield
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(_lib_mod.launch_torch_stream())
+    yield
+    e1.record(_lib_mod.launch_torch_stream())
+    rec.append((e0, e1))
 
 
 def scratch(nbytes: int, device) -> torch.Tensor:
@@ -272,45 +287,38 @@ class LayerNormJobs:
     def begin(self):
         self.n = self.flushed = 0
 
-    def bwd(self, dy, x, mean, rstd, gamma, resid, dx, dgamma, dbeta):
-        rows, cols = x.shape
-        key = (ptr(dgamma), ptr(dbeta), rows, cols)
+    def _slot(self, key, dgamma, dbeta, cols, partial_bytes):
+        """The partial buffer of the pass's next job: the table's when `key` matches it; else the table is forgotten
+        from here on and a buffer of partial_bytes() bytes joins it."""
         i = self.n
-        if i < len(self.keys) and self.keys[i] != key:           # the pass changed: forget the table from here on
+        if i < len(self.keys) and self.keys[i] != key:           # the pass changed
             del self.keys[i:], self.rows_host[i:], self.parts[i:]
             self.table = None
         if i == len(self.keys):
-            nbytes = lib.vsom_layernorm_bwd_workspace_bytes(rows, cols)
+            nbytes = partial_bytes()
             part = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             self.keys.append(key); self.parts.append(part)
             self.rows_host.append([ptr(part), ptr(dgamma), ptr(dbeta), ((nbytes // (8 * cols)) << 32) | cols])
             self.max_cols = max(self.max_cols, cols)
             self.table = None
-        part = self.parts[i]
+        self.n += 1
+        return self.parts[i]
+
+    def bwd(self, dy, x, mean, rstd, gamma, resid, dx, dgamma, dbeta):
+        rows, cols = x.shape
+        part = self._slot((ptr(dgamma), ptr(dbeta), rows, cols), dgamma, dbeta, cols,
+                          lambda: lib.vsom_layernorm_bwd_workspace_bytes(rows, cols))
         check(lib.vsom_layernorm_bwd_partial(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(resid), ptr(dx), rows, cols,
                                              ptr(part), part.numel(), stream()), "vsom_layernorm_bwd_partial")
-        self.n += 1
         return dx
 
     def bwd_linear_fused(self, dy, Wt, x, mean, rstd, gamma, resid, dx, dgamma, dbeta):
         """dX of the Linear whose input-gradient GEMM (dy, Wt) feeds this LayerNorm's dY, in one launch
         (linear_bwd_input_ln_partial); one job of the table, like `bwd`."""
         rows, cols = x.shape
-        key = (ptr(dgamma), ptr(dbeta), rows, cols, "fused")
-        i = self.n
-        if i < len(self.keys) and self.keys[i] != key:
-            del self.keys[i:], self.rows_host[i:], self.parts[i:]
-            self.table = None
-        if i == len(self.keys):
-            nbytes = lib.vsom_linear_bwd_input_ln_partial_bytes(rows, cols)
-            part = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self.keys.append(key); self.parts.append(part)
-            self.rows_host.append([ptr(part), ptr(dgamma), ptr(dbeta), ((nbytes // (8 * cols)) << 32) | cols])
-            self.max_cols = max(self.max_cols, cols)
-            self.table = None
-        part = self.parts[i]
+        part = self._slot((ptr(dgamma), ptr(dbeta), rows, cols, "fused"), dgamma, dbeta, cols,
+                          lambda: lib.vsom_linear_bwd_input_ln_partial_bytes(rows, cols))
         linear_bwd_input_ln_partial(dy, Wt, x, mean, rstd, gamma, resid, dx, part)
-        self.n += 1
         return dx
 
     def flush(self):
@@ -467,14 +475,8 @@ def bmu_cosine_x3_fwd(x, W, dist: Optional[torch.Tensor], bmu, inv_nx, inv_nw, r
     assert reranked is None or (reranked.dtype == torch.int32 and reranked.is_cuda)
     nbytes = lib.vsom_bmu_cosine_x3_workspace_bytes(B, K, L)
     ws = scratch(nbytes, x.device)
-    rec = _timers.get("bmu_cosine_dots")
-    if rec is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(_lib_mod.launch_torch_stream())
-    check(lib.vsom_bmu_cosine_x3_dots(ptr(x), _rows(x), ptr(W), B, K, L, ptr(ws), ws.numel(), stream()), "vsom_bmu_cosine_x3_dots")
-    if rec is not None:
-        e1.record(_lib_mod.launch_torch_stream())
-        rec.append((e0, e1))
+    with _timed("bmu_cosine_dots"):
+        check(lib.vsom_bmu_cosine_x3_dots(ptr(x), _rows(x), ptr(W), B, K, L, ptr(ws), ws.numel(), stream()), "vsom_bmu_cosine_x3_dots")
     check(lib.vsom_bmu_cosine_x3_finalize(ptr(x), _rows(x), ptr(W), ptr(ws), ws.numel(), ptr(dist), ptr(bmu), ptr(inv_nx),
                                           ptr(inv_nw), ptr(reranked), B, K, L, stream()), "vsom_bmu_cosine_x3_finalize")
     return dist, bmu
@@ -512,15 +514,9 @@ def bmu_cosine_x3_planes_fwd(x, W, xplanes, wplanes, dist: Optional[torch.Tensor
     if nbytes == 0:
         raise ValueError(f"bmu_cosine_x3_planes_fwd: shape B={B} K={K} L={L} is not covered by the planes form")
     ws = scratch(nbytes, x.device)
-    rec = _timers.get("bmu_cosine_dots")
-    if rec is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(_lib_mod.launch_torch_stream())
-    check(lib.vsom_bmu_cosine_x3_planes_dots(ptr(xplanes), ptr(wplanes), B, K, L, ptr(ws), ws.numel(), stream()),
-          "vsom_bmu_cosine_x3_planes_dots")
-    if rec is not None:
-        e1.record(_lib_mod.launch_torch_stream())
-        rec.append((e0, e1))
+    with _timed("bmu_cosine_dots"):
+        check(lib.vsom_bmu_cosine_x3_planes_dots(ptr(xplanes), ptr(wplanes), B, K, L, ptr(ws), ws.numel(), stream()),
+              "vsom_bmu_cosine_x3_planes_dots")
     check(lib.vsom_bmu_cosine_x3_planes_finalize(ptr(x), _rows(x), ptr(W), ptr(xplanes), ptr(wplanes), ptr(ws), ws.numel(),
                                                  ptr(dist), ptr(bmu), ptr(inv_nx), ptr(inv_nw), ptr(reranked), B, K, L, stream()),
           "vsom_bmu_cosine_x3_planes_finalize")
@@ -534,14 +530,8 @@ def bmu_cosine_fwd(x, W, inv_nx, inv_nw, dist: Optional[torch.Tensor], bmu):
     assert W.is_contiguous() and W.shape[1] == L and bmu.dtype == torch.int64 and (dist is None or dist.is_contiguous())
     nbytes = lib.vsom_bmu_cosine_workspace_bytes(B, K, L)
     ws = scratch(nbytes, x.device)
-    rec = _timers.get("bmu_cosine_dots")
-    if rec is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(_lib_mod.launch_torch_stream())
-    check(lib.vsom_bmu_cosine_dots(ptr(x), _rows(x), ptr(W), B, K, L, ptr(ws), ws.numel(), stream()), "vsom_bmu_cosine_dots")
-    if rec is not None:
-        e1.record(_lib_mod.launch_torch_stream())
-        rec.append((e0, e1))
+    with _timed("bmu_cosine_dots"):
+        check(lib.vsom_bmu_cosine_dots(ptr(x), _rows(x), ptr(W), B, K, L, ptr(ws), ws.numel(), stream()), "vsom_bmu_cosine_dots")
     check(lib.vsom_bmu_cosine_finalize(ptr(ws), ws.numel(), ptr(inv_nx), ptr(inv_nw), ptr(dist), ptr(bmu), B, K, L, stream()),
           "vsom_bmu_cosine_finalize")
     return dist, bmu

@@ -110,7 +110,7 @@ class _StepTape:
         w = m.som_layer._wplanes
         self.id, self.key, self.gout_in, self.som_bufs = tid, self._key(m), a.gout_in, m._ctx[2]
         self.arena, self.planes = weakref.ref(m.arena), (lambda: None) if w is None else weakref.ref(w)
-        self.started, self.comm_dirty, self.side = list(m._started), m._comm_dirty, m.vit._side
+        self.started, self.comm_dirty = list(m._started), m._comm_dirty
 
     def valid(self, m, a) -> bool:
         return (self.key == self._key(m) and self.arena() is m.arena and self.planes() is m.som_layer._wplanes
@@ -132,7 +132,7 @@ class _StepTape:
             self.gout_in.copy_(gout.detach().reshape(1))
             ops.tape_replay(self.id, 2)
         ops.tape_replay(self.id, 3)
-        m._started, m._comm_dirty, m.vit._side = list(self.started), self.comm_dirty, self.side
+        m._started, m._comm_dirty = list(self.started), self.comm_dirty
 
     def close(self):
         if self.id:

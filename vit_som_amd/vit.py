@@ -81,6 +81,80 @@ def _trainable_order(vit: "ViTAutoencoder"):
 
 
 
+# ------------------------------------------------------------------------------------ backward schedule
+class _BackwardSchedule:
+    """What one backward pass runs where: built by whoever drives the pass (_ViTOwner._backward; the autograd functions
+    below, single stream) and handed down to _decoder_bwd / _encoder_bwd / _block_bwd.
+
+    side     the stream of the weight-gradient GEMMs, or None: everything on the launch stream
+    pending  one event per block whose side work the main stream has not yet waited for
+    jobs     the pass's ops.LayerNormJobs (dgamma / dbeta reductions left to the owner's flushes), or None
+    WT       weight -> its transposed copy or None; None when the driver keeps no copies
+    G        parameter name (without the owner's prefix) -> its gradient view
+
+    Weight-gradient GEMMs (and their slab reductions) are off the backward's critical path: nothing
+    reads dW before the optimizer.  With a side stream they run concurrently with the dX / LayerNorm /
+    attention chain and fill its tail rounds and the small-grid gaps.  Ordering: (1) a side GEMM waits
+    for the main-stream kernel that produced its dY; (2) the dY buffers (gout / g1 from a ring of five,
+    dh / dqkv from two sets) are rewritten two blocks later at the earliest, and the entry of block j
+    waits for the side work of block j+2 (_side_join) -- a wait that has normally long been satisfied,
+    so the main stream does not stall on the ~15 us cross-stream signalling latency a wait on the
+    PREVIOUS block costs; (3) the driver joins the side stream before anything reads the gradients.
+    The saved activations the GEMMs read are not written during a backward pass."""
+    __slots__ = ("side", "pending", "jobs", "WT", "G")
+
+    def __init__(self, G, side=None, jobs=None, WT=None):
+        self.G, self.side, self.jobs, self.WT = G, side, jobs, WT
+        self.pending = []
+
+    def _event(self):
+        """Pooled library events (re-recording one is safe once the waits on its previous record are enqueued; the pool is
+        far longer than the few events whose wait is deferred by a block or two)."""
+        return Event.pooled()
+
+    def _dx(self, dy, weight, dx, **kw):
+        """dX = dY W: from the transposed weight copy when the driver keeps one (NT kernel family)."""
+        wt = self.WT(weight) if self.WT is not None else None
+        if wt is not None:
+            return ops.linear_bwd_input_t(dy, wt, dx, **kw)
+        return ops.linear_bwd_input(dy, weight, dx, **kw)
+
+    def _dw(self, dy, x, gw, gb):
+        side = self.side
+        if side is None:
+            return ops.linear_bwd_weight(dy, x, gw, gb)
+        self._event().record().wait(side)       # recorded on the main (current) stream: dy is final here
+        with on_stream(side):
+            ops.linear_bwd_weight(dy, x, gw, gb)
+
+    def _side_join(self, keep: int = 1):
+        """Main stream waits for the side work of all but the `keep` most recent blocks."""
+        while len(self.pending) > keep:
+            self.pending.pop(0).wait()
+
+    def _side_mark(self):
+        if self.side is not None:
+            self.pending.append(self._event().record(self.side))
+
+    def _ln_bwd(self, dy, x, mean, rstd, gamma, resid, dx, dgamma, dbeta):
+        """LayerNorm backward; with a job list the dgamma / dbeta reduction is left to the driver's next flush."""
+        if self.jobs is not None and ops.layernorm_bwd_deferrable(*x.shape):
+            return self.jobs.bwd(dy, x, mean, rstd, gamma, resid, dx, dgamma, dbeta)
+        return ops.layernorm_bwd(dy, x, mean, rstd, gamma, resid, dx, dgamma, dbeta)
+
+    def _dx_ln(self, dy, weight, da, x, mean, rstd, gamma, resid, dx, dgamma, dbeta):
+        """dX of a Linear, then the backward of the LayerNorm whose output fed it: one launch (the LayerNorm backward in
+        the GEMM's epilogue, the product never stored) where the transposed weight copy, the shape and the GEMM mode allow
+        it (hooks.ln_bwd_fused), else the GEMM into the scratch `da` and _ln_bwd.  Same dX bits either way."""
+        wt = self.WT(weight) if (self.WT is not None and hooks.ln_bwd_fused) else None
+        if wt is not None and ops.linear_bwd_input_ln_supported(dy.shape[0], dy.shape[1], x.shape[1]):
+            if self.jobs is not None:
+                return self.jobs.bwd_linear_fused(dy, wt, x, mean, rstd, gamma, resid, dx, dgamma, dbeta)
+            return ops.linear_bwd_input_ln(dy, wt, x, mean, rstd, gamma, resid, dx, dgamma, dbeta)
+        self._dx(dy, weight, da)
+        return self._ln_bwd(da, x, mean, rstd, gamma, resid, dx, dgamma, dbeta)
+
+
 # ------------------------------------------------------------------------------------ ViT autoencoder
 class ViTAutoencoder(nn.Module):
     """MAE-style unmasked ViT autoencoder (models/vit.py:66-240); compute on the HIP kernels."""
@@ -106,6 +180,8 @@ class ViTAutoencoder(nn.Module):
         self.decoder_pred = _Affine((patch_size ** 2 * in_chans, decoder_embed_dim), (patch_size ** 2 * in_chans,))
         self.initialize_weights()
         self._acts: Dict[int, _Acts] = {}
+        self._dec_only = None       # the decoder-only buffer set of decode_prototypes (_decoder_buffers_for)
+        self._fwd_side = None       # the stream the last forward ran its second chain on; None: it was not split
 
     # -- init: same distributions as vit.py:100-125 ------------------------------------------
     def initialize_weights(self):
@@ -163,14 +239,14 @@ class ViTAutoencoder(nn.Module):
         forward tensors, dn and pred -- no encoder layer, no backward temporary (about a tenth of _buffers_for(B)).
         One set is kept, apart from self._acts: decoding prototypes between epochs neither evicts nor touches the
         training batch's buffers."""
-        d = self.__dict__.get("_dec_only")
+        d = self._dec_only
         if d is not None and d.B == B and d.device == device:
             return d
         E, DE = self.embed_dim, self.decoder_embed_dim
         N = self.patch_embed.num_patches + 1
         T = B * N
         f = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)   # noqa: E731
-        self.__dict__["_dec_only"] = None                                     # the old set goes before the new one comes
+        self._dec_only = None                                                 # the old set goes before the new one comes
         d = _Acts()
         d.device, d.B, d.N, d.T = device, B, N, T
         d.xe = torch.zeros(T, E, dtype=torch.float32, device=device)          # the CLS rows stay zero (decode_prototype)
@@ -178,7 +254,7 @@ class ViTAutoencoder(nn.Module):
         d.dec = [self._layer_acts(f, B, N, DE, self.decoder_num_heads, b.hidden) for b in self.decoder_blocks]
         d.dn, d.mean_d, d.rstd_d = f(T, DE), f(T), f(T)
         d.pred = f(T, self.patch_embed.patch_size[0] ** 2 * self.in_chans)
-        self.__dict__["_dec_only"] = d
+        self._dec_only = d
         return d
 
     def _buffers_for(self, B: int, device) -> _Acts:
@@ -230,30 +306,31 @@ class ViTAutoencoder(nn.Module):
         ops.linear_residual_fwd(L.hact, blk.mlp["2"].weight, blk.mlp["2"].bias, L.x1, T, L.x2)
         return L.x2
 
-    def _encode(self, x: torch.Tensor, a: _Acts):
-        cur = self._encode_trunk(x, a, len(self.blocks))
+    def _encode(self, x: torch.Tensor, a: _Acts, side=None):
+        cur = self._encode_trunk(x, a, len(self.blocks), side)
         ops.layernorm_fwd(cur, self.norm.weight, self.norm.bias, a.xe, a.mean_e, a.rstd_e, self.eps)
         return a.xe
 
-    def _encode_trunk(self, x: torch.Tensor, a: _Acts, depth: int):
-        """Patch embedding and encoder blocks [0, depth) -> the output of block depth - 1 ([T, E]; the tokens when 0)."""
+    def _encode_trunk(self, x: torch.Tensor, a: _Acts, depth: int, side=None):
+        """Patch embedding and encoder blocks [0, depth) -> the output of block depth - 1 ([T, E]; the tokens when 0).
+        `side`: a stream to borrow for the second chain of a split forward (None: one the ViT creates and keeps)."""
         E = self.embed_dim
         p = self.patch_embed.patch_size[0]
         a.version += 1
         ops.patch_embed_fwd(x, self.patch_embed.proj.weight.view(E, -1), self.patch_embed.proj.bias, self.pos_embed[0],
                             self.cls_token.view(E), a.tok0, a.xp, p)
         cur = a.tok0
-        side = None
         if cur.is_cuda and a.B % 2 == 0 and a.B >= 64 and hooks.fwd_split:
             # the owner (ViTSOM) lends the stream its backward uses for the weight gradients -- idle during
             # the forward; a stream of its own would compete for the few hardware queues of the process
             # (measured: erratic, sometimes slower than one chain)
-            side = self.__dict__.get("_lent_stream")
             if side is None or side.device != cur.device:
-                side = self.__dict__.get("_fwd_side")
+                side = self._fwd_side
                 if side is None or side.device != cur.device:
                     side = torch.cuda.Stream(device=cur.device)
-        self.__dict__["_fwd_side"] = side
+        else:
+            side = None
+        self._fwd_side = side
         if side is not None:
             # The forward is one dependent chain per image: the two halves of the batch run as two chains
             # on two streams (row-sliced views of the same buffers, so the results are the same bits and
@@ -268,7 +345,7 @@ class ViTAutoencoder(nn.Module):
                         Lh.__dict__[k] = v[h * Bh:(h + 1) * Bh] if k == "lse" else v[h * Th:(h + 1) * Th]
                     return Lh
                 cuts = a.__dict__["_enc_halves"] = [[cut(L, h) for L in a.enc] for h in (0, 1)]
-            self._event().record().wait(side)
+            Event.pooled().record().wait(side)
             # All blocks by default (A/B in one process, round 2: 0 / 6 / 12 of 12 blocks split -> 11.77 / 11.81 /
             # 11.68 ms per step; round 1 kept it to half because the f32-MFMA BMU pass ran slower right after a dense
             # forward -- the bf16 BMU pass does not).
@@ -281,7 +358,7 @@ class ViTAutoencoder(nn.Module):
                 c0 = self._block_fwd(self.blocks[i], cuts[0][i], c0, Bh, a.N)
                 with on_stream(side):
                     c1 = self._block_fwd(self.blocks[i], cuts[1][i], c1, Bh, a.N)
-            self._event().record(side).wait()
+            Event.pooled().record(side).wait()
             cur = a.enc[nsplit - 1].x2 if nsplit > 0 else a.tok0
             for blk, L in zip(self.blocks[nsplit:depth], a.enc[nsplit:depth]):
                 cur = self._block_fwd(blk, L, cur, a.B, a.N)
@@ -424,141 +501,75 @@ class ViTAutoencoder(nn.Module):
             ops.proto_mosaic(d.pred[:m * (n + 1)], n, p, C, k0, (rows, cols), images=images, canvas=canvas, gap=gap)
         return images, canvas
 
-    # -- backward -----------------------------------------------------------------------------
-    @staticmethod
-    def _dx(WT, dy, weight, dx, **kw):
-        """dX = dY W: from the transposed weight copy when the owner keeps one (NT kernel family)."""
-        wt = WT(weight) if WT is not None else None
-        if wt is not None:
-            return ops.linear_bwd_input_t(dy, wt, dx, **kw)
-        return ops.linear_bwd_input(dy, weight, dx, **kw)
-
-    # Weight-gradient GEMMs (and their slab reductions) are off the backward's critical path: nothing
-    # reads dW before the optimizer.  With a side stream set (ViTSOM does, on the GPU) they run
-    # concurrently with the dX / LayerNorm / attention chain and fill its tail rounds and the
-    # small-grid gaps.  Ordering: (1) a side GEMM waits for the main-stream kernel that produced
-    # its dY; (2) the dY buffers (gout / g1 from a ring of five, dh / dqkv from two sets) are rewritten
-    # two blocks later at the earliest, and the entry of block j waits for the side work of block
-    # j+2 (_side_join) -- a wait that has normally long been satisfied, so the main stream does not
-    # stall on the ~15 us cross-stream signalling latency a wait on the PREVIOUS block costs;
-    # (3) the owner joins the side stream before anything reads the gradients.  The saved
-    # activations the GEMMs read are not written during a backward pass.
-    _side = None
-
-    def _event(self):
-        """Pooled library events (re-recording one is safe once the waits on its previous record are enqueued; the pool is
-        far longer than the few events whose wait is deferred by a block or two)."""
-        return Event.pooled()
-
-    def _dw(self, dy, x, gw, gb):
-        side = self._side
-        if side is None:
-            return ops.linear_bwd_weight(dy, x, gw, gb)
-        self._event().record().wait(side)       # recorded on the main (current) stream: dy is final here
-        with on_stream(side):
-            ops.linear_bwd_weight(dy, x, gw, gb)
-
-    def _side_join(self, keep: int = 1):
-        """Main stream waits for the side work of all but the `keep` most recent blocks."""
-        pend = self.__dict__.setdefault("_side_pending", [])
-        if self._side is None:
-            pend.clear()
-            return
-        while len(pend) > keep:
-            pend.pop(0).wait()
-
-    def _side_mark(self):
-        if self._side is not None:
-            self.__dict__.setdefault("_side_pending", []).append(self._event().record(self._side))
-
-    def _ln_bwd(self, dy, x, mean, rstd, gamma, resid, dx, dgamma, dbeta):
-        """LayerNorm backward; with a job list lent by the owner (ViTSOM._backward) the dgamma / dbeta reduction is
-        left to the owner's next flush."""
-        jobs = self.__dict__.get("_ln_jobs")
-        if jobs is not None and ops.layernorm_bwd_deferrable(*x.shape):
-            return jobs.bwd(dy, x, mean, rstd, gamma, resid, dx, dgamma, dbeta)
-        return ops.layernorm_bwd(dy, x, mean, rstd, gamma, resid, dx, dgamma, dbeta)
-
-    def _dx_ln(self, WT, dy, weight, da, x, mean, rstd, gamma, resid, dx, dgamma, dbeta):
-        """dX of a Linear, then the backward of the LayerNorm whose output fed it: one launch (the LayerNorm backward in
-        the GEMM's epilogue, the product never stored) where the transposed weight copy, the shape and the GEMM mode allow
-        it (hooks.ln_bwd_fused), else the GEMM into the scratch `da` and _ln_bwd.  Same dX bits either way."""
-        wt = WT(weight) if (WT is not None and hooks.ln_bwd_fused) else None
-        if wt is not None and ops.linear_bwd_input_ln_supported(dy.shape[0], dy.shape[1], x.shape[1]):
-            jobs = self.__dict__.get("_ln_jobs")
-            if jobs is not None:
-                return jobs.bwd_linear_fused(dy, wt, x, mean, rstd, gamma, resid, dx, dgamma, dbeta)
-            return ops.linear_bwd_input_ln(dy, wt, x, mean, rstd, gamma, resid, dx, dgamma, dbeta)
-        self._dx(WT, dy, weight, da)
-        return self._ln_bwd(da, x, mean, rstd, gamma, resid, dx, dgamma, dbeta)
-
-    def _block_bwd(self, blk: Block, L: _Acts, x_in, gout, a: _Acts, G, prefix: str, bufs, WT=None, parity: int = 0):
+    # -- backward (the streams, events and deferred reductions of a pass: _BackwardSchedule) ---
+    def _block_bwd(self, blk: Block, L: _Acts, x_in, gout, a: _Acts, sched: _BackwardSchedule, prefix: str, bufs, parity: int = 0):
         """gout: gradient w.r.t. the block output [T,dim]; returns gradient w.r.t. x_in (in bufs)."""
         T, dim, hid = a.T, blk.dim, blk.hidden
-        self._side_join(keep=1)            # side work of the block before the previous one must be done
+        G = sched.G
+        sched._side_join(keep=1)           # side work of the block before the previous one must be done
         g1, g0 = bufs
         dh = a.dh2[parity][:T * hid].view(T, hid)
         da = a.da[:T * dim].view(T, dim)
         dqkv = a.dqkv2[parity][:T * 3 * dim].view(T, 3 * dim)
-        self._dw(gout, L.hact, G(f"{prefix}.mlp.2.weight"), G(f"{prefix}.mlp.2.bias"))
-        self._dx(WT, gout, blk.mlp["2"].weight, dh, gelu_grad=L.hpre)
-        self._dw(dh, L.a2, G(f"{prefix}.mlp.0.weight"), G(f"{prefix}.mlp.0.bias"))
-        self._dx_ln(WT, dh, blk.mlp["0"].weight, da, L.x1, L.mean2, L.rstd2, blk.norm2.weight, gout, g1,
+        sched._dw(gout, L.hact, G(f"{prefix}.mlp.2.weight"), G(f"{prefix}.mlp.2.bias"))
+        sched._dx(gout, blk.mlp["2"].weight, dh, gelu_grad=L.hpre)
+        sched._dw(dh, L.a2, G(f"{prefix}.mlp.0.weight"), G(f"{prefix}.mlp.0.bias"))
+        sched._dx_ln(dh, blk.mlp["0"].weight, da, L.x1, L.mean2, L.rstd2, blk.norm2.weight, gout, g1,
                     G(f"{prefix}.norm2.weight"), G(f"{prefix}.norm2.bias"))
-        self._dw(g1, L.ao, G(f"{prefix}.attn.proj.weight"), G(f"{prefix}.attn.proj.bias"))
-        self._dx(WT, g1, blk.attn.proj.weight, da)
+        sched._dw(g1, L.ao, G(f"{prefix}.attn.proj.weight"), G(f"{prefix}.attn.proj.bias"))
+        sched._dx(g1, blk.attn.proj.weight, da)
         ops.attention_bwd(L.qkv, L.ao, da, L.lse, dqkv, a.delta, a.B, a.N, blk.heads, dim // blk.heads)
-        self._dw(dqkv, L.a1, G(f"{prefix}.attn.qkv.weight"), G(f"{prefix}.attn.qkv.bias"))
-        self._dx_ln(WT, dqkv, blk.attn.qkv.weight, da, x_in, L.mean1, L.rstd1, blk.norm1.weight, g1, g0,
+        sched._dw(dqkv, L.a1, G(f"{prefix}.attn.qkv.weight"), G(f"{prefix}.attn.qkv.bias"))
+        sched._dx_ln(dqkv, blk.attn.qkv.weight, da, x_in, L.mean1, L.rstd1, blk.norm1.weight, g1, g0,
                     G(f"{prefix}.norm1.weight"), G(f"{prefix}.norm1.bias"))
-        self._side_mark()
+        sched._side_mark()
         return g0
 
     def _views(self, a: _Acts, dim: int):
         return [b[:a.T * dim].view(a.T, dim) for b in a.g]
 
-    def _decoder_bwd(self, a: _Acts, G, WT=None, before_dxe=None):
+    def _decoder_bwd(self, a: _Acts, sched: _BackwardSchedule, before_dxe=None):
         """a.dpred holds dL/dpred; writes decoder grads and dL/d(xe) into a.d_xe -- overwriting it, or,
         when `before_dxe` is given, calling it and then ADDING to what a.d_xe holds (the SOM input
         gradient written concurrently on another stream; `before_dxe` waits for it)."""
-        DE = self.decoder_embed_dim
+        G, DE = sched.G, self.decoder_embed_dim
         ring = self._views(a, DE)
         gA = ring[0]
         ops.linear_bwd_weight(a.dpred, a.dn, G("decoder_pred.weight"), G("decoder_pred.bias"))
         dn_grad = a.da[:a.T * DE].view(a.T, DE)
-        self._dx(WT, a.dpred, self.decoder_pred.weight, dn_grad)
+        sched._dx(a.dpred, self.decoder_pred.weight, dn_grad)
         x_last = a.dec[-1].x2 if a.dec else a.dec0
-        self._ln_bwd(dn_grad, x_last, a.mean_d, a.rstd_d, self.decoder_norm.weight, None, gA,
-                          G("decoder_norm.weight"), G("decoder_norm.bias"))
+        sched._ln_bwd(dn_grad, x_last, a.mean_d, a.rstd_d, self.decoder_norm.weight, None, gA,
+                      G("decoder_norm.weight"), G("decoder_norm.bias"))
         gout, pos = gA, 0
         for j, i in enumerate(reversed(range(len(self.decoder_blocks)))):
             x_in = a.dec[i - 1].x2 if i > 0 else a.dec0
             bufs = [ring[(pos + 1) % 5], ring[(pos + 2) % 5]]
-            gout = self._block_bwd(self.decoder_blocks[i], a.dec[i], x_in, gout, a, G, f"decoder_blocks.{i}", bufs, WT, j & 1)
+            gout = self._block_bwd(self.decoder_blocks[i], a.dec[i], x_in, gout, a, sched, f"decoder_blocks.{i}", bufs, j & 1)
             pos = (pos + 2) % 5
         ops.linear_bwd_weight(gout, a.xe, G("decoder_embed.weight"), G("decoder_embed.bias"))
         if before_dxe is not None:
             before_dxe()
-        self._dx(WT, gout, self.decoder_embed.weight, a.d_xe, accumulate=before_dxe is not None)
+        sched._dx(gout, self.decoder_embed.weight, a.d_xe, accumulate=before_dxe is not None)
 
-    def _encoder_bwd(self, a: _Acts, G, WT=None, on_block=None, depth=None):
+    def _encoder_bwd(self, a: _Acts, sched: _BackwardSchedule, on_block=None, depth=None):
         """a.d_xe holds dL/d(xe); writes every encoder gradient.  on_block(i) is called once block i's
         backward (main chain and weight-gradient side work) has been enqueued.  With `depth` given, the caller has
         already run the final norm and blocks [depth, D) and left dL/d(output of block depth - 1) in the first
         [T, E] gradient buffer (self._views(a, E)[0]); only blocks [0, depth) and the patch embedding run."""
-        self._side_join(keep=0)            # the decoder's blocks may still be reading the shared buffers
-        E = self.embed_dim
+        sched._side_join(keep=0)           # the decoder's blocks may still be reading the shared buffers
+        G, E = sched.G, self.embed_dim
         ring = self._views(a, E)
         gA = ring[0]
         if depth is None:
             depth = len(self.blocks)
             x_last = a.enc[-1].x2 if a.enc else a.tok0
-            self._ln_bwd(a.d_xe, x_last, a.mean_e, a.rstd_e, self.norm.weight, None, gA, G("norm.weight"), G("norm.bias"))
+            sched._ln_bwd(a.d_xe, x_last, a.mean_e, a.rstd_e, self.norm.weight, None, gA, G("norm.weight"), G("norm.bias"))
         gout, pos = gA, 0
         for j, i in enumerate(reversed(range(depth))):
             x_in = a.enc[i - 1].x2 if i > 0 else a.tok0
             bufs = [ring[(pos + 1) % 5], ring[(pos + 2) % 5]]
-            gout = self._block_bwd(self.blocks[i], a.enc[i], x_in, gout, a, G, f"blocks.{i}", bufs, WT, j & 1)
+            gout = self._block_bwd(self.blocks[i], a.enc[i], x_in, gout, a, sched, f"blocks.{i}", bufs, j & 1)
             pos = (pos + 2) % 5
             if on_block is not None:
                 on_block(i)
@@ -603,25 +614,21 @@ class _VitForwardFn(torch.autograd.Function):
         named = _trainable_order(vit)
         with torch.no_grad():
             grads = {n: torch.zeros_like(p) for n, p in named}
-            G = grads.__getitem__
+            sched = _BackwardSchedule(grads.__getitem__)          # single stream: this is not the fused step
             E, N, B = vit.embed_dim, a.N, a.B
-            side, vit._side = vit._side, None                     # single stream: this is not the fused step
-            try:
-                if g_recon is not None:
-                    dp = a.dpred.view(B, N, -1)
-                    dp[:, 0].zero_()
-                    dp[:, 1:].copy_(vit.patchify(g_recon.float()))
-                    vit._decoder_bwd(a, G)
-                else:
-                    a.d_xe.zero_()
-                d = a.d_xe.view(B, N, E)
-                if g_cls is not None:
-                    d[:, 0].add_(g_cls)
-                if g_patches is not None:
-                    d[:, 1:].add_(g_patches)
-                vit._encoder_bwd(a, G)
-            finally:
-                vit._side = side
+            if g_recon is not None:
+                dp = a.dpred.view(B, N, -1)
+                dp[:, 0].zero_()
+                dp[:, 1:].copy_(vit.patchify(g_recon.float()))
+                vit._decoder_bwd(a, sched)
+            else:
+                a.d_xe.zero_()
+            d = a.d_xe.view(B, N, E)
+            if g_cls is not None:
+                d[:, 0].add_(g_cls)
+            if g_patches is not None:
+                d[:, 1:].add_(g_patches)
+            vit._encoder_bwd(a, sched)
         return (None, None, None) + tuple(grads[n] for n, _ in named)
 
 
@@ -645,13 +652,9 @@ class _VitDecoderFn(torch.autograd.Function):
         named = _trainable_order(vit)
         with torch.no_grad():
             grads = {n: torch.zeros_like(p) for n, p in named}
-            side, vit._side = vit._side, None
-            try:
-                dp = a.dpred.view(a.B, a.N, -1)
-                dp[:, 0].zero_()
-                dp[:, 1:].copy_(g_patches.float())
-                vit._decoder_bwd(a, grads.__getitem__)
-            finally:
-                vit._side = side
+            dp = a.dpred.view(a.B, a.N, -1)
+            dp[:, 0].zero_()
+            dp[:, 1:].copy_(g_patches.float())
+            vit._decoder_bwd(a, _BackwardSchedule(grads.__getitem__))
             gx = a.d_xe.view(a.B, a.N, vit.embed_dim).clone()
         return (gx, None) + tuple(grads[n] for n, _ in named)

@@ -15,7 +15,7 @@ from ._lib import stream_wait_stream
 from .optim import FusedAdamW, param_groups_lrd
 from .step import _ArenaOwner
 from .tuning import hooks
-from .vit import ViTAutoencoder, _Affine
+from .vit import ViTAutoencoder, _Affine, _BackwardSchedule
 
 _LOSS_RING = 16     # the loss terms of a step stay readable until this many further steps have run
 _STEP_STREAMS: Dict[int, tuple] = {}        # device index -> (side stream, SOM stream), shared by every model of the process
@@ -45,6 +45,8 @@ class _ViTOwner(_ArenaOwner, _Base):
         self._n_train: Optional[int] = None
         self._est_steps: Optional[int] = None
         self._last: Dict[str, torch.Tensor] = {}
+        self._side_stream = self._som_stream = None
+        self._sched: Optional[_BackwardSchedule] = None     # what the last host-driven backward pass ran with
 
     @property
     def _vit(self) -> ViTAutoencoder:
@@ -124,7 +126,7 @@ class _ViTOwner(_ArenaOwner, _Base):
 
     def _ensure_streams(self, device):
         """The two extra HIP streams of the step (kept to two: a process has few hardware queues)."""
-        if getattr(self, "_side_stream", None) is None or self._side_stream.device != device:
+        if self._side_stream is None or self._side_stream.device != device:
             # one pair per device for the whole process: which hardware queue a stream lands on depends on how many
             # streams the process has created, and two of a model's streams on one queue serialise (measured: the 3rd, 5th
             # ... model of a process ran its step 1.4x slower at batch 128)
@@ -134,7 +136,6 @@ class _ViTOwner(_ArenaOwner, _Base):
                 pair = _STEP_STREAMS[key] = (torch.cuda.Stream(device=device), torch.cuda.Stream(device=device))
             self._side_stream = pair[0]      # weight-gradient GEMMs; second forward chain
             self._som_stream = pair[1]       # SOM backward + early all-reduce; the prototypes' plane image in the forward
-        self._vit.__dict__["_lent_stream"] = self._side_stream
 
     def _log(self, *a, **k):
         """self.log / self.log_dict when a Lightning trainer is attached (vit_som.py:95-101); a no-op otherwise.
@@ -169,31 +170,30 @@ class _ViTOwner(_ArenaOwner, _Base):
 
     @torch.no_grad()
     def _backward(self):
-        """All backward kernels; overwrites the whole gradient arena (no accumulation).  The subclass's
-        _head_backward(a, extra, Gv, reduce) runs the part above the encoder, starting each of its buckets with
+        """All backward kernels; overwrites the whole gradient arena (no accumulation).  The pass's streams, deferred
+        LayerNorm reductions, W^T copies and gradient views travel in one _BackwardSchedule.  The subclass's
+        _head_backward(a, extra, sched, reduce) runs the part above the encoder, starting each of its buckets with
         reduce(name[, streams]), and returns the `depth` of ViTAutoencoder._encoder_bwd that is left: None for the
         whole encoder from dL/d(xe) in a.d_xe."""
         x, a, extra = self._ctx
-        vit = self._vit
         self._grads_reduced = False
         self._exchange_reset()
+        side = None
         if hooks.side_stream:
             self._ensure_streams(x.device)
-            vit._side = self._side_stream
-        else:
-            vit._side = None
+            side = self._side_stream
         Gv = self._G(self._vit_name + ".")
         self._refresh_weight_transposes()
         # the LayerNorm backwards leave their dgamma / dbeta reductions to one launch per exchange piece (or one in all)
         jobs = None
         if hooks.ln_reduce_batched:
-            jobs = a.__dict__.get("ln_jobs")
+            jobs = getattr(a, "ln_jobs", None)
             if jobs is None:
                 jobs = a.ln_jobs = ops.LayerNormJobs(x.device)
             jobs.begin()
         buckets = self._exchange_buckets() if self._overlap_enabled() else {}
         main = torch.cuda.current_stream()
-        vit.__dict__["_ln_jobs"] = jobs
+        sched = self._sched = _BackwardSchedule(Gv, side, jobs, self._WT)
 
         def flush():
             if jobs is not None:
@@ -206,18 +206,15 @@ class _ViTOwner(_ArenaOwner, _Base):
             if b is not None:
                 flush()
                 if streams is None:
-                    streams = [st for st in (main, vit._side) if st is not None]
+                    streams = [st for st in (main, side) if st is not None]
                 self._reduce_early(*b, streams=streams)
 
-        try:
-            depth = self._head_backward(a, extra, Gv, reduce)
-            vit._encoder_bwd(a, Gv, self._WT, lambda i: reduce(f"enc{i}"), depth=depth)
-            flush()
-            if vit._side is not None:
-                stream_wait_stream(None, vit._side)     # every gradient is final from here on
-                vit.__dict__.setdefault("_side_pending", []).clear()
-        finally:
-            vit.__dict__["_ln_jobs"] = None
+        depth = self._head_backward(a, extra, sched, reduce)
+        self._vit._encoder_bwd(a, sched, lambda i: reduce(f"enc{i}"), depth=depth)
+        flush()
+        if side is not None:
+            stream_wait_stream(None, side)              # every gradient is final from here on
+            sched.pending.clear()
 
     # -- reference API ----------------------------------------------------------------------------
     def configure_optimizers(self):
