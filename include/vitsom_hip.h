@@ -521,6 +521,45 @@ int vsom_augment_batch(const unsigned char* src, long N, int C, int H, int W, co
                        int B, int S, int R, int off, const float* mean, const float* std, uint64_t seed, int epoch,
                        float* out, unsigned char* out_u8, vsom_stream_t stream);
 
+/* RandAugment and timm's rand-m9 auto-augment (data/data.py:288-301): the training transform with both policies.
+ * vsom_randaug_plan writes a second record of VSOM_RANDAUG_PARAMS int32 per sample (16-byte aligned rows), drawn with
+ * Philox4x32-10 under stream 2 -- counter (block, index, 2, epoch), key seed -- so no draw of vsom_augment_plan moves:
+ *   word 0       flip 1: RandomHorizontalFlip(flip1_p), applied before the second crop
+ *   word 1       flip 2: timm's flip (probability 1/2), applied after the second crop
+ *   words 2-5    the policy's pick for slots 0 .. 3 (index into torchvision's 14 ops / timm's 15 ops; -1: stage empty)
+ *   word 6       bit t set: timm slot t is applied (each with probability 1/2);  word 7: 0
+ *   words 8 + 16 s .. 23 + 16 s, s = 0 .. 3: op slot s (0, 1: the torchvision stage; 2, 3: the timm stage)
+ *     +0   primitive: 0 none, 1 affine NEAREST, 2 affine BICUBIC, 3 brightness, 4 color, 5 contrast, 6 sharpness,
+ *          7 posterize, 8 solarize, 9 solarize-add (threshold 128), 10 invert, 11 autocontrast, 12 equalize
+ *     +1   integer parameter: bits kept (posterize, 0 .. 8), threshold (solarize, 0 .. 256), addend (solarize-add)
+ *     +2   fp32 blend factor of the four enhance primitives (bit pattern)
+ *     +3   fill of the affine primitives: R | G << 8 | B << 16 (one channel: the low byte)
+ *     +4 .. +15  six doubles a0 .. a5: the inverse map (x_in, y_in) = (a0 x + a1 y + a2, a3 x + a4 y + a5) as
+ *          Image.transform(size, AFFINE, data) takes it
+ * Words 2-7 are for the reader of a record; vsom_augment_batch_ra reads words 0, 1 and the slots only.
+ * torchvision stage, randaug_n (0 .. 2) slots: one of {Identity, ShearX, ShearY, TranslateX, TranslateY, Rotate, Brightness,
+ * Color, Contrast, Sharpness, Posterize, Solarize, AutoContrast, Equalize} at magnitude bin 9 of 31 (shear 0.09, translate
+ * int(150/331 S 0.3) px, rotate 9 degrees, enhance 1 +- 0.27, 7 bits, threshold 178.5), signed ones negated with
+ * probability 1/2; NEAREST, fill fill_tv.  timm stage (autoaugment != 0), 2 slots: one of {AutoContrast, Equalize, Invert,
+ * Rotate, PosterizeIncreasing, SolarizeIncreasing, SolarizeAdd, Color, Contrast, Brightness, SharpnessIncreasing, ShearX,
+ * ShearY, TranslateXRel, TranslateYRel} at m = clamp(N(9, 0.5), 0, 10) (rotate 3 m degrees, shear 0.03 m, translate
+ * 0.045 m S px, enhance max(0.1, 1 +- 0.09 m), 4 - int(0.4 m) bits, threshold 256 - int(25.6 m), addend min(128, int(11 m)));
+ * BICUBIC, fill fill_timm.  Rotations follow Image.rotate about (S / 2, S / 2).  fill_*: R | G << 8 | B << 16. */
+#define VSOM_RANDAUG_PARAMS 72
+int vsom_randaug_plan(const int64_t* index, long N, int B, int S, int randaug_n, int autoaugment, double flip1_p, uint32_t fill_tv,
+                      uint32_t fill_timm, uint64_t seed, int epoch, int32_t* ra, vsom_stream_t stream);
+/* vsom_augment_batch with R = S, off = 0 and the record `ra` ([B, VSOM_RANDAUG_PARAMS], 16-byte aligned) between its
+ * stages: crop 1 -> slots 0, 1 -> flip 1 -> crop 2 (params' h2 > 0) -> flip 2 -> slots 2, 3 -> level / 255, Normalize, erase.
+ * params (required) gives the crop boxes and the erase box; its merged flip (word 8) is not read.  Every primitive is PIL's,
+ * byte for byte: Image.transform(AFFINE) in 16.16 fixed point (NEAREST) or in doubles with coordinates accumulated pixel by
+ * pixel (BICUBIC), ImageEnhance's fp32 blend with its degenerate images, ImageOps' tables.  A slot that is not a record
+ * the plan would write is made safe, never refused (the records live on the device): an unknown primitive does nothing, the
+ * integer parameter is clamped to 0 .. 256, NaN coefficients become 0 and others are clamped to +-16384, a NaN factor
+ * becomes 1. */
+int vsom_augment_batch_ra(const unsigned char* src, long N, int C, int H, int W, const int64_t* index, const int32_t* params,
+                          const int32_t* ra, int B, int S, const float* mean, const float* std, uint64_t seed, int epoch,
+                          float* out, unsigned char* out_u8, vsom_stream_t stream);
+
 /* ------------------------------------------------------------------ small utilities */
 int vsom_fill(float* p, long n, float value, vsom_stream_t stream);
 /* out[0] = ca * a[0] + cb * b[0]: the step's total loss from its two device-side sums (vit_som.py:93,98); `counter`

@@ -6,7 +6,12 @@ do with torchvision, timm and a worker pool, for the fixed-size data sets, as on
     DeviceLoader     TensorLoader's order, sharding and length; yields (x float32, y int64) device tensors
 
 Every random decision is a function of (seed, epoch, dataset index) (ops.augment_plan), never of the batch or the rank, so N
-ranks see exactly the images one rank sees.  Not applied: RandAugment / timm's rand-m9 auto-augment (photometric stages).
+ranks see exactly the images one rank sees.
+
+torchvision's RandAugment(num_ops=randaug_n) after the first crop and timm's rand-m9-mstd0.5-inc1 after the second are opt-in
+(`auto_augment=True`): ops.randaug_plan draws a second record per sample -- two flips and four op slots, each a PIL primitive
+with its parameters -- and ops.augment_batch_ra executes it between the crops, every primitive byte for byte PIL's.  Without
+the option the two policies are not applied and the two flips of the reference merge into one (from_config warns).
 """
 import math
 import warnings
@@ -54,12 +59,20 @@ class DeviceTransform:
     """build_transform (data.py:254-315) as numbers: what ops.augment_plan / ops.augment_batch need."""
 
     def __init__(self, train, num_channels, input_size, mean, std, plain=False, scale=(0.08, 1.0), ratio=(0.75, 1.3333),
-                 two_stage=True, flip_p=0.5, erase_p=0.25):
+                 two_stage=True, flip_p=0.5, erase_p=0.25, auto_augment=False, randaug_n=0, autoaugment=False, flip1_p=0.5):
         self.train, self.C, self.S, self.plain = bool(train), int(num_channels), int(input_size), bool(plain)
         self.mean, self.std = tuple(float(m) for m in mean), tuple(float(s) for s in std)
         self.augment = self.train and not self.plain
         self.scale, self.ratio = tuple(float(v) for v in scale), tuple(float(v) for v in ratio)
         self.two_stage, self.flip_p, self.erase_p = bool(two_stage), float(flip_p), float(erase_p)
+        # auto_augment: RandAugment (randaug_n slots, NEAREST, fill 0) and timm's rand-m9 (autoaugment: two slots, BICUBIC,
+        # fill = timm's img_mean) through ops.randaug_plan / ops.augment_batch_ra; flip1_p: the reference's own flip
+        self.auto_augment = bool(auto_augment) and self.train and not self.plain
+        self.randaug_n, self.autoaugment, self.flip1_p = int(randaug_n), bool(autoaugment), float(flip1_p)
+        if self.auto_augment and not 0 <= self.randaug_n <= 2:
+            raise ValueError(f"DeviceTransform: randaug_n = {self.randaug_n} (the record holds 0 to 2 torchvision slots)")
+        self.fill_tv = (0,) * self.C
+        self.fill_timm = tuple(min(255, round(255 * m)) for m in self.mean)
         if self.train or self.plain:
             self.R, self.off = self.S, 0
         else:                                                  # Resize(int(S / crop_pct)) + CenterCrop(S), data.py:306-310
@@ -69,7 +82,7 @@ class DeviceTransform:
         self._dev = {}
 
     @classmethod
-    def from_config(cls, config, train, strict=False):
+    def from_config(cls, config, train, strict=False, auto_augment=False):
         d = config["data"]
         name, S, C = d["dataset"], int(d["input_size"]), int(d["num_channels"])
         if name in VARIABLE_SIZE_SETS:
@@ -93,7 +106,7 @@ class DeviceTransform:
                 raise ValueError(f"DeviceTransform: remode '{a.get('remode')}' (only 'pixel' is implemented)")
             if int(a.get("recount", 1)) > 1:
                 raise ValueError("DeviceTransform: recount > 1 (one erase box per image is implemented)")
-            if int(a.get("randaug_n", 2)) > 0 or a.get("autoaugment", True):
+            if not auto_augment and (int(a.get("randaug_n", 2)) > 0 or a.get("autoaugment", True)):
                 by_default = [k for k in ("randaug_n", "autoaugment") if k not in a]
                 msg = ("DeviceTransform: RandAugment / auto-augment (randaug_n, autoaugment) are not applied by the device "
                        "pipeline: crops, flip and random erasing only")
@@ -106,7 +119,8 @@ class DeviceTransform:
         # RandomHorizontalFlip(p1) then timm's own flip (0.5): one flip with the probability that exactly one happens
         flip_p = p1 * (1.0 - TIMM_HFLIP) + TIMM_HFLIP * (1.0 - p1)
         return cls(train, C, S, mean, std, scale=a.get("resize_scale", (0.08, 1.0)), ratio=a.get("resize_ratio", (0.75, 1.3333)),
-                   two_stage=True, flip_p=flip_p, erase_p=float(a.get("reprob", 0.25)))
+                   two_stage=True, flip_p=flip_p, erase_p=float(a.get("reprob", 0.25)), auto_augment=auto_augment,
+                   randaug_n=int(a.get("randaug_n", 2)), autoaugment=bool(a.get("autoaugment", True)), flip1_p=p1)
 
     def stats(self, device):
         """(mean, std) as float32 tensors on `device`."""
@@ -116,9 +130,9 @@ class DeviceTransform:
                               torch.tensor(self.std, dtype=torch.float32, device=device))
         return self._dev[key]
 
-    def apply(self, dataset, index, out, params, seed, epoch, out_u8=None):
+    def apply(self, dataset, index, out, params, seed, epoch, out_u8=None, ra=None):
         """out[:len(index)] <- the transformed rows `index` (int64, on the device) of `dataset`; two launches when training
-        with augmentation, one otherwise."""
+        with augmentation (three with auto_augment, which also needs the record buffer `ra`), one otherwise."""
         src = dataset.images
         if src.shape[1] != self.C:
             raise ValueError(f"DeviceTransform: {src.shape[1]}-channel data, {self.C}-channel transform")
@@ -127,6 +141,12 @@ class DeviceTransform:
             ops.augment_plan(index, params, src.shape[0], src.shape[2], self.S, self.scale, (math.log(self.ratio[0]), math.log(self.ratio[1])),
                              TIMM_SCALE if self.two_stage else None, (math.log(TIMM_RATIO[0]), math.log(TIMM_RATIO[1])),
                              self.flip_p, self.erase_p, seed, epoch)
+        if self.auto_augment:
+            if ra is None:
+                raise ValueError("DeviceTransform.apply: auto_augment needs the record buffer `ra` [B, ops.RANDAUG_PARAMS] int32")
+            ops.randaug_plan(index, ra, src.shape[0], self.S, self.randaug_n, self.autoaugment, self.flip1_p, self.fill_tv,
+                             self.fill_timm, seed, epoch)
+            return ops.augment_batch_ra(src, index, params, ra, out, self.S, mean, std, seed, epoch, out_u8=out_u8)
         return ops.augment_batch(src, index, params if self.augment else None, out, self.S, self.R, self.off, mean, std, seed, epoch,
                                  out_u8=out_u8)
 
@@ -171,7 +191,9 @@ class DeviceLoader:
         if self._ring is None:
             t, dev, B = self.transform, self.dataset.images.device, self.batch_size
             self._ring = [(torch.empty(B, t.C, t.S, t.S, dtype=torch.float32, device=dev),
-                           torch.zeros(B, ops.AUGMENT_PARAMS, dtype=torch.int32, device=dev)) for _ in range(2)]
+                           torch.zeros(B, ops.AUGMENT_PARAMS, dtype=torch.int32, device=dev),
+                           torch.zeros(B, ops.RANDAUG_PARAMS, dtype=torch.int32, device=dev) if t.auto_augment else None)
+                          for _ in range(2)]
         return self._ring
 
     def __iter__(self):
@@ -186,8 +208,8 @@ class DeviceLoader:
             # A ring of two pre-allocated batches: the batch handed out last time stays intact while this one is written.
             # Nothing waits: the kernels go to the stream the consumer's step is queued on, so this launch runs after every
             # earlier reader of the slot it overwrites (the step before last) -- stream order alone guarantees it.
-            x, params = ring[self._slot]
+            x, params, ra = ring[self._slot]
             self._slot ^= 1
-            self.transform.apply(self.dataset, j, x, params, self.seed, epoch)
+            self.transform.apply(self.dataset, j, x, params, self.seed, epoch, ra=ra)
             # the labels are not ring views: consumers collect them over a whole loader (evaluation.py)
             yield x[:b], self.dataset.labels[j]

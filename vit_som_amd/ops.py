@@ -752,6 +752,42 @@ def augment_batch(src, index, params, out, S, R, off, mean, std, seed, epoch, ou
     return out
 
 
+RANDAUG_PARAMS = 72
+
+
+def _pack_fill(fill):
+    fill = tuple(int(v) for v in fill) + (0,) * (3 - len(fill))
+    assert len(fill) == 3 and all(0 <= v <= 255 for v in fill)
+    return fill[0] | fill[1] << 8 | fill[2] << 16
+
+
+def randaug_plan(index, ra, N, S, randaug_n, autoaugment, flip1_p, fill_tv, fill_timm, seed, epoch):
+    """ra[b] <- the RandAugment / rand-m9 record of row index[b] in `epoch` (see vsom_randaug_plan); fills: one level per channel."""
+    assert index.is_cuda and index.dtype == torch.int64 and index.is_contiguous() and index.dim() == 1
+    assert ra.is_cuda and ra.dtype == torch.int32 and ra.is_contiguous()
+    assert ra.dim() == 2 and ra.shape[0] >= index.numel() and ra.shape[1] == RANDAUG_PARAMS
+    check(lib.vsom_randaug_plan(ptr(index), int(N), index.numel(), int(S), int(randaug_n), int(bool(autoaugment)), float(flip1_p),
+                                _pack_fill(fill_tv), _pack_fill(fill_timm), int(seed), int(epoch), ptr(ra), stream()), "vsom_randaug_plan")
+    return ra
+
+
+def augment_batch_ra(src, index, params, ra, out, S, mean, std, seed, epoch, out_u8=None):
+    """out[b] <- the training transform of row index[b] with the op slots of `ra` between the crops (see vsom_augment_batch_ra)."""
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 4
+    assert index.is_cuda and index.dtype == torch.int64 and index.is_contiguous() and index.dim() == 1
+    N, C, H, W = src.shape
+    B = index.numel()
+    _f32(out, "out"), _f32(mean, "mean"), _f32(std, "std")
+    assert out.is_contiguous() and out.numel() >= B * C * S * S and mean.numel() == C and std.numel() == C
+    for t, width in ((params, AUGMENT_PARAMS), (ra, RANDAUG_PARAMS)):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.shape[0] >= B and t.shape[1] == width
+    if out_u8 is not None:
+        assert out_u8.is_cuda and out_u8.dtype == torch.uint8 and out_u8.is_contiguous() and out_u8.numel() >= B * C * S * S
+    check(lib.vsom_augment_batch_ra(ptr(src), N, C, H, W, ptr(index), ptr(params), ptr(ra), B, int(S), ptr(mean), ptr(std), int(seed),
+                                    int(epoch), ptr(out), ptr(out_u8), stream()), "vsom_augment_batch_ra")
+    return out
+
+
 # ---------------------------------------------------------------- k-means (evaluate_kmeans)
 def kmeans_workspace_bytes(N: int, D: int, k: int) -> int:
     return lib.vsom_kmeans_workspace_bytes(N, D, k)

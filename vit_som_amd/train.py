@@ -9,7 +9,7 @@ Data comes from a `make_loaders(config, rank, world_size)` callable returning
 torchvision/timm and downloads (absent offline), so the default is a synthetic, class-structured
 in-memory set of the configured shape; `device_loaders` (--device-data, --data-npz PATH) keeps the
 images on the GPU as uint8 and applies the configs' crop / flip / erase augmentation there
-(vit_som_amd.data).  One process per GPU: under torchrun (WORLD_SIZE > 1) every rank takes an
+(vit_som_amd.data); --device-randaug adds the configs' RandAugment and timm rand-m9 auto-augment.  One process per GPU: under torchrun (WORLD_SIZE > 1) every rank takes an
 interleaved shard of each loader and gradients are summed by one RCCL all-reduce.
 
     python -m vit_som_amd.train --config configs/vit_som/vit_som_cifar-10.yaml [--runs 5] [--epochs N]
@@ -102,12 +102,14 @@ def synthetic_loaders(config, rank=0, world_size=1, n_train=2048, n_val=256, n_t
             TensorLoader(xv, yv, bs, rank=rank, world_size=world_size), TensorLoader(xs, ys, bs, rank=rank, world_size=world_size))
 
 
-def device_loaders(config, rank=0, world_size=1, n_train=2048, n_val=256, n_test=256, seed=0, npz=None, strict=False):
+def device_loaders(config, rank=0, world_size=1, n_train=2048, n_val=256, n_test=256, seed=0, npz=None, strict=False,
+                   auto_augment=False):
     """A `make_loaders` whose input side runs on the device (vit_som_amd.data): the images live on the GPU as uint8, the train
     loader applies the config's training transform (crops, flip, random erasing), val / test the evaluation transform.
     Default data: synthetic_loaders' class-structured set, quantised to 8 bits (level = 255 clip(x / 4 + 1 / 2, 0, 1)).
     `npz`: a local file with `images` / `labels` (and optionally `test_images` / `test_labels`; without them the last tenth
-    of the rows is held out) -- validation and test then share the held-out part."""
+    of the rows is held out) -- validation and test then share the held-out part.  `auto_augment`: the train loader also
+    applies the config's RandAugment and timm rand-m9 auto-augment (DeviceTransform.from_config(auto_augment=True))."""
     from .data import DeviceDataset, DeviceLoader, DeviceTransform
     hp, d = config["hyperparameters"], config["data"]
     C, S, bs = d["num_channels"], d["input_size"], hp["batch_size"]
@@ -132,7 +134,7 @@ def device_loaders(config, rank=0, world_size=1, n_train=2048, n_val=256, n_test
             x = templates[y] + 0.5 * torch.randn(n, C, S, S, generator=g)
             return DeviceDataset((x / 4 + 0.5).clamp_(0, 1).mul_(255).round_().to(torch.uint8), y, dev)
         train_set, val_set, test_set = make(n_train), make(n_val), make(n_test)
-    t_train = DeviceTransform.from_config(config, True, strict=strict)
+    t_train = DeviceTransform.from_config(config, True, strict=strict, auto_augment=auto_augment)
     t_eval = DeviceTransform.from_config(config, False)
     return (DeviceLoader(train_set, bs, t_train, shuffle=True, rank=rank, world_size=world_size, seed=seed, drop_last=True),
             DeviceLoader(val_set, bs, t_eval, rank=rank, world_size=world_size),
@@ -297,8 +299,10 @@ if __name__ == "__main__":
     ap.add_argument("--epochs", type=int, default=None)
     ap.add_argument("--device-data", action="store_true", help="keep the data on the GPU as uint8 and augment it there")
     ap.add_argument("--data-npz", type=str, default=None, help="a local .npz with images / labels (implies --device-data)")
+    ap.add_argument("--device-randaug", action="store_true",
+                    help="also apply the config's RandAugment / timm rand-m9 auto-augment on the GPU (implies --device-data)")
     a = ap.parse_args()
     loaders = synthetic_loaders
-    if a.device_data or a.data_npz:
-        loaders = lambda c, r, w: device_loaders(c, r, w, npz=a.data_npz)     # noqa: E731
+    if a.device_data or a.data_npz or a.device_randaug:
+        loaders = lambda c, r, w: device_loaders(c, r, w, npz=a.data_npz, auto_augment=a.device_randaug)     # noqa: E731
     main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs, make_loaders=loaders)
