@@ -560,6 +560,38 @@ int vsom_augment_batch_ra(const unsigned char* src, long N, int C, int H, int W,
                           const int32_t* ra, int B, int S, const float* mean, const float* std, uint64_t seed, int epoch,
                           float* out, unsigned char* out_u8, vsom_stream_t stream);
 
+/* ------------------------------------------------------------------ data: image sets of varying size (augment_ragged.hip)
+ * The set is one flat uint8 buffer `data` of data_bytes bytes: image n is planar [C][H_n][W_n] at byte offsets[n] (int64,
+ * a multiple of 16), with shapes[n] = {H_n, W_n} (int32 [N, 2]); C is 1 or 3 for the whole set and max_h, max_w bound every
+ * side (at most 2048).  The transform is vsom_augment_plan's and vsom_augment_batch's -- the same plan row, Philox counters,
+ * PIL resampler and output stage -- for outputs up to S = 224 and crops of up to 8 x their output side (33 taps).
+ * vsom_augment_plan_ragged: vsom_augment_plan with box 1 drawn on the sample's own H_n x W_n.  On a table whose rows are
+ * all (H, H) it writes what vsom_augment_plan(H) writes, bit for bit. */
+int vsom_augment_plan_ragged(const int64_t* index, const int32_t* shapes, long N, int B, int S, double scale0, double scale1,
+                             double log_ratio0, double log_ratio1, int two_stage, double scale2_0, double scale2_1,
+                             double log_ratio2_0, double log_ratio2_1, double flip_p, double erase_p, uint64_t seed, int epoch,
+                             int32_t* params, vsom_stream_t stream);
+/* Bytes of the 8-bit [B, C, S, S] image between the two training launches (16-byte aligned; one buffer serves every batch
+ * of a stream). */
+size_t vsom_augment_ragged_scratch_bytes(int B, int C, int S);
+/* out[b] (fp32 [B, C, S, S], 16-byte aligned) = the transform applied to image index[b].
+ * Training (params != NULL, R == S): crop box 1 of the H_n x W_n image -> S x S into `scratch`; box 2 of that (h2 > 0; else the
+ * image as it is) -> S x S; flip, level / 255, Normalize, erase as vsom_augment_batch does them.  Two launches.
+ * Evaluation (params == NULL): torchvision's Resize(R) of a rectangle -- the shorter side becomes R, the longer
+ * int(R * long / short) (a double division, truncated) -- then CenterCrop(S) at top = rint((Rh - S) / 2.0), left likewise
+ * (half to even), level / 255, Normalize.  Only the S x S window of the resize is computed.  One launch, no scratch.
+ * Every resize is Image.crop(box).resize(size, BICUBIC) byte for byte: horizontal pass first, 8-bit intermediate, taps stop
+ * at the box.  On a set whose images are all H x H, H <= 64, out and out_u8 equal vsom_augment_batch's bit for bit.
+ * Limits (checked before any launch): S <= 224, R <= 256, C 1 or 3, max_h, max_w <= 2048 and <= 8 S (training) or 8 R
+ * (evaluation); data, out, params, scratch 16-byte aligned, out_u8 4-byte aligned.
+ * Tables on the device cannot be refused, so they are made safe: the index is clamped into [0, N), the shape into
+ * [1, max_h] x [1, max_w], the offset so that the image lies inside data[0, data_bytes), every box inside its image.  A bad
+ * table reads wrong pixels, never outside the buffer. */
+int vsom_augment_batch_ragged(const unsigned char* data, size_t data_bytes, const int64_t* offsets, const int32_t* shapes, long N,
+                              int C, int max_h, int max_w, const int64_t* index, const int32_t* params, int B, int S, int R,
+                              const float* mean, const float* std, uint64_t seed, int epoch, void* scratch, size_t scratch_bytes,
+                              float* out, unsigned char* out_u8, vsom_stream_t stream);
+
 /* ------------------------------------------------------------------ small utilities */
 int vsom_fill(float* p, long n, float value, vsom_stream_t stream);
 /* out[0] = ca * a[0] + cb * b[0]: the step's total loss from its two device-side sums (vit_som.py:93,98); `counter`

@@ -127,6 +127,12 @@ SIGNATURES = {
                                     C.c_int, c_fp, c_stream]),
     "vsom_augment_batch_ra": (C.c_int, [c_fp, C.c_long, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, C.c_int, C.c_int, c_fp, c_fp,
                                         C.c_uint64, C.c_int, c_fp, c_fp, c_stream]),
+    "vsom_augment_plan_ragged": (C.c_int, [c_fp, c_fp, C.c_long, C.c_int, C.c_int] + [C.c_double] * 4 + [C.c_int] + [C.c_double] * 6
+                                 + [C.c_uint64, C.c_int, c_fp, c_stream]),
+    "vsom_augment_ragged_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "vsom_augment_batch_ragged": (C.c_int, [c_fp, C.c_size_t, c_fp, c_fp, C.c_long, C.c_int, C.c_int, C.c_int, c_fp, c_fp, C.c_int,
+                                            C.c_int, C.c_int, c_fp, c_fp, C.c_uint64, C.c_int, c_fp, C.c_size_t, c_fp, c_fp,
+                                            c_stream]),
     "vsom_kmeans_workspace_bytes": (C.c_size_t, [C.c_long, C.c_int, C.c_int]),
     "vsom_kmeans_assign": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_size_t,
                                      c_stream]),

@@ -788,6 +788,51 @@ def augment_batch_ra(src, index, params, ra, out, S, mean, std, seed, epoch, out
     return out
 
 
+# ---------------------------------------------------------------- data pipeline, image sets of varying size
+def augment_plan_ragged(index, shapes, params, S, scale, log_ratio, scale2, log_ratio2, flip_p, erase_p, seed, epoch):
+    """augment_plan with box 1 drawn on each sample's own (H_n, W_n) = shapes[index[b]] (see vsom_augment_plan_ragged)."""
+    assert index.is_cuda and index.dtype == torch.int64 and index.is_contiguous() and index.dim() == 1
+    assert shapes.is_cuda and shapes.dtype == torch.int32 and shapes.is_contiguous() and shapes.dim() == 2 and shapes.shape[1] == 2
+    assert params.is_cuda and params.dtype == torch.int32 and params.is_contiguous()
+    assert params.dim() == 2 and params.shape[0] >= index.numel() and params.shape[1] == AUGMENT_PARAMS
+    two = scale2 is not None
+    s2, l2 = (scale2, log_ratio2) if two else ((0.0, 0.0), (0.0, 0.0))
+    check(lib.vsom_augment_plan_ragged(ptr(index), ptr(shapes), shapes.shape[0], index.numel(), int(S), float(scale[0]), float(scale[1]),
+                                       float(log_ratio[0]), float(log_ratio[1]), int(two), float(s2[0]), float(s2[1]), float(l2[0]),
+                                       float(l2[1]), float(flip_p), float(erase_p), int(seed), int(epoch), ptr(params), stream()),
+          "vsom_augment_plan_ragged")
+    return params
+
+
+def augment_ragged_scratch_bytes(B: int, C: int, S: int) -> int:
+    return lib.vsom_augment_ragged_scratch_bytes(int(B), int(C), int(S))
+
+
+def augment_batch_ragged(data, offsets, shapes, C, max_h, max_w, index, params, out, S, R, mean, std, seed, epoch, scratch=None,
+                         out_u8=None):
+    """out[b] <- the transformed image index[b] of the ragged uint8 set (data, offsets, shapes) (see vsom_augment_batch_ragged);
+    params = None: the evaluation transform Resize(R) -> CenterCrop(S); otherwise `scratch` (uint8,
+    augment_ragged_scratch_bytes(B, C, S)) holds the image between the two crops."""
+    assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous() and data.dim() == 1
+    assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.dim() == 1
+    assert shapes.is_cuda and shapes.dtype == torch.int32 and shapes.is_contiguous() and tuple(shapes.shape) == (offsets.numel(), 2)
+    assert index.is_cuda and index.dtype == torch.int64 and index.is_contiguous() and index.dim() == 1
+    N, B = offsets.numel(), index.numel()
+    _f32(out, "out"), _f32(mean, "mean"), _f32(std, "std")
+    assert out.is_contiguous() and out.numel() >= B * C * S * S and mean.numel() == C and std.numel() == C
+    if params is not None:
+        assert params.is_cuda and params.dtype == torch.int32 and params.is_contiguous()
+        assert params.shape[0] >= B and params.shape[1] == AUGMENT_PARAMS
+        assert scratch is not None and scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous()
+    if out_u8 is not None:
+        assert out_u8.is_cuda and out_u8.dtype == torch.uint8 and out_u8.is_contiguous() and out_u8.numel() >= B * C * S * S
+    check(lib.vsom_augment_batch_ragged(ptr(data), data.numel(), ptr(offsets), ptr(shapes), N, int(C), int(max_h), int(max_w),
+                                        ptr(index), ptr(params), B, int(S), int(R), ptr(mean), ptr(std), int(seed), int(epoch),
+                                        ptr(scratch), 0 if scratch is None else scratch.numel(), ptr(out), ptr(out_u8), stream()),
+          "vsom_augment_batch_ragged")
+    return out
+
+
 # ---------------------------------------------------------------- k-means (evaluate_kmeans)
 def kmeans_workspace_bytes(N: int, D: int, k: int) -> int:
     return lib.vsom_kmeans_workspace_bytes(N, D, k)

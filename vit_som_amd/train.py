@@ -109,12 +109,50 @@ def device_loaders(config, rank=0, world_size=1, n_train=2048, n_val=256, n_test
     Default data: synthetic_loaders' class-structured set, quantised to 8 bits (level = 255 clip(x / 4 + 1 / 2, 0, 1)).
     `npz`: a local file with `images` / `labels` (and optionally `test_images` / `test_labels`; without them the last tenth
     of the rows is held out) -- validation and test then share the held-out part.  `auto_augment`: the train loader also
-    applies the config's RandAugment and timm rand-m9 auto-augment (DeviceTransform.from_config(auto_augment=True))."""
-    from .data import DeviceDataset, DeviceLoader, DeviceTransform
+    applies the config's RandAugment and timm rand-m9 auto-augment (DeviceTransform.from_config(auto_augment=True)).
+    Images of different sizes: a file with an `offsets` key is a ragged set as tools/pack_images.py writes it (`data`,
+    `offsets`, `shapes`, `labels`, `channels`, optionally the same under `test_`; otherwise the last tenth is held out), and
+    a config that names a variable-size image set (flowers-17 / -102) without a file gets a synthetic ragged set of the
+    same class structure with sides drawn in [S, 2 S].  Both go through RaggedDeviceDataset and the variable-size transform."""
+    from .data import VARIABLE_SIZE_SETS, DeviceDataset, DeviceLoader, DeviceTransform, RaggedDeviceDataset
     hp, d = config["hyperparameters"], config["data"]
     C, S, bs = d["num_channels"], d["input_size"], hp["batch_size"]
     dev = torch.device("cuda", torch.cuda.current_device())
+    ragged = False
     if npz is not None:
+        with np.load(npz) as z:
+            ragged = "offsets" in z
+    if ragged:
+        full = RaggedDeviceDataset.from_npz(npz, "cpu")
+        with np.load(npz) as z:
+            has_test = "test_offsets" in z
+        if has_test:
+            train_set = RaggedDeviceDataset.from_npz(npz, dev)
+            val_set = test_set = RaggedDeviceDataset.from_npz(npz, dev, prefix="test_")
+        else:
+            k = len(full) - max(len(full) // 10, 1)
+            cut = int(full.offsets[k])                         # image k starts the held-out part
+            train_set = RaggedDeviceDataset(full.data[:cut], full.offsets[:k], full.shapes[:k], full.labels[:k], full.C, dev)
+            val_set = test_set = RaggedDeviceDataset(full.data[cut:], full.offsets[k:] - cut, full.shapes[k:], full.labels[k:],
+                                                     full.C, dev)
+    elif npz is None and d["dataset"] in VARIABLE_SIZE_SETS and d["dataset"] != "reuters":
+        ragged = True
+        ncls = max(int(d["num_classes"]), 1) if d["num_classes"] > 0 else 10
+        g = torch.Generator().manual_seed(seed)
+        templates = (torch.randn(ncls, C, S, S, generator=g) / 4 + 0.5).clamp_(0, 1).mul_(255)
+
+        def make(n):
+            # a class = its template stretched to the image's own h x w (nearest pixel) plus noise of +-32 levels
+            y = torch.randint(0, ncls, (n,), generator=g)
+            sides = torch.randint(S, 2 * S + 1, (n, 2), generator=g)
+            images = []
+            for c, (h, w) in zip(y.tolist(), sides.tolist()):
+                rows, cols = torch.arange(h) * S // h, torch.arange(w) * S // w
+                img = templates[c][:, rows][:, :, cols] + torch.randint(-32, 33, (C, h, w), generator=g)
+                images.append(img.clamp_(0, 255).to(torch.uint8).numpy())
+            return RaggedDeviceDataset.from_arrays(images, y, dev, layout="CHW")
+        train_set, val_set, test_set = make(n_train), make(n_val), make(n_test)
+    elif npz is not None:
         with np.load(npz) as z:
             xi, yi = torch.from_numpy(z["images"]), torch.from_numpy(z["labels"].astype(np.int64))
             if "test_images" in z:
@@ -134,8 +172,8 @@ def device_loaders(config, rank=0, world_size=1, n_train=2048, n_val=256, n_test
             x = templates[y] + 0.5 * torch.randn(n, C, S, S, generator=g)
             return DeviceDataset((x / 4 + 0.5).clamp_(0, 1).mul_(255).round_().to(torch.uint8), y, dev)
         train_set, val_set, test_set = make(n_train), make(n_val), make(n_test)
-    t_train = DeviceTransform.from_config(config, True, strict=strict, auto_augment=auto_augment)
-    t_eval = DeviceTransform.from_config(config, False)
+    t_train = DeviceTransform.from_config(config, True, strict=strict, auto_augment=auto_augment, variable_size=ragged)
+    t_eval = DeviceTransform.from_config(config, False, variable_size=ragged)
     return (DeviceLoader(train_set, bs, t_train, shuffle=True, rank=rank, world_size=world_size, seed=seed, drop_last=True),
             DeviceLoader(val_set, bs, t_eval, rank=rank, world_size=world_size),
             DeviceLoader(test_set, bs, t_eval, rank=rank, world_size=world_size))
