@@ -379,6 +379,36 @@ int vsom_proto_mosaic(const float* pred, int chunk, int n, int p, int C, float* 
 int vsom_last_label(const int64_t* bmu, const int64_t* label, long n, long first_ordinal, int K,
                     unsigned long long* cells, int* out_of_range, vsom_stream_t stream);
 
+/* Map quality (no counterpart in the reference): one fold per batch over what the BMU pass left, no host synchronisation.
+ * dist [B, K] f32 (row stride K), bmu [B] int64, grid_positions [K, 2] f32 (the layer's buffer).  The accumulators are
+ * zeroed by the caller once per evaluation (nearest: all-ones = "no sample"); the kernel only adds, or min-folds nearest:
+ *   second[i]  (optional, NULL to skip) = first argmin over k != bmu[i] of dist[i, k] (float comparison: -0.0 == 0.0;
+ *              lowest index on a tie) -- exact on the dist it is given;
+ *   te[0]     += 1 when |pos[bmu[i]] - pos[second[i]]|^2 > adj_r2 (fp64 arithmetic on the fp32 positions);
+ *   hits[b]   += 1, qe_fix[b] += llrint(dist[i, b] * 2^32) for b = bmu[i]: fixed point, so the sums do not depend on the
+ *              order the atomics land in (per cell, sum |dist| must stay below 2^31);
+ *   nearest[k] = min over ALL samples i of (ordered_key(dist[i, k]) << 32) | (first_ordinal + i), ordered_key(v) =
+ *              bits(v) with the sign bit set for v >= +0, ~bits(v) otherwise: order-preserving on fp32 (-0.0 below
+ *              +0.0); ties go to the lowest ordinal.
+ * A row with bmu outside [0, K), a NaN distance or |dist[i, bmu]| >= 2^31 is counted in bad[0] and skipped entirely.
+ * K < 2: VSOM_EINVAL.  first_ordinal + B >= 2^31: VSOM_EUNSUPPORTED.  B == 0: nothing is launched.
+ * Rows are read 16 bytes per lane when K % 4 == 0 and dist is 16-byte aligned. */
+int vsom_map_stats(const float* dist, const int64_t* bmu, long B, int K, const float* grid_positions, float adj_r2,
+                   long first_ordinal, long long* hits, long long* qe_fix, long long* te, unsigned long long* nearest,
+                   int* bad, int64_t* second, vsom_stream_t stream);
+/* U-matrix: for every unit k of W [K, L] (f32, contiguous) the units j != k with |pos_j - pos_k|^2 <= adj_r2 in ascending
+ * index order -> nbr_idx [K, 8] int32 (padded with -1), their distance to unit k -> nbr_dist [K, 8] f32 (0 in the padding)
+ * and u [K] f32 = the mean of the valid entries, summed in slot order in fp64 (0 for a unit with no neighbour).
+ * Distances are accumulated over the whole row in fp64 from exact products / differences of the fp32 values, in a fixed
+ * order, and rounded to fp32 once:  VSOM_DIST_COSINE 1 - <a,b> / (max(|a|, 1e-12) max(|b|, 1e-12));  VSOM_DIST_EUCLIDEAN
+ * sqrt(sum (a - b)^2) (the difference form: neighbouring prototypes are close);  VSOM_DIST_MANHATTAN sum |a - b|.
+ * Any other distance: VSOM_EUNSUPPORTED.  A unit with more than 8 units within adj_r2 cannot be known on the host (the
+ * positions live on the device): the kernel keeps the first 8 and raises status[0] (zeroed by the caller) to the largest
+ * count seen; the caller reads it after the launch and treats a non-zero value as VSOM_EUNSUPPORTED.
+ * Rows are read 16 bytes per lane when L % 4 == 0 and W is 16-byte aligned. */
+int vsom_umatrix(const float* W, int K, int L, const float* grid_positions, float adj_r2, int distance, int* nbr_idx,
+                 float* nbr_dist, float* u, int* status, vsom_stream_t stream);
+
 /* k-means of evaluate_kmeans (evaluation.py:54-91): the data-touching steps of sklearn.cluster.KMeans
  * (sklearn/cluster/_kmeans.py, algorithm="lloyd", dense fp32, unit sample weights).  X is [N, D] with row stride ldx;
  * centres are [k, D] contiguous; labels int64.  Every sum has a fixed order (no floating-point atomics): results are

@@ -119,6 +119,8 @@ SIGNATURES = {
     "vsom_proto_mosaic": (C.c_int, [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, c_stream]),
     "vsom_last_label": (C.c_int, [c_fp, c_fp, C.c_long, C.c_long, C.c_int, c_fp, c_fp, c_stream]),
+    "vsom_map_stats": (C.c_int, [c_fp, c_fp, C.c_long, C.c_int, c_fp, C.c_float, C.c_long, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_stream]),
+    "vsom_umatrix": (C.c_int, [c_fp, C.c_int, C.c_int, c_fp, C.c_float, C.c_int, c_fp, c_fp, c_fp, c_fp, c_stream]),
     "vsom_augment_plan": (C.c_int, [c_fp, C.c_long, C.c_int, C.c_int, C.c_int] + [C.c_double] * 4 + [C.c_int] + [C.c_double] * 6
                           + [C.c_uint64, C.c_int, c_fp, c_stream]),
     "vsom_augment_batch": (C.c_int, [c_fp, C.c_long, C.c_int, C.c_int, C.c_int, c_fp, c_fp, C.c_int, C.c_int, C.c_int, C.c_int,

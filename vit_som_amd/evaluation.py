@@ -10,9 +10,13 @@ the HIP k-means (kmeans.py); visualize_umap_progression (:267-323) embeds the la
 UMAP (umap.py).  The two pictures of the map itself: visualize_decoded_prototypes / decode_prototype (:153-222) push the
 prototypes through the ViT decoder in batches and assemble the mosaic on the device (`vsom_proto_mosaic`);
 visualize_label_heatmap (:224-265) folds (BMU, label) pairs into a last-label-per-cell table (`vsom_last_label`).
+Map quality has no counterpart in the reference: evaluate_map_quality folds the distances and BMUs every predict() leaves
+in the SOM layer's buffers into quantization error, topographic error, hit map and nearest sample per unit
+(`vsom_map_stats`), umatrix / visualize_umatrix / visualize_hit_map draw the map without labels (`vsom_umatrix`).
 """
 import os
 import time
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -375,6 +379,164 @@ def visualize_label_heatmap(model, config, dataloader, output_dir="experiments/p
         if draw_label_heatmap(heatmap, output_dir, model_arch, _epoch(model)) is not None:
             print(f"Saved label heatmap visualization to {output_dir}")
     return heatmap
+
+
+# ------------------------------------------------------------------------------------ map quality
+@dataclass
+class MapQuality:
+    """Host values of one evaluate_map_quality pass.  Arrays are [rows, cols], unit k at divmod(k, cols)."""
+    quantization_error: float            # mean over the samples of dist[i, bmu[i]]
+    topographic_error: float             # share of samples whose best and second-best units are not grid neighbours
+    hits: np.ndarray                     # int64: samples per unit
+    dead_units: int                      # units no sample hit
+    cell_quantization_error: np.ndarray  # float64: mean dist of the samples a unit won, NaN where hits == 0
+    nearest_sample: np.ndarray           # int64: loader ordinal of the sample closest to the unit (over ALL samples), -1 if none
+    nearest_distance: np.ndarray         # float32: its distance, NaN if none
+    n_samples: int
+    inference_time: float
+
+
+def _key_to_float(key):
+    """Inverse of vsom_map_stats' ordered_key on a uint32 array -> float32."""
+    key = np.asarray(key, dtype=np.uint32)
+    bits = np.where(key & np.uint32(0x80000000), key ^ np.uint32(0x80000000), ~key).astype(np.uint32)
+    return bits.view(np.float32)
+
+
+_SIGN64 = -(1 << 63)
+
+
+def evaluate_map_quality(model, config, dataloader):
+    """Quantization error, topographic error, hit map and the nearest sample of every unit over the loader -> MapQuality.
+    For vit_som and desom.  Every batch goes through predict(); the distances [B, K] and BMUs it leaves in the SOM layer's
+    buffers are folded on the device by one `vsom_map_stats` launch (integer atomics only: the report is bitwise
+    reproducible) -- no clone and no host synchronisation in the loop; rows the kernel refused (a NaN distance, a BMU off
+    the map, a distance of 2^31 or more) are counted and raise ValueError at the end.  Neighbourhood on the grid is
+    SOMLayer.adjacency_radius2() applied to the layer's own grid_positions, so both topologies take the same path.
+    The second-best unit is the argmin, BMU excluded, of the distances the BMU pass wrote: the cosine pass re-ranks exactly
+    only the prototypes within its window of the minimum, so a runner-up outside that window is chosen among distances
+    that each carry the contraction's rounding error.  With model.world_size > 1 every rank folds its shard, ordinals are
+    shifted so that rank r's samples follow rank r - 1's, and one SUM and one MIN all-reduce combine the tables: every
+    rank returns the whole set's report."""
+    model.eval()
+    d = config["data"]
+    C, S = d["num_channels"], d["input_size"]
+    model_arch = config["hyperparameters"]["model_arch"]
+    if model_arch not in ("vit_som", "desom"):
+        raise ValueError(f"evaluate_map_quality: unknown model_arch {model_arch!r}")
+    som = model.som_layer
+    rows, cols = som.map_size
+    K = rows * cols
+    dev = model.arena.device
+    adj_r2 = som.adjacency_radius2()
+    sums = torch.zeros(2 * K + 1, dtype=torch.int64, device=dev)          # hits | qe_fix | te: one all-reduce
+    hits, qe_fix, te = sums[:K], sums[K:2 * K], sums[2 * K:]
+    nearest = torch.full((K,), -1, dtype=torch.int64, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    seen, start = 0, time.time()
+    for x, _ in dataloader:
+        x = x.to(dev, non_blocking=True)
+        x = x.reshape(-1, C, S, S) if model_arch == "vit_som" else x.reshape(x.shape[0], -1)
+        bmu, _ = model.predict(x)
+        s = som._buffers_for(bmu.shape[0], bmu.device)                  # the set predict() has just written
+        if s.bmu.data_ptr() != bmu.data_ptr():
+            raise RuntimeError("evaluate_map_quality: predict() did not leave its distances in the SOM layer's buffers")
+        ops.map_stats(s.dist, s.bmu, som.grid_positions, adj_r2, seen, hits, qe_fix, te, nearest, bad)
+        seen += bmu.shape[0]
+    world = _world(model)
+    if world > 1:
+        import torch.distributed as dist
+        counts = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(world)]
+        dist.all_gather(counts, torch.tensor([seen], dtype=torch.int64, device=dev))
+        before = sum(int(c) for c in counts[:int(getattr(model, "rank", 0))])
+        seen = sum(int(c) for c in counts)
+        if seen >= 2 ** 31:
+            raise ValueError("evaluate_map_quality: more than 2^31 - 1 samples")
+        both = torch.cat([sums, bad.long()])
+        dist.all_reduce(both)
+        sums, bad = both[:-1], both[-1:]
+        hits, qe_fix, te = sums[:K], sums[K:2 * K], sums[2 * K:]
+        # the words are unsigned: flipping the top bit makes int64 order their order (an empty cell, all-ones, stays largest)
+        nearest = torch.where(nearest != -1, nearest + before, nearest) ^ _SIGN64
+        dist.all_reduce(nearest, op=dist.ReduceOp.MIN)
+        nearest = nearest ^ _SIGN64
+    nbad = int(bad.item())
+    if nbad:
+        raise ValueError(f"{nbad} rows had a BMU outside the {rows} x {cols} map, a NaN distance or a distance of 2^31 or more")
+    h = hits.cpu().numpy()
+    q = qe_fix.cpu().numpy()
+    near = nearest.cpu().numpy()
+    n_te = int(te.item())
+    inference_time = time.time() - start
+    scale = float(2 ** 32)
+    total = sum(int(v) for v in q)                         # Python integers: the sum over the cells cannot overflow
+    empty = near == -1
+    report = MapQuality(
+        quantization_error=total / scale / seen if seen else float("nan"),
+        topographic_error=n_te / seen if seen else float("nan"),
+        hits=h.reshape(rows, cols),
+        dead_units=int((h == 0).sum()),
+        cell_quantization_error=np.where(h > 0, q / scale / np.maximum(h, 1), np.nan).reshape(rows, cols),
+        nearest_sample=np.where(empty, -1, near & 0xFFFFFFFF).astype(np.int64).reshape(rows, cols),
+        nearest_distance=np.where(empty, np.float32("nan"), _key_to_float((near >> 32) & 0xFFFFFFFF)).astype(np.float32).reshape(rows, cols),
+        n_samples=int(seen),
+        inference_time=inference_time)
+    print(f"Quantization error: {report.quantization_error:.4f}, Topographic error: {report.topographic_error:.4f}, "
+          f"Dead units: {report.dead_units}/{K}, Inference Time: {inference_time:.3f}")
+    return report
+
+
+def umatrix(model):
+    """-> (u [rows, cols] float32, nbr_idx [K, 8] int32, nbr_dist [K, 8] float32) as host arrays: for every unit its grid
+    neighbours (SOMLayer.adjacency_radius2() on the layer's grid_positions; ascending index order, -1 padding), the
+    distance of their prototypes to the unit's in the layer's distance function, and the mean of those (`vsom_umatrix`:
+    fp64 accumulation; the euclidean distance in its difference form).  Needs no data and touches no training buffer."""
+    som = model.som_layer
+    rows, cols = som.map_size
+    u, nbr_idx, nbr_dist = ops.umatrix(som.prototypes.detach().contiguous(), som.grid_positions, som.adjacency_radius2(), som._dist_mode)
+    return u.view(rows, cols).cpu().numpy(), nbr_idx.cpu().numpy(), nbr_dist.cpu().numpy()
+
+
+def _draw_map(who, values, label, annotate, path):
+    plt = _pyplot(who)
+    if plt is None:
+        return None
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    fig = plt.figure(figsize=(10, 8))
+    im = plt.imshow(values, cmap="viridis", interpolation="nearest")
+    plt.colorbar(im, label=label)
+    if annotate and max(values.shape) <= 24:
+        mid = 0.5 * (float(values.min()) + float(values.max()))
+        for (r, c), v in np.ndenumerate(values):
+            plt.text(c, r, str(int(v)), ha="center", va="center", fontsize=7, color="white" if v <= mid else "black")
+    plt.axis("off")
+    plt.savefig(path, bbox_inches="tight")
+    plt.close(fig)
+    return path
+
+
+def visualize_umatrix(model, config, output_dir="experiments/plots"):
+    """The U-matrix as one image -> {output_dir}/{model_arch}_epoch_{epoch}_umatrix.png (rank 0; skipped with a warning when
+    matplotlib is missing).  Returns u [rows, cols] float32."""
+    model_arch = config["hyperparameters"]["model_arch"]
+    u, _, _ = umatrix(model)
+    if int(getattr(model, "rank", 0)) == 0:
+        path = os.path.join(output_dir, f"{model_arch}_epoch_{_epoch(model)}_umatrix.png")
+        if _draw_map("visualize_umatrix", u, "mean distance to the grid neighbours", False, path) is not None:
+            print(f"Saved U-matrix visualization to {output_dir}")
+    return u
+
+
+def visualize_hit_map(model, config, dataloader, output_dir="experiments/plots"):
+    """Samples per unit (evaluate_map_quality's hits) as one image -> {output_dir}/{model_arch}_epoch_{epoch}_hit_map.png
+    (rank 0; skipped with a warning when matplotlib is missing).  Returns hits [rows, cols] int64."""
+    model_arch = config["hyperparameters"]["model_arch"]
+    hits = evaluate_map_quality(model, config, dataloader).hits
+    if int(getattr(model, "rank", 0)) == 0:
+        path = os.path.join(output_dir, f"{model_arch}_epoch_{_epoch(model)}_hit_map.png")
+        if _draw_map("visualize_hit_map", hits, "samples", True, path) is not None:
+            print(f"Saved hit map visualization to {output_dir}")
+    return hits
 
 
 def evaluate_classification(model, config, dataloader):

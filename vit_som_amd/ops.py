@@ -715,6 +715,42 @@ def last_label(bmu, label, first_ordinal, cells, bad):
     return cells
 
 
+def map_stats(dist, bmu, grid_positions, adj_r2, first_ordinal, hits, qe_fix, te, nearest, bad, second=None):
+    """One batch folded into the map-quality accumulators (see vsom_map_stats): hits / qe_fix [K] and te [1] int64 zeroed by
+    the caller, nearest [K] int64 set to -1 (all-ones), bad [1] int32; `second` [B] int64 receives the runner-up units."""
+    _f32(dist, "dist")
+    _f32(grid_positions, "grid_positions")
+    B, K = dist.shape
+    assert dist.is_contiguous() and grid_positions.is_contiguous() and tuple(grid_positions.shape) == (K, 2)
+    assert bmu.dtype == torch.int64 and bmu.is_contiguous() and bmu.numel() == B
+    for t, n in ((hits, K), (qe_fix, K), (te, 1), (nearest, K)):
+        assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and t.numel() == n
+    assert bad.dtype == torch.int32 and bad.numel() == 1
+    if second is not None:
+        assert second.dtype == torch.int64 and second.is_contiguous() and second.numel() == B
+    check(lib.vsom_map_stats(ptr(dist), ptr(bmu), B, K, ptr(grid_positions), float(adj_r2), int(first_ordinal), ptr(hits),
+                             ptr(qe_fix), ptr(te), ptr(nearest), ptr(bad), ptr(second), stream()), "vsom_map_stats")
+
+
+def umatrix(W, grid_positions, adj_r2, distance):
+    """-> (u [K] f32, nbr_idx [K, 8] int32, nbr_dist [K, 8] f32) on the device (see vsom_umatrix).  The status word is read
+    here, after the launch: a unit with more than 8 units within adj_r2 raises VsomError (VSOM_EUNSUPPORTED)."""
+    _f32(W, "W")
+    _f32(grid_positions, "grid_positions")
+    K, L = W.shape
+    assert W.is_contiguous() and grid_positions.is_contiguous() and tuple(grid_positions.shape) == (K, 2)
+    u = torch.empty(K, dtype=torch.float32, device=W.device)
+    nbr_idx = torch.empty(K, 8, dtype=torch.int32, device=W.device)
+    nbr_dist = torch.empty(K, 8, dtype=torch.float32, device=W.device)
+    status = torch.zeros(1, dtype=torch.int32, device=W.device)
+    check(lib.vsom_umatrix(ptr(W), K, L, ptr(grid_positions), float(adj_r2), int(distance), ptr(nbr_idx), ptr(nbr_dist), ptr(u),
+                           ptr(status), stream()), "vsom_umatrix")
+    most = int(status.item())
+    if most:
+        raise _lib_mod.VsomError(f"vsom_umatrix failed with status -3: a unit has {most} units within adj_r2={adj_r2} (8 are kept)")
+    return u, nbr_idx, nbr_dist
+
+
 # ---------------------------------------------------------------- data pipeline (vit_som_amd.data)
 AUGMENT_PARAMS = 16
 

@@ -173,6 +173,11 @@ class SOMLayer(_Base):
             raise ValueError(f"Unsupported topology: {self.topology}")
         self.register_buffer("grid_positions", positions)
 
+    def adjacency_radius2(self) -> float:
+        """Two units are grid neighbours when their grid_positions lie within this squared distance: square lattice
+        distances^2 are 1, 2, 4, ... (2.25 takes the 8 around a cell), hexagonal ones 1, 3, ... (1.5 takes the 6)."""
+        return {"square": 2.25, "hexa": 1.5}[self.topology]
+
     def _buffers_for(self, B: int, device) -> _Acts:
         s = self._bufs.get(B)
         if s is not None and s.device == device:

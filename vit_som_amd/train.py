@@ -27,7 +27,7 @@ import numpy as np
 import torch
 import yaml
 
-from .evaluation import evaluate_classification, evaluate_clustering
+from .evaluation import evaluate_classification, evaluate_clustering, evaluate_map_quality
 from .classifier import ViTClassifier
 from .model import ViTSOM
 
@@ -274,9 +274,11 @@ def main_vit(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, 
     return all_metrics
 
 
-def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print):
+def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print, map_quality=False):
     """train_vit_som.py:27-130; a config with hyperparameters.model_arch == "vit" runs main_vit (train_vit.py) instead.
-    model_states_dir defaults to experiments/states/vit_som (experiments/states/vit for the ViT baseline)."""
+    model_states_dir defaults to experiments/states/vit_som (experiments/states/vit for the ViT baseline).
+    map_quality: after each run's final evaluation also run evaluate_map_quality on the training loader with the model that
+    was evaluated, and report quantization_error / topographic_error next to the other metrics (ViT-SOM only)."""
     if config["hyperparameters"].get("model_arch") == "vit":
         return main_vit(config, n_runs=n_runs, max_epochs=max_epochs, make_loaders=make_loaders,
                         model_states_dir=model_states_dir or "experiments/states/vit", log=log)
@@ -294,6 +296,8 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
     torch.manual_seed(0)                                                  # pl.seed_everything(0)
     np.random.seed(0)
     all_metrics = {k: [] for k in ("accuracy", "precision", "recall", "f1", "purity", "nmi", "run_duration", "inference_time")}
+    if map_quality:
+        all_metrics.update(quantization_error=[], topographic_error=[])
     for run in range(n_runs):
         log(f"Starting run {run + 1} for {dataset_name}...")
         start = time.time()
@@ -313,6 +317,7 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
             acc, prec, rec, f1, inf_t = evaluate_classification(model, config, test_loader)
             for k, v in (("accuracy", acc), ("precision", prec), ("recall", rec), ("f1", f1)):
                 all_metrics[k].append(v)
+            evaluated = model
         else:
             # the reference reloads the last checkpoint (train_vit_som.py:111): rank 0 wrote it, every rank loads that file
             path = os.path.join(model_states_dir, "last.ckpt")
@@ -323,6 +328,13 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
             purity, nmi, inf_t = evaluate_clustering(final_model, config, train_loader)
             all_metrics["purity"].append(purity)
             all_metrics["nmi"].append(nmi)
+            evaluated = final_model
+        if map_quality:
+            mq = evaluate_map_quality(evaluated, config, train_loader)
+            log(f"Map quality: quantization error {mq.quantization_error:.4f}, topographic error {mq.topographic_error:.4f}, "
+                f"dead units {mq.dead_units}/{mq.hits.size}")
+            all_metrics["quantization_error"].append(mq.quantization_error)
+            all_metrics["topographic_error"].append(mq.topographic_error)
         all_metrics["run_duration"].append(run_duration)
         all_metrics["inference_time"].append(inf_t)
     if n_runs > 1:
@@ -339,8 +351,10 @@ if __name__ == "__main__":
     ap.add_argument("--data-npz", type=str, default=None, help="a local .npz with images / labels (implies --device-data)")
     ap.add_argument("--device-randaug", action="store_true",
                     help="also apply the config's RandAugment / timm rand-m9 auto-augment on the GPU (implies --device-data)")
+    ap.add_argument("--map-quality", action="store_true",
+                    help="after each run also report the map's quantization and topographic error on the training set")
     a = ap.parse_args()
     loaders = synthetic_loaders
     if a.device_data or a.data_npz or a.device_randaug:
         loaders = lambda c, r, w: device_loaders(c, r, w, npz=a.data_npz, auto_augment=a.device_randaug)     # noqa: E731
-    main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs, make_loaders=loaders)
+    main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs, make_loaders=loaders, map_quality=a.map_quality)
