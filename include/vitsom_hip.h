@@ -114,6 +114,31 @@ int vsom_set_wgrad_tiles(int mode);
    the partial layout and its size query do not depend on the setting.  Other values: VSOM_EINVAL. */
 int vsom_set_ln_tiles(int mode);
 
+/* Which kernel an entry point would launch ("Which kernel runs"), as one line of text in `out`:
+ *     engine=<name> tile=<rows>x<cols> planes=<n> fast=<0|1> threads=<n> splits=<n> workgroups=<n>
+ * engine: f32 | x6 (the generic GEMM kernels), x6_tn (weight-gradient tiles), x6_ln (LayerNorm-fused tiles), attn_two_launch
+ * | attn_fused | attn_shared | attn_shared_bf16x3; planes = bf16 pieces per operand (0: fp32 products); fast = 16-byte
+ * buffer loads.  Pure host arithmetic under the current GEMM mode and hooks: nothing is launched and no GPU is needed; the
+ * library itself never calls it.  M, N, K are the entry point's own shape arguments in its own order ((B, K, L) for the SOM
+ * entries; (N tokens, H, hd) for VSOM_PLAN_ATTENTION_BWD, workgroups per image).  flags bit 0: every operand is 16-byte
+ * aligned with leading dimensions that are multiples of 4 (what the model's buffers are).  VSOM_EUNSUPPORTED where the
+ * entry point would refuse the shape, VSOM_EINVAL on an unknown op, a non-positive shape or a buffer too small for the line. */
+#define VSOM_PLAN_LINEAR_FWD 0
+#define VSOM_PLAN_LINEAR_GELU_FWD 1
+#define VSOM_PLAN_LINEAR_RELU_FWD 2
+#define VSOM_PLAN_LINEAR_RESIDUAL_FWD 3
+#define VSOM_PLAN_LINEAR_BWD_INPUT 4
+#define VSOM_PLAN_LINEAR_BWD_INPUT_GELU 5
+#define VSOM_PLAN_LINEAR_BWD_INPUT_T 6
+#define VSOM_PLAN_LINEAR_BWD_INPUT_T_GELU 7
+#define VSOM_PLAN_LINEAR_BWD_WEIGHT 8
+#define VSOM_PLAN_LINEAR_BWD_INPUT_LN 9
+#define VSOM_PLAN_SOM_BWD_GW 10
+#define VSOM_PLAN_SOM_BWD_GX 11
+#define VSOM_PLAN_BMU_COSINE_DOTS 12
+#define VSOM_PLAN_ATTENTION_BWD 13
+int vsom_describe_plan(int op, int M, int N, int K, int flags, char* out, size_t out_bytes);
+
 /* dW[N,K] = dY[M,N]^T * X[M,K] ;  db[N] = column sums of dY (db may be NULL)
  * -- autograd of nn.Linear w.r.t. weight/bias.  The reduction over the M token rows is split
  * across workgroups into fp32 slabs in `ws` and summed in a fixed order (deterministic). */

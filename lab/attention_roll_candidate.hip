@@ -1633,12 +1633,12 @@ static int launch_fwd_t(const float* qkv, float* out, float* lse, int B, int N, 
             const size_t roll_lds = ((lds + 15) & ~(size_t)15) + (size_t)attn_tiles(N) * 16 * HDP * sizeof(float);   // + the query image
             hipLaunchKernelGGL((attn_fwd_roll_kernel<HDP, EXTRA>), dim3(cdiv(nitems, ipw)), dim3(64 * attn_waves(N)), roll_lds, st, qkv,
                                out, lse, N, H, hd, 1.0f / sqrtf((float)hd), nitems);
-            VSOM_LAUNCH_CHECK("attn_fwd_roll_kernel");
+            return launch_status("attn_fwd_roll_kernel");
         }
     }
     hipLaunchKernelGGL((attn_fwd_kernel<HDP, EXTRA>), dim3(B * H), dim3(64 * attn_waves(N)), lds, st, qkv, out, lse, N, H, hd,
                        1.0f / sqrtf((float)hd));
-    VSOM_LAUNCH_CHECK("attn_fwd_kernel");
+    return launch_status("attn_fwd_kernel");
 }
 template <int HDP, bool EXTRA>
 static int launch_bwd_t(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
@@ -1656,13 +1656,13 @@ static int launch_bwd_t(const float* qkv, const float* out, const float* dout, c
             const int nitems = B * H, ipw = mode >= 2 ? mode : 3;
             hipLaunchKernelGGL((attn_bwd_roll_kernel<HDP, EXTRA>), dim3(cdiv(nitems, ipw)), block, roll_lds, st, qkv, out, dout, lse,
                                dqkv, delta, N, H, hd, scale, nitems, (unsigned)((long)B * H * N * 4));
-            VSOM_LAUNCH_CHECK("attn_bwd_roll_kernel");
+            return launch_status("attn_bwd_roll_kernel");
         }
     }
     if (ACfg<HDP>::VEC && fused_lds <= 80 * 1024 && mode) {
         hipLaunchKernelGGL((attn_bwd_fused_kernel<HDP, EXTRA>), dim3(B * H), block, fused_lds, st, qkv, out, dout, lse, dqkv,
                            delta, N, H, hd, scale);
-        VSOM_LAUNCH_CHECK("attn_bwd_fused_kernel");
+        return launch_status("attn_bwd_fused_kernel");
     }
     hipLaunchKernelGGL((attn_bwd_dq_kernel<HDP, EXTRA>), dim3(B * H), block, attn_lds_bytes(N, HDP, false, HDP), st, qkv, out,
                        dout, lse, dqkv, delta, N, H, hd, scale);
@@ -1670,7 +1670,7 @@ static int launch_bwd_t(const float* qkv, const float* out, const float* dout, c
     if (rc) return rc;
     hipLaunchKernelGGL((attn_bwd_dkv_kernel<HDP, EXTRA>), dim3(B * H), block, attn_lds_bytes(N, HDP, true, 2 * HDP), st, qkv,
                        dout, lse, delta, dqkv, N, H, hd, scale);
-    VSOM_LAUNCH_CHECK("attn_bwd_dkv_kernel");
+    return launch_status("attn_bwd_dkv_kernel");
 }
 template <int HDP>
 static int launch_fwd(const float* qkv, float* out, float* lse, int B, int N, int H, int hd, hipStream_t st) {

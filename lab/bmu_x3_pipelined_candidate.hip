@@ -447,7 +447,7 @@ int vsom_bmu_cosine_x3_dots(const float* X, long ldx, const float* W, int B, int
     // dynamic LDS: two buffers of 2 planes x (BM + BN) rows x 64 B
     if (bmu_x3_big(B)) hipLaunchKernelGGL((bmu_x3_kernel<2, 3, 4, 2>), dim3(bmu_x3_tiles(B, K) * splits), dim3(512), 4 * (256 + 192) * X6_RS, stream, g);
     else hipLaunchKernelGGL((bmu_x3_kernel<2, 2, 2, 2>), dim3(bmu_x3_tiles(B, K) * splits), dim3(256), 4 * (128 + 128) * X6_RS, stream, g);
-    VSOM_LAUNCH_CHECK("bmu_x3_kernel");
+    return launch_status("bmu_x3_kernel");
 }
 
 /* stage 2: norms, distances, first minimum, exact re-rank of the near-minimum candidates.  reranked (nullable):
@@ -471,7 +471,7 @@ int vsom_bmu_cosine_x3_finalize(const float* X, long ldx, const float* W, const 
     else
     hipLaunchKernelGGL(bmu_x3_finalize_kernel<false>, dim3(B), dim3(256), 0, stream, g.slab, g.slab_stride, splits, X, ldx, W, inv_nx,
                        inv_nw, dist, bmu, K, L, reranked);
-    VSOM_LAUNCH_CHECK("bmu_x3_finalize_kernel");
+    return launch_status("bmu_x3_finalize_kernel");
 }
 
 }  // extern "C"

@@ -492,7 +492,7 @@ static int launch_panel(RpP& p, hipStream_t st) {
     const size_t lds = 2 * KS * 3 * RP_FRAG;
     if (p.gamma) hipLaunchKernelGGL((linear_rp_panel_kernel<KS, EPI, true, WAVES>), grid, block, lds, st, p);
     else hipLaunchKernelGGL((linear_rp_panel_kernel<KS, EPI, false, WAVES>), grid, block, lds, st, p);
-    VSOM_LAUNCH_CHECK("linear_rp_panel_kernel");
+    return launch_status("linear_rp_panel_kernel");
 }
 template <int EPI, int WAVES>
 static int launch_panel_k(RpP& p, hipStream_t st) {
@@ -505,7 +505,7 @@ static int launch_panel_k(RpP& p, hipStream_t st) {
 template <int NT, int EPI, int WAVES>
 static int launch_stream(RpP& p, hipStream_t st) {
     hipLaunchKernelGGL((linear_rp_stream_kernel<NT, EPI, WAVES>), dim3(cdiv(p.g.M, 32 * WAVES)), dim3(64 * WAVES), 2 * NT * 6 * RP_FRAG, st, p);
-    VSOM_LAUNCH_CHECK("linear_rp_stream_kernel");
+    return launch_status("linear_rp_stream_kernel");
 }
 static int rp_waves() { return rp_env("VSOM_RP_WAVES", 4) == 8 ? 8 : 4; }
 template <int EPI>
@@ -550,7 +550,7 @@ int vsom_weight_images_prepare(const float* params_base, void* images_base, cons
     VSOM_REQUIRE(aligned16(images_base), VSOM_EALIGN, "weight_images_prepare: images must be 16-byte aligned");
     hipLaunchKernelGGL(weight_image_kernel, dim3(cdiv(max_fragments, 4), count), dim3(256), 0, stream, params_base,
                        static_cast<char*>(images_base), table);
-    VSOM_LAUNCH_CHECK("weight_image_kernel");
+    return launch_status("weight_image_kernel");
 }
 
 int vsom_linear_planes(const vsom_linear_planes_args* a, vsom_stream_t stream) {

@@ -1,0 +1,82 @@
+"""Which kernel runs ("Which kernel runs"), pinned on the host: vsom_describe_plan must report, for every entry
+of PLAN_ROWS, the engine, tile, plane count and load path the table gives -- in all three GEMM modes and every setting of
+the family's hook.  Pure host code: no GPU needed."""
+import ctypes
+import re
+
+import pytest
+
+from launch_plan_rows import HOOK_DEFAULTS, HOOK_VALUES, MODES, PLAN_ROWS, TABLE_ROWS, UNSUPPORTED
+
+LINE = re.compile(r"engine=(\S+) tile=(\d+x\d+) planes=(\d+) fast=([01]) threads=(\d+) splits=(\d+) workgroups=(\d+)$")
+
+
+def describe(lib, op, shape, aligned):
+    """(engine, tile, planes, fast, threads, splits, workgroups), or None where the entry point refuses the shape."""
+    buf = ctypes.create_string_buffer(160)
+    rc = lib.vsom_describe_plan(op, *shape, int(aligned), buf, len(buf))
+    if rc == -3:
+        return None
+    assert rc == 0, (rc, op, shape)
+    m = LINE.match(buf.value.decode())
+    assert m, buf.value
+    return (m.group(1), m.group(2)) + tuple(int(g) for g in m.groups()[2:])
+
+
+@pytest.fixture(scope="module")
+def ops():
+    from vit_som_amd import ops as _ops
+    return _ops
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from vit_som_amd._lib import lib as _lib
+    return _lib
+
+
+def test_plan_rows_cover_the_table():
+    assert {r.row for r in PLAN_ROWS} == TABLE_ROWS
+
+
+@pytest.mark.parametrize("row", PLAN_ROWS, ids=lambda r: f"{r.row}-op{r.op}-{'x'.join(map(str, r.shape))}")
+def test_describe_plan_matches_the_table(ops, lib, row):
+    prev = ops.get_gemm_mode()
+    setter = getattr(ops, "set_" + row.hook) if row.hook else None
+    try:
+        for mode in MODES:
+            ops.set_gemm_mode(mode)
+            for hook in (HOOK_VALUES[row.hook] if row.hook else (None,)):
+                if setter:
+                    setter(hook)
+                want = row.expect[mode]
+                if isinstance(want, dict):
+                    want = want[hook]
+                got = describe(lib, row.op, row.shape, row.aligned)
+                if want is UNSUPPORTED:
+                    assert got is None, (mode, hook, got)
+                else:
+                    assert got is not None and got[:4] == want, (mode, hook, got, want)
+    finally:
+        ops.set_gemm_mode(prev)
+        if setter:
+            setter(HOOK_DEFAULTS[row.hook])
+
+
+def test_describe_plan_grid_arithmetic(lib):
+    """Workgroups = tiles x splits, the split count canonical (every split owns a k-tile of 32)."""
+    got = describe(lib, 0, (300, 200, 64), 1)                       # 3 x 4 tiles of 128 x 64, one split
+    assert got[5:] == (1, 12)
+    got = describe(lib, 12, (512, 1600, 12288), 1)                  # BMU dots: 4 x 25 tiles, split over L
+    assert got[6] == 100 * got[5] and -(-384 // -(-384 // got[5])) == got[5]
+    got = describe(lib, 8, (70, 12, 24), 1)                         # generic dW: 3 k-tiles bound the splits
+    assert got[5] <= 3 and got[6] == got[5]
+
+
+def test_describe_plan_rejects_bad_calls(lib):
+    buf = ctypes.create_string_buffer(160)
+    assert lib.vsom_describe_plan(99, 8, 8, 8, 1, buf, len(buf)) == -1
+    assert lib.vsom_describe_plan(0, 0, 8, 8, 1, buf, len(buf)) == -1
+    assert lib.vsom_describe_plan(0, 8, 8, 8, 1, buf, 8) == -1          # line does not fit
+    assert lib.vsom_describe_plan(0, 8, 8, 8, 1, None, 0) == -1
+    assert lib.vsom_describe_plan(13, 17, 2, 24, 1, buf, len(buf)) == -3   # head dim 24

@@ -84,6 +84,30 @@ def test_wide_plan_split_counts(lib):
         ops.set_wgrad_tiles(2)
 
 
+def test_described_split_counts_are_the_planned_ones(lib):
+    """The same plan read directly (vsom_describe_plan): split count and workgroups of the tile kernels."""
+    import ctypes
+    import re
+    from vit_som_amd import ops
+    buf = ctypes.create_string_buffer(160)
+    try:
+        for mode in (0, 1, 2):
+            ops.set_wgrad_tiles(mode)
+            for M, N, K in step_shapes(512):
+                s = planned_splits(mode, M, N, K)
+                if s is None:
+                    continue
+                assert lib.vsom_describe_plan(8, M, N, K, 1, buf, len(buf)) == 0
+                m = re.match(r"engine=x6_tn tile=(\d+)x(\d+) .* splits=(\d+) workgroups=(\d+)$", buf.value.decode())
+                assert m, buf.value
+                rows, cols, splits, wgs = map(int, m.groups())
+                assert splits == s and wgs == (N // rows) * (K // cols) * s, (mode, M, N, K, buf.value)
+                assert (rows, cols) == ((192, 192) if mode and N % 192 == 0 and K % 192 == 0 else
+                                        (192, 64) if N % 192 == 0 and K % 64 == 0 else (96, 96))
+    finally:
+        ops.set_wgrad_tiles(2)
+
+
 def test_set_wgrad_tiles_rejects_unknown_modes(lib):
     assert lib.vsom_set_wgrad_tiles(3) != 0
     assert lib.vsom_set_wgrad_tiles(-1) != 0

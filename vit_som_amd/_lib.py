@@ -34,6 +34,7 @@ SIGNATURES = {
     "vsom_get_gemm_mode": (C.c_int, []),
     "vsom_set_wgrad_tiles": (C.c_int, [C.c_int]),
     "vsom_set_ln_tiles": (C.c_int, [C.c_int]),
+    "vsom_describe_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "vsom_linear_bwd_weight_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "vsom_linear_bwd_weight": (C.c_int, [c_fp, C.c_long, c_fp, C.c_long, c_fp, c_fp, C.c_int, C.c_int, C.c_int,
                                          c_fp, C.c_size_t, c_stream]),

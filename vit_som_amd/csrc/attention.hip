@@ -41,9 +41,12 @@ namespace vsom {
 
 int gemm_grad_products();          // gemm_f32.hip: 3 in VSOM_GEMM_SPLIT_BF16_GRAD3 mode
 
-// test / measurement hook (vsom_set_attention_fused): 0 keeps the short-sequence backward as two launches, 1 is the
-// default (one launch; scores shared between its phases where the shape allows; at hd = 64 in the default GEMM mode its
-// products run on the two-piece bf16 split), 2 one launch with recomputed scores, 3 = 1 with fp32 products in every mode
+// test / measurement hook (vsom_set_attention_fused), consumed by attn_bwd_plan:
+//   0 = the short-sequence backward as two launches,
+//   1 = the default: one launch, scores shared between its phases where the shape allows; at hd = 64 in the default GEMM
+//       mode its products run on the two-piece bf16 split,
+//   2 = one launch with recomputed scores,
+//   3 = 1 with fp32 products in every GEMM mode.
 static std::atomic<int> g_attn_fused{1};
 
 // tools/attn_lab.hip builds this file with VSOM_ATTN_STAMPS: thread 0 of every workgroup records the 100 MHz
@@ -1296,44 +1299,68 @@ static int launch_fwd_t(const float* qkv, float* out, float* lse, int B, int N, 
     const size_t lds = attn_lds_bytes(N, HDP, false, HDP + 2);
     VSOM_LAUNCH((attn_fwd_kernel<HDP, EXTRA>), dim3(B * H), dim3(64 * attn_waves(N)), lds, st, qkv, out, lse, N, H, hd,
                        1.0f / sqrtf((float)hd));
-    VSOM_LAUNCH_CHECK("attn_fwd_kernel");
+    return launch_status("attn_fwd_kernel");
 }
+// Form of the backward ("Which kernel runs"); `hook` is vsom_set_attention_fused's value (see g_attn_fused),
+// `grad_products` gemm_grad_products().
+enum AttnBwd : int { ATTN_BWD_TWO_LAUNCH = 0, ATTN_BWD_FUSED = 1, ATTN_BWD_SHARED = 2, ATTN_BWD_SHARED_BF16X3 = 3 };
+static size_t attn_shared_lds_bytes(int N, int hdp) { return attn_fused_lds_bytes(N, hdp) + 2 * hdp * sizeof(float); }
+static AttnBwd attn_bwd_plan(int N, int hdp, int hook, int grad_products) {
+    const bool vec = hdp % 16 == 0;                     // ACfg<HDP>::VEC: the one-launch forms are vector-path kernels
+    const int nt = attn_tiles(N), nrows = use_extra(N) ? N : nt * 16;
+    // scores shared between the phases: they must fit the LDS the K / V slices leave, one tile row per wave
+    if (vec && (hook == 1 || hook == 3) && nt <= 4 && attn_waves(N) == nt && 16 * nt * (16 * nt + 4) <= nrows * (hdp + 4) &&
+        attn_shared_lds_bytes(N, hdp) <= 80 * 1024)
+        // the mode whose gradient GEMMs run on the two-piece split (hook 3: fp32 products)
+        return (hdp == 64 && grad_products == 3 && hook == 1) ? ATTN_BWD_SHARED_BF16X3 : ATTN_BWD_SHARED;
+    // all four slices in LDS and still two workgroups per CU -> one fused launch
+    if (vec && hook != 0 && attn_fused_lds_bytes(N, hdp) <= 80 * 1024) return ATTN_BWD_FUSED;
+    return ATTN_BWD_TWO_LAUNCH;
+}
+
+int attn_bwd_threads(int N) { return 64 * attn_waves(N); }
+int attn_bwd_plan_now(int N, int hd) {                   // for vsom_describe_plan (gemm_f32.hip)
+    const int hdp = attn_hdp(hd);
+    return hdp ? (int)attn_bwd_plan(N, hdp, g_attn_fused.load(std::memory_order_relaxed), gemm_grad_products()) : -1;
+}
+
 template <int HDP, bool EXTRA>
 static int launch_bwd_t(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
                         float* delta, int B, int N, int H, int hd, hipStream_t st) {
     const float scale = 1.0f / sqrtf((float)hd);
-    const dim3 block(64 * attn_waves(N));
-    // all four slices in LDS and still two workgroups per CU -> one fused launch (vector path only)
-    const size_t fused_lds = attn_fused_lds_bytes(N, HDP);
-    const int mode = g_attn_fused.load(std::memory_order_relaxed);     // 0: two launches, 1: default, 2: fused with recomputed scores
-    if constexpr (ACfg<HDP>::VEC) {
-        const int nt = attn_tiles(N), nrows = use_extra(N) ? N : nt * 16;
-        const size_t shared_lds = fused_lds + 2 * HDP * sizeof(float);
-        if ((mode == 1 || mode == 3) && nt <= 4 && attn_waves(N) == nt && 16 * nt * (16 * nt + 4) <= nrows * (HDP + 4) && shared_lds <= 80 * 1024) {
+    const dim3 grid(B * H), block(64 * attn_waves(N));
+    const AttnBwd plan = attn_bwd_plan(N, HDP, g_attn_fused.load(std::memory_order_relaxed), gemm_grad_products());
+    switch (plan) {
+        case ATTN_BWD_SHARED_BF16X3:
             if constexpr (HDP == 64) {
-                if (gemm_grad_products() == 3 && mode == 1) {   // the mode whose gradient GEMMs run on the two-piece split (hook 3: fp32 products)
-                    VSOM_LAUNCH((attn_bwd_shared_kernel<HDP, EXTRA, true>), dim3(B * H), block, shared_lds, st, qkv, out, dout, lse,
-                                dqkv, delta, N, H, hd, scale);
-                    VSOM_LAUNCH_CHECK("attn_bwd_shared_kernel");
-                }
+                VSOM_LAUNCH((attn_bwd_shared_kernel<HDP, EXTRA, true>), grid, block, attn_shared_lds_bytes(N, HDP), st, qkv, out,
+                            dout, lse, dqkv, delta, N, H, hd, scale);
+                return launch_status("attn_bwd_shared_kernel");
             }
-            VSOM_LAUNCH((attn_bwd_shared_kernel<HDP, EXTRA>), dim3(B * H), block, shared_lds, st, qkv, out, dout, lse, dqkv,
-                               delta, N, H, hd, scale);
-            VSOM_LAUNCH_CHECK("attn_bwd_shared_kernel");
+            break;
+        case ATTN_BWD_SHARED:
+            if constexpr (ACfg<HDP>::VEC) {
+                VSOM_LAUNCH((attn_bwd_shared_kernel<HDP, EXTRA>), grid, block, attn_shared_lds_bytes(N, HDP), st, qkv, out, dout,
+                            lse, dqkv, delta, N, H, hd, scale);
+                return launch_status("attn_bwd_shared_kernel");
+            }
+            break;
+        case ATTN_BWD_FUSED:
+            VSOM_LAUNCH((attn_bwd_fused_kernel<HDP, EXTRA>), grid, block, attn_fused_lds_bytes(N, HDP), st, qkv, out, dout, lse,
+                        dqkv, delta, N, H, hd, scale);
+            return launch_status("attn_bwd_fused_kernel");
+        case ATTN_BWD_TWO_LAUNCH: {
+            VSOM_LAUNCH((attn_bwd_dq_kernel<HDP, EXTRA>), grid, block, attn_lds_bytes(N, HDP, false, HDP), st, qkv, out, dout,
+                        lse, dqkv, delta, N, H, hd, scale);
+            const int rc = launch_status("attn_bwd_dq_kernel");
+            if (rc) return rc;
+            VSOM_LAUNCH((attn_bwd_dkv_kernel<HDP, EXTRA>), grid, block, attn_lds_bytes(N, HDP, true, 2 * HDP), st, qkv, dout,
+                        lse, delta, dqkv, N, H, hd, scale);
+            return launch_status("attn_bwd_dkv_kernel");
         }
     }
-    if (ACfg<HDP>::VEC && fused_lds <= 80 * 1024 && mode) {
-        VSOM_LAUNCH((attn_bwd_fused_kernel<HDP, EXTRA>), dim3(B * H), block, fused_lds, st, qkv, out, dout, lse, dqkv,
-                           delta, N, H, hd, scale);
-        VSOM_LAUNCH_CHECK("attn_bwd_fused_kernel");
-    }
-    VSOM_LAUNCH((attn_bwd_dq_kernel<HDP, EXTRA>), dim3(B * H), block, attn_lds_bytes(N, HDP, false, HDP), st, qkv, out,
-                       dout, lse, dqkv, delta, N, H, hd, scale);
-    int rc = hip_status(hipGetLastError(), "attn_bwd_dq_kernel");
-    if (rc) return rc;
-    VSOM_LAUNCH((attn_bwd_dkv_kernel<HDP, EXTRA>), dim3(B * H), block, attn_lds_bytes(N, HDP, true, 2 * HDP), st, qkv,
-                       dout, lse, delta, dqkv, N, H, hd, scale);
-    VSOM_LAUNCH_CHECK("attn_bwd_dkv_kernel");
+    set_error("attention_bwd: plan %d has no kernel at head dim %d", (int)plan, HDP);
+    return VSOM_EUNSUPPORTED;
 }
 template <int HDP>
 static int launch_fwd(const float* qkv, float* out, float* lse, int B, int N, int H, int hd, hipStream_t st) {
@@ -1424,7 +1451,7 @@ int vsom_attention_probs(const float* qkv, const float* lse, float* probs, int B
     VSOM_REQUIRE(B > 0 && N > 0 && H > 0 && hd > 0, VSOM_EINVAL, "attention_probs: bad shape B=%d N=%d H=%d hd=%d", B, N, H, hd);
     const int by = cdiv((long)N * N, 256) < 64 ? cdiv((long)N * N, 256) : 64;
     VSOM_LAUNCH(attn_probs_kernel, dim3(B * H, by), dim3(256), 0, stream, qkv, lse, probs, N, H, hd, 1.0f / sqrtf((float)hd));
-    VSOM_LAUNCH_CHECK("attn_probs_kernel");
+    return launch_status("attn_probs_kernel");
 }
 
 }  // extern "C"

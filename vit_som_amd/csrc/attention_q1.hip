@@ -167,7 +167,7 @@ int vsom_attention_q1_fwd(const float* q, const float* kv, float* o, float* lse,
         case 32: VSOM_LAUNCH(attention_q1_fwd_kernel<32>, grid, block, 0, stream, q, kv, o, lse, N, H, scale); break;
         default: VSOM_LAUNCH(attention_q1_fwd_kernel<64>, grid, block, 0, stream, q, kv, o, lse, N, H, scale); break;
     }
-    VSOM_LAUNCH_CHECK("attention_q1_fwd_kernel");
+    return launch_status("attention_q1_fwd_kernel");
 }
 
 int vsom_attention_q1_bwd(const float* dout, const float* o, const float* lse, const float* q, const float* kv, float* dq,
@@ -185,7 +185,7 @@ int vsom_attention_q1_bwd(const float* dout, const float* o, const float* lse, c
         case 32: VSOM_LAUNCH(attention_q1_bwd_kernel<32>, grid, block, 0, stream, dout, o, lse, q, kv, dq, dkv, N, H, scale); break;
         default: VSOM_LAUNCH(attention_q1_bwd_kernel<64>, grid, block, 0, stream, dout, o, lse, q, kv, dq, dkv, N, H, scale); break;
     }
-    VSOM_LAUNCH_CHECK("attention_q1_bwd_kernel");
+    return launch_status("attention_q1_bwd_kernel");
 }
 
 int vsom_rows_add(const float* src, long lds, float* dst, long ldd, int rows, int cols, vsom_stream_t stream) {
@@ -193,7 +193,7 @@ int vsom_rows_add(const float* src, long lds, float* dst, long ldd, int rows, in
     const long n = (long)rows * cols;
     const int grid = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
     VSOM_LAUNCH(rows_add_kernel, dim3(grid), dim3(256), 0, stream, src, lds, dst, ldd, rows, cols);
-    VSOM_LAUNCH_CHECK("rows_add_kernel");
+    return launch_status("rows_add_kernel");
 }
 
 }  // extern "C"

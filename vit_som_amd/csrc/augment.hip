@@ -723,7 +723,7 @@ int vsom_augment_plan(const int64_t* index, long N, int B, int H, int S, double 
     const vsom::BoxDraw d1 = {scale0, scale1, log_ratio0, log_ratio1}, d2 = {scale2_0, scale2_1, log_ratio2_0, log_ratio2_1};
     VSOM_LAUNCH(vsom::augment_plan_kernel, dim3(vsom::cdiv(B, 256)), dim3(256), 0, stream, index, N, B, H, S, d1, d2, two_stage,
                 flip_p, erase_p, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)epoch, params);
-    VSOM_LAUNCH_CHECK("augment_plan_kernel");
+    return vsom::launch_status("augment_plan_kernel");
 }
 
 int vsom_augment_batch(const unsigned char* src, long N, int C, int H, int W, const int64_t* index, const int32_t* params, int B,
@@ -742,7 +742,7 @@ int vsom_augment_batch(const unsigned char* src, long N, int C, int H, int W, co
                  "augment_batch: out and params must be 16-byte aligned");
     VSOM_LAUNCH(vsom::augment_batch_kernel, dim3(B), dim3(vsom::AUG_THREADS), 0, stream, src, N, C, H, index, params, S, R, off, mean, std,
                 (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)epoch, out, out_u8);
-    VSOM_LAUNCH_CHECK("augment_batch_kernel");
+    return vsom::launch_status("augment_batch_kernel");
 }
 
 int vsom_randaug_plan(const int64_t* index, long N, int B, int S, int randaug_n, int autoaugment, double flip1_p, uint32_t fill_tv,
@@ -757,7 +757,7 @@ int vsom_randaug_plan(const int64_t* index, long N, int B, int S, int randaug_n,
     const vsom::RaPolicy pol = {randaug_n, autoaugment != 0, flip1_p, fill_tv, fill_timm};
     VSOM_LAUNCH(vsom::randaug_plan_kernel, dim3(vsom::cdiv(B, 256)), dim3(256), 0, stream, index, N, B, S, pol, (uint32_t)seed,
                 (uint32_t)(seed >> 32), (uint32_t)epoch, ra);
-    VSOM_LAUNCH_CHECK("randaug_plan_kernel");
+    return vsom::launch_status("randaug_plan_kernel");
 }
 
 int vsom_augment_batch_ra(const unsigned char* src, long N, int C, int H, int W, const int64_t* index, const int32_t* params,
@@ -774,7 +774,7 @@ int vsom_augment_batch_ra(const unsigned char* src, long N, int C, int H, int W,
                  "augment_batch_ra: out, params and the record must be 16-byte aligned");
     VSOM_LAUNCH(vsom::augment_batch_ra_kernel, dim3(B), dim3(vsom::AUG_THREADS), 0, stream, src, N, C, H, index, params, ra, S, mean,
                 std, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)epoch, out, out_u8);
-    VSOM_LAUNCH_CHECK("augment_batch_ra_kernel");
+    return vsom::launch_status("augment_batch_ra_kernel");
 }
 
 }  // extern "C"

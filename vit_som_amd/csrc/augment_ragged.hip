@@ -337,7 +337,7 @@ int vsom_augment_plan_ragged(const int64_t* index, const int32_t* shapes, long N
     const vsom::BoxDraw d1 = {scale0, scale1, log_ratio0, log_ratio1}, d2 = {scale2_0, scale2_1, log_ratio2_0, log_ratio2_1};
     VSOM_LAUNCH(vsom::augment_plan_ragged_kernel, dim3(vsom::cdiv(B, 256)), dim3(256), 0, stream, index, shapes, N, B, S, d1, d2,
                 two_stage, flip_p, erase_p, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)epoch, params);
-    VSOM_LAUNCH_CHECK("augment_plan_ragged_kernel");
+    return vsom::launch_status("augment_plan_ragged_kernel");
 }
 
 int vsom_augment_batch_ragged(const unsigned char* data, size_t data_bytes, const int64_t* offsets, const int32_t* shapes, long N,
@@ -374,7 +374,7 @@ int vsom_augment_batch_ragged(const unsigned char* data, size_t data_bytes, cons
     const dim3 grid(B, vsom::cdiv(S, vsom::RG_BAND));
     if (!params) {
         VSOM_LAUNCH(vsom::ragged_pass_kernel, grid, dim3(vsom::RG_THREADS), 0, stream, a);
-        VSOM_LAUNCH_CHECK("ragged_pass_kernel (evaluation)");
+        return vsom::launch_status("ragged_pass_kernel (evaluation)");
     }
     a.mode = vsom::RG_CROP1;
     VSOM_LAUNCH(vsom::ragged_pass_kernel, grid, dim3(vsom::RG_THREADS), 0, stream, a);
@@ -384,7 +384,7 @@ int vsom_augment_batch_ragged(const unsigned char* data, size_t data_bytes, cons
     a.data = (const unsigned char*)scratch;
     a.data_bytes = (long)B * C * S * S;
     VSOM_LAUNCH(vsom::ragged_pass_kernel, grid, dim3(vsom::RG_THREADS), 0, stream, a);
-    VSOM_LAUNCH_CHECK("ragged_pass_kernel (crop 2)");
+    return vsom::launch_status("ragged_pass_kernel (crop 2)");
 }
 
 }  // extern "C"

@@ -670,7 +670,7 @@ int vsom_bmu_cosine_x3_dots(const float* X, long ldx, const float* W, int B, int
     g.x_bytes = (unsigned)xb; g.w_bytes = (unsigned)wb;
     if (bmu_x3_big(B)) VSOM_LAUNCH((bmu_x3_kernel<2, 3, 4, 2>), dim3(bmu_x3_tiles(B, K) * splits), dim3(512), 0, stream, g);
     else VSOM_LAUNCH((bmu_x3_kernel<2, 2, 2, 2>), dim3(bmu_x3_tiles(B, K) * splits), dim3(256), 0, stream, g);
-    VSOM_LAUNCH_CHECK("bmu_x3_kernel");
+    return launch_status("bmu_x3_kernel");
 }
 
 /* stage 2: norms, distances, first minimum, exact re-rank of the near-minimum candidates.  reranked (nullable):
@@ -694,7 +694,7 @@ int vsom_bmu_cosine_x3_finalize(const float* X, long ldx, const float* W, const 
     else
     VSOM_LAUNCH(bmu_x3_finalize_kernel<false>, dim3(B), dim3(256), 0, stream, g.slab, g.slab_stride, splits, X, ldx, W, inv_nx,
                        inv_nw, dist, bmu, K, L, reranked);
-    VSOM_LAUNCH_CHECK("bmu_x3_finalize_kernel");
+    return launch_status("bmu_x3_finalize_kernel");
 }
 
 /* ---------------------------------------------------------------- pre-split plane images (see planes_kernel above) */
@@ -723,7 +723,7 @@ int vsom_bmu_planes_from(const float* src, long ld, int R, int L, void* planes, 
     if (rc) return rc;
     q.src = src; q.ld = ld;
     VSOM_LAUNCH(planes_kernel<false>, dim3(q.nrb * cdiv(L, PL_CHUNK)), dim3(256), 0, stream, q);
-    VSOM_LAUNCH_CHECK("planes_kernel");
+    return launch_status("planes_kernel");
 }
 
 int vsom_adamw_step_planes(float* p, const float* g, float* m, float* v, const float* wd_per_chunk, long n, float lr,
@@ -747,7 +747,7 @@ int vsom_adamw_step_planes(float* p, const float* g, float* m, float* v, const f
     long nflat = (q.flat_n4 + 255) / 256;
     if (nflat > 8192) nflat = 8192;
     VSOM_LAUNCH(planes_kernel<true>, dim3(q.nblk_planes + (int)nflat), dim3(256), 0, stream, q);
-    VSOM_LAUNCH_CHECK("planes_kernel<adamw>");
+    return launch_status("planes_kernel<adamw>");
 }
 
 int vsom_bmu_cosine_x3_planes_supported(int B, int K, int L) {
@@ -780,7 +780,7 @@ int vsom_bmu_cosine_x3_planes_dots(const void* xplanes, const void* wplanes, int
     g.stages_per_split = 2 * cdiv(cdiv(L, 32), splits);
     g.slab = static_cast<float*>(ws); g.slab_stride = (long)B * K;
     VSOM_LAUNCH(bmu_x3_planes_kernel, dim3(bmu_x3_tiles(B, K) * splits), dim3(512), PL_LDS, stream, g);
-    VSOM_LAUNCH_CHECK("bmu_x3_planes_kernel");
+    return launch_status("bmu_x3_planes_kernel");
 }
 
 /* stage 2 for the planes form: norms from the images' partials, then the same finalize kernel */
@@ -805,7 +805,7 @@ int vsom_bmu_cosine_x3_planes_finalize(const float* X, long ldx, const float* W,
     else
         VSOM_LAUNCH(bmu_x3_finalize_kernel<false>, dim3(B), dim3(256), 0, stream, slab, slab_stride, splits, X, ldx, W, inv_nx,
                     inv_nw, dist, bmu, K, L, reranked);
-    VSOM_LAUNCH_CHECK("bmu_x3_finalize_kernel");
+    return launch_status("bmu_x3_finalize_kernel");
 }
 
 }  // extern "C"

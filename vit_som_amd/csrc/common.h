@@ -32,7 +32,8 @@ inline int hip_status(hipError_t e, const char* what) {
         }                                  \
     } while (0)
 
-#define VSOM_LAUNCH_CHECK(name) return ::vsom::hip_status(hipGetLastError(), name)
+// status of the launch just issued: every launcher ends a path with `return launch_status("kernel")`
+inline int launch_status(const char* name) { return hip_status(hipGetLastError(), name); }
 
 // ---- launch tape (tape.hip): every kernel launch of the library goes through VSOM_LAUNCH.  Normally that IS
 // hipLaunchKernelGGL; while the calling thread records a tape (vsom_tape_begin) the launch is also kept -- kernel, grid, block,
@@ -48,7 +49,7 @@ struct TapeRec;
 extern thread_local TapeRec* g_tape_rec;                    // non-null while this thread records (and is not paused)
 void tape_push(TapeOp&& op);
 
-// The launch itself runs unchanged (the caller's VSOM_LAUNCH_CHECK sees its status); the recorded op checks it on replay.
+// The launch itself runs unchanged (the caller's launch_status() sees its status); the recorded op checks it on replay.
 template <class F>
 inline void launch_or_record(F&& f, const char* what) {
     f();

@@ -478,7 +478,22 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmP g) {
     gemm_epilogue<WM, WN, EPI>(g, acc, bm0 + wm0, bn0 + wn0, r, h, z);
 }
 
-// host-side launcher (gemm_f32.hip)
+// ---- host side (gemm_f32.hip).  Which kernel a GEMM runs is a value: gemm_plan() computes it from the shape, the alignment
+// and the GEMM mode, launch_gemm() switches on it.  The table is DESIGN.md section 4c.
+enum GemmEngine : int { GEMM_ENGINE_F32 = 0, GEMM_ENGINE_X6 = 1 };       // f32 MFMA (this file) / split-bf16 (gemm_x6.h)
+struct GemmPlan {
+    int engine;               // GemmEngine
+    int tile_m;               // tile height, 64 or 128; every tile is 64 columns wide
+    int planes;               // bf16 pieces per operand of the split engine: 3 (six products) or 2 (three); 0 for f32
+    bool fast;                // 16-byte bounds-checked buffer loads (the split engine has no other form)
+    int splits;               // canonical reduction split count: every split owns at least one k-tile
+    int ktiles_per_split;
+    int tiles;                // output tiles
+    int grid;                 // workgroups = tiles * splits
+};
+// Pure: `mode` is the GEMM mode (VSOM_GEMM_*), `products` GemmP::products, `fast` as computed by launch_gemm.
+GemmPlan gemm_plan(bool a_kc, bool b_kc, int epi, int M, int N, int K, bool fast, int mode, int products, int splits);
+int gemm_mode();
 int launch_gemm(bool a_kc, bool b_kc, int epi, GemmP g, int splits, hipStream_t stream);
 int linear_bwd_weight_impl(const float* dY, long lddy, const float* X, long ldx, float* dW, float* db, int M, int N,
                            int K, int a_seg, int a_stride, int a_off, void* ws, size_t ws_bytes,
@@ -547,7 +562,9 @@ int reduce_slabs2_internal(const float* slabs, long stride, int nslabs, float* o
                            long n2, hipStream_t stream);
 int sum_partials(const float* part, int n, float* out, hipStream_t stream);
 int choose_splits(int tiles, int ktiles, int max_splits, bool prefer_xcd_multiple = false);
-int gemm_tile_m(bool a_kc, bool b_kc, int M);
+int bmu_splits(int B, int K, int L);                          // som.hip
+int attn_bwd_threads(int N);                                  // attention.hip
+int attn_bwd_plan_now(int N, int hd);                         // attention.hip: AttnBwd under the current hook and mode, -1: hd unsupported
 int gemm_grad_products();     // 3 in VSOM_GEMM_SPLIT_BF16_GRAD3 mode (gradient GEMMs on the two-piece split), else 6
 
 }  // namespace vsom

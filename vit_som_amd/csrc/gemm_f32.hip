@@ -24,7 +24,6 @@ const char* last_error() { return g_err; }
 // GEMMs of the Linear layers on the two-piece split, three products).
 static std::atomic<int> g_gemm_mode{VSOM_GEMM_SPLIT_BF16_GRAD3};
 int gemm_mode() { return g_gemm_mode.load(std::memory_order_relaxed); }
-static bool split_engine() { return gemm_mode() != VSOM_GEMM_F32; }
 int gemm_grad_products() { return gemm_mode() == VSOM_GEMM_SPLIT_BF16_GRAD3 ? 3 : 6; }
 
 // One tile configuration: 128 x 64 (4 waves, each 32 x 64 = two 32x32 accumulators).  Measured
@@ -32,111 +31,148 @@ int gemm_grad_products() { return gemm_mode() == VSOM_GEMM_SPLIT_BF16_GRAD3 ? 3 
 // workgroups per CU instead of two and half the epilogue per workgroup.
 static long operand_bytes(long rows, long ld, long cols) { return ((rows - 1) * ld + cols) * 4; }
 
-// Tile height for a GEMM: 128 rows normally; the k-strided ("TN") weight-gradient GEMMs also have a
-// 64 x 64 tile, used when their output height (192 = proj / fc2 rows, 96, ...) would otherwise pad
-// 128-row tiles by >= 10 %.
-int gemm_tile_m(bool a_kc, bool b_kc, int M) {
-    if (a_kc || b_kc) return 128;
-    const double w128 = (double)cdiv(M, 128) * 128, w64 = (double)cdiv(M, 64) * 64;
-    return (w128 > 1.10 * w64) ? 64 : 128;
+// ---- the launch plan ("Which kernel runs").
+// The kernels a (layout, epilogue) pair has beside the f32 128 x 64 pair that every one has.  gemm_plan() chooses among
+// them and dispatch_gemm() instantiates exactly them: a form that is false here is neither planned nor compiled.
+struct GemmForms {
+    bool x6;            // the split-bf16 engine at 128 x 64, three planes
+    bool x6_tile64;     // ... and at 64 x 64 (three planes only)
+    bool x6_planes2;    // ... and at 128 x 64 on two planes (three products), for GemmP::products == 3
+    bool f32_tile64;    // the f32 engine at 64 x 64
+};
+static constexpr GemmForms gemm_forms(bool a_kc, bool b_kc, int epi) {
+    if (a_kc && b_kc) {                                         // "NT": the slab epilogue (BMU pass) stays exact f32
+        const bool x6 = epi != EPI_SLAB;
+        return {x6, x6, x6 && (epi == EPI_NONE || epi == EPI_GELU_BWD), false};       // two planes: the input-gradient GEMMs
+    }
+    if (a_kc) return {epi == EPI_ROWAXPY, false, epi == EPI_ROWAXPY, false};          // "NN": the SOM's gX only
+    return {true, true, epi == EPI_ROWAXPY, true};                                    // "TN" (both k-strided)
+}
+// No plan has two planes under the slab epilogue, so nothing launches this kernel.  It is instantiated to keep the library's
+// kernel set (62 in this file) what the bitwise tests and the build time were measured with; retiring it is a change of its own.
+template __global__ void gemm_x6_kernel<false, false, 1, 2, 4, 1, EPI_SLAB, 2>(const GemmP);
+
+// 16-byte vector loads run along k for k-contiguous operands and along the tile's columns for k-strided ones
+static bool gemm_vec_extents(bool a_kc, bool b_kc, int M, int N, int K) { return (a_kc ? K : M) % 4 == 0 && (b_kc ? K : N) % 4 == 0; }
+
+GemmPlan gemm_plan(bool a_kc, bool b_kc, int epi, int M, int N, int K, bool fast, int mode, int products, int splits) {
+    const GemmForms f = gemm_forms(a_kc, b_kc, epi);
+    GemmPlan p;
+    p.fast = fast;
+    p.engine = (f.x6 && fast && mode != VSOM_GEMM_F32) ? GEMM_ENGINE_X6 : GEMM_ENGINE_F32;
+    if (!a_kc && !b_kc) {
+        // the weight-gradient layout: 64-row tiles when the output height (192 = proj / fc2 rows, 96, ...) would otherwise
+        // pad 128-row tiles by >= 10 %
+        const double w128 = (double)cdiv(M, 128) * 128, w64 = (double)cdiv(M, 64) * 64;
+        p.tile_m = (w128 > 1.10 * w64) ? 64 : 128;
+    } else {
+        // 64 x 64 only for problems of at most 64 rows.  (Rounds 1-2 chose between the two with a "rounds of 256
+        // workgroups" model fitted to each GEMM running ALONE, which sent about half of the step's GEMMs to 64 x 64.
+        // Inside the step two kernels share the chip nearly all the time (tools/timeline.py), and there the larger tile
+        // wins: every GEMM of this family on 128 x 64 is 0.3 ms per step faster, A/B on one box 11.07-11.14 ->
+        // 10.77-10.83 ms; restricting 64 x 64 to launches of < 512 or < 256 large tiles: 10.91 / 10.85.)
+        p.tile_m = (f.x6_tile64 && p.engine == GEMM_ENGINE_X6 && M <= 64) ? 64 : 128;
+    }
+    // the 64 x 64 tile has the three-plane form only, also where three products were asked for
+    p.planes = p.engine == GEMM_ENGINE_F32 ? 0 : (f.x6_planes2 && products == 3 && p.tile_m == 128) ? 2 : 3;
+    const int ktiles = K > 0 ? cdiv(K, 32) : 1;
+    if (splits > ktiles) splits = ktiles;
+    if (splits < 1) splits = 1;
+    p.ktiles_per_split = cdiv(ktiles, splits);
+    p.splits = cdiv(ktiles, p.ktiles_per_split);
+    p.tiles = cdiv(M, p.tile_m) * cdiv(N, 64);
+    p.grid = p.tiles * p.splits;
+    return p;
 }
 
+// (engine, tile height, planes, fast) as one switch label
+static constexpr int plan_key(int engine, int tile_m, int planes, bool fast) { return ((engine * 2 + (tile_m == 64)) * 4 + planes) * 2 + fast; }
+
 template <bool A_KC, bool B_KC, int EPI>
-static int launch_t(GemmP& g, int splits, hipStream_t stream) {
-    const int BM = gemm_tile_m(A_KC, B_KC, g.M), BN = 64;
-    const int tiles = cdiv(g.M, BM) * cdiv(g.N, BN);
-    dim3 grid(tiles * splits, 1, 1), block(256);
-    // extent of each operand in bytes; rows of a k-strided A may be remapped (a_seg)
-    const long a_rows = A_KC ? g.M : (g.a_seg ? (long)((g.K - 1) / g.a_seg) * g.a_stride + g.a_off + (g.K - 1) % g.a_seg + 1 : g.K);
-    const long a_cols = A_KC ? g.K : g.M;
-    const long b_rows = B_KC ? g.N : g.K, b_cols = B_KC ? g.K : g.N;
-    const long ab = operand_bytes(a_rows, g.lda, a_cols), bb = operand_bytes(b_rows, g.ldb, b_cols);
-    const bool fast = g.a_vec && g.b_vec && (a_cols % 4 == 0) && (b_cols % 4 == 0) && ab < 0xFFFF0000L && bb < 0xFFFF0000L;
-    g.a_bytes = (unsigned)ab; g.b_bytes = (unsigned)bb;
-    g.n_major = bb > ab;        // share the larger operand's panel between neighbouring workgroups
-    if constexpr (!A_KC && !B_KC && (EPI == EPI_SLAB || EPI == EPI_ROWAXPY)) {
-        if (fast && split_engine()) {
-            if (BM == 64) VSOM_LAUNCH((gemm_x6_kernel<false, false, 1, 1, 2, 2, EPI>), grid, block, 0, stream, g);
-            else if (EPI == EPI_ROWAXPY && g.products == 3) VSOM_LAUNCH((gemm_x6_kernel<false, false, 1, 2, 4, 1, EPI, 2>), grid, block, 0, stream, g);
-            else VSOM_LAUNCH((gemm_x6_kernel<false, false, 1, 2, 4, 1, EPI>), grid, block, 0, stream, g);
-            VSOM_LAUNCH_CHECK("gemm_x6_kernel");
-        }
-    }
-    if constexpr (!A_KC && !B_KC) {
-        if (BM == 64) {
-            if (fast) VSOM_LAUNCH((gemm_f32_kernel<A_KC, B_KC, 1, 1, 2, 2, EPI, true>), grid, block, 0, stream, g);
-            else VSOM_LAUNCH((gemm_f32_kernel<A_KC, B_KC, 1, 1, 2, 2, EPI, false>), grid, block, 0, stream, g);
-            VSOM_LAUNCH_CHECK("gemm_f32_kernel");
-        }
-    }
-    if constexpr (A_KC && !B_KC && EPI == EPI_ROWAXPY) {
-        if (fast && split_engine()) {
-            if (g.products == 3) VSOM_LAUNCH((gemm_x6_kernel<true, false, 1, 2, 4, 1, EPI, 2>), grid, block, 0, stream, g);
-            else VSOM_LAUNCH((gemm_x6_kernel<true, false, 1, 2, 4, 1, EPI>), grid, block, 0, stream, g);
-            VSOM_LAUNCH_CHECK("gemm_x6_kernel");
-        }
-    }
-    if constexpr (A_KC && B_KC && EPI != EPI_SLAB) {
-        if (fast && split_engine()) {
-            // 128 x 64 tiles; 64 x 64 only for problems of at most 64 rows.  (Rounds 1-2 chose between the two with a
-            // "rounds of 256 workgroups" model fitted to each GEMM running ALONE, which sent about half of the step's
-            // GEMMs to 64 x 64.  Inside the step two kernels share the chip nearly all the time (tools/timeline.py), and
-            // there the larger tile wins: every GEMM of this family on 128 x 64 is 0.3 ms per step faster, A/B on one box
-            // 11.07-11.14 -> 10.77-10.83 ms; restricting 64 x 64 to launches of < 512 or < 256 large tiles: 10.91 / 10.85.)
-            if (g.M <= 64) {
-                dim3 grid64(cdiv(g.M, 64) * cdiv(g.N, 64) * splits, 1, 1);
-                VSOM_LAUNCH((gemm_x6_kernel<true, true, 1, 1, 2, 2, EPI>), grid64, block, 0, stream, g);
-                VSOM_LAUNCH_CHECK("gemm_x6_kernel");
+static int dispatch_gemm(const GemmPlan& p, const GemmP& g, hipStream_t stream) {
+    constexpr GemmForms F = gemm_forms(A_KC, B_KC, EPI);
+    const dim3 grid(p.grid), block(256);
+    switch (plan_key(p.engine, p.tile_m, p.planes, p.fast)) {
+        case plan_key(GEMM_ENGINE_F32, 128, 0, false):
+            VSOM_LAUNCH((gemm_f32_kernel<A_KC, B_KC, 1, 2, 4, 1, EPI, false>), grid, block, 0, stream, g);
+            return launch_status("gemm_f32_kernel");
+        case plan_key(GEMM_ENGINE_F32, 128, 0, true):
+            VSOM_LAUNCH((gemm_f32_kernel<A_KC, B_KC, 1, 2, 4, 1, EPI, true>), grid, block, 0, stream, g);
+            return launch_status("gemm_f32_kernel");
+        case plan_key(GEMM_ENGINE_F32, 64, 0, false):
+            if constexpr (F.f32_tile64) {
+                VSOM_LAUNCH((gemm_f32_kernel<A_KC, B_KC, 1, 1, 2, 2, EPI, false>), grid, block, 0, stream, g);
+                return launch_status("gemm_f32_kernel");
             }
-            if constexpr (EPI == EPI_NONE || EPI == EPI_GELU_BWD) {          // the input-gradient GEMMs: three products on request
-                if (g.products == 3) {
-                    VSOM_LAUNCH((gemm_x6_kernel<true, true, 1, 2, 4, 1, EPI, 2>), grid, block, 0, stream, g);
-                    VSOM_LAUNCH_CHECK("gemm_x6_kernel");
-                }
+            break;
+        case plan_key(GEMM_ENGINE_F32, 64, 0, true):
+            if constexpr (F.f32_tile64) {
+                VSOM_LAUNCH((gemm_f32_kernel<A_KC, B_KC, 1, 1, 2, 2, EPI, true>), grid, block, 0, stream, g);
+                return launch_status("gemm_f32_kernel");
             }
-            VSOM_LAUNCH((gemm_x6_kernel<true, true, 1, 2, 4, 1, EPI>), grid, block, 0, stream, g);
-            VSOM_LAUNCH_CHECK("gemm_x6_kernel");
-        }
+            break;
+        case plan_key(GEMM_ENGINE_X6, 64, 3, true):
+            if constexpr (F.x6_tile64) {
+                VSOM_LAUNCH((gemm_x6_kernel<A_KC, B_KC, 1, 1, 2, 2, EPI>), grid, block, 0, stream, g);
+                return launch_status("gemm_x6_kernel");
+            }
+            break;
+        case plan_key(GEMM_ENGINE_X6, 128, 3, true):
+            if constexpr (F.x6) {
+                VSOM_LAUNCH((gemm_x6_kernel<A_KC, B_KC, 1, 2, 4, 1, EPI>), grid, block, 0, stream, g);
+                return launch_status("gemm_x6_kernel");
+            }
+            break;
+        case plan_key(GEMM_ENGINE_X6, 128, 2, true):
+            if constexpr (F.x6_planes2) {
+                VSOM_LAUNCH((gemm_x6_kernel<A_KC, B_KC, 1, 2, 4, 1, EPI, 2>), grid, block, 0, stream, g);
+                return launch_status("gemm_x6_kernel");
+            }
+            break;
     }
-    if (fast)
-        VSOM_LAUNCH((gemm_f32_kernel<A_KC, B_KC, 1, 2, 4, 1, EPI, true>), grid, block, 0, stream, g);
-    else
-        VSOM_LAUNCH((gemm_f32_kernel<A_KC, B_KC, 1, 2, 4, 1, EPI, false>), grid, block, 0, stream, g);
-    VSOM_LAUNCH_CHECK("gemm_f32_kernel");
+    set_error("gemm: plan (engine %d, tile %d x 64, %d planes) has no kernel for layout (%d,%d) epilogue %d", p.engine, p.tile_m,
+              p.planes, (int)A_KC, (int)B_KC, EPI);
+    return VSOM_EUNSUPPORTED;
 }
 
 int launch_gemm(bool a_kc, bool b_kc, int epi, GemmP g, int splits, hipStream_t stream) {
     VSOM_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, VSOM_EINVAL, "gemm: non-positive shape M=%d N=%d K=%d", g.M, g.N, g.K);
     VSOM_REQUIRE(g.A && g.B, VSOM_EINVAL, "gemm: null operand");
-    const int ktiles = cdiv(g.K, 32);
-    if (splits < 1) splits = 1;
-    if (splits > ktiles) splits = ktiles;
-    g.ktiles_per_split = cdiv(ktiles, splits);
-    splits = cdiv(ktiles, g.ktiles_per_split);
-    // 16-byte vector loads need an aligned base and row stride; the vector runs along k for
-    // k-contiguous operands and along the tile's columns for k-strided ones.
+    // 16-byte vector loads need an aligned base and row stride
     g.a_vec = aligned16(g.A) && (g.lda % 4 == 0);
     g.b_vec = aligned16(g.B) && (g.ldb % 4 == 0);
+    // extent of each operand in bytes; rows of a k-strided A may be remapped (a_seg)
+    const long a_rows = a_kc ? g.M : (g.a_seg ? (long)((g.K - 1) / g.a_seg) * g.a_stride + g.a_off + (g.K - 1) % g.a_seg + 1 : g.K);
+    const long a_cols = a_kc ? g.K : g.M;
+    const long b_rows = b_kc ? g.N : g.K, b_cols = b_kc ? g.K : g.N;
+    const long ab = operand_bytes(a_rows, g.lda, a_cols), bb = operand_bytes(b_rows, g.ldb, b_cols);
+    const bool fast = g.a_vec && g.b_vec && gemm_vec_extents(a_kc, b_kc, g.M, g.N, g.K) && ab < 0xFFFF0000L && bb < 0xFFFF0000L;
+    g.a_bytes = (unsigned)ab; g.b_bytes = (unsigned)bb;
+    g.n_major = bb > ab;        // share the larger operand's panel between neighbouring workgroups
+
+    const GemmPlan p = gemm_plan(a_kc, b_kc, epi, g.M, g.N, g.K, fast, gemm_mode(), g.products, splits);
+    g.ktiles_per_split = p.ktiles_per_split;
+
     if (a_kc && b_kc) {
         switch (epi) {
-            case EPI_BIAS: return launch_t<true, true, EPI_BIAS>(g, splits, stream);
-            case EPI_BIAS_GELU: return launch_t<true, true, EPI_BIAS_GELU>(g, splits, stream);
-            case EPI_BIAS_RELU: return launch_t<true, true, EPI_BIAS_RELU>(g, splits, stream);
-            case EPI_BIAS_RES: return launch_t<true, true, EPI_BIAS_RES>(g, splits, stream);
-            case EPI_SLAB: return launch_t<true, true, EPI_SLAB>(g, splits, stream);
-            case EPI_NONE: return launch_t<true, true, EPI_NONE>(g, splits, stream);
-            case EPI_GELU_BWD: return launch_t<true, true, EPI_GELU_BWD>(g, splits, stream);
+            case EPI_BIAS: return dispatch_gemm<true, true, EPI_BIAS>(p, g, stream);
+            case EPI_BIAS_GELU: return dispatch_gemm<true, true, EPI_BIAS_GELU>(p, g, stream);
+            case EPI_BIAS_RELU: return dispatch_gemm<true, true, EPI_BIAS_RELU>(p, g, stream);
+            case EPI_BIAS_RES: return dispatch_gemm<true, true, EPI_BIAS_RES>(p, g, stream);
+            case EPI_SLAB: return dispatch_gemm<true, true, EPI_SLAB>(p, g, stream);
+            case EPI_NONE: return dispatch_gemm<true, true, EPI_NONE>(p, g, stream);
+            case EPI_GELU_BWD: return dispatch_gemm<true, true, EPI_GELU_BWD>(p, g, stream);
         }
     } else if (a_kc && !b_kc) {
         switch (epi) {
-            case EPI_NONE: return launch_t<true, false, EPI_NONE>(g, splits, stream);
-            case EPI_GELU_BWD: return launch_t<true, false, EPI_GELU_BWD>(g, splits, stream);
-            case EPI_ROWAXPY: return launch_t<true, false, EPI_ROWAXPY>(g, splits, stream);
+            case EPI_NONE: return dispatch_gemm<true, false, EPI_NONE>(p, g, stream);
+            case EPI_GELU_BWD: return dispatch_gemm<true, false, EPI_GELU_BWD>(p, g, stream);
+            case EPI_ROWAXPY: return dispatch_gemm<true, false, EPI_ROWAXPY>(p, g, stream);
         }
     } else if (!a_kc && !b_kc) {
         switch (epi) {
-            case EPI_SLAB: return launch_t<false, false, EPI_SLAB>(g, splits, stream);
-            case EPI_ROWAXPY: return launch_t<false, false, EPI_ROWAXPY>(g, splits, stream);
+            case EPI_SLAB: return dispatch_gemm<false, false, EPI_SLAB>(p, g, stream);
+            case EPI_ROWAXPY: return dispatch_gemm<false, false, EPI_ROWAXPY>(p, g, stream);
         }
     }
     set_error("gemm: layout/epilogue combination (%d,%d,%d) not instantiated", (int)a_kc, (int)b_kc, epi);
@@ -168,7 +204,7 @@ int reduce_slabs2_internal(const float* slabs, long stride, int nslabs, float* o
         VSOM_LAUNCH((reduce_slabs_kernel<4, 4>), dim3(nb1 + nb2), dim3(256), 0, stream, slabs, stride, nslabs, out1, n1,
                            out2, off2, n2, nb1, vec);
     }
-    VSOM_LAUNCH_CHECK("reduce_slabs_kernel");
+    return launch_status("reduce_slabs_kernel");
 }
 
 int reduce_slabs_internal(const float* slabs, long stride, int nslabs, float* out, long n, hipStream_t stream) {
@@ -214,10 +250,15 @@ int choose_splits(int tiles, int ktiles, int max_splits, bool prefer_xcd_multipl
     }
     return best_s;
 }
-// Weight-gradient plan: tile configuration of gemm_x6_tn_kernel (0 = none fits: the generic k-strided
-// kernel; 1 = 192 x 64, 2 = 96 x 96, 3 = 192 x 192) and the number of reduction splits -- a function of the shape
-// and the switches only, so that the workspace query and the launch agree.
-struct TnPlan { int cfg; int splits; };
+// Weight-gradient plan ("Which kernel runs"): the tile of gemm_x6_tn_kernel, or TN_GENERIC where none fits (the
+// generic k-strided GEMM of launch_gemm), and the number of reduction splits -- a function of the shape and the switches
+// only, so that the workspace query and the launch agree.
+enum TnTile : int { TN_GENERIC = 0, TN_192x64 = 1, TN_96x96 = 2, TN_192x192 = 3 };
+struct TnPlan {
+    int tile;                   // TnTile
+    int rows, cols, threads;    // of one workgroup's tile (rows of dW = N, columns = K); 0 for TN_GENERIC
+    int splits;
+};
 // test / measurement hook (vsom_set_wgrad_tiles): 0 = the 192 x 64 tiles only, 1 = 192 x 192 tiles at the split count
 // of the 192 x 64 plan (bitwise the same dW and db), 2 = 192 x 192 tiles with their own split count (default)
 static std::atomic<int> g_wgrad_tiles{2};
@@ -227,53 +268,75 @@ static int splits_for(int tiles, int ktiles, int target) {
     if (s < 1) s = 1;
     return cdiv(ktiles, cdiv(ktiles, s));
 }
-static TnPlan bwd_weight_plan(int M, int N, int K) {
-    TnPlan p;
-    p.cfg = (N % 192 == 0 && K % 64 == 0) ? 1 : (N % 96 == 0 && K % 96 == 0) ? 2 : 0;
-    if (p.cfg == 0) {
-        p.splits = choose_splits(cdiv(N, gemm_tile_m(false, false, N)) * cdiv(K, 64), cdiv(M, 32), 128);
-        return p;
-    }
-    const int tiles = p.cfg == 1 ? (N / 192) * (K / 64) : (N / 96) * (K / 96);
+static TnPlan bwd_weight_plan(int M, int N, int K, int mode, int wide) {
     const int ktiles = cdiv(M, 32);
+    if (N % 192 == 0 && K % 192 == 0 && wide && mode == VSOM_GEMM_SPLIT_BF16_GRAD3) {
+        // 192 x 192: one 112 KB workgroup per CU.  Workgroups for three quarters of the CUs: inside the step the rest serve
+        // the backward chain (round 5, in-step A/B on one box: 256 / 192 / 160 / 128 workgroups -> -0.22 / -0.31 / -0.25 /
+        // -0.13 ms per step against the 192 x 64 plan; alone 256 is fastest).  Hook 1 keeps the 192 x 64 plan's splits.
+        const int splits = wide == 2 ? splits_for((N / 192) * (K / 192), ktiles, 3 * device_cus() / 4)
+                                     : splits_for((N / 192) * (K / 64), ktiles, 384);
+        return {TN_192x192, 192, 192, 768, splits};
+    }
     // 384 workgroups.  Alone the kernel is fastest with two resident workgroups per CU (512), but inside the step, where it
     // shares the chip with the backward chain, fewer and longer reduction ranges win -- and more so since the gradient GEMMs
     // run three products (round 3, lab builds A/B on one box: 768 / 512 / 384 / 320 / 256 / 192 workgroups ->
     // +0.17 / 0 / -0.08...-0.10 / 0 / +0.15 / +0.45 ms per step; rounding the count to a multiple of 8: no difference)
-    p.splits = splits_for(tiles, ktiles, 384);
-    const int wide = g_wgrad_tiles.load(std::memory_order_relaxed);
-    if (wide && gemm_grad_products() == 3 && N % 192 == 0 && K % 192 == 0) {
-        p.cfg = 3;
-        // 192 x 192: one 112 KB workgroup per CU.  Workgroups for three quarters of the CUs: inside the step the rest serve
-        // the backward chain (round 5, in-step A/B on one box: 256 / 192 / 160 / 128 workgroups -> -0.22 / -0.31 / -0.25 /
-        // -0.13 ms per step against the 192 x 64 plan; alone 256 is fastest)
-        if (wide == 2) p.splits = splits_for((N / 192) * (K / 192), ktiles, 3 * device_cus() / 4);
-    }
-    return p;
+    if (N % 192 == 0 && K % 64 == 0) return {TN_192x64, 192, 64, 256, splits_for((N / 192) * (K / 64), ktiles, 384)};
+    if (N % 96 == 0 && K % 96 == 0) return {TN_96x96, 96, 96, 192, splits_for((N / 96) * (K / 96), ktiles, 384)};
+    const int tiles = gemm_plan(false, false, EPI_SLAB, N, K, M, true, mode, 0, 1).tiles;
+    return {TN_GENERIC, 0, 0, 0, choose_splits(tiles, ktiles, 128)};
+}
+// The tile kernels exist on the split engine only, load 16 bytes at a time (`vec`: aligned operands below 4 GB) and take a
+// row map only in whole k-tiles; otherwise the generic GEMM runs at the plan's split count.
+static bool bwd_weight_tiled(const TnPlan& p, int mode, bool vec, int M, int a_seg) {
+    return p.tile != TN_GENERIC && mode != VSOM_GEMM_F32 && vec && (a_seg == 0 || (a_seg % 32 == 0 && M % a_seg == 0));
 }
 static long pad4(long n) { return (n + 3) & ~3L; }
 
 // ---- input-gradient GEMM + LayerNorm backward (EPI_LN_BWD): one column tile spanning the LayerNorm's width (the A row
 // panel is read once instead of three / one and a half times), 64 x 192 (2 x 2 waves of 32 x 96) for the encoder and
 // 128 x 96 (4 waves of 32 x 96) for the decoder.  128 x 192 (4 waves of 32 x 192) needs more than 256 registers per lane
-// with the epilogue: one workgroup per CU, or spills.
-static bool ln_fused_width(int K) { return K == 192 || K == 96; }
-static int ln_fused_tiles(int M, int K) { return cdiv(M, K == 192 ? 64 : 128); }
-// test / measurement hook (vsom_set_ln_tiles): 0 = the 64 x 192 tiles only, 1 = 192 x 192 tiles (gemm_x6_ln_wide_kernel) for
-// the encoder width in the three-product mode (default).  Both write the same dX and per-64-row partials, bit for bit.
+// with the epilogue: one workgroup per CU, or spills.  192 x 192 (gemm_x6_ln_wide_kernel): the transposed weight is staged
+// and split once per 192 rows (round 6); its partials keep the 64-row layout, so the workspace and
+// finish_many do not change.
+enum LnTile : int { LN_NONE = 0, LN_64x192 = 1, LN_128x96 = 2, LN_192x192 = 3 };
+struct LnPlan {
+    bool supported;             // vsom_linear_bwd_input_ln_supported
+    int tile;                   // LnTile; LN_NONE when K is no fused width
+    int rows, threads;          // of one workgroup (its tile is K columns wide)
+    int planes;                 // 2 in the three-product mode, else 3
+    int parts;                  // row tiles of the dgamma / dbeta partials: 64 rows (K = 192) or 128 (K = 96), whatever the tile
+    int grid;
+};
+// test / measurement hook (vsom_set_ln_tiles): 0 = the 64 x 192 tiles only, 1 = 192 x 192 tiles for the encoder width in
+// the three-product mode (default).  Both write the same dX and per-64-row partials, bit for bit.
 static std::atomic<int> g_ln_tiles{1};
+static LnPlan ln_fused_plan(int M, int N, int K, int mode, int ln_tiles) {
+    LnPlan p = {};
+    if (M <= 0 || (K != 192 && K != 96)) return p;
+    p.planes = mode == VSOM_GEMM_SPLIT_BF16_GRAD3 ? 2 : 3;
+    p.parts = cdiv(M, K == 192 ? 64 : 128);
+    // the column reduction of the one-call form must be the wide single-pass reducer that finish_many runs (>= 32 slabs)
+    p.supported = N > 0 && mode != VSOM_GEMM_F32 && p.parts >= 32;
+    if (K == 192 && p.planes == 2 && ln_tiles == 1) { p.tile = LN_192x192; p.rows = 192; p.threads = 768; }
+    else if (K == 192) { p.tile = LN_64x192; p.rows = 64; p.threads = 256; }
+    else { p.tile = LN_128x96; p.rows = 128; p.threads = 256; }
+    p.grid = cdiv(M, p.rows);
+    return p;
+}
 
 static int linear_bwd_input_ln_launch(const float* dY, long lddy, const float* Wt, int M, int N, int K, const float* X,
                                       const float* mean, const float* rstd, const float* gamma, const float* resid,
-                                      float* dX, float* part, size_t part_bytes, hipStream_t stream) {
+                                      float* dX, float* part, size_t part_bytes, const LnPlan& p, hipStream_t stream) {
     VSOM_REQUIRE(dY && Wt && X && mean && rstd && gamma && dX, VSOM_EINVAL, "linear_bwd_input_ln: null pointer");
     VSOM_REQUIRE(M > 0 && N > 0 && lddy >= N, VSOM_EINVAL, "linear_bwd_input_ln: bad shape M=%d N=%d lddy=%ld", M, N, lddy);
-    VSOM_REQUIRE(vsom_linear_bwd_input_ln_supported(M, N, K), VSOM_EUNSUPPORTED,
+    VSOM_REQUIRE(p.supported, VSOM_EUNSUPPORTED,
                  "linear_bwd_input_ln: unsupported (M=%d N=%d K=%d, gemm mode %d)", M, N, K, gemm_mode());
     VSOM_REQUIRE(aligned16(dY) && aligned16(Wt) && aligned16(X) && aligned16(gamma) && aligned16(dX) &&
                  (!resid || aligned16(resid)) && lddy % 4 == 0 && N % 4 == 0, VSOM_EALIGN,
                  "linear_bwd_input_ln: operands must be 16-byte aligned (lddy, N multiples of 4)");
-    VSOM_REQUIRE(part && aligned16(part) && part_bytes >= vsom_linear_bwd_input_ln_partial_bytes(M, K), VSOM_EWORKSPACE,
+    VSOM_REQUIRE(part && aligned16(part) && part_bytes >= (size_t)p.parts * 2 * (size_t)K * sizeof(float), VSOM_EWORKSPACE,
                  "linear_bwd_input_ln: partial buffer too small or misaligned");
     const long ab = operand_bytes(M, lddy, N), bb = operand_bytes(K, N, N);
     VSOM_REQUIRE(ab < 0xFFFF0000L && (long)M * K * 4 < 0xFFFF0000L, VSOM_EUNSUPPORTED, "linear_bwd_input_ln: operand larger than 4 GB");
@@ -285,22 +348,26 @@ static int linear_bwd_input_ln_launch(const float* dY, long lddy, const float* W
     g.a_bytes = (unsigned)ab; g.b_bytes = (unsigned)bb;
     g.products = gemm_grad_products();
     g.ln_x = X; g.ln_mean = mean; g.ln_rstd = rstd; g.ln_gamma = gamma; g.ln_resid = resid; g.ln_part = part;
-    const bool x3 = g.products == 3;
-    if (K == 192 && x3 && g_ln_tiles.load(std::memory_order_relaxed) == 1) {
-        // 192 x 192: the transposed weight is staged and split once per 192 rows (round 6); the partials keep
-        // the 64-row layout, so the workspace and finish_many do not change
-        VSOM_LAUNCH((gemm_x6_ln_wide_kernel<3, 6, 2, 2>), dim3(cdiv(M, 192)), dim3(768), 0, stream, g);
-        VSOM_LAUNCH_CHECK("gemm_x6_ln_wide_kernel");
+    const dim3 grid(p.grid), block(p.threads);
+    switch (p.tile * 4 + p.planes) {
+        case LN_192x192 * 4 + 2:
+            VSOM_LAUNCH((gemm_x6_ln_wide_kernel<3, 6, 2, 2>), grid, block, 0, stream, g);
+            return launch_status("gemm_x6_ln_wide_kernel");
+        case LN_64x192 * 4 + 2:
+            VSOM_LAUNCH((gemm_x6_ln_kernel<3, 2, 2, 2>), grid, block, 0, stream, g);
+            return launch_status("gemm_x6_ln_kernel");
+        case LN_64x192 * 4 + 3:
+            VSOM_LAUNCH((gemm_x6_ln_kernel<3, 2, 2, 3>), grid, block, 0, stream, g);
+            return launch_status("gemm_x6_ln_kernel");
+        case LN_128x96 * 4 + 2:
+            VSOM_LAUNCH((gemm_x6_ln_kernel<3, 4, 1, 2>), grid, block, 0, stream, g);
+            return launch_status("gemm_x6_ln_kernel");
+        case LN_128x96 * 4 + 3:
+            VSOM_LAUNCH((gemm_x6_ln_kernel<3, 4, 1, 3>), grid, block, 0, stream, g);
+            return launch_status("gemm_x6_ln_kernel");
     }
-    const dim3 grid(ln_fused_tiles(M, K)), block(256);
-    if (K == 192) {
-        if (x3) VSOM_LAUNCH((gemm_x6_ln_kernel<3, 2, 2, 2>), grid, block, 0, stream, g);
-        else VSOM_LAUNCH((gemm_x6_ln_kernel<3, 2, 2, 3>), grid, block, 0, stream, g);
-    } else {
-        if (x3) VSOM_LAUNCH((gemm_x6_ln_kernel<3, 4, 1, 2>), grid, block, 0, stream, g);
-        else VSOM_LAUNCH((gemm_x6_ln_kernel<3, 4, 1, 3>), grid, block, 0, stream, g);
-    }
-    VSOM_LAUNCH_CHECK("gemm_x6_ln_kernel");
+    set_error("linear_bwd_input_ln: plan (tile %d, %d planes) has no kernel", p.tile, p.planes);
+    return VSOM_EUNSUPPORTED;
 }
 
 
@@ -314,49 +381,49 @@ int linear_bwd_weight_impl(const float* dY, long lddy, const float* X, long ldx,
                  "linear_bwd_weight: workspace too small (%zu < %zu)", ws_bytes,
                  vsom_linear_bwd_weight_workspace_bytes(M, N, K));
     VSOM_REQUIRE(aligned16(ws), VSOM_EALIGN, "linear_bwd_weight: workspace must be 16-byte aligned");
-    const TnPlan plan = bwd_weight_plan(M, N, K);
+    const TnPlan plan = bwd_weight_plan(M, N, K, gemm_mode(), g_wgrad_tiles.load(std::memory_order_relaxed));
     const int splits = plan.splits;
     const long wlen = pad4((long)N * K), blen = pad4(N);
     float* slab = static_cast<float*>(ws);
     const long a_last = a_seg ? (long)((M - 1) / a_seg) * a_stride + a_off + (M - 1) % a_seg : M - 1;
     const long ab = (a_last * lddy + N) * 4, bb = ((long)(M - 1) * ldx + K) * 4;
-    const bool tn_ok = plan.cfg != 0 && split_engine() && aligned16(dY) && aligned16(X) &&
-                       lddy % 4 == 0 && ldx % 4 == 0 && ab < 0xFFFF0000L && bb < 0xFFFF0000L &&
-                       (a_seg == 0 || (a_seg % 32 == 0 && M % a_seg == 0));
-    if (tn_ok) {
-        TnP t = {};
-        t.dY = dY; t.X = X; t.ldy = lddy; t.ldx = ldx; t.T = M; t.NO = N; t.KI = K;
-        t.ktiles_per_split = cdiv(cdiv(M, 32), splits);
-        t.a_seg = a_seg; t.a_stride = a_stride; t.a_off = a_off;
-        t.slab = slab; t.slab_stride = wlen + blen;
-        t.slab_bias = db ? slab + wlen : nullptr; t.slab_bias_stride = wlen + blen;
-        t.a_bytes = (unsigned)ab; t.b_bytes = (unsigned)bb;
-        const bool x3 = gemm_grad_products() == 3;
-        if (plan.cfg == 3) {
-            VSOM_LAUNCH((gemm_x6_tn_kernel<3, 1, 2, 6, 2, 2>), dim3((N / 192) * (K / 192) * splits), dim3(768), 0, stream, t);
-        } else if (plan.cfg == 1) {
-            if (x3) VSOM_LAUNCH((gemm_x6_tn_kernel<3, 1, 2, 2, 2>), dim3((N / 192) * (K / 64) * splits), dim3(256), 0, stream, t);
-            else VSOM_LAUNCH((gemm_x6_tn_kernel<3, 1, 2, 2, 3>), dim3((N / 192) * (K / 64) * splits), dim3(256), 0, stream, t);
-        } else {
-            if (x3) VSOM_LAUNCH((gemm_x6_tn_kernel<3, 1, 1, 3, 2>), dim3((N / 96) * (K / 96) * splits), dim3(192), 0, stream, t);
-            else VSOM_LAUNCH((gemm_x6_tn_kernel<3, 1, 1, 3, 3>), dim3((N / 96) * (K / 96) * splits), dim3(192), 0, stream, t);
-        }
-        const int rc = hip_status(hipGetLastError(), "gemm_x6_tn_kernel");
+    const bool vec = aligned16(dY) && aligned16(X) && lddy % 4 == 0 && ldx % 4 == 0 && ab < 0xFFFF0000L && bb < 0xFFFF0000L;
+    if (!bwd_weight_tiled(plan, gemm_mode(), vec, M, a_seg)) {
+        // GEMM rows = n, cols = k, reduction = m; both operands k-strided
+        GemmP g = {};
+        g.A = dY; g.lda = lddy; g.B = X; g.ldb = ldx;
+        g.M = N; g.N = K; g.K = M;
+        g.a_seg = a_seg; g.a_stride = a_stride; g.a_off = a_off;
+        g.slab = slab; g.slab_stride = wlen + blen;
+        g.slab_bias = db ? slab + wlen : nullptr; g.slab_bias_stride = wlen + blen;
+        int rc = launch_gemm(false, false, EPI_SLAB, g, splits, stream);
         if (rc) return rc;
-        return reduce_slabs2_internal(slab, wlen + blen, splits, dW, (long)N * K, db, wlen, db ? N : 0, stream);
+        // launch_gemm may have reduced the split count (canonical form): unused slabs were never written
+        const int used = cdiv(cdiv(M, 32), cdiv(cdiv(M, 32), splits));
+        return reduce_slabs2_internal(slab, wlen + blen, used, dW, (long)N * K, db, wlen, db ? N : 0, stream);
     }
-    // GEMM rows = n, cols = k, reduction = m; both operands k-strided
-    GemmP g = {};
-    g.A = dY; g.lda = lddy; g.B = X; g.ldb = ldx;
-    g.M = N; g.N = K; g.K = M;
-    g.a_seg = a_seg; g.a_stride = a_stride; g.a_off = a_off;
-    g.slab = slab; g.slab_stride = wlen + blen;
-    g.slab_bias = db ? slab + wlen : nullptr; g.slab_bias_stride = wlen + blen;
-    int rc = launch_gemm(false, false, EPI_SLAB, g, splits, stream);
+    TnP t = {};
+    t.dY = dY; t.X = X; t.ldy = lddy; t.ldx = ldx; t.T = M; t.NO = N; t.KI = K;
+    t.ktiles_per_split = cdiv(cdiv(M, 32), splits);
+    t.a_seg = a_seg; t.a_stride = a_stride; t.a_off = a_off;
+    t.slab = slab; t.slab_stride = wlen + blen;
+    t.slab_bias = db ? slab + wlen : nullptr; t.slab_bias_stride = wlen + blen;
+    t.a_bytes = (unsigned)ab; t.b_bytes = (unsigned)bb;
+    const dim3 grid((N / plan.rows) * (K / plan.cols) * splits), block(plan.threads);
+    const int planes = gemm_grad_products() == 3 ? 2 : 3;
+    switch (plan.tile * 4 + planes) {
+        case TN_192x192 * 4 + 2: VSOM_LAUNCH((gemm_x6_tn_kernel<3, 1, 2, 6, 2, 2>), grid, block, 0, stream, t); break;
+        case TN_192x64 * 4 + 2: VSOM_LAUNCH((gemm_x6_tn_kernel<3, 1, 2, 2, 2>), grid, block, 0, stream, t); break;
+        case TN_192x64 * 4 + 3: VSOM_LAUNCH((gemm_x6_tn_kernel<3, 1, 2, 2, 3>), grid, block, 0, stream, t); break;
+        case TN_96x96 * 4 + 2: VSOM_LAUNCH((gemm_x6_tn_kernel<3, 1, 1, 3, 2>), grid, block, 0, stream, t); break;
+        case TN_96x96 * 4 + 3: VSOM_LAUNCH((gemm_x6_tn_kernel<3, 1, 1, 3, 3>), grid, block, 0, stream, t); break;
+        default:
+            set_error("linear_bwd_weight: plan (tile %d, %d planes) has no kernel", plan.tile, planes);
+            return VSOM_EUNSUPPORTED;
+    }
+    const int rc = launch_status("gemm_x6_tn_kernel");
     if (rc) return rc;
-    // launch_gemm may have reduced the split count (canonical form): unused slabs were never written
-    const int used = cdiv(cdiv(M, 32), cdiv(cdiv(M, 32), splits));
-    return reduce_slabs2_internal(slab, wlen + blen, used, dW, (long)N * K, db, wlen, db ? N : 0, stream);
+    return reduce_slabs2_internal(slab, wlen + blen, splits, dW, (long)N * K, db, wlen, db ? N : 0, stream);
 }
 
 }  // namespace vsom
@@ -447,14 +514,14 @@ int vsom_linear_bwd_input_t(const float* dY, long lddy, const float* Wt, float* 
     return launch_gemm(true, true, EPI_NONE, g, 1, stream);
 }
 
-int vsom_linear_bwd_input_ln_supported(int M, int N, int K) {
-    // the column reduction of the one-call form must be the wide single-pass reducer that finish_many runs (>= 32 slabs)
-    return M > 0 && N > 0 && split_engine() && ln_fused_width(K) && ln_fused_tiles(M, K) >= 32;
+static LnPlan ln_fused_plan_now(int M, int N, int K) {
+    return ln_fused_plan(M, N, K, gemm_mode(), g_ln_tiles.load(std::memory_order_relaxed));
 }
 
+int vsom_linear_bwd_input_ln_supported(int M, int N, int K) { return ln_fused_plan_now(M, N, K).supported; }
+
 size_t vsom_linear_bwd_input_ln_partial_bytes(int M, int K) {
-    if (M <= 0 || !ln_fused_width(K)) return 0;
-    return (size_t)ln_fused_tiles(M, K) * 2 * (size_t)K * sizeof(float);
+    return (size_t)ln_fused_plan_now(M, 1, K).parts * 2 * (size_t)K * sizeof(float);       // whatever N, mode and hook
 }
 
 int vsom_linear_bwd_input_ln(const float* dY, long lddy, const float* Wt, int M, int N, int K, const float* X,
@@ -462,17 +529,18 @@ int vsom_linear_bwd_input_ln(const float* dY, long lddy, const float* Wt, int M,
                              float* dgamma, float* dbeta, void* ws, size_t ws_bytes, vsom_stream_t stream) {
     VSOM_REQUIRE(dgamma && dbeta, VSOM_EINVAL, "linear_bwd_input_ln: null pointer");
     float* part = static_cast<float*>(ws);
-    const int rc = linear_bwd_input_ln_launch(dY, lddy, Wt, M, N, K, X, mean, rstd, gamma, resid, dX, part, ws_bytes, stream);
+    const LnPlan p = ln_fused_plan_now(M, N, K);
+    const int rc = linear_bwd_input_ln_launch(dY, lddy, Wt, M, N, K, X, mean, rstd, gamma, resid, dX, part, ws_bytes, p, stream);
     if (rc) return rc;
     // same reducer, arguments and order as vsom_layernorm_bwd_finish_many on this job
-    return reduce_slabs2_internal(part, 2L * K, ln_fused_tiles(M, K), dgamma, K, dbeta, K, K, stream);
+    return reduce_slabs2_internal(part, 2L * K, p.parts, dgamma, K, dbeta, K, K, stream);
 }
 
 int vsom_linear_bwd_input_ln_partial(const float* dY, long lddy, const float* Wt, int M, int N, int K, const float* X,
                                      const float* mean, const float* rstd, const float* gamma, const float* resid,
                                      float* dX, void* part, size_t part_bytes, vsom_stream_t stream) {
     return linear_bwd_input_ln_launch(dY, lddy, Wt, M, N, K, X, mean, rstd, gamma, resid, dX, static_cast<float*>(part),
-                                      part_bytes, stream);
+                                      part_bytes, ln_fused_plan_now(M, N, K), stream);
 }
 
 int vsom_set_gemm_mode(int mode) {
@@ -495,9 +563,72 @@ int vsom_set_wgrad_tiles(int mode) {
     return VSOM_OK;
 }
 
+// The (layout, epilogue, GEMM shape, products, splits) of each entry point that is one launch_gemm call.
+static int describe_gemm(bool a_kc, bool b_kc, int epi, int M, int N, int K, bool vec, int products, int splits, char* out,
+                         size_t out_bytes) {
+    const bool fast = vec && gemm_vec_extents(a_kc, b_kc, M, N, K);
+    const GemmPlan p = gemm_plan(a_kc, b_kc, epi, M, N, K, fast, gemm_mode(), products, splits);
+    const int n = snprintf(out, out_bytes, "engine=%s tile=%dx64 planes=%d fast=%d threads=256 splits=%d workgroups=%d",
+                           p.engine == GEMM_ENGINE_X6 ? "x6" : "f32", p.tile_m, p.planes, (int)p.fast, p.splits, p.grid);
+    VSOM_REQUIRE(n > 0 && (size_t)n < out_bytes, VSOM_EINVAL, "describe_plan: buffer too small");
+    return VSOM_OK;
+}
+
+int vsom_describe_plan(int op, int M, int N, int K, int flags, char* out, size_t out_bytes) {
+    VSOM_REQUIRE(out && out_bytes > 0, VSOM_EINVAL, "describe_plan: null buffer");
+    out[0] = 0;
+    VSOM_REQUIRE(M > 0 && N > 0 && K > 0, VSOM_EINVAL, "describe_plan: non-positive shape %d %d %d", M, N, K);
+    const bool vec = flags & 1;
+    const int g3 = gemm_grad_products();
+    int n = 0;
+    switch (op) {
+        case VSOM_PLAN_LINEAR_FWD: return describe_gemm(true, true, EPI_BIAS, M, N, K, vec, 0, 1, out, out_bytes);
+        case VSOM_PLAN_LINEAR_GELU_FWD: return describe_gemm(true, true, EPI_BIAS_GELU, M, N, K, vec, 0, 1, out, out_bytes);
+        case VSOM_PLAN_LINEAR_RELU_FWD: return describe_gemm(true, true, EPI_BIAS_RELU, M, N, K, vec, 0, 1, out, out_bytes);
+        case VSOM_PLAN_LINEAR_RESIDUAL_FWD: return describe_gemm(true, true, EPI_BIAS_RES, M, N, K, vec, 0, 1, out, out_bytes);
+        // dX[M,K] = dY[M,N] W: the reduction runs over N
+        case VSOM_PLAN_LINEAR_BWD_INPUT: return describe_gemm(true, false, EPI_NONE, M, K, N, vec, 0, 1, out, out_bytes);
+        case VSOM_PLAN_LINEAR_BWD_INPUT_GELU: return describe_gemm(true, false, EPI_GELU_BWD, M, K, N, vec, 0, 1, out, out_bytes);
+        case VSOM_PLAN_LINEAR_BWD_INPUT_T: return describe_gemm(true, true, EPI_NONE, M, K, N, vec, g3, 1, out, out_bytes);
+        case VSOM_PLAN_LINEAR_BWD_INPUT_T_GELU: return describe_gemm(true, true, EPI_GELU_BWD, M, K, N, vec, g3, 1, out, out_bytes);
+        // (B, K, L): gW[K,L] reduces over the batch, gX[B,L] over the prototypes, the dots [B,K] over L
+        case VSOM_PLAN_SOM_BWD_GW: return describe_gemm(false, false, EPI_ROWAXPY, N, K, M, vec, g3, 1, out, out_bytes);
+        case VSOM_PLAN_SOM_BWD_GX: return describe_gemm(true, false, EPI_ROWAXPY, M, K, N, vec, g3, 1, out, out_bytes);
+        case VSOM_PLAN_BMU_COSINE_DOTS: return describe_gemm(true, true, EPI_SLAB, M, N, K, vec, 0, bmu_splits(M, N, K), out, out_bytes);
+        case VSOM_PLAN_LINEAR_BWD_WEIGHT: {
+            const TnPlan p = bwd_weight_plan(M, N, K, gemm_mode(), g_wgrad_tiles.load(std::memory_order_relaxed));
+            if (!bwd_weight_tiled(p, gemm_mode(), vec, M, 0))
+                return describe_gemm(false, false, EPI_SLAB, N, K, M, vec, 0, p.splits, out, out_bytes);
+            n = snprintf(out, out_bytes, "engine=x6_tn tile=%dx%d planes=%d fast=1 threads=%d splits=%d workgroups=%d", p.rows, p.cols,
+                         g3 == 3 ? 2 : 3, p.threads, p.splits, (N / p.rows) * (K / p.cols) * p.splits);
+            break;
+        }
+        case VSOM_PLAN_LINEAR_BWD_INPUT_LN: {
+            const LnPlan p = ln_fused_plan_now(M, N, K);
+            VSOM_REQUIRE(p.supported && vec, VSOM_EUNSUPPORTED, "describe_plan: linear_bwd_input_ln does not take M=%d N=%d K=%d", M, N, K);
+            n = snprintf(out, out_bytes, "engine=x6_ln tile=%dx%d planes=%d fast=1 threads=%d splits=1 workgroups=%d", p.rows, K, p.planes,
+                         p.threads, p.grid);
+            break;
+        }
+        case VSOM_PLAN_ATTENTION_BWD: {
+            static const char* const form[] = {"attn_two_launch", "attn_fused", "attn_shared", "attn_shared_bf16x3"};
+            const int plan = attn_bwd_plan_now(M, K);
+            VSOM_REQUIRE(plan >= 0, VSOM_EUNSUPPORTED, "describe_plan: attention head dim %d not supported", K);
+            n = snprintf(out, out_bytes, "engine=%s tile=16x16 planes=%d fast=1 threads=%d splits=1 workgroups=%d", form[plan],
+                         plan == 3 ? 2 : 0, attn_bwd_threads(M), N);
+            break;
+        }
+        default:
+            set_error("describe_plan: unknown op %d", op);
+            return VSOM_EINVAL;
+    }
+    VSOM_REQUIRE(n > 0 && (size_t)n < out_bytes, VSOM_EINVAL, "describe_plan: buffer too small");
+    return VSOM_OK;
+}
+
 size_t vsom_linear_bwd_weight_workspace_bytes(int M, int N, int K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
-    const int s = bwd_weight_plan(M, N, K).splits;
+    const int s = bwd_weight_plan(M, N, K, gemm_mode(), g_wgrad_tiles.load(std::memory_order_relaxed)).splits;
     return (size_t)s * (size_t)(pad4((long)N * K) + pad4(N)) * sizeof(float);
 }
 

@@ -443,7 +443,7 @@ int launch_assign(const AssignP& p, int G, hipStream_t stream) {
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, KM_LDS + 2 * KM_MAX_K * 4);
     VSOM_REQUIRE(attr_rc == 0, VSOM_EUNSUPPORTED, "kmeans_assign: cannot reserve %d bytes of LDS", KM_LDS);
     VSOM_LAUNCH((kmeans_assign_kernel<KC, VEC>), dim3(G), dim3(KM_THREADS), lds, stream, p);
-    VSOM_LAUNCH_CHECK("kmeans_assign_kernel");
+    return launch_status("kmeans_assign_kernel");
 }
 
 // centre tile width: the largest multiple of 64*VEC with KC*dt floats in KM_LDS, not wider than D needs
@@ -512,7 +512,7 @@ int vsom_kmeans_update(const float* centers_old, float* centers_new, long N, int
     VSOM_LAUNCH(kmeans_centres_kernel, dim3(P), dim3(KM_RED_THREADS), 0, stream, w.slabs, G, k, D, w.sums, counts, w.amax, centers_old,
                 centers_new, w.part);
     VSOM_LAUNCH(kmeans_shift_kernel, dim3(1), dim3(KM_RED_THREADS), 0, stream, w.part, P, status);
-    VSOM_LAUNCH_CHECK("kmeans_update");
+    return launch_status("kmeans_update");
 }
 
 int vsom_kmeans_relocate(const float* X, long ldx, long N, int D, int k, const int64_t* labels, const int64_t* moves,
@@ -533,7 +533,7 @@ int vsom_kmeans_relocate(const float* X, long ldx, long N, int D, int k, const i
     VSOM_LAUNCH(kmeans_centres_kernel, dim3(P), dim3(KM_RED_THREADS), 0, stream, (const float*)nullptr, 0, k, D, w.sums, counts, w.amax,
                 centers_old, centers_new, w.part);
     VSOM_LAUNCH(kmeans_shift_kernel, dim3(1), dim3(KM_RED_THREADS), 0, stream, w.part, P, status);
-    VSOM_LAUNCH_CHECK("kmeans_relocate");
+    return launch_status("kmeans_relocate");
 }
 
 int vsom_kmeanspp_dist(const float* X, long ldx, long N, int D, const int64_t* candidates, int n_candidates,
@@ -545,7 +545,7 @@ int vsom_kmeanspp_dist(const float* X, long ldx, long N, int D, const int64_t* c
     VSOM_LAUNCH(kmeanspp_dist_kernel, dim3(cdiv(N, 4)), dim3(256), 0, stream, X, ldx, N, D, candidates, n_candidates, closest,
                 dist);
     VSOM_LAUNCH(kmeanspp_pot_kernel, dim3(n_candidates), dim3(KM_RED_THREADS), 0, stream, dist, N, pots);
-    VSOM_LAUNCH_CHECK("kmeanspp_dist");
+    return launch_status("kmeanspp_dist");
 }
 
 int vsom_kmeans_colvar(const float* X, long ldx, long N, int D, int k, double* out, void* ws, size_t ws_bytes,
@@ -559,7 +559,7 @@ int vsom_kmeans_colvar(const float* X, long ldx, long N, int D, int k, double* o
     double* part = reinterpret_cast<double*>(w.slabs);
     VSOM_LAUNCH(kmeans_colstats_kernel, dim3(cdiv(D, 256), KM_COLVAR_CHUNKS), dim3(256), 0, stream, X, ldx, N, D, part);
     VSOM_LAUNCH(kmeans_colvar_kernel, dim3(1), dim3(KM_RED_THREADS), 0, stream, part, KM_COLVAR_CHUNKS, N, D, out);
-    VSOM_LAUNCH_CHECK("kmeans_colvar");
+    return launch_status("kmeans_colvar");
 }
 
 }  // extern "C"

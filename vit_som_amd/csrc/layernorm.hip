@@ -259,13 +259,13 @@ int vsom_layernorm_fwd(const float* X, const float* gamma, const float* beta, fl
             case 3: VSOM_LAUNCH(layernorm_fwd_v4_kernel<3>, g16, block, 0, stream, X, gamma, beta, Y, mean, rstd, rows, cols, eps); break;
             default: VSOM_LAUNCH(layernorm_fwd_v4_kernel<4>, g16, block, 0, stream, X, gamma, beta, Y, mean, rstd, rows, cols, eps); break;
         }
-        VSOM_LAUNCH_CHECK("layernorm_fwd_v4_kernel");
+        return launch_status("layernorm_fwd_v4_kernel");
     }
     if (cols <= 256)
         VSOM_LAUNCH(layernorm_fwd_kernel<4>, grid, block, 0, stream, X, gamma, beta, Y, mean, rstd, rows, cols, eps);
     else
         VSOM_LAUNCH(layernorm_fwd_kernel<16>, grid, block, 0, stream, X, gamma, beta, Y, mean, rstd, rows, cols, eps);
-    VSOM_LAUNCH_CHECK("layernorm_fwd_kernel");
+    return launch_status("layernorm_fwd_kernel");
 }
 
 size_t vsom_layernorm_bwd_workspace_bytes(int rows, int cols) {
@@ -330,7 +330,7 @@ int vsom_layernorm_bwd_finish_many(const int64_t* jobs_dev, int first, int count
     VSOM_REQUIRE(jobs_dev && first >= 0 && count >= 0 && max_cols > 0 && 2L * max_cols <= 4096, VSOM_EINVAL, "layernorm_bwd_finish_many: bad arguments");
     if (count == 0) return VSOM_OK;
     VSOM_LAUNCH(ln_finish_many_kernel, dim3(2 * cdiv(max_cols, 64), count), dim3(1024), 0, stream, jobs_dev + (long)first * VSOM_LN_JOB_WORDS);
-    VSOM_LAUNCH_CHECK("ln_finish_many_kernel");
+    return launch_status("ln_finish_many_kernel");
 }
 
 }  // extern "C"

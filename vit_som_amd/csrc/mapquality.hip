@@ -258,7 +258,7 @@ int vsom_map_stats(const float* dist, const int64_t* bmu, long B, int K, const f
         VSOM_LAUNCH(vsom::map_stats_kernel<false>, grid, dim3(256), 0, stream, dist, bmu, B, K, grid_positions, adj_r2, first_ordinal, h,
                     q, t, nearest, bad, second);
     }
-    VSOM_LAUNCH_CHECK("map_stats_kernel");
+    return vsom::launch_status("map_stats_kernel");
 }
 
 int vsom_umatrix(const float* W, int K, int L, const float* grid_positions, float adj_r2, int distance, int* nbr_idx,
@@ -278,7 +278,7 @@ int vsom_umatrix(const float* W, int K, int L, const float* grid_positions, floa
         if (vec) VSOM_UMATRIX(VSOM_DIST_MANHATTAN, true); else VSOM_UMATRIX(VSOM_DIST_MANHATTAN, false);
     }
 #undef VSOM_UMATRIX
-    VSOM_LAUNCH_CHECK("umatrix_kernel");
+    return vsom::launch_status("umatrix_kernel");
 }
 
 }  // extern "C"

@@ -134,7 +134,7 @@ int vsom_proto_mosaic(const float* pred, int chunk, int n, int p, int C, float* 
         VSOM_LAUNCH(vsom::proto_mosaic_kernel<false>, dim3(chunk), dim3(256), 0, stream, pred, n, g, p, C, images, canvas, k0, cols,
                     rows, gap);
     }
-    VSOM_LAUNCH_CHECK("proto_mosaic_kernel");
+    return vsom::launch_status("proto_mosaic_kernel");
 }
 
 int vsom_last_label(const int64_t* bmu, const int64_t* label, long n, long first_ordinal, int K, unsigned long long* cells,
@@ -145,7 +145,7 @@ int vsom_last_label(const int64_t* bmu, const int64_t* label, long n, long first
     if (n == 0) return VSOM_OK;
     VSOM_LAUNCH(vsom::last_label_kernel, dim3(vsom::grid_1d(n, 256, 2048)), dim3(256), 0, stream, bmu, label, n, first_ordinal, K,
                 cells, out_of_range);
-    VSOM_LAUNCH_CHECK("last_label_kernel");
+    return vsom::launch_status("last_label_kernel");
 }
 
 }  // extern "C"

@@ -250,14 +250,14 @@ int vsom_fill(float* p, long n, float value, vsom_stream_t stream) {
     VSOM_REQUIRE(p && n >= 0, VSOM_EINVAL, "fill: bad arguments");
     if (n == 0) return VSOM_OK;
     VSOM_LAUNCH(fill_kernel, dim3(grid_for(n, 1024, 4096)), dim3(256), 0, stream, p, n, value);
-    VSOM_LAUNCH_CHECK("fill_kernel");
+    return launch_status("fill_kernel");
 }
 
 int vsom_scale_by(float* p, long n, const float* scale_dev, vsom_stream_t stream) {
     VSOM_REQUIRE(p && scale_dev && n >= 0, VSOM_EINVAL, "scale_by: bad arguments");
     if (n == 0) return VSOM_OK;
     VSOM_LAUNCH(scale_by_kernel, dim3(grid_for(n, 1024, 4096)), dim3(256), 0, stream, p, n, scale_dev);
-    VSOM_LAUNCH_CHECK("scale_by_kernel");
+    return launch_status("scale_by_kernel");
 }
 
 int vsom_scaled_mul(float* out, const float* a, const float* b, long n, const float* scale_dev, float factor,
@@ -265,13 +265,13 @@ int vsom_scaled_mul(float* out, const float* a, const float* b, long n, const fl
     VSOM_REQUIRE(out && a && n >= 0, VSOM_EINVAL, "scaled_mul: bad arguments");
     if (n == 0) return VSOM_OK;
     VSOM_LAUNCH(scaled_mul_kernel, dim3(grid_for(n, 1024, 4096)), dim3(256), 0, stream, out, a, b, n, scale_dev, factor);
-    VSOM_LAUNCH_CHECK("scaled_mul_kernel");
+    return launch_status("scaled_mul_kernel");
 }
 
 int vsom_lincomb2(float* out, const float* a, float ca, const float* b, float cb, int64_t* counter, vsom_stream_t stream) {
     VSOM_REQUIRE(out && a && b, VSOM_EINVAL, "lincomb2: null pointer");
     VSOM_LAUNCH(lincomb2_kernel, dim3(1), dim3(64), 0, stream, out, a, ca, b, cb, reinterpret_cast<long long*>(counter));
-    VSOM_LAUNCH_CHECK("lincomb2_kernel");
+    return launch_status("lincomb2_kernel");
 }
 
 int vsom_loss_parts(float* parts, const float* main_sum, float main_scale, const float* som_sum, float som_coef, float som_scale,
@@ -279,7 +279,7 @@ int vsom_loss_parts(float* parts, const float* main_sum, float main_scale, const
     VSOM_REQUIRE(parts && main_sum && som_sum, VSOM_EINVAL, "loss_parts: null pointer");
     VSOM_LAUNCH(loss_parts_kernel, dim3(1), dim3(64), 0, stream, parts, main_sum, main_scale, som_sum, som_coef, som_scale,
                        reinterpret_cast<long long*>(counter));
-    VSOM_LAUNCH_CHECK("loss_parts_kernel");
+    return launch_status("loss_parts_kernel");
 }
 
 int vsom_transpose_many(const float* src_base, float* dst_base, const long long* table, int count, int max_rows,
@@ -289,7 +289,7 @@ int vsom_transpose_many(const float* src_base, float* dst_base, const long long*
     VSOM_REQUIRE(count <= 65535, VSOM_EINVAL, "transpose_many: more than 65535 tensors");
     dim3 grid(cdiv(max_rows, 32) * cdiv(max_cols, 32), count);
     VSOM_LAUNCH(transpose_many_kernel, grid, dim3(256), 0, stream, src_base, dst_base, table);
-    VSOM_LAUNCH_CHECK("transpose_many_kernel");
+    return launch_status("transpose_many_kernel");
 }
 
 int vsom_patch_embed_fwd(const float* img, const float* Wpe, const float* bpe, const float* pos,
@@ -311,7 +311,7 @@ int vsom_patch_embed_fwd(const float* img, const float* Wpe, const float* bpe, c
     rc = launch_gemm(true, true, EPI_BIAS_RES, q, 1, stream);
     if (rc) return rc;
     VSOM_LAUNCH(cls_rows_kernel, dim3(cdiv((long)B * E, 256)), dim3(256), 0, stream, cls_token, pos, tokens, B, Ntok, E);
-    VSOM_LAUNCH_CHECK("cls_rows_kernel");
+    return launch_status("cls_rows_kernel");
 }
 
 size_t vsom_patch_embed_bwd_workspace_bytes(int B, int C, int S, int p, int E) {
@@ -332,7 +332,7 @@ int vsom_patch_embed_bwd(const float* dtokens, const float* xp_ws, float* dWpe, 
     int rc = linear_bwd_weight_impl(dtokens, E, xp_ws, pd, dWpe, dbpe, M, E, pd, n, Ntok, 1, ws, ws_bytes, stream);
     if (rc) return rc;
     VSOM_LAUNCH(cls_grad_kernel, dim3(cdiv(E, 32)), dim3(256), 0, stream, dtokens, dcls_token, B, Ntok, E);
-    VSOM_LAUNCH_CHECK("cls_grad_kernel");
+    return launch_status("cls_grad_kernel");
 }
 
 size_t vsom_l1_unpatchify_workspace_bytes(int B, int C, int S, int p) {
@@ -397,7 +397,7 @@ int vsom_adamw_step(float* p, const float* g, float* m, float* v, const float* w
     const long n4 = n / 4;
     VSOM_LAUNCH(adamw_kernel, dim3(grid_for(n4, 256, 8192)), dim3(256), 0, stream, p, g, m, v, wd_per_chunk, n4,
                 adamw_constants(lr, beta1, beta2, eps, step, grad_scale, adamw));
-    VSOM_LAUNCH_CHECK("adamw_kernel");
+    return launch_status("adamw_kernel");
 }
 
 }  // extern "C"
@@ -445,13 +445,13 @@ int vsom_contingency(const int64_t* a, const int64_t* b, long n, int na, int nb,
     if (n == 0) return VSOM_OK;
     VSOM_LAUNCH(vsom::contingency_kernel, dim3(vsom::grid_for(n, 256, 2048)), dim3(256), 0, stream, a, b, n, na, nb,
                        table, out_of_range);
-    VSOM_LAUNCH_CHECK("contingency_kernel");
+    return launch_status("contingency_kernel");
 }
 
 int vsom_argmax_rows(const float* X, long ldx, int rows, int cols, int64_t* out, vsom_stream_t stream) {
     VSOM_REQUIRE(X && out && rows > 0 && cols > 0 && ldx >= cols, VSOM_EINVAL, "argmax_rows: bad arguments");
     VSOM_LAUNCH(vsom::argmax_rows_kernel, dim3(vsom::cdiv(rows, 4)), dim3(256), 0, stream, X, ldx, rows, cols, out);
-    VSOM_LAUNCH_CHECK("argmax_rows_kernel");
+    return launch_status("argmax_rows_kernel");
 }
 
 }  // extern "C"

@@ -108,8 +108,9 @@ __global__ __launch_bounds__(256) void bmu_finalize_kernel(const float* __restri
     }
 }
 
-static int bmu_splits(int B, int K, int L) {
-    return choose_splits(cdiv(B, 128) * cdiv(K, 64), cdiv(L, 32), 32, true);
+// reduction splits of the X.W^T launch (vsom_bmu_cosine_dots); its tile count depends on neither alignment nor GEMM mode
+int bmu_splits(int B, int K, int L) {
+    return choose_splits(gemm_plan(true, true, EPI_SLAB, B, K, L, true, gemm_mode(), 0, 1).tiles, cdiv(L, 32), 32, true);
 }
 
 // ------------------------------------------------------------------ neighbourhood / loss / coefficients
@@ -223,12 +224,12 @@ int bmu_finalize_plain(const float* slab, long slab_stride, int nslabs, float* d
                        hipStream_t stream) {
     VSOM_LAUNCH(bmu_finalize_kernel, dim3(B), dim3(256), 0, stream, slab, slab_stride, nslabs, (const float*)nullptr,
                        (const float*)nullptr, dist, bmu, K, 2);
-    VSOM_LAUNCH_CHECK("bmu_finalize_kernel");
+    return launch_status("bmu_finalize_kernel");
 }
 
 int sum_partials(const float* part, int n, float* out, hipStream_t stream) {
     VSOM_LAUNCH(sum_partials_kernel, dim3(1), dim3(256), 0, stream, part, n, out);
-    VSOM_LAUNCH_CHECK("sum_partials_kernel");
+    return launch_status("sum_partials_kernel");
 }
 
 }  // namespace vsom
@@ -243,11 +244,11 @@ int vsom_row_inv_norm(const float* X, long ldx, int rows, int cols, float eps, f
     const int vec = aligned16(X) && (ldx % 4 == 0);
     if (vec && cols % 4 == 0 && cols >= 4096) {
         VSOM_LAUNCH(row_inv_norm_wide_kernel, dim3(rows), dim3(256), 0, stream, X, ldx, cols, eps, inv_norm, 0);
-        VSOM_LAUNCH_CHECK("row_inv_norm_wide_kernel");
+        return launch_status("row_inv_norm_wide_kernel");
     }
     VSOM_LAUNCH(row_inv_norm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, stream, X, ldx, rows, cols, eps,
                        inv_norm, vec, 0);
-    VSOM_LAUNCH_CHECK("row_inv_norm_kernel");
+    return launch_status("row_inv_norm_kernel");
 }
 
 int vsom_row_sqnorm(const float* X, long ldx, int rows, int cols, float* sqnorm, vsom_stream_t stream) {
@@ -255,11 +256,11 @@ int vsom_row_sqnorm(const float* X, long ldx, int rows, int cols, float* sqnorm,
     const int vec = aligned16(X) && (ldx % 4 == 0);
     if (vec && cols % 4 == 0 && cols >= 4096) {
         VSOM_LAUNCH(row_inv_norm_wide_kernel, dim3(rows), dim3(256), 0, stream, X, ldx, cols, 0.f, sqnorm, 1);
-        VSOM_LAUNCH_CHECK("row_inv_norm_wide_kernel");
+        return launch_status("row_inv_norm_wide_kernel");
     }
     VSOM_LAUNCH(row_inv_norm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, stream, X, ldx, rows, cols, 0.f, sqnorm,
                        vec, 1);
-    VSOM_LAUNCH_CHECK("row_inv_norm_kernel");
+    return launch_status("row_inv_norm_kernel");
 }
 
 size_t vsom_bmu_cosine_workspace_bytes(int B, int K, int L) {
@@ -288,7 +289,7 @@ int vsom_bmu_cosine_finalize(const void* ws, size_t ws_bytes, const float* inv_n
                  "bmu_cosine_finalize: workspace too small");
     VSOM_LAUNCH(bmu_finalize_kernel, dim3(B), dim3(256), 0, stream, (const float*)ws, (long)B * K,
                        bmu_splits(B, K, L), inv_nx, inv_nw, dist, bmu, K, 0);
-    VSOM_LAUNCH_CHECK("bmu_finalize_kernel");
+    return launch_status("bmu_finalize_kernel");
 }
 
 int vsom_bmu_euclid_fwd(const float* X, long ldx, const float* W, const float* sq_x, const float* sq_w, float* dist,
@@ -298,7 +299,7 @@ int vsom_bmu_euclid_fwd(const float* X, long ldx, const float* W, const float* s
     if (rc) return rc;
     VSOM_LAUNCH(bmu_finalize_kernel, dim3(B), dim3(256), 0, stream, (const float*)ws, (long)B * K,
                        bmu_splits(B, K, L), sq_x, sq_w, dist, bmu, K, 1);
-    VSOM_LAUNCH_CHECK("bmu_finalize_kernel");
+    return launch_status("bmu_finalize_kernel");
 }
 
 int vsom_bmu_cosine_fwd(const float* X, long ldx, const float* W, const float* inv_nx, const float* inv_nw,

@@ -243,7 +243,7 @@ int vsom_som_bwd_manhattan(const float* X, long ldx, const float* W, const float
     if (rc) return rc;
     VSOM_LAUNCH(l1_bwd_x_kernel, dim3(cdiv(B, 64) * cdiv(L, 64)), dim3(256), 0, stream, X, ldx, W, coef, gX, ldgx,
                        accumulate_gx, B, K, L, vw, vc);
-    VSOM_LAUNCH_CHECK("l1_bwd_x_kernel");
+    return launch_status("l1_bwd_x_kernel");
 }
 
 }  // extern "C"

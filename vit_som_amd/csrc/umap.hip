@@ -376,7 +376,7 @@ int vsom_umap_knn(const float* X, long ldx, long N, int D, int k, int metric, in
     }
     VSOM_LAUNCH(umap_knn_merge_kernel, dim3(cdiv(N, KNN_MERGE_ROWS)), dim3(KNN_MERGE_ROWS * 64), 0, stream,
                 (const float*)w.cand_d, (const int*)w.cand_i, (int)N, k, pl.chunks, knn_idx, knn_dist);
-    VSOM_LAUNCH_CHECK("umap_knn");
+    return launch_status("umap_knn");
 }
 
 long vsom_umap_neg_sample(uint64_t seed, int epoch, long edge, long p, long N) {
@@ -407,7 +407,7 @@ int vsom_umap_epoch(const int64_t* indptr, const int64_t* indices, const double*
         case 3: VSOM_LAUNCH(umap_epoch_kernel<3>, grid, dim3(EPOCH_THREADS), 0, stream, p); break;
         default: VSOM_LAUNCH(umap_epoch_kernel<4>, grid, dim3(EPOCH_THREADS), 0, stream, p); break;
     }
-    VSOM_LAUNCH_CHECK("umap_epoch");
+    return launch_status("umap_epoch");
 }
 
 }  // extern "C"

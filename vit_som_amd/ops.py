@@ -599,8 +599,10 @@ def fill(t, value):
 
 
 def set_attention_fused(fused):
-    """Test / measurement hook: False (0) runs the short-sequence attention backward as two launches, True (1) is the
-    default (one launch, scores shared between its phases where the shape allows), 2 = one launch with recomputed scores."""
+    """Test / measurement hook (include/vitsom_hip.h, vsom_set_attention_fused): False (0) runs the short-sequence attention
+    backward as two launches, True (1) is the default (one launch, scores shared between its phases where the shape allows;
+    at hd = 64 in the default GEMM mode its products run on the two-piece bf16 split), 2 = one launch with recomputed
+    scores, 3 = 1 with fp32 products in every GEMM mode."""
     global _attention_fused
     check(lib.vsom_set_attention_fused(int(fused)), "vsom_set_attention_fused")
     _attention_fused = int(fused)
