@@ -210,7 +210,8 @@ int vsom_attention_bwd(const float* qkv, const float* out, const float* dout, co
                        float* dqkv, float* delta_ws, int B, int N, int H, int hd,
                        vsom_stream_t stream);
 /* probs[B,H,N,N] = softmax(q k^T * hd^-0.5) -- the attention maps of `return_attn=True` (vit.py:33-34,41-42), formed
- * from qkv and the lse the forward saved (the fused kernels never materialise them).  Visualisation path only. */
+ * from qkv (the fused kernels never materialise them); each row is normalised by its own scores, `lse` must be a valid
+ * pointer but is not read.  Visualisation path only. */
 int vsom_attention_probs(const float* qkv, const float* lse, float* probs, int B, int N, int H, int hd,
                          vsom_stream_t stream);
 /* test hook: 0 = run the short-sequence backward as two launches (dQ, then dK/dV), 1 = one launch whose phases share
@@ -253,7 +254,10 @@ int vsom_bmu_cosine_dots(const float* X, long ldx, const float* W, int B, int K,
 int vsom_bmu_cosine_finalize(const void* ws, size_t ws_bytes, const float* inv_nx, const float* inv_nw,
                              float* dist, int64_t* bmu, int B, int K, int L, vsom_stream_t stream);
 /* Best-matching-unit search, euclidean: dist = torch.cdist(X, W, p=2) in its matmul form
- * sqrt(clamp_min(|x|^2 + |w|^2 - 2 x.w, 1e-30)) -- som_layer.py:117-118; same workspace as cosine. */
+ * sqrt(|x|^2 + |w|^2 - 2 x.w) (torch.cdist's matmul form) -- som_layer.py:117-118; same workspace as cosine.  A squared
+ * distance at or below 2^-20 (|x|^2 + |w|^2) -- the rounding noise of this form -- is reported as exactly 0, and the
+ * SOM backward gives the subgradient 0 there (torch's at d == 0): a sample within ~1e-3 sqrt(|x|^2 + |w|^2) of a prototype
+ * neither pulls nor is pulled by it, where torch's clamp_min(1e-30) would return noise or 1e-15.  NaN stays NaN. */
 int vsom_bmu_euclid_fwd(const float* X, long ldx, const float* W, const float* sq_x, const float* sq_w,
                         float* dist, int64_t* bmu, int B, int K, int L, void* ws, size_t ws_bytes,
                         vsom_stream_t stream);

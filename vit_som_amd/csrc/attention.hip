@@ -156,6 +156,43 @@ __device__ __forceinline__ f32x4 score_x3(const SplitFrag& a, const SplitFrag& b
     }
     return acc;
 }
+// The score product q . k itself takes a THIRD piece of both operands and six products (hi + lo + rest is the fp32 value
+// exactly; what is dropped is 2^-24 of a product, fp32's own rounding): the score goes through an exponential, and one
+// that is off by 2^-17 |s| makes P wrong by that much relatively -- nothing at |s| ~ 5, 1e-3 on the saturated rows
+// (|s| ~ 150) of a trained model.  dP, and the three accumulations, stay on two pieces: their error is relative to the
+// value, not amplified.  (+3 us on the 64 us launch at B 512, N 65; two pieces with the same normalisation still miss by
+// 1e-4 on saturated rows.)
+struct SplitFrag3 { abf16x8 hi[2], lo[2], rest[2]; };
+__device__ __forceinline__ void split_frag3(const float (&f)[16], SplitFrag3& o) {
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        float v[8], w[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = f[8 * m + j];
+        split8(v, o.hi[m], o.lo[m]);
+        const abf16x8 h = o.hi[m], l = o.lo[m];
+        abf16x8 t;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { w[j] = (v[j] - (float)h[j]) - (float)l[j]; t[j] = (__bf16)w[j]; }
+        o.rest[m] = t;
+    }
+}
+__device__ __forceinline__ f32x4 score_x6(const SplitFrag3& a, const SplitFrag3& b) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.rest[m], b.hi[m], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi[m], b.rest[m], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.lo[m], b.lo[m], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.lo[m], b.hi[m], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi[m], b.lo[m], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi[m], b.hi[m], acc, 0, 0, 0);
+    }
+    return acc;
+}
+typedef SplitFrag3 ScoreFrag;
+__device__ __forceinline__ void split_score(const float (&f)[16], ScoreFrag& o) { split_frag3(f, o); }
+__device__ __forceinline__ f32x4 score_qk(const ScoreFrag& a, const ScoreFrag& b) { return score_x6(a, b); }
 // Cross-lane reductions without the LDS crossbar (ds_bpermute: an LDS instruction and its latency per step; these
 // sit on the kernels' serial chains).  Over the 4 lane groups (l >> 4): v_permlane16_swap / v_permlane32_swap
 // (gfx950) of two copies of v leave the even and the odd partner in the two results; within a group of 16
@@ -1100,8 +1137,9 @@ __global__ __launch_bounds__(256) void attn_bwd_shared_kernel(const float* __res
         if (wave == 0 && lane == 0) { delta[srow0] = D0; Es[0] = D0; }
     }
     f32x4 pT[4], dsT[4];
-    SplitFrag qs, dos;
-    if constexpr (BF16X3 && HDP == 64) { split_frag(qf, qs); split_frag(dof, dos); }
+    ScoreFrag qs;
+    SplitFrag dos;
+    if constexpr (BF16X3 && HDP == 64) { split_score(qf, qs); split_frag(dof, dos); }
     {
         const int query = own;
         const bool qok = ook;
@@ -1112,12 +1150,18 @@ __global__ __launch_bounds__(256) void attn_bwd_shared_kernel(const float* __res
         if constexpr (BF16X3 && HDP == 64) {
             // D_i = dO_i . O_i = sum_j p_ij dP_ij: taken from the blocks the wave forms anyway, so the O rows are never read
             // (an eighth of the kernel's HBM traffic).  All tiles' P and dP first, then D, then dS and the accumulation.
-            float s0 = 0.f, dp0 = 0.f, p0 = 0.f, dsum = 0.f;
+            // The row's probabilities are normalised by the kernel's OWN scores (maximum and sum over the row, which the
+            // wave holds whole), not by the forward's log-sum-exp: exp(s - lse) with a split-rounded s is off by the score's
+            // error, and D = sum_j p_ij dP_ij then no longer cancels dP on a saturated row -- p (dP - D) came out at
+            // 1e-5 |dP| instead of 0, in front of the largest key of the row.  Normalised this way sum_j p_ij = 1 and
+            // sum_j dS_ij = 0 hold to rounding whatever the scores' precision.  (Rows 1 .. N - 1 of the EXTRA form and all
+            // rows otherwise.  Token 0 as a QUERY -- tok0_dq_partial, p0k below -- keeps exact-f32 scores against the
+            // forward's lse, which is the fp32 kernels' form and needs no cure.)
+            float s0 = 0.f, dp0 = 0.f, p0 = 0.f, dsum = 0.f, mx = -INFINITY, z = 0.f;
             if (EXTRA) {                                               // token 0 as a key
                 s0 = frag_dot_row<HDP>(qf, Ks, qp) * scale;
                 dp0 = frag_dot_row<HDP>(dof, Vs, qp);
-                p0 = __expf(s0 - lq);
-                if (qp == 0) dsum = p0 * dp0;                          // (the four lane groups hold the same p0, dp0: counted once)
+                mx = s0;
             }
             f32x4 dpT[4];
 #pragma unroll
@@ -1126,21 +1170,46 @@ __global__ __launch_bounds__(256) void attn_bwd_shared_kernel(const float* __res
                     float kf[16], vf[16];
                     load_frag_lds<HDP>(kf, Ks, tok<EXTRA>(t, 0) + r, qp);
                     load_frag_lds<HDP>(vf, Vs, tok<EXTRA>(t, 0) + r, qp);
-                    SplitFrag ka, va;
-                    split_frag(kf, ka);
+                    ScoreFrag ka;
+                    SplitFrag va;
+                    split_score(kf, ka);
                     split_frag(vf, va);
-                    const f32x4 sc = score_x3(ka, qs);
+                    const f32x4 sc = score_qk(ka, qs);
                     dpT[t] = score_x3(va, dos);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int key = tok<EXTRA>(t, 4 * qp + e);
-                        const float p = (EXTRA || (key < N && qok)) ? __expf(sc[e] * scale - lq) : 0.f;
+                        pT[t][e] = (EXTRA || key < N) ? sc[e] * scale : -INFINITY;
+                        mx = fmaxf(mx, pT[t][e]);
+                    }
+                }
+            }
+            mx = group_max(mx);                                        // (a live row has a live key: finite)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                if (t < ntile) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float p = qok ? __expf(pT[t][e] - mx) : 0.f;
                         pT[t][e] = p;
+                        z += p;
                         dsum = fmaf(p, dpT[t][e], dsum);
                     }
                 }
             }
-            const float D = group_sum(dsum);
+            z = group_sum(z);
+            dsum = group_sum(dsum);
+            if (EXTRA) {                                               // (the four lane groups hold the same p0, dp0: counted once)
+                p0 = qok ? __expf(s0 - mx) : 0.f;
+                z += p0;
+                dsum = fmaf(p0, dp0, dsum);
+            }
+            const float inv = qok ? 1.0f / z : 0.f;
+            p0 *= inv;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (t < ntile) pT[t] *= inv;
+            const float D = dsum * inv;
             if (qp == 0 && qok) { delta[srow0 + query] = D; Es[query] = D; }
             if (EXTRA) axpy_row<HDP>(dq, p0 * (dp0 - D) * scale, Ks, qp);
 #pragma unroll
@@ -1376,21 +1445,40 @@ static int launch_bwd(const float* qkv, const float* out, const float* dout, con
 
 
 // ------------------------------------------------------------------ attention maps (return_attn=True, vit.py:33-34,41-42)
-// probs[b,h,i,j] = exp(scale * q_i . k_j - lse[b,h,i]) from the qkv buffer and the log-sum-exp the forward saved: the
-// softmax probabilities the fused kernels never write.  Visualisation path only (tools/evaluation.py); plain VALU.
-__global__ __launch_bounds__(256) void attn_probs_kernel(const float* __restrict__ qkv, const float* __restrict__ lse,
-                                                         float* __restrict__ probs, int N, int H, int hd, float scale) {
+// probs[b,h,i,:] = softmax_j(scale * q_i . k_j): the probabilities the fused kernels never write.  One wave per query row,
+// the scores parked in the output row (every lane re-reads only what it wrote), then the row's own maximum and sum.  The
+// log-sum-exp the forward saved is no longer read: exp(s - lse) carries the rounding of s itself -- this dot product and
+// the forward's run in different orders and differ by an ulp or two of |s| -- so a saturated row came out at
+// 1 +- 3e-5 and did not sum to 1; normalised by its own scores the dominant entry is exp(0) / sum.
+// Visualisation path only (tools/evaluation.py); plain VALU.
+__global__ __launch_bounds__(256) void attn_probs_kernel(const float* __restrict__ qkv, float* __restrict__ probs, int N, int H,
+                                                         int hd, float scale) {
     const int bh = blockIdx.x, b = bh / H, h = bh % H;
     const int E3 = 3 * H * hd;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float* q0 = qkv + (long)b * N * E3 + h * hd;
     const float* k0 = q0 + H * hd;
-    for (long idx = (long)blockIdx.y * 256 + threadIdx.x; idx < (long)N * N; idx += (long)gridDim.y * 256) {
-        const int i = (int)(idx / N), j = (int)(idx % N);
+    for (int i = blockIdx.y * 4 + wave; i < N; i += gridDim.y * 4) {       // i is uniform in a wave: the shuffles are whole
         const float* q = q0 + (long)i * E3;
-        const float* k = k0 + (long)j * E3;
-        float s = 0.f;
-        for (int d = 0; d < hd; ++d) s = fmaf(q[d], k[d], s);
-        probs[((long)bh * N + i) * N + j] = __expf(s * scale - lse[(long)bh * N + i]);
+        float* p = probs + ((long)bh * N + i) * N;
+        float m = -INFINITY;
+        for (int j = lane; j < N; j += 64) {
+            const float* k = k0 + (long)j * E3;
+            float s = 0.f;
+            for (int d = 0; d < hd; ++d) s = fmaf(q[d], k[d], s);
+            s *= scale;
+            p[j] = s;
+            m = fmaxf(m, s);
+        }
+        m = wave_max(m);
+        float z = 0.f;
+        for (int j = lane; j < N; j += 64) {
+            const float e = __expf(p[j] - m);
+            p[j] = e;
+            z += e;
+        }
+        const float inv = 1.0f / wave_sum(z);
+        for (int j = lane; j < N; j += 64) p[j] *= inv;
     }
 }
 
@@ -1449,8 +1537,8 @@ int vsom_attention_bwd(const float* qkv, const float* out, const float* dout, co
 int vsom_attention_probs(const float* qkv, const float* lse, float* probs, int B, int N, int H, int hd, vsom_stream_t stream) {
     VSOM_REQUIRE(qkv && lse && probs, VSOM_EINVAL, "attention_probs: null pointer");
     VSOM_REQUIRE(B > 0 && N > 0 && H > 0 && hd > 0, VSOM_EINVAL, "attention_probs: bad shape B=%d N=%d H=%d hd=%d", B, N, H, hd);
-    const int by = cdiv((long)N * N, 256) < 64 ? cdiv((long)N * N, 256) : 64;
-    VSOM_LAUNCH(attn_probs_kernel, dim3(B * H, by), dim3(256), 0, stream, qkv, lse, probs, N, H, hd, 1.0f / sqrtf((float)hd));
+    const int by = cdiv(N, 4) < 64 ? cdiv(N, 4) : 64;                    // four query rows (waves) per workgroup
+    VSOM_LAUNCH(attn_probs_kernel, dim3(B * H, by), dim3(256), 0, stream, qkv, probs, N, H, hd, 1.0f / sqrtf((float)hd));
     return launch_status("attn_probs_kernel");
 }
 

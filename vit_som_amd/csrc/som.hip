@@ -55,6 +55,21 @@ __global__ __launch_bounds__(256) void row_inv_norm_wide_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------ BMU finalize
+// Euclidean distance in torch.cdist's matmul form, |x|^2 + |w|^2 - 2 x.w.  The three terms are rounded at the scale of
+// |x|^2 + |w|^2, so a squared distance below a few ulp of that sum is rounding noise: a sample that sits on its prototype
+// comes out at +-1e-3 |x| or so, not at 0 (and torch's clamp_min(1e-30) turns a negative one into 1e-15).  Neither is a
+// distance the backward may divide by: h / d then scales the GEMM form of sum_i coef_ik (x_i - w_k), whose two halves
+// no longer cancel, by up to 1e15.  Below EUCLID_RESOLUTION (16 ulp) of |x|^2 + |w|^2 the distance is therefore reported
+// as exactly 0 -- what it is to the precision of this form -- and som_neigh_*_kernel gives torch's subgradient 0 there.
+// Above it nothing changes: the same fma, the same square root.  This is a change of training behaviour, small and on
+// purpose: a sample within ~1e-3 sqrt(|x|^2 + |w|^2) of a prototype neither pulls nor is pulled by it.  A NaN operand
+// stays a NaN distance (it never wins the argmin) instead of becoming a perfect match.
+constexpr float EUCLID_RESOLUTION = 9.5367431640625e-07f;      // 2^-20
+__device__ __forceinline__ float euclid_from_dot(float sq_x, float sq_w, float dot) {
+    const float s = sq_x + sq_w, d2 = fmaf(-2.0f, dot, s);
+    return d2 <= EUCLID_RESOLUTION * s ? 0.f : sqrtf(d2);          // (a NaN compares false and goes through the root)
+}
+
 // dist[i,k] = 1 - (sum_s slab[s][i,k]) * inv_nx[i] * inv_nw[k];  bmu[i] = first argmin_k.
 // One workgroup per sample row; (value, index) reduction with lowest-index tie-break, so
 // bmu is EXACTLY torch.argmin of the distances this kernel writes.
@@ -83,9 +98,8 @@ __global__ __launch_bounds__(256) void bmu_finalize_kernel(const float* __restri
         for (int u = 0; u < 4; ++u) {
             const int k = k0 + 256 * u;
             if (k >= K) break;
-            // euclidean: torch.cdist's matmul form  sqrt(clamp_min(|x|^2 + |w|^2 - 2 x.w, 1e-30))
             const float d = euclid == 2 ? dot[u]      // manhattan: the slabs already hold partial distances
-                          : euclid ? sqrtf(fmaxf(fmaf(-2.0f, dot[u], rx + inv_nw[k]), 1e-30f)) : 1.0f - dot[u] * rx * inv_nw[k];
+                          : euclid ? euclid_from_dot(rx, inv_nw[k], dot[u]) : 1.0f - dot[u] * rx * inv_nw[k];
             if (dist) dist[(long)i * K + k] = d;
             if (d < best || (d == best && k < bidx)) { best = d; bidx = k; }
         }

@@ -383,7 +383,8 @@ def attention_bwd(qkv, out, dout, lse, dqkv, delta, B, N, H, hd):
 
 
 def attention_probs(qkv, lse, probs, B, N, H, hd):
-    """probs[B,H,N,N] = softmax(q k^T / sqrt(hd)) from qkv and the saved log-sum-exp (attention maps, vit.py:41-42)."""
+    """probs[B,H,N,N] = softmax(q k^T / sqrt(hd)) from qkv, each row normalised by its own scores (attention maps,
+    vit.py:41-42); `lse` is kept in the signature and must be a device tensor, but is no longer read."""
     assert qkv.is_contiguous() and lse.is_contiguous() and probs.is_contiguous() and probs.shape == (B, H, N, N)
     _f32(qkv, "qkv"); _f32(probs, "probs")
     check(lib.vsom_attention_probs(ptr(qkv), ptr(lse), ptr(probs), B, N, H, hd, stream()), "vsom_attention_probs")
