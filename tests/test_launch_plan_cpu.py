@@ -6,7 +6,7 @@ import re
 
 import pytest
 
-from launch_plan_rows import HOOK_DEFAULTS, HOOK_VALUES, MODES, PLAN_ROWS, TABLE_ROWS, UNSUPPORTED
+from launch_plan_rows import ATTENTION_BWD, GRAD3, HOOK_DEFAULTS, HOOK_VALUES, MODES, PLAN_ROWS, TABLE_ROWS, UNSUPPORTED
 
 LINE = re.compile(r"engine=(\S+) tile=(\d+x\d+) planes=(\d+) fast=([01]) threads=(\d+) splits=(\d+) workgroups=(\d+)$")
 
@@ -61,6 +61,47 @@ def test_describe_plan_matches_the_table(ops, lib, row):
         ops.set_gemm_mode(prev)
         if setter:
             setter(HOOK_DEFAULTS[row.hook])
+
+
+def attention_bwd_plan(N, hd, hook, mode):
+    """(engine, waves) of the attention backward, restated from DESIGN.md's table and LDS layout (not from the C++)."""
+    extra = N >= 17 and N % 16 == 1
+    nt = (N - 1) // 16 if extra else -(-N // 16)
+    nrows = N if extra else 16 * nt
+    nrp = (nrows + 3) & ~3
+    waves = 8 if nt >= 8 else min(nt, 4)
+    hdp = hd if hd in (16, 32, 64) else (4 if hd <= 4 else 8)
+    fused = 4 * (4 * nrows * (hdp + 4) + 2 * nrp + 3 * hdp * waves)
+    shared = fused + 8 * hdp
+    vec = hdp % 16 == 0
+    if (vec and hook in (1, 3) and nt <= 4 and waves == nt and 16 * nt * (16 * nt + 4) <= nrows * (hdp + 4)
+            and shared <= 81920):
+        return ("attn_shared_bf16x3" if hdp == 64 and mode == GRAD3 and hook == 1 else "attn_shared"), waves
+    if vec and hook != 0 and fused <= 81920:
+        return "attn_fused", waves
+    return "attn_two_launch", waves
+
+
+def test_attention_backward_plan_over_the_whole_range(ops, lib):
+    """Engine and workgroup size for every N = 1..320, head dim, hook and GEMM mode: pins attn_bwd_plan and the LDS
+    byte counts it rests on, where PLAN_ROWS pins single shapes."""
+    prev = ops.get_gemm_mode()
+    bad = []
+    try:
+        for mode in MODES:
+            ops.set_gemm_mode(mode)
+            for hook in HOOK_VALUES["attention_fused"]:
+                ops.set_attention_fused(hook)
+                for hd in (2, 4, 8, 16, 32, 64):
+                    for N in range(1, 321):
+                        engine, waves = attention_bwd_plan(N, hd, hook, mode)
+                        got = describe(lib, ATTENTION_BWD, (N, 2, hd), 1)
+                        if got is None or (got[0], got[4]) != (engine, 64 * waves):
+                            bad.append((mode, hook, hd, N, got, engine, 64 * waves))
+    finally:
+        ops.set_gemm_mode(prev)
+        ops.set_attention_fused(HOOK_DEFAULTS["attention_fused"])
+    assert not bad, (len(bad), bad[:8])
 
 
 def test_describe_plan_grid_arithmetic(lib):

@@ -314,20 +314,23 @@ def test_attention(ops, gemm_mode, B, N, H, hd):
 
 
 @pytest.mark.parametrize("B,N,H,hd", [(4, 65, 3, 64), (3, 64, 2, 64), (2, 50, 3, 64), (3, 33, 2, 64), (2, 17, 1, 64), (2, 65, 3, 32),
-                                       (2, 49, 2, 16), (2, 197, 2, 8)])
+                                       (2, 49, 2, 16), (2, 197, 2, 8), (2, 81, 2, 16), (2, 90, 2, 16), (1, 129, 2, 16)])
 def test_attention_backward_forms_give_the_same_bits(ops, gemm_mode, B, N, H, hd):
     """The short-sequence backward exists as two launches (hook 0), as one launch whose dK/dV phase re-uses the P and dS
-    blocks of the dQ phase (1, the default where the shape allows) and as one launch that recomputes them (2): same
-    arithmetic in the same order, so the gradients must be identical bit for bit -- incl. a ragged last tile (N = 50)
-    and shapes on which the default falls back to the other forms.  (In the default GEMM mode form 1 runs its products on
-    the two-piece bf16 split at hd = 64: equal to the others within that mode's tolerance, and still deterministic.)"""
+    blocks of the dQ phase (1, the default where the shape allows; 3, the same with fp32 products in every GEMM mode) and
+    as one launch that recomputes them (2): same arithmetic in the same order, so the gradients must be identical bit for
+    bit -- incl. a ragged last tile (N = 50) and shapes on which the default falls back to the other forms.  The fused
+    kernel's loops over more than one tile per wave: N = 81 (EXTRA form, 5 tiles on 4 waves), N = 90 (padded form, 6 tiles
+    on 4 waves, ragged last tile); its 8-wave form: N = 129 (EXTRA form, 8 tiles).  (In the default GEMM mode form 1 runs
+    its products on the two-piece bf16 split at hd = 64: equal to the others within that mode's tolerance, and still
+    deterministic.)"""
     E = H * hd
     qkv, dout = dev(rnd(B, N, 3 * E, seed=11)), dev(rnd(B, N, E, seed=12))
     out = torch.empty(B, N, E, device=DEV); lse = torch.empty(B, H, N, device=DEV)
     ops.attention_fwd(qkv, out, lse, B, N, H, hd)
     got = []
     try:
-        for mode in (0, 1, 2):
+        for mode in (0, 1, 2, 3):
             ops.set_attention_fused(mode)
             dqkv = torch.full((B, N, 3 * E), float("nan"), device=DEV); delta = torch.full((B, H, N), float("nan"), device=DEV)
             ops.attention_bwd(qkv, out, dout, lse, dqkv, delta, B, N, H, hd)

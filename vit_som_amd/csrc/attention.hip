@@ -24,17 +24,20 @@
 // adds them in wave order.  (It used to be a fifth, VALU-only wave.  A 5-wave workgroup puts two waves
 // on one SIMD, and that SIMD's register file then decides the residency of the whole CU: 3 workgroups
 // instead of 4 in the forward, ONE instead of 2 in the fused backward -- measured with
-// tools/attn_lab.hip / tools/occupancy_probe.hip; with 4 waves the LDS footprint is the limit again.)
+// lab/attn_lab.hip / lab/occupancy_probe.hip; with 4 waves the LDS footprint is the limit again.)
 #include "common.h"
+#include "attention_layout.h"
 
 #include <atomic>
 
 #include <stdlib.h>
 
-// The general kernels, the fused backward and the lab variants (tools/attention_roll_candidate.hip) must give the
-// same bits (the tests flip between them): no implicit mul+add contraction -- where the compiler fuses depends on
-// the surrounding code, and two forward variants did differ by 1 ulp in 1 % of the outputs at hd = 32.  fmaf()
-// where a fused operation is meant.
+// The four forms of the backward (vsom_set_attention_fused 0 .. 3: two launches, one launch with the scores shared or
+// recomputed, the shared form with fp32 products in every GEMM mode) must agree bit for bit, the split-bf16 products of
+// form 1 aside; tests/test_ops_gpu.py::test_attention_backward_forms_give_the_same_bits checks it.
+// So: no implicit mul+add contraction -- where the compiler fuses depends on the surrounding code, and two forward
+// variants did differ by 1 ulp in 1 % of the outputs at hd = 32 -- fmaf() where a fused operation is meant, and the
+// tile arithmetic the forms have in common is written once (dq_tile, dkv_tile and their parts below).
 #pragma clang fp contract(off)
 
 namespace vsom {
@@ -49,7 +52,7 @@ int gemm_grad_products();          // gemm_f32.hip: 3 in VSOM_GEMM_SPLIT_BF16_GR
 //   3 = 1 with fp32 products in every GEMM mode.
 static std::atomic<int> g_attn_fused{1};
 
-// tools/attn_lab.hip builds this file with VSOM_ATTN_STAMPS: thread 0 of every workgroup records the 100 MHz
+// lab/attn_lab.hip builds this file with VSOM_ATTN_STAMPS: thread 0 of every workgroup records the 100 MHz
 // real-time counter at four points (+ the hardware id of its wave); the library build compiles none of it
 #ifdef VSOM_ATTN_STAMPS
 __device__ unsigned long long* g_attn_stamps = nullptr;          // [grid][16]
@@ -557,26 +560,81 @@ __device__ __forceinline__ void tok0_dkv_combine(const float* q0, const float* d
     }
 }
 
-// LDS carve shared by the three two-slice kernels: two [nrows][S] slices, optional row statistics, the two
-// token-0 vectors of the EXTRA layout, and the tile waves' token-0 partials (`paw` floats per wave)
+// ---- the backward's tile arithmetic, written once for the forms that must give the same bits -------------------
+// D = dO . O of the wave's 16 own rows
+template <int HDP>
+__device__ __forceinline__ float rows_dot(const float (&a)[ACfg<HDP>::NMM], const float (&b)[ACfg<HDP>::NMM]) {
+    float D = 0.f;
+#pragma unroll
+    for (int mm = 0; mm < ACfg<HDP>::NMM; ++mm) D = fmaf(a[mm], b[mm], D);
+    return group_sum(D);
+}
+// token 0 as a key of the wave's 16 query rows (EXTRA): dq += p_i0 (dP_i0 - D_i) scale * k_0
+template <int HDP>
+__device__ __forceinline__ void dq_key0(f32x4 (&dq)[ACfg<HDP>::NDT], const float (&qf)[ACfg<HDP>::NMM],
+                                        const float (&dof)[ACfg<HDP>::NMM], const float* Ks, const float* Vs, float lq, float D,
+                                        float scale, int qp) {
+    const float s0 = frag_dot_row<HDP>(qf, Ks, qp) * scale;
+    const float dp0 = frag_dot_row<HDP>(dof, Vs, qp);
+    const float p0 = __expf(s0 - lq);
+    axpy_row<HDP>(dq, p0 * (dp0 - D) * scale, Ks, qp);
+}
+// P^T and dS^T of key tile t for the wave's 16 query rows (fragments qf, dof; log-sum-exp lq, D)
 template <int HDP, bool EXTRA>
-struct Carve {
-    int ntile, nrows, nrp;
-    float *Y0, *Y1, *L0, *L1, *X0, *X1, *PA;
-    __device__ __forceinline__ Carve(float* smem, int N, bool with_stats) {
-        constexpr int S = ACfg<HDP>::S;
-        ntile = EXTRA ? (N - 1) >> 4 : (N + 15) >> 4;
-        nrows = EXTRA ? N : ntile << 4;
-        nrp = (nrows + 3) & ~3;
-        Y0 = smem;
-        Y1 = Y0 + nrows * S;
-        L0 = Y1 + nrows * S;
-        L1 = L0 + (with_stats ? nrp : 0);
-        X0 = L1 + (with_stats ? nrp : 0);
-        X1 = X0 + HDP;
-        PA = X1 + HDP;
+__device__ __forceinline__ void dq_scores(f32x4& p, f32x4& ds, const float (&qf)[ACfg<HDP>::NMM],
+                                          const float (&dof)[ACfg<HDP>::NMM], const float* Ks, const float* Vs, int t, int N,
+                                          bool qok, float lq, float D, float scale, int r, int qp) {
+    f32x4 s, dp;
+    score_tile2<HDP>(Ks, tok<EXTRA>(t, 0), qf, Vs, tok<EXTRA>(t, 0), dof, r, qp, s, dp);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int key = tok<EXTRA>(t, 4 * qp + e);
+        p[e] = (EXTRA || (key < N && qok)) ? __expf(s[e] * scale - lq) : 0.f;
+        ds[e] = p[e] * (dp[e] - D) * scale;
     }
-};
+}
+// dQ^T of the wave's 16 query rows over all keys
+template <int HDP, bool EXTRA>
+__device__ __forceinline__ void dq_tile(f32x4 (&dq)[ACfg<HDP>::NDT], const float (&qf)[ACfg<HDP>::NMM],
+                                        const float (&dof)[ACfg<HDP>::NMM], const float* Ks, const float* Vs, int ntile, int N,
+                                        bool qok, float lq, float D, float scale, int r, int qp) {
+#pragma unroll
+    for (int dt = 0; dt < ACfg<HDP>::NDT; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (EXTRA) dq_key0<HDP>(dq, qf, dof, Ks, Vs, lq, D, scale, qp);
+    for (int t = 0; t < ntile; ++t) {
+        f32x4 p, ds;
+        dq_scores<HDP, EXTRA>(p, ds, qf, dof, Ks, Vs, t, N, qok, lq, D, scale, r, qp);
+        accum_tile<HDP>(dq, Ks, tok<EXTRA>(t, 0), r, qp, ds);
+    }
+}
+// dK^T, dV^T of the wave's 16 key rows over all queries (Ls, Es: log-sum-exp and D of every row)
+template <int HDP, bool EXTRA>
+__device__ __forceinline__ void dkv_tile(f32x4 (&dk)[ACfg<HDP>::NDT], f32x4 (&dv)[ACfg<HDP>::NDT],
+                                         const float (&kf)[ACfg<HDP>::NMM], const float (&vf)[ACfg<HDP>::NMM], const float* Qs,
+                                         const float* Ds, const float* Ls, const float* Es, int ntile, int N, bool kok,
+                                         float scale, int r, int qp) {
+#pragma unroll
+    for (int dt = 0; dt < ACfg<HDP>::NDT; ++dt) { dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    if (EXTRA) {                                                   // token 0 as a query
+        const float s0 = frag_dot_row<HDP>(kf, Qs, qp) * scale;
+        const float dp0 = frag_dot_row<HDP>(vf, Ds, qp);
+        const float p0 = __expf(s0 - Ls[0]);
+        axpy_row<HDP>(dv, p0, Ds, qp);
+        axpy_row<HDP>(dk, p0 * (dp0 - Es[0]) * scale, Qs, qp);
+    }
+    for (int t = 0; t < ntile; ++t) {
+        f32x4 s, dp;                                              // rows: queries of tile t, col: own key
+        score_tile2<HDP>(Qs, tok<EXTRA>(t, 0), kf, Ds, tok<EXTRA>(t, 0), vf, r, qp, s, dp);
+        f32x4 p, ds;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int query = tok<EXTRA>(t, 4 * qp + e);
+            p[e] = (EXTRA || (query < N && kok)) ? __expf(s[e] * scale - Ls[query]) : 0.f;
+            ds[e] = p[e] * (dp[e] - Es[query]) * scale;
+        }
+        accum_tile2<HDP>(dv, Ds, p, dk, Qs, ds, tok<EXTRA>(t, 0), r, qp);
+    }
+}
 
 // ------------------------------------------------------------------ forward
 template <int HDP, bool EXTRA>
@@ -586,24 +644,24 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const float* __restric
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NDT = ACfg<HDP>::NDT;
     constexpr int NMM = ACfg<HDP>::NMM;
-    constexpr int S = ACfg<HDP>::S;
-    constexpr int PAW = HDP + 2;                   // token-0 partial of a wave: o[HDP], m, l
     const int b = blockIdx.x / H, h = blockIdx.x % H;
     const int E = H * hd, E3 = 3 * E;
-    const Carve<HDP, EXTRA> cv(smem, N, false);
-    const int ntile = cv.ntile;
-    float* Ks = cv.Y0;
-    float* Vs = cv.Y1;
-    const float* base = qkv + (long)b * N * E3 + h * hd;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
     const int r = lane & 15, qp = lane >> 4;
+    const AttnLayout<float*> lay(smem, N, HDP, EXTRA, nwaves, ATTN_LDS_FWD);
+    const int ntile = lay.ntile;
+    float* Ks = lay.Y0;
+    float* Vs = lay.Y1;
+    float* X0 = lay.X0;                                                // q of token 0
+    float* PA = lay.PA;
+    const float* base = qkv + (long)b * N * E3 + h * hd;
     // the wave's first query fragment is requested BEFORE the K/V staging (latency overlaps it)
     float qf[NMM];
     ATTN_STAMP(0);
     ATTN_STAMP_HWID();
     load_frag<HDP>(qf, base + (long)tok<EXTRA>(wave, r) * E3, qp, tok<EXTRA>(wave, r) < N, hd);
-    stage_rows_pair<HDP>(Ks, base + E, E3, Vs, base + 2 * E, E3, N, cv.nrows, hd);
-    if (EXTRA) stage_vec<HDP>(cv.X0, base, hd);                       // q of token 0
+    stage_rows_pair<HDP>(Ks, base + E, E3, Vs, base + 2 * E, E3, N, lay.nrows, hd);
+    if (EXTRA) stage_vec<HDP>(X0, base, hd);
     __syncthreads();
     ATTN_STAMP(1);
 
@@ -676,7 +734,7 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const float* __restric
         if (EXTRA) {                                                   // token 0 as a query against this tile's 16 keys
             __builtin_amdgcn_sched_barrier(0);                         // keep its LDS reads out of the tile's register peak
             const int row0 = tok<EXTRA>(qt, 0);
-            const float sc = tile_rows_dot<HDP>(cv.X0, Ks, row0, r, qp) * scale;
+            const float sc = tile_rows_dot<HDP>(X0, Ks, row0, r, qp) * scale;
             const float mnew = fmaxf(x0m, tile_max(sc));
             const float p = __expf(sc - mnew);
             const float alpha = __expf(x0m - mnew);
@@ -686,27 +744,26 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const float* __restric
         }
     }
     if (EXTRA) {
-        float* pa = cv.PA + wave * PAW;
+        float* pa = PA + wave * lay.paw;
         if (HDP >= 64 || lane < HDP) pa[lane] = x0o;
         if (lane == 0) { pa[HDP] = x0m; pa[HDP + 1] = x0l; }
-        const float s00 = (wave == 0) ? vec_dot<HDP>(cv.X0, Ks, lane) * scale : 0.f;
+        const float s00 = (wave == 0) ? vec_dot<HDP>(X0, Ks, lane) * scale : 0.f;
         __syncthreads();
         if (wave == 0) {                                               // key 0 itself, then the waves in order
             float m = s00;
-            for (int w = 0; w < nwaves; ++w) m = fmaxf(m, cv.PA[w * PAW + HDP]);
+            for (int w = 0; w < nwaves; ++w) m = fmaxf(m, PA[w * lay.paw + HDP]);
             float l = __expf(s00 - m);
             float o = (HDP >= 64 || lane < HDP) ? l * Vs[lane] : 0.f;
             for (int w = 0; w < nwaves; ++w) {
-                const float a = __expf(cv.PA[w * PAW + HDP] - m);
-                l = fmaf(cv.PA[w * PAW + HDP + 1], a, l);
-                if (HDP >= 64 || lane < HDP) o = fmaf(cv.PA[w * PAW + lane], a, o);
+                const float a = __expf(PA[w * lay.paw + HDP] - m);
+                l = fmaf(PA[w * lay.paw + HDP + 1], a, l);
+                if (HDP >= 64 || lane < HDP) o = fmaf(PA[w * lay.paw + lane], a, o);
             }
             if (lane < hd) out[((long)b * N) * E + h * hd + lane] = o / l;
             if (lane == 0) lse[((long)b * H + h) * N] = m + logf(l);
         }
     }
     ATTN_STAMP(3);
-    (void)S;
 }
 
 // ------------------------------------------------------------------ backward: dQ (+ D = rowsum(dO * O))
@@ -722,15 +779,18 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const float* __restric
     constexpr int NMM = ACfg<HDP>::NMM;
     const int b = blockIdx.x / H, h = blockIdx.x % H;
     const int E = H * hd, E3 = 3 * E;
-    const Carve<HDP, EXTRA> cv(smem, N, false);
-    const int ntile = cv.ntile;
-    float* Ks = cv.Y0;
-    float* Vs = cv.Y1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const int r = lane & 15, qp = lane >> 4;
+    const AttnLayout<float*> lay(smem, N, HDP, EXTRA, nwaves, ATTN_LDS_DQ);
+    const int ntile = lay.ntile;
+    float* Ks = lay.Y0;
+    float* Vs = lay.Y1;
+    float* X0 = lay.X0;                                                // q of token 0
+    float* X1 = lay.X1;                                                // dO of token 0
+    float* PA = lay.PA;
     const float* base = qkv + (long)b * N * E3 + h * hd;
     const long obase = (long)b * N * E + h * hd;
     const long srow0 = ((long)b * H + h) * N;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    const int r = lane & 15, qp = lane >> 4;
     float qf[NMM], dof[NMM], of[NMM];
     float lq_first = 0.f;                          // log-sum-exp of the wave's first query row, requested with the fragments
     {
@@ -745,16 +805,16 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const float* __restric
         if (lane < hd) o0 = out[obase + lane];
         l0 = lse[srow0];
     }
-    stage_rows_pair<HDP>(Ks, base + E, E3, Vs, base + 2 * E, E3, N, cv.nrows, hd);
+    stage_rows_pair<HDP>(Ks, base + E, E3, Vs, base + 2 * E, E3, N, lay.nrows, hd);
     if (EXTRA) {
-        stage_vec<HDP>(cv.X0, base, hd);                               // q of token 0
-        stage_vec<HDP>(cv.X1, dout + obase, hd);                       // dO of token 0
+        stage_vec<HDP>(X0, base, hd);
+        stage_vec<HDP>(X1, dout + obase, hd);
     }
     __syncthreads();
 
     float D0 = 0.f, gq0 = 0.f;
     if (EXTRA) {
-        D0 = wave_sum64((HDP >= 64 || lane < HDP) ? cv.X1[lane] * o0 : 0.f);
+        D0 = wave_sum64((HDP >= 64 || lane < HDP) ? X1[lane] * o0 : 0.f);
         if (wave == 0 && lane == 0) delta[srow0] = D0;
     }
 
@@ -766,42 +826,20 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const float* __restric
             load_frag<HDP>(dof, dout + obase + (long)query * E, qp, qok, hd);
             load_frag<HDP>(of, out + obase + (long)query * E, qp, qok, hd);
         }
-        float D = 0.f;
-#pragma unroll
-        for (int mm = 0; mm < NMM; ++mm) D = fmaf(dof[mm], of[mm], D);
-        D = group_sum(D);
+        const float D = rows_dot<HDP>(dof, of);
         const long srow = srow0 + query;
         if (qp == 0 && qok) delta[srow] = D;
         const float lq = (qt == wave) ? lq_first : (qok ? lse[srow] : 0.f);
         f32x4 dq[NDT];
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (EXTRA) {                                                   // token 0 as a key
-            const float s0 = frag_dot_row<HDP>(qf, Ks, qp) * scale;
-            const float dp0 = frag_dot_row<HDP>(dof, Vs, qp);
-            const float p0 = __expf(s0 - lq);
-            axpy_row<HDP>(dq, p0 * (dp0 - D) * scale, Ks, qp);
-        }
-        for (int t = 0; t < ntile; ++t) {
-            f32x4 s, dp;
-            score_tile2<HDP>(Ks, tok<EXTRA>(t, 0), qf, Vs, tok<EXTRA>(t, 0), dof, r, qp, s, dp);
-            f32x4 ds;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int key = tok<EXTRA>(t, 4 * qp + e);
-                const float p = (EXTRA || (key < N && qok)) ? __expf(s[e] * scale - lq) : 0.f;
-                ds[e] = p * (dp[e] - D) * scale;
-            }
-            accum_tile<HDP>(dq, Ks, tok<EXTRA>(t, 0), r, qp, ds);
-        }
+        dq_tile<HDP, EXTRA>(dq, qf, dof, Ks, Vs, ntile, N, qok, lq, D, scale, r, qp);
         store_rows<HDP>(dq, dqkv + ((long)b * N + query) * E3 + h * hd, qp, qok, hd);
-        if (EXTRA) gq0 += tok0_dq_partial<HDP>(cv.X0, cv.X1, Ks, Vs, tok<EXTRA>(qt, 0), l0, D0, scale, lane, r, qp);
+        if (EXTRA) gq0 += tok0_dq_partial<HDP>(X0, X1, Ks, Vs, tok<EXTRA>(qt, 0), l0, D0, scale, lane, r, qp);
     }
     if (EXTRA) {
-        if (HDP >= 64 || lane < HDP) cv.PA[wave * HDP + lane] = gq0;
+        if (HDP >= 64 || lane < HDP) PA[wave * lay.paw + lane] = gq0;
         __syncthreads();
         if (wave == 0)
-            tok0_dq_combine<HDP>(cv.X0, cv.X1, Ks, Vs, cv.PA, HDP, nwaves, l0, D0, scale,
+            tok0_dq_combine<HDP>(X0, X1, Ks, Vs, PA, lay.paw, nwaves, l0, D0, scale,
                                  dqkv + (long)b * N * E3 + h * hd, hd, lane);
     }
 }
@@ -819,15 +857,18 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const float* __restri
     constexpr int NMM = ACfg<HDP>::NMM;
     const int b = blockIdx.x / H, h = blockIdx.x % H;
     const int E = H * hd, E3 = 3 * E;
-    const Carve<HDP, EXTRA> cv(smem, N, true);
-    const int ntile = cv.ntile;
-    float* Qs = cv.Y0;
-    float* Ds = cv.Y1;
-    float* Ls = cv.L0;
-    float* Es = cv.L1;
-    const float* base = qkv + (long)b * N * E3 + h * hd;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
     const int r = lane & 15, qp = lane >> 4;
+    const AttnLayout<float*> lay(smem, N, HDP, EXTRA, nwaves, ATTN_LDS_DKV);
+    const int ntile = lay.ntile;
+    float* Qs = lay.Y0;
+    float* Ds = lay.Y1;
+    float* Ls = lay.L0;
+    float* Es = lay.L1;
+    float* X0 = lay.X0;                                                // k of token 0
+    float* X1 = lay.X1;                                                // v of token 0
+    float* PA = lay.PA;
+    const float* base = qkv + (long)b * N * E3 + h * hd;
     float kf[NMM], vf[NMM];
     {
         const int k0 = tok<EXTRA>(wave, r);
@@ -842,16 +883,16 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const float* __restri
         l_r = lse[((long)b * H + h) * N + i0];
         e_r = delta[((long)b * H + h) * N + i0];
     }
-    stage_rows_pair<HDP>(Qs, base, E3, Ds, dout + (long)b * N * E + h * hd, E, N, cv.nrows, hd);
-    if (i0 < cv.nrp) { Ls[i0] = l_r; Es[i0] = e_r; }
-    for (int i = threadIdx.x + blockDim.x; i < cv.nrp; i += blockDim.x) {
+    stage_rows_pair<HDP>(Qs, base, E3, Ds, dout + (long)b * N * E + h * hd, E, N, lay.nrows, hd);
+    if (i0 < lay.nrp) { Ls[i0] = l_r; Es[i0] = e_r; }
+    for (int i = threadIdx.x + blockDim.x; i < lay.nrp; i += blockDim.x) {
         const long srow = ((long)b * H + h) * N + i;
         Ls[i] = (i < N) ? lse[srow] : 0.f;
         Es[i] = (i < N) ? delta[srow] : 0.f;
     }
     if (EXTRA) {
-        stage_vec<HDP>(cv.X0, base + E, hd);                           // k of token 0
-        stage_vec<HDP>(cv.X1, base + 2 * E, hd);                       // v of token 0
+        stage_vec<HDP>(X0, base + E, hd);
+        stage_vec<HDP>(X1, base + 2 * E, hd);
     }
     __syncthreads();
 
@@ -865,41 +906,21 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const float* __restri
             load_frag<HDP>(vf, base + (long)key * E3 + 2 * E, qp, kok, hd);
         }
         f32x4 dk[NDT], dv[NDT];
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt) { dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        if (EXTRA) {                                                   // token 0 as a query
-            const float s0 = frag_dot_row<HDP>(kf, Qs, qp) * scale;
-            const float dp0 = frag_dot_row<HDP>(vf, Ds, qp);
-            const float p0 = __expf(s0 - Ls[0]);
-            axpy_row<HDP>(dv, p0, Ds, qp);
-            axpy_row<HDP>(dk, p0 * (dp0 - Es[0]) * scale, Qs, qp);
-        }
-        for (int t = 0; t < ntile; ++t) {
-            f32x4 s, dp;                                              // rows: queries of tile t, col: own key
-            score_tile2<HDP>(Qs, tok<EXTRA>(t, 0), kf, Ds, tok<EXTRA>(t, 0), vf, r, qp, s, dp);
-            f32x4 p, ds;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int query = tok<EXTRA>(t, 4 * qp + e);
-                p[e] = (EXTRA || (query < N && kok)) ? __expf(s[e] * scale - Ls[query]) : 0.f;
-                ds[e] = p[e] * (dp[e] - Es[query]) * scale;
-            }
-            accum_tile2<HDP>(dv, Ds, p, dk, Qs, ds, tok<EXTRA>(t, 0), r, qp);
-        }
+        dkv_tile<HDP, EXTRA>(dk, dv, kf, vf, Qs, Ds, Ls, Es, ntile, N, kok, scale, r, qp);
         float* drow = dqkv + ((long)b * N + key) * E3 + h * hd;
         store_rows<HDP>(dk, drow + E, qp, kok, hd);
         store_rows<HDP>(dv, drow + 2 * E, qp, kok, hd);
-        if (EXTRA) tok0_dkv_partial<HDP>(cv.X0, cv.X1, Qs, Ds, Ls, Es, tok<EXTRA>(kt, 0), scale, lane, r, qp, gk0, gv0);
+        if (EXTRA) tok0_dkv_partial<HDP>(X0, X1, Qs, Ds, Ls, Es, tok<EXTRA>(kt, 0), scale, lane, r, qp, gk0, gv0);
     }
     if (EXTRA) {
         if (HDP >= 64 || lane < HDP) {
-            cv.PA[wave * 2 * HDP + lane] = gk0;
-            cv.PA[wave * 2 * HDP + HDP + lane] = gv0;
+            PA[wave * lay.paw + lane] = gk0;
+            PA[wave * lay.paw + HDP + lane] = gv0;
         }
         __syncthreads();
         if (wave == 0) {
             float* drow = dqkv + (long)b * N * E3 + h * hd;
-            tok0_dkv_combine<HDP>(Qs, Ds, cv.X0, cv.X1, cv.PA, 2 * HDP, nwaves, Ls[0], Es[0], scale, drow + E,
+            tok0_dkv_combine<HDP>(Qs, Ds, X0, X1, PA, lay.paw, nwaves, Ls[0], Es[0], scale, drow + E,
                                   drow + 2 * E, hd, lane);
         }
     }
@@ -920,24 +941,22 @@ __global__ __launch_bounds__(512) void attn_bwd_fused_kernel(const float* __rest
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NDT = ACfg<HDP>::NDT;
     constexpr int NMM = ACfg<HDP>::NMM;
-    constexpr int S = ACfg<HDP>::S;
     const int b = blockIdx.x / H, h = blockIdx.x % H;
     const int E = H * hd, E3 = 3 * E;
-    const int ntile = EXTRA ? (N - 1) >> 4 : (N + 15) >> 4;
-    const int nrows = EXTRA ? N : ntile << 4;
-    const int nrp = (nrows + 3) & ~3;
-    float* Ks = smem;
-    float* Vs = Ks + nrows * S;
-    float* Qs = Vs + nrows * S;
-    float* Ds = Qs + nrows * S;
-    float* Ls = Ds + nrows * S;
-    float* Es = Ls + nrp;
-    float* PA = Es + nrp;                                              // [nwaves][3 HDP]: gq | gk | gv of token 0
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const int r = lane & 15, qp = lane >> 4;
+    const AttnLayout<float*> lay(smem, N, HDP, EXTRA, nwaves, ATTN_LDS_FUSED);
+    const int ntile = lay.ntile, nrows = lay.nrows, nrp = lay.nrp;
+    float* Ks = lay.Y0;
+    float* Vs = lay.Y1;
+    float* Qs = lay.Y2;
+    float* Ds = lay.Y3;
+    float* Ls = lay.L0;
+    float* Es = lay.L1;
+    float* PA = lay.PA;                                                // [nwaves][3 HDP]: gq | gk | gv of token 0
     const float* base = qkv + (long)b * N * E3 + h * hd;
     const long obase = (long)b * N * E + h * hd;
     const long srow0 = ((long)b * H + h) * N;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    const int r = lane & 15, qp = lane >> 4;
     float qf[NMM], dof[NMM], of[NMM];
     ATTN_STAMP(0);
     ATTN_STAMP_HWID();
@@ -978,44 +997,22 @@ __global__ __launch_bounds__(512) void attn_bwd_fused_kernel(const float* __rest
             load_frag<HDP>(dof, dout + obase + (long)query * E, qp, qok, hd);
             load_frag<HDP>(of, out + obase + (long)query * E, qp, qok, hd);
         }
-        float D = 0.f;
-#pragma unroll
-        for (int mm = 0; mm < NMM; ++mm) D = fmaf(dof[mm], of[mm], D);
-        D = group_sum(D);
+        const float D = rows_dot<HDP>(dof, of);
         if (qp == 0 && qok) { delta[srow0 + query] = D; Es[query] = D; }
         const float lq = qok ? Ls[query] : 0.f;
         f32x4 dq[NDT];
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (EXTRA) {                                                   // token 0 as a key
-            const float s0 = frag_dot_row<HDP>(qf, Ks, qp) * scale;
-            const float dp0 = frag_dot_row<HDP>(dof, Vs, qp);
-            const float p0 = __expf(s0 - lq);
-            axpy_row<HDP>(dq, p0 * (dp0 - D) * scale, Ks, qp);
-        }
-        for (int t = 0; t < ntile; ++t) {
-            f32x4 sc, dp;
-            score_tile2<HDP>(Ks, tok<EXTRA>(t, 0), qf, Vs, tok<EXTRA>(t, 0), dof, r, qp, sc, dp);
-            f32x4 ds;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int key = tok<EXTRA>(t, 4 * qp + e);
-                const float p = (EXTRA || (key < N && qok)) ? __expf(sc[e] * scale - lq) : 0.f;
-                ds[e] = p * (dp[e] - D) * scale;
-            }
-            accum_tile<HDP>(dq, Ks, tok<EXTRA>(t, 0), r, qp, ds);
-        }
+        dq_tile<HDP, EXTRA>(dq, qf, dof, Ks, Vs, ntile, N, qok, lq, D, scale, r, qp);
         store_rows<HDP>(dq, dqkv + ((long)b * N + query) * E3 + h * hd, qp, qok, hd);
         if (EXTRA) gq0 += tok0_dq_partial<HDP>(Qs, Ds, Ks, Vs, tok<EXTRA>(qt, 0), l0, D0, scale, lane, r, qp);
     }
-    if (EXTRA && (HDP >= 64 || lane < HDP)) PA[wave * 3 * HDP + lane] = gq0;
+    if (EXTRA && (HDP >= 64 || lane < HDP)) PA[wave * lay.paw + lane] = gq0;
     __syncthreads();                                                   // Es (D of every row) and the dQ partials complete
     ATTN_STAMP(2);
 
     // ---- phase 2: dK, dV
     float gk0 = 0.f, gv0 = 0.f;
     if (EXTRA && wave == 0)
-        tok0_dq_combine<HDP>(Qs, Ds, Ks, Vs, PA, 3 * HDP, nwaves, l0, D0, scale, dqkv + (long)b * N * E3 + h * hd, hd, lane);
+        tok0_dq_combine<HDP>(Qs, Ds, Ks, Vs, PA, lay.paw, nwaves, l0, D0, scale, dqkv + (long)b * N * E3 + h * hd, hd, lane);
     for (int kt = wave; kt < ntile; kt += nwaves) {
         const int key = tok<EXTRA>(kt, r);
         const bool kok = key < N;
@@ -1023,27 +1020,7 @@ __global__ __launch_bounds__(512) void attn_bwd_fused_kernel(const float* __rest
         load_frag_lds<HDP>(kf, Ks, key, qp);                           // own rows from the staged slices (rows N .. nrows-1
         load_frag_lds<HDP>(vf, Vs, key, qp);                           // of the padded layout are staged as zeros)
         f32x4 dk[NDT], dv[NDT];
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt) { dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        if (EXTRA) {                                                   // token 0 as a query
-            const float s0 = frag_dot_row<HDP>(kf, Qs, qp) * scale;
-            const float dp0 = frag_dot_row<HDP>(vf, Ds, qp);
-            const float p0 = __expf(s0 - Ls[0]);
-            axpy_row<HDP>(dv, p0, Ds, qp);
-            axpy_row<HDP>(dk, p0 * (dp0 - Es[0]) * scale, Qs, qp);
-        }
-        for (int t = 0; t < ntile; ++t) {
-            f32x4 sc, dp;                                              // rows: queries of tile t, col: own key
-            score_tile2<HDP>(Qs, tok<EXTRA>(t, 0), kf, Ds, tok<EXTRA>(t, 0), vf, r, qp, sc, dp);
-            f32x4 p, ds;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int query = tok<EXTRA>(t, 4 * qp + e);
-                p[e] = (EXTRA || (query < N && kok)) ? __expf(sc[e] * scale - Ls[query]) : 0.f;
-                ds[e] = p[e] * (dp[e] - Es[query]) * scale;
-            }
-            accum_tile2<HDP>(dv, Ds, p, dk, Qs, ds, tok<EXTRA>(t, 0), r, qp);
-        }
+        dkv_tile<HDP, EXTRA>(dk, dv, kf, vf, Qs, Ds, Ls, Es, ntile, N, kok, scale, r, qp);
         float* drow = dqkv + ((long)b * N + key) * E3 + h * hd;
         store_rows<HDP>(dk, drow + E, qp, kok, hd);
         store_rows<HDP>(dv, drow + 2 * E, qp, kok, hd);
@@ -1051,13 +1028,13 @@ __global__ __launch_bounds__(512) void attn_bwd_fused_kernel(const float* __rest
     }
     if (EXTRA) {
         if (HDP >= 64 || lane < HDP) {
-            PA[wave * 3 * HDP + HDP + lane] = gk0;
-            PA[wave * 3 * HDP + 2 * HDP + lane] = gv0;
+            PA[wave * lay.paw + HDP + lane] = gk0;
+            PA[wave * lay.paw + 2 * HDP + lane] = gv0;
         }
         __syncthreads();
         if (wave == 0) {
             float* drow = dqkv + (long)b * N * E3 + h * hd;
-            tok0_dkv_combine<HDP>(Qs, Ds, Ks, Vs, PA + HDP, 3 * HDP, nwaves, Ls[0], Es[0], scale, drow + E, drow + 2 * E, hd,
+            tok0_dkv_combine<HDP>(Qs, Ds, Ks, Vs, PA + HDP, lay.paw, nwaves, Ls[0], Es[0], scale, drow + E, drow + 2 * E, hd,
                                   lane);
         }
     }
@@ -1086,9 +1063,13 @@ __global__ __launch_bounds__(256) void attn_bwd_shared_kernel(const float* __res
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NDT = ACfg<HDP>::NDT;
     constexpr int NMM = ACfg<HDP>::NMM;
-    constexpr int S = ACfg<HDP>::S;
     const int b = blockIdx.x / H, h = blockIdx.x % H;
     const int E = H * hd, E3 = 3 * E;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const int r = lane & 15, qp = lane >> 4;
+    // The ATTN_LDS_FUSED layout of attention_layout.h followed by X2, X3, carved by hand: built from AttnLayout, this kernel
+    // alone came out with other LDS read pairs and wait counts (<16,true>, <64,true,true>), the other kernels did not.
+    constexpr int S = ACfg<HDP>::S;
     const int ntile = EXTRA ? (N - 1) >> 4 : (N + 15) >> 4;           // == number of waves, <= 4
     const int nrows = EXTRA ? N : ntile << 4;
     const int nrp = (nrows + 3) & ~3;
@@ -1107,8 +1088,6 @@ __global__ __launch_bounds__(256) void attn_bwd_shared_kernel(const float* __res
     const float* base = qkv + (long)b * N * E3 + h * hd;
     const long obase = (long)b * N * E + h * hd;
     const long srow0 = ((long)b * H + h) * N;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-    const int r = lane & 15, qp = lane >> 4;
     float qf[NMM], dof[NMM], of[NMM];
     ATTN_STAMP(0);
     ATTN_STAMP_HWID();
@@ -1223,29 +1202,13 @@ __global__ __launch_bounds__(256) void attn_bwd_shared_kernel(const float* __res
                 }
             }
         } else {
-            float D = 0.f;
-#pragma unroll
-            for (int mm = 0; mm < NMM; ++mm) D = fmaf(dof[mm], of[mm], D);
-            D = group_sum(D);
+            const float D = rows_dot<HDP>(dof, of);
             if (qp == 0 && qok) { delta[srow0 + query] = D; Es[query] = D; }
-            if (EXTRA) {                                                   // token 0 as a key
-                const float s0 = frag_dot_row<HDP>(qf, Ks, qp) * scale;
-                const float dp0 = frag_dot_row<HDP>(dof, Vs, qp);
-                const float p0 = __expf(s0 - lq);
-                axpy_row<HDP>(dq, p0 * (dp0 - D) * scale, Ks, qp);
-            }
+            if (EXTRA) dq_key0<HDP>(dq, qf, dof, Ks, Vs, lq, D, scale, qp);
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 if (t < ntile) {
-                    f32x4 sc, dp;
-                    score_tile2<HDP>(Ks, tok<EXTRA>(t, 0), qf, Vs, tok<EXTRA>(t, 0), dof, r, qp, sc, dp);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int key = tok<EXTRA>(t, 4 * qp + e);
-                        const float p = (EXTRA || (key < N && qok)) ? __expf(sc[e] * scale - lq) : 0.f;
-                        pT[t][e] = p;
-                        dsT[t][e] = p * (dp[e] - D) * scale;
-                    }
+                    dq_scores<HDP, EXTRA>(pT[t], dsT[t], qf, dof, Ks, Vs, t, N, qok, lq, D, scale, r, qp);
                     accum_tile<HDP>(dq, Ks, tok<EXTRA>(t, 0), r, qp, dsT[t]);
                 }
             }
@@ -1341,7 +1304,7 @@ static bool use_extra(int N) { return N >= 17 && (N % 16) == 1; }
 static int attn_tiles(int N) { return use_extra(N) ? (N - 1) / 16 : cdiv(N, 16); }
 static int attn_waves(int N) {          // every wave is an MFMA (tile) wave; 1..4 or 8 of them: a workgroup whose wave count
     const int ntile = attn_tiles(N);    // is not a multiple of 4 puts ceil(w/4) waves on the first SIMDs, and those SIMDs' register
-    if (ntile >= 8) return 8;           // files then bound the residency of the CU (tools/occupancy_probe.hip: 5 waves of
+    if (ntile >= 8) return 8;           // files then bound the residency of the CU (lab/occupancy_probe.hip: 5 waves of
     return ntile > 4 ? 4 : ntile;       // 124 VGPRs -> 2 workgroups per CU where 4 waves give 4)
 }
 static int attn_hdp(int hd) {
@@ -1350,22 +1313,15 @@ static int attn_hdp(int hd) {
     if (hd <= 8) return 8;
     return 0;
 }
-// paw = token-0 partial floats per wave: forward hdp + 2, dQ hdp, dK/dV 2 hdp
-static int attn_stride(int hdp) { return hdp + 4; }        // ACfg<HDP>::S
-static size_t attn_lds_bytes(int N, int hdp, bool with_stats, int paw) {
-    const int nrows = use_extra(N) ? N : cdiv(N, 16) * 16;
-    const int nrp = (nrows + 3) & ~3;
-    return ((size_t)2 * nrows * attn_stride(hdp) + (with_stats ? 2 * nrp : 0) + 2 * hdp + (size_t)attn_waves(N) * paw) * sizeof(float);
+static size_t attn_lds_bytes(int N, int hdp, AttnLds kind) {
+    return AttnLayout<size_t>(0, N, hdp, use_extra(N), attn_waves(N), kind).end * sizeof(float);
 }
-static size_t attn_fused_lds_bytes(int N, int hdp) {
-    const int nrows = use_extra(N) ? N : cdiv(N, 16) * 16;
-    const int nrp = (nrows + 3) & ~3;
-    return ((size_t)4 * nrows * attn_stride(hdp) + 2 * nrp + (size_t)attn_waves(N) * 3 * hdp) * sizeof(float);
-}
+// attn_bwd_shared_kernel: the fused layout + k, v of token 0 (the K / V regions are reused between its phases)
+static size_t attn_shared_lds_bytes(int N, int hdp) { return attn_lds_bytes(N, hdp, ATTN_LDS_FUSED) + 2 * hdp * sizeof(float); }
 
 template <int HDP, bool EXTRA>
 static int launch_fwd_t(const float* qkv, float* out, float* lse, int B, int N, int H, int hd, hipStream_t st) {
-    const size_t lds = attn_lds_bytes(N, HDP, false, HDP + 2);
+    const size_t lds = attn_lds_bytes(N, HDP, ATTN_LDS_FWD);
     VSOM_LAUNCH((attn_fwd_kernel<HDP, EXTRA>), dim3(B * H), dim3(64 * attn_waves(N)), lds, st, qkv, out, lse, N, H, hd,
                        1.0f / sqrtf((float)hd));
     return launch_status("attn_fwd_kernel");
@@ -1373,17 +1329,17 @@ static int launch_fwd_t(const float* qkv, float* out, float* lse, int B, int N, 
 // Form of the backward ("Which kernel runs"); `hook` is vsom_set_attention_fused's value (see g_attn_fused),
 // `grad_products` gemm_grad_products().
 enum AttnBwd : int { ATTN_BWD_TWO_LAUNCH = 0, ATTN_BWD_FUSED = 1, ATTN_BWD_SHARED = 2, ATTN_BWD_SHARED_BF16X3 = 3 };
-static size_t attn_shared_lds_bytes(int N, int hdp) { return attn_fused_lds_bytes(N, hdp) + 2 * hdp * sizeof(float); }
 static AttnBwd attn_bwd_plan(int N, int hdp, int hook, int grad_products) {
     const bool vec = hdp % 16 == 0;                     // ACfg<HDP>::VEC: the one-launch forms are vector-path kernels
-    const int nt = attn_tiles(N), nrows = use_extra(N) ? N : nt * 16;
+    const AttnLayout<size_t> fused(0, N, hdp, use_extra(N), attn_waves(N), ATTN_LDS_FUSED);
+    const int nt = fused.ntile, nrows = fused.nrows;
     // scores shared between the phases: they must fit the LDS the K / V slices leave, one tile row per wave
     if (vec && (hook == 1 || hook == 3) && nt <= 4 && attn_waves(N) == nt && 16 * nt * (16 * nt + 4) <= nrows * (hdp + 4) &&
         attn_shared_lds_bytes(N, hdp) <= 80 * 1024)
         // the mode whose gradient GEMMs run on the two-piece split (hook 3: fp32 products)
         return (hdp == 64 && grad_products == 3 && hook == 1) ? ATTN_BWD_SHARED_BF16X3 : ATTN_BWD_SHARED;
     // all four slices in LDS and still two workgroups per CU -> one fused launch
-    if (vec && hook != 0 && attn_fused_lds_bytes(N, hdp) <= 80 * 1024) return ATTN_BWD_FUSED;
+    if (vec && hook != 0 && fused.end * sizeof(float) <= 80 * 1024) return ATTN_BWD_FUSED;
     return ATTN_BWD_TWO_LAUNCH;
 }
 
@@ -1402,29 +1358,32 @@ static int launch_bwd_t(const float* qkv, const float* out, const float* dout, c
     switch (plan) {
         case ATTN_BWD_SHARED_BF16X3:
             if constexpr (HDP == 64) {
-                VSOM_LAUNCH((attn_bwd_shared_kernel<HDP, EXTRA, true>), grid, block, attn_shared_lds_bytes(N, HDP), st, qkv, out,
-                            dout, lse, dqkv, delta, N, H, hd, scale);
+                VSOM_LAUNCH((attn_bwd_shared_kernel<HDP, EXTRA, true>), grid, block, attn_shared_lds_bytes(N, HDP), st,
+                            qkv, out, dout, lse, dqkv, delta, N, H, hd, scale);
                 return launch_status("attn_bwd_shared_kernel");
             }
             break;
         case ATTN_BWD_SHARED:
             if constexpr (ACfg<HDP>::VEC) {
-                VSOM_LAUNCH((attn_bwd_shared_kernel<HDP, EXTRA>), grid, block, attn_shared_lds_bytes(N, HDP), st, qkv, out, dout,
-                            lse, dqkv, delta, N, H, hd, scale);
+                VSOM_LAUNCH((attn_bwd_shared_kernel<HDP, EXTRA>), grid, block, attn_shared_lds_bytes(N, HDP), st, qkv,
+                            out, dout, lse, dqkv, delta, N, H, hd, scale);
                 return launch_status("attn_bwd_shared_kernel");
             }
             break;
         case ATTN_BWD_FUSED:
-            VSOM_LAUNCH((attn_bwd_fused_kernel<HDP, EXTRA>), grid, block, attn_fused_lds_bytes(N, HDP), st, qkv, out, dout, lse,
-                        dqkv, delta, N, H, hd, scale);
-            return launch_status("attn_bwd_fused_kernel");
+            if constexpr (ACfg<HDP>::VEC) {
+                VSOM_LAUNCH((attn_bwd_fused_kernel<HDP, EXTRA>), grid, block, attn_lds_bytes(N, HDP, ATTN_LDS_FUSED), st, qkv,
+                            out, dout, lse, dqkv, delta, N, H, hd, scale);
+                return launch_status("attn_bwd_fused_kernel");
+            }
+            break;
         case ATTN_BWD_TWO_LAUNCH: {
-            VSOM_LAUNCH((attn_bwd_dq_kernel<HDP, EXTRA>), grid, block, attn_lds_bytes(N, HDP, false, HDP), st, qkv, out, dout,
-                        lse, dqkv, delta, N, H, hd, scale);
+            VSOM_LAUNCH((attn_bwd_dq_kernel<HDP, EXTRA>), grid, block, attn_lds_bytes(N, HDP, ATTN_LDS_DQ), st, qkv, out,
+                        dout, lse, dqkv, delta, N, H, hd, scale);
             const int rc = launch_status("attn_bwd_dq_kernel");
             if (rc) return rc;
-            VSOM_LAUNCH((attn_bwd_dkv_kernel<HDP, EXTRA>), grid, block, attn_lds_bytes(N, HDP, true, 2 * HDP), st, qkv, dout,
-                        lse, delta, dqkv, N, H, hd, scale);
+            VSOM_LAUNCH((attn_bwd_dkv_kernel<HDP, EXTRA>), grid, block, attn_lds_bytes(N, HDP, ATTN_LDS_DKV), st, qkv,
+                        dout, lse, delta, dqkv, N, H, hd, scale);
             return launch_status("attn_bwd_dkv_kernel");
         }
     }
@@ -1486,8 +1445,8 @@ static int attn_check(const char* who, int B, int N, int H, int hd, int* hdp) {
     VSOM_REQUIRE(B > 0 && N > 0 && H > 0 && hd > 0, VSOM_EINVAL, "%s: bad shape B=%d N=%d H=%d hd=%d", who, B, N, H, hd);
     *hdp = attn_hdp(hd);
     VSOM_REQUIRE(*hdp != 0, VSOM_EUNSUPPORTED, "%s: head dim %d not supported (1..8, 16, 32, 64)", who, hd);
-    VSOM_REQUIRE(attn_lds_bytes(N, *hdp, true, 2 * *hdp) <= 160 * 1024, VSOM_EUNSUPPORTED,
-                 "%s: N=%d hd=%d needs %zu B of LDS (> 160 KiB)", who, N, hd, attn_lds_bytes(N, *hdp, true, 2 * *hdp));
+    const size_t lds = attn_lds_bytes(N, *hdp, ATTN_LDS_DKV);      // the largest of the two-slice layouts
+    VSOM_REQUIRE(lds <= 160 * 1024, VSOM_EUNSUPPORTED, "%s: N=%d hd=%d needs %zu B of LDS (> 160 KiB)", who, N, hd, lds);
     return VSOM_OK;
 }
 
