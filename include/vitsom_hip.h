@@ -505,6 +505,46 @@ int vsom_umap_epoch(const int64_t* indptr, const int64_t* indices, const double*
                     double* epoch_of_next_negative_sample, const float* Y_in, float* Y_out, long N, int dim, float a,
                     float b, float gamma, float alpha, int epoch, uint64_t seed, vsom_stream_t stream);
 
+/* k-nearest-neighbour probe of evaluate_knn (no counterpart in the reference).  No floating-point atomics, every sum in
+ * one fixed order: two runs are bitwise equal.
+ * For every row of Q [Nq, D] (row stride ldq) the k nearest rows of the bank chunk X [Nb, D] (row stride ldx):
+ * idx int64 [Nq, k] = index_base + row, dist f32 [Nq, k], ascending by (distance, index).  Distances are those of
+ * vsom_umap_knn (same metrics, same zero-row conventions, an f32 matrix-core contraction with the squared norms summed
+ * in its order: a query identical to a bank row is at exactly 0); any other metric: VSOM_EUNSUPPORTED.  Unlike there
+ * nothing is put first artificially.
+ * accumulate == 0: the lists start empty, an empty slot being (+inf, -1).  accumulate != 0: idx / dist hold on entry a
+ * result of earlier calls over OTHER index ranges and are folded with this chunk.  The dot product of a (query, bank
+ * row) pair is summed in one order over D that depends neither on where the rows fall in a tile, nor on Nq, Nb or the
+ * chunking, so a bank streamed in any number of pieces, in any order, gives bit for bit the lists of one call over the
+ * whole bank.  Nb < k is legal: the unfilled tail stays (+inf, -1).
+ * exclude (may be NULL): exclude[i] is a global bank ordinal that query i never receives (leave-one-out when queries
+ * and bank are the same set).
+ * 1 <= k <= 64 (more: VSOM_EUNSUPPORTED); 1 <= Nq, Nb <= 2^31 - 129; ldq, ldx >= D >= 1; index_base >= 0.  Rows are
+ * loaded 16 bytes per lane when D % 4 == 0 and both pointers and strides are 16-byte aligned, element-wise otherwise.
+ * Workspace: vsom_knn_query_workspace_bytes(Nq, Nb, k) (host arithmetic, monotone in each argument; 0 for a
+ * non-positive size); too small or NULL: VSOM_EWORKSPACE. */
+size_t vsom_knn_query_workspace_bytes(long Nq, long Nb, int k);
+int vsom_knn_query(const float* Q, long ldq, long Nq, const float* X, long ldx, long Nb, int D, int k, int metric,
+                   int64_t index_base, int accumulate, const int64_t* exclude, int64_t* idx, float* dist, void* ws,
+                   size_t ws_bytes, vsom_stream_t stream);
+/* The class vote over such lists, one wave per query: scores[i, c] (fp64) = the weights of query i's neighbours j with
+ * bank_labels[idx[i, j]] == c, added in neighbour order j = 0 .. k-1; pred[i] = the first argmax (ties go to the
+ * lowest class, as vsom_argmax_rows).  weights:
+ *   VSOM_KNN_UNIFORM   1;
+ *   VSOM_KNN_DISTANCE  sklearn's rule: 1 / d in fp64 from the stored fp32 distance; if any counted neighbour of the
+ *                      query is at distance 0 those get 1 and the others 0;
+ *   VSOM_KNN_SOFTMAX   exp(-d / temperature) in fp64, temperature > 0 (else VSOM_EINVAL): for cosine the DINO-style
+ *                      exp(sim / T) vote up to a common factor, and it cannot overflow.
+ * An entry with idx < 0 is skipped; an idx >= n_bank or a label outside [0, n_classes) is skipped and counted in
+ * status[0]; a query left without a counted neighbour gets pred = -1 and is counted in status[1] (status int32 [2],
+ * zeroed by the caller).  scores [Nq, n_classes] may be NULL.  k <= 64, n_classes <= 1024: else VSOM_EUNSUPPORTED. */
+#define VSOM_KNN_UNIFORM 0
+#define VSOM_KNN_DISTANCE 1
+#define VSOM_KNN_SOFTMAX 2
+int vsom_knn_vote(const int64_t* idx, const float* dist, long Nq, int k, const int64_t* bank_labels, long n_bank,
+                  int n_classes, int weights, float temperature, int64_t* pred, double* scores, int* status,
+                  vsom_stream_t stream);
+
 /* SOMLayer.som_loss(weights, distances) = mean(weights * distances) for ARBITRARY weights (som_layer.py:137-142):
    loss_sum <- sum_ik weights[i,k] dist[i,k]; with coef/row_dot/col_dot given, also the backward coefficients of
    grad_scale * that sum w.r.t. the distances' inputs (what vsom_som_bwd consumes) -- with weights = an upstream

@@ -149,6 +149,11 @@ SIGNATURES = {
     "vsom_umap_neg_sample": (C.c_long, [C.c_uint64, C.c_int, C.c_long, C.c_long, C.c_long]),
     "vsom_umap_epoch": (C.c_int, [c_fp] * 8 + [C.c_long, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
                                                C.c_uint64, c_stream]),
+    "vsom_knn_query_workspace_bytes": (C.c_size_t, [C.c_long, C.c_long, C.c_int]),
+    "vsom_knn_query": (C.c_int, [c_fp, C.c_long, C.c_long, c_fp, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int,
+                                 c_fp, c_fp, c_fp, c_fp, C.c_size_t, c_stream]),
+    "vsom_knn_vote": (C.c_int, [c_fp, c_fp, C.c_long, C.c_int, c_fp, C.c_long, C.c_int, C.c_int, C.c_float, c_fp, c_fp, c_fp,
+                                c_stream]),
     "vsom_fill": (C.c_int, [c_fp, C.c_long, C.c_float, c_stream]),
     "vsom_scaled_mul": (C.c_int, [c_fp, c_fp, c_fp, C.c_long, c_fp, C.c_float, c_stream]),
     "vsom_som_weighted_loss": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_float, c_fp, c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_int,

@@ -7,20 +7,12 @@
 //   vsom_umap_epoch   one synchronous epoch of optimize_layout_euclidean: one thread per vertex, walking its CSR row.
 //
 // No floating-point atomics anywhere and every sum has one fixed order: a fit is bitwise reproducible.
-#include "gemm_f32.h"
+#include "knn_common.h"
 
 namespace vsom {
 namespace {
 
-constexpr int KNN_BM = 128;                  // rows per workgroup (4 waves x 32)
-constexpr int KNN_BN = 64;                   // columns per tile (two 32 x 32 accumulators per wave)
-constexpr int KNN_THREADS = 256;
-constexpr int KNN_MAX_K = 64;                // one list entry per lane
-constexpr int KNN_TARGET_BLOCKS = 2048;      // workgroups wanted per launch (8 per CU): the column chunking stops there
-constexpr int KNN_MERGE_ROWS = 4;            // rows per merge workgroup (one wave each)
-constexpr int EPOCH_THREADS = 256;
-
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
+constexpr int EPOCH_THREADS = 256;            // the kNN tile, list and order definitions: knn_common.h
 
 // (row blocks, column tiles, chunks): chunks split every row's columns so that a small N still fills the GPU; the
 // candidate buffer holds chunks * N * k entries, at most about max(N, KNN_TARGET_BLOCKS * KNN_BM) * k.
@@ -66,63 +58,6 @@ __host__ __device__ __forceinline__ uint64_t umap_neg_hash(uint64_t seed, int ep
     return splitmix64(splitmix64(seed ^ (uint64_t)edge) ^ (((uint64_t)(uint32_t)epoch << 32) | (uint64_t)(uint32_t)p));
 }
 
-// Squared row norms in the order in which the MFMA loop of umap_knn_tile_kernel sums a row's products with itself:
-// in groups of 8, k = kb + s then kb + 4 + s for s = 0..3 (lane half h feeds k = kb + 4h + s to MFMA step s; the
-// instruction is bitwise fma(a_k1 b_k1, fma(a_k0 b_k0, c))).  So sq[i] is <x_i, x_i> of the contraction bit for bit,
-// and the euclidean distance between two identical rows is exactly 0.
-__global__ __launch_bounds__(256) void umap_sqnorm_kernel(const float* __restrict__ X, long ldx, long N, int D,
-                                                         float* __restrict__ sq) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const float* x = X + i * ldx;
-    float s = 0.f;
-    for (int kb = 0; kb < D; kb += 8) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float a0 = kb + j < D ? x[kb + j] : 0.f;
-            const float a1 = kb + 4 + j < D ? x[kb + 4 + j] : 0.f;
-            s = fmaf(a0, a0, s);
-            s = fmaf(a1, a1, s);
-        }
-    }
-    sq[i] = s;
-}
-
-// Strict total order of the lists: (distance, index) lexicographic.
-__device__ __forceinline__ bool knn_less(float d0, int i0, float d1, int i1) { return d0 < d1 || (d0 == d1 && i0 < i1); }
-
-// Insert the wave's candidates (lane l offers (cd, ci)) into a row's sorted list (lane j < k holds entry j), lowest
-// lane first.  The result is the k smallest of list and candidates in (distance, index) order: it does not depend on
-// the order of insertion, hence neither on the tiling nor on the chunking.
-__device__ __forceinline__ void knn_insert(float& ld, int& li, float cd, int ci, int k, int lane) {
-    const float kd = __shfl(ld, k - 1, 64);
-    const int ki = __shfl(li, k - 1, 64);
-    unsigned long long mask = __ballot(knn_less(cd, ci, kd, ki));
-    while (mask) {
-        const int s = __builtin_ctzll(mask);
-        mask &= mask - 1;
-        const float xd = __shfl(cd, s, 64);
-        const int xi = __shfl(ci, s, 64);
-        const int pos = __popcll(__ballot(lane < k && knn_less(ld, li, xd, xi)));
-        const float ud = __shfl_up(ld, 1, 64);
-        const int ui = __shfl_up(li, 1, 64);
-        if (pos < k) {
-            if (lane > pos) { ld = ud; li = ui; }
-            else if (lane == pos) { ld = xd; li = xi; }
-        }
-    }
-}
-
-// Distance from the dot product and the two squared norms (umap-learn's definitions; cosine of a zero row: 0 against
-// another zero row, 1 against any other row).
-__device__ __forceinline__ float knn_distance(float dot, float si, float sj, int metric) {
-    if (metric == VSOM_DIST_EUCLIDEAN) return sqrtf(fmaxf(si + sj - 2.f * dot, 0.f));
-    if (si == 0.f && sj == 0.f) return 0.f;
-    if (si == 0.f || sj == 0.f) return 1.f;
-    if (dot == si && dot == sj) return 0.f;                          // identical rows
-    return fmaxf(1.f - dot / (sqrtf(si) * sqrtf(sj)), 0.f);
-}
-
 struct KnnP {
     const float* X;
     long ldx;
@@ -136,7 +71,7 @@ struct KnnP {
 };
 
 // One workgroup = 128 rows x one column chunk.  Per 64-column tile: the 128 x 64 block of X X^T on the f32 matrix
-// cores (wave w owns rows 32w..32w+31; operand tiles staged global -> registers -> LDS as in gemm_f32_kernel), the
+// cores (knn_tile_dots in knn_common.h: wave w owns rows 32w..32w+31), the
 // distances into LDS, then every wave folds each of its 32 rows' 64 candidates into that row's list (registers: lane j
 // holds entry j).  Row i against itself gets distance -1: it sorts before every real distance (>= 0) and is written
 // out as 0, so row i comes first even when a duplicate of it has a lower index.  At the end the lists go to the
@@ -146,8 +81,6 @@ __global__ __launch_bounds__(KNN_THREADS) void umap_knn_tile_kernel(const KnnP p
     constexpr int BM = KNN_BM, BN = KNN_BN;
     __shared__ __attribute__((aligned(16))) float lds[(BM + BN) * 36];
     __shared__ float sd[BM][BN + 1];
-    float* As = lds;
-    float* Bs = lds + BM * 36;
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -155,70 +88,20 @@ __global__ __launch_bounds__(KNN_THREADS) void umap_knn_tile_kernel(const KnnP p
     const int bm0 = blockIdx.x * BM;
     const int chunk = blockIdx.y;
     const int ct0 = (int)((long)chunk * p.ct / p.chunks), ct1 = (int)((long)(chunk + 1) * p.ct / p.chunks);
-    const int K = p.D, ktiles = (K + 31) >> 5;
 
     float ld_[32];
     int li_[32];
 #pragma unroll
     for (int rr = 0; rr < 32; ++rr) { ld_[rr] = INFINITY; li_[rr] = 0x7fffffff; }
 
-    StageRegs<BM> sa;
-    StageRegs<BN> sb;
-    __amdgpu_buffer_rsrc_t rs;
-    OffKC<BM> oa;
-    OffKC<BN> ob;
-    if constexpr (FAST) {
-        rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.X), 0, (int)p.x_bytes, 0x00020000);
-        init_kc<BM>(oa, p.ldx, bm0, p.N, t);
-    }
+    const KnnOperand X = {p.X, p.ldx, p.N, p.x_bytes, p.vec};
+    KnnStage<FAST> st;
+    knn_stage_init<FAST>(st, X, bm0, X, t);
 
     for (int ctile = ct0; ctile < ct1; ++ctile) {
         const int bn0 = ctile * BN;
-        if constexpr (FAST) init_kc<BN>(ob, p.ldx, bn0, p.N, t);
-        auto gload = [&](int kt) {
-            const int k0 = kt << 5;
-            if constexpr (FAST) {
-                load_kc_fast<BM>(sa, rs, oa, k0, K, t);
-                load_kc_fast<BN>(sb, rs, ob, k0, K, t);
-            } else {
-                load_kc<BM>(sa, p.X, p.ldx, bm0, p.N, k0, K, p.vec, t);
-                load_kc<BN>(sb, p.X, p.ldx, bn0, p.N, k0, K, p.vec, t);
-            }
-        };
-        auto lstore = [&]() {
-            store_kc<BM>(sa, As, t);
-            store_kc<BN>(sb, Bs, t);
-        };
         f32x16 acc[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[j][v] = 0.f;
-        auto mfma_tile = [&]() {
-#pragma unroll
-            for (int kb = 0; kb < 32; kb += 8) {
-                const f32x4 a = *reinterpret_cast<const f32x4*>(As + (wm0 + r) * 36 + kb + 4 * h);
-                f32x4 b[2];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) b[j] = *reinterpret_cast<const f32x4*>(Bs + (j * 32 + r) * 36 + kb + 4 * h);
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b[j][s], acc[j], 0, 0, 0);
-            }
-        };
-        gload(0);
-        lstore();
-        __syncthreads();
-        for (int kt = 0; kt + 1 < ktiles; ++kt) {
-            gload(kt + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_tile();
-            __syncthreads();
-            lstore();
-            __syncthreads();
-        }
-        mfma_tile();
+        knn_tile_dots<FAST>(st, X, bm0, X, bn0, p.D, lds, t, acc);
 
         // accumulator register v of tile j: row (v & 3) + 8 (v >> 2) + 4h, column 32j + r
 #pragma unroll
@@ -361,7 +244,7 @@ int vsom_umap_knn(const float* X, long ldx, long N, int D, int k, int metric, in
                  "umap_knn: workspace too small or misaligned");
     const KnnPlan pl = knn_plan(N);
     const KnnWs w = knn_layout(ws, N, k);
-    VSOM_LAUNCH(umap_sqnorm_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, X, ldx, N, D, w.sq);
+    VSOM_LAUNCH(knn_sqnorm_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, X, ldx, N, D, w.sq);
     KnnP p = {};
     p.X = X; p.ldx = ldx; p.N = (int)N; p.D = D; p.k = k; p.metric = metric; p.sq = w.sq;
     p.cand_d = w.cand_d; p.cand_i = w.cand_i; p.ct = pl.ct; p.chunks = pl.chunks;

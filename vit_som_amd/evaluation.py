@@ -13,6 +13,9 @@ visualize_label_heatmap (:224-265) folds (BMU, label) pairs into a last-label-pe
 Map quality has no counterpart in the reference: evaluate_map_quality folds the distances and BMUs every predict() leaves
 in the SOM layer's buffers into quantization error, topographic error, hit map and nearest sample per unit
 (`vsom_map_stats`), umatrix / visualize_umatrix / visualize_hit_map draw the map without labels (`vsom_umatrix`).
+evaluate_knn (no counterpart either) asks how much class information the latents carry: every test sample is classified by
+a weighted vote of its k nearest training samples in latent space (knn.py: `vsom_knn_query` / `vsom_knn_vote`), the training
+set streamed through a fixed-size device buffer.
 """
 import os
 import time
@@ -23,6 +26,7 @@ import torch
 
 from . import ops
 from .kmeans import KMeans
+from .knn import KNNClassifier
 from .umap import UMAP
 
 
@@ -537,6 +541,117 @@ def visualize_hit_map(model, config, dataloader, output_dir="experiments/plots")
         if _draw_map("visualize_hit_map", hits, "samples", True, path) is not None:
             print(f"Saved hit map visualization to {output_dir}")
     return hits
+
+
+# ------------------------------------------------------------------------------------ kNN probe
+@dataclass
+class KNNReport:
+    """Host values of one evaluate_knn pass.  confusion[t, p] counts the test samples of class t predicted as p."""
+    accuracy: float
+    per_class_accuracy: np.ndarray       # float64 [C]: NaN for a class without a test sample
+    confusion: np.ndarray                # int64 [C, C]
+    n_train: int                         # bank rows (over all ranks)
+    n_test: int                          # queries (over all ranks)
+    k: int
+    inference_time: float
+
+
+def _knn_features(model, arch):
+    """x -> the [B, D] float32 features the probe compares (views of the model's buffers: copy before the next batch)."""
+    if arch == "vit_som" and hasattr(model, "get_latent_representation"):
+        return lambda x, C, S: model.get_latent_representation(x.reshape(-1, C, S, S))
+    if arch == "desom" and hasattr(model, "autoencoder"):
+        return lambda x, C, S: model(x.reshape(x.shape[0], -1))[1]
+    raise ValueError(f"evaluate_knn: needs a vit_som model (get_latent_representation) or a desom model (x_encoded); got "
+                     f"{type(model).__name__} with model_arch {arch!r}")
+
+
+def evaluate_knn(model, config, train_loader, test_loader, k=20, weights="softmax", metric="cosine", temperature=0.07,
+                 bank_rows=4096, num_labels=None):
+    """k-nearest-neighbour probe of the latents -> KNNReport: every sample of test_loader is classified by the weighted vote
+    (KNNClassifier) of its k nearest samples of train_loader in feature space; nothing is trained.  Features: for vit_som
+    model.get_latent_representation(x) (what visualize_umap_progression embeds), for desom the x_encoded that
+    evaluate_kmeans clusters; any other model raises ValueError.
+    Pass 1 keeps the test features and labels on the device.  Pass 2 copies each training batch's features into a buffer of
+    `bank_rows` rows (the loaders and the model reuse their buffers: features are copied, never kept as views) and folds the
+    buffer into the neighbour lists whenever it is full and once at the end, so the query matrix is re-read once per
+    `bank_rows` training rows, not once per batch; the lists do not depend on bank_rows (knn.py).  Then one vote launch and one
+    `vsom_contingency` launch.  No host synchronisation inside either loop.  Labels must lie in [0, num_labels) (default
+    data.num_classes, or 256 when the config has none; at most 1024).
+    With model.world_size > 1 each rank keeps its own shard of the test queries and every bank buffer is all-gathered
+    (rank 0's rows first) before it is folded, so every rank must see the same number of training rows; the confusion
+    counts are summed over the ranks and every rank returns the whole set's report."""
+    model.eval()
+    d = config["data"]
+    C, S = d["num_channels"], d["input_size"]
+    feats = _knn_features(model, config["hyperparameters"]["model_arch"])
+    dev = model.arena.device
+    L = int(num_labels) if num_labels else (int(d.get("num_classes", 0)) if int(d.get("num_classes", 0)) > 0 else 256)
+    bank_rows = int(bank_rows)
+    if bank_rows < 1:
+        raise ValueError(f"evaluate_knn: bank_rows must be positive, got {bank_rows}")
+    clf = KNNClassifier(n_neighbors=k, weights=weights, metric=metric, temperature=temperature, n_classes=L)
+    clf._validate()
+    world, start = _world(model), time.time()
+    queries, labels = [], []
+    with torch.no_grad():
+        for x, y in test_loader:
+            f = feats(x.to(dev, non_blocking=True), C, S)
+            queries.append(f.reshape(f.shape[0], -1).float().clone())
+            labels.append(y.to(dev, non_blocking=True).reshape(-1).long())
+        if not queries:
+            raise ValueError("evaluate_knn: the test loader is empty")
+        Q, yq = torch.cat(queries).contiguous(), torch.cat(labels).contiguous()
+        clf.partial_fit_query(Q)
+        buf = torch.empty(bank_rows, Q.shape[1], dtype=torch.float32, device=dev)
+        ybuf = torch.empty(bank_rows, dtype=torch.int64, device=dev)
+        fill = 0
+
+        def fold(n):
+            bx, by = buf[:n], ybuf[:n]
+            if world > 1:
+                bx, by = _gather_rows(bx, world).contiguous(), _gather_rows(by, world).contiguous()
+            if bx.shape[0]:
+                clf.update(bx, by)
+
+        for x, y in train_loader:
+            f = feats(x.to(dev, non_blocking=True), C, S)
+            f = f.reshape(f.shape[0], -1)
+            y = y.to(dev, non_blocking=True).reshape(-1)
+            off = 0
+            while off < f.shape[0]:
+                n = min(f.shape[0] - off, bank_rows - fill)
+                buf[fill:fill + n].copy_(f[off:off + n])
+                ybuf[fill:fill + n].copy_(y[off:off + n])
+                fill, off = fill + n, off + n
+                if fill == bank_rows:
+                    fold(fill)
+                    fill = 0
+        if fill or world > 1:
+            fold(fill)
+    n_train = clf._seen
+    if n_train < clf.n_neighbors:
+        raise ValueError(f"evaluate_knn: k={clf.n_neighbors} exceeds the {n_train} training samples")
+    pred = clf.predict()
+    table = _Table(L, L, dev)
+    table.add(yq, pred)                                   # cm[true, pred]; a label outside [0, L) is counted and raises below
+    cm = table.numpy(world)
+    refused = clf._status[:1].long()
+    if world > 1:
+        import torch.distributed as dist
+        dist.all_reduce(refused)
+    if int(refused.item()):
+        raise ValueError(f"evaluate_knn: {int(refused.item())} neighbour labels fell outside [0, {L}); pass num_labels= for larger label sets")
+    inference_time = time.time() - start
+    true_sum = cm.sum(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        per_class = np.where(true_sum > 0, np.diag(cm) / true_sum, np.nan)
+    n_test = int(cm.sum())
+    report = KNNReport(accuracy=float(np.diag(cm).sum() / n_test) if n_test else float("nan"), per_class_accuracy=per_class,
+                       confusion=cm.astype(np.int64), n_train=int(n_train), n_test=n_test, k=int(clf.n_neighbors),
+                       inference_time=inference_time)
+    print(f"kNN accuracy (k={report.k}, {weights}, {metric}): {report.accuracy:.3f}, Inference Time: {inference_time:.3f}")
+    return report
 
 
 def evaluate_classification(model, config, dataloader):

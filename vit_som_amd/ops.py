@@ -966,6 +966,48 @@ def umap_epoch(indptr, indices, eps, next_s, eps_neg, next_neg, Y_in, Y_out, a, 
     return Y_out
 
 
+# ---------------------------------------------------------------- kNN probe (evaluate_knn)
+KNN_MAX_K = 64                                                   # csrc/knn_common.h: one list entry per lane
+KNN_MAX_CLASSES = 1024                                           # csrc/knn.hip: the vote's LDS score table
+KNN_UNIFORM, KNN_DISTANCE, KNN_SOFTMAX = 0, 1, 2                 # VSOM_KNN_*
+
+
+def knn_query(Q, X, k, metric, idx, dist, index_base=0, accumulate=False, exclude=None):
+    """idx int64 [Nq, k] / dist f32 [Nq, k]: the exact k nearest rows of the bank chunk X for every row of Q, as
+    index_base + row, ascending by (distance, index); with accumulate the lists already in idx / dist (from other index
+    ranges) are folded with this chunk.  exclude int64 [Nq]: a global bank ordinal each query never receives."""
+    Nq, D, ldq = _kmeans_x(Q)
+    Nb, Db, ldx = _kmeans_x(X)
+    assert Db == D, "Q and X must have the same width"
+    assert idx.dtype == torch.int64 and idx.is_contiguous() and idx.shape == (Nq, k)
+    _f32(dist, "dist")
+    assert dist.is_contiguous() and dist.shape == (Nq, k)
+    if exclude is not None:
+        assert exclude.dtype == torch.int64 and exclude.is_cuda and exclude.is_contiguous() and exclude.numel() == Nq
+    ws = scratch(lib.vsom_knn_query_workspace_bytes(Nq, Nb, k), Q.device)
+    check(lib.vsom_knn_query(ptr(Q), ldq, Nq, ptr(X), ldx, Nb, D, int(k), int(metric), int(index_base), int(bool(accumulate)),
+                             ptr(exclude), ptr(idx), ptr(dist), ptr(ws), ws.numel(), stream()), "vsom_knn_query")
+    return idx, dist
+
+
+def knn_vote(idx, dist, bank_labels, n_classes, weights, temperature, pred, status, scores=None):
+    """pred int64 [Nq] = first argmax of the fp64 class scores of each query's neighbour list (weights KNN_UNIFORM /
+    KNN_DISTANCE / KNN_SOFTMAX); scores fp64 [Nq, n_classes] optionally; status int32 [2] (zeroed by the caller) counts
+    refused neighbours and queries left without one (pred -1)."""
+    Nq, k = idx.shape
+    assert idx.dtype == torch.int64 and idx.is_cuda and idx.is_contiguous()
+    _f32(dist, "dist")
+    assert dist.is_contiguous() and dist.shape == (Nq, k)
+    assert bank_labels.dtype == torch.int64 and bank_labels.is_cuda and bank_labels.is_contiguous()
+    assert pred.dtype == torch.int64 and pred.is_contiguous() and pred.numel() == Nq
+    assert status.dtype == torch.int32 and status.numel() == 2 and status.is_cuda
+    if scores is not None:
+        assert scores.dtype == torch.float64 and scores.is_contiguous() and scores.shape == (Nq, n_classes)
+    check(lib.vsom_knn_vote(ptr(idx), ptr(dist), Nq, k, ptr(bank_labels), bank_labels.numel(), int(n_classes), int(weights),
+                            float(temperature), ptr(pred), ptr(scores), ptr(status), stream()), "vsom_knn_vote")
+    return pred
+
+
 # ---------------------------------------------------------------- data-parallel exchange (RCCL)
 COMM_ID_BYTES = 128
 

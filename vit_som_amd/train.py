@@ -27,7 +27,7 @@ import numpy as np
 import torch
 import yaml
 
-from .evaluation import evaluate_classification, evaluate_clustering, evaluate_map_quality
+from .evaluation import evaluate_classification, evaluate_clustering, evaluate_knn, evaluate_map_quality
 from .classifier import ViTClassifier
 from .model import ViTSOM
 
@@ -274,11 +274,14 @@ def main_vit(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, 
     return all_metrics
 
 
-def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print, map_quality=False):
+def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print, map_quality=False,
+         knn_eval=False):
     """train_vit_som.py:27-130; a config with hyperparameters.model_arch == "vit" runs main_vit (train_vit.py) instead.
     model_states_dir defaults to experiments/states/vit_som (experiments/states/vit for the ViT baseline).
     map_quality: after each run's final evaluation also run evaluate_map_quality on the training loader with the model that
-    was evaluated, and report quantization_error / topographic_error next to the other metrics (ViT-SOM only)."""
+    was evaluated, and report quantization_error / topographic_error next to the other metrics (ViT-SOM only).
+    knn_eval: likewise run evaluate_knn with that model (bank = the training loader, queries = the test loader) and report
+    knn_accuracy."""
     if config["hyperparameters"].get("model_arch") == "vit":
         return main_vit(config, n_runs=n_runs, max_epochs=max_epochs, make_loaders=make_loaders,
                         model_states_dir=model_states_dir or "experiments/states/vit", log=log)
@@ -298,6 +301,8 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
     all_metrics = {k: [] for k in ("accuracy", "precision", "recall", "f1", "purity", "nmi", "run_duration", "inference_time")}
     if map_quality:
         all_metrics.update(quantization_error=[], topographic_error=[])
+    if knn_eval:
+        all_metrics.update(knn_accuracy=[])
     for run in range(n_runs):
         log(f"Starting run {run + 1} for {dataset_name}...")
         start = time.time()
@@ -335,6 +340,10 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
                 f"dead units {mq.dead_units}/{mq.hits.size}")
             all_metrics["quantization_error"].append(mq.quantization_error)
             all_metrics["topographic_error"].append(mq.topographic_error)
+        if knn_eval:
+            kr = evaluate_knn(evaluated, config, train_loader, test_loader)
+            log(f"kNN probe: accuracy {kr.accuracy:.4f} (k={kr.k}, {kr.n_train} training / {kr.n_test} test samples)")
+            all_metrics["knn_accuracy"].append(kr.accuracy)
         all_metrics["run_duration"].append(run_duration)
         all_metrics["inference_time"].append(inf_t)
     if n_runs > 1:
@@ -342,7 +351,7 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
     return all_metrics
 
 
-if __name__ == "__main__":
+def _parser():
     ap = argparse.ArgumentParser(description="ViT-SOM / ViT training driver (MI355X)")
     ap.add_argument("--config", type=str, required=True)
     ap.add_argument("--runs", type=int, default=5)
@@ -353,8 +362,15 @@ if __name__ == "__main__":
                     help="also apply the config's RandAugment / timm rand-m9 auto-augment on the GPU (implies --device-data)")
     ap.add_argument("--map-quality", action="store_true",
                     help="after each run also report the map's quantization and topographic error on the training set")
-    a = ap.parse_args()
+    ap.add_argument("--knn-eval", action="store_true",
+                    help="after each run also report the k-nearest-neighbour accuracy of the latents (bank: training set, queries: test set)")
+    return ap
+
+
+if __name__ == "__main__":
+    a = _parser().parse_args()
     loaders = synthetic_loaders
     if a.device_data or a.data_npz or a.device_randaug:
         loaders = lambda c, r, w: device_loaders(c, r, w, npz=a.data_npz, auto_augment=a.device_randaug)     # noqa: E731
-    main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs, make_loaders=loaders, map_quality=a.map_quality)
+    main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs, make_loaders=loaders, map_quality=a.map_quality,
+         knn_eval=a.knn_eval)
