@@ -479,7 +479,12 @@ int vsom_kmeans_colvar(const float* X, long ldx, long N, int D, int k, double* o
  * metric VSOM_DIST_EUCLIDEAN: the true distance sqrt(max(|x|^2 + |y|^2 - 2 <x,y>, 0)); VSOM_DIST_COSINE:
  * 1 - <x,y> / (|x| |y|) clamped at 0, 0 when both rows are zero and 1 when exactly one is.  <x,y> is an f32 matrix-core
  * contraction; the squared norms are summed in its order, so identical rows are at distance exactly 0.
- * 1 <= k <= 64, k < N.  Workspace: vsom_umap_knn_workspace_bytes(N, k) (host arithmetic; 0 for a non-positive size). */
+ * This is the search of vsom_knn_query with the set as its own bank (one kernel, csrc/knn.hip); only here is row i put
+ * first.
+ * 1 <= k <= 64, k < N.  Workspace: vsom_umap_knn_workspace_bytes(N, k) (host arithmetic; 0 for a non-positive size): the
+ * N squared norms and two candidate slabs (f32 distances, i32 rows) of chunks * rb * 128 * k entries each, rb =
+ * ceil(N / 128) row blocks and chunks = min(ceil(N / 64), ceil(2048 / rb)) column chunks, every section rounded up to
+ * 256 bytes; at least 8 N k bytes. */
 size_t vsom_umap_knn_workspace_bytes(long N, int k);
 int vsom_umap_knn(const float* X, long ldx, long N, int D, int k, int metric, int64_t* knn_idx, float* knn_dist, void* ws,
                   size_t ws_bytes, vsom_stream_t stream);

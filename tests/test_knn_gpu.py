@@ -202,7 +202,8 @@ def test_element_wise_loads_give_the_same_bits(lists_333):
 @pytest.mark.parametrize("metric", ["cosine", "euclidean"])
 def test_leave_one_out_equals_umap_knn(metric, N):
     """Queries = bank with exclude = arange(N): no row returns itself, and the lists are columns 1 .. k of vsom_umap_knn
-    with k + 1 on the same data (no duplicate rows), distances bit for bit: the shared header, pinned from both sides."""
+    with k + 1 on the same data (no duplicate rows), distances bit for bit: the query and the self mode of the one search,
+    held together."""
     from vit_som_amd import ops
     D, k = 32, 15
     X = _randn(1, N, D, seed=5)[1].to(DEV)
@@ -217,6 +218,36 @@ def test_leave_one_out_equals_umap_knn(metric, N):
     # without exclude every row finds itself first, at exactly 0
     idx0, dist0 = _query(X, X, k, metric)
     assert torch.equal(idx0[:, 0], ar) and (dist0[:, 0] == 0).all() and torch.equal(idx0[:, 1:], idx[:, :-1])
+
+
+@pytest.mark.parametrize("N,D", [(461, 32), (130, 3)])                 # 130 x 3: two row blocks, element-wise loads, D below one 8-group
+@pytest.mark.parametrize("metric", ["cosine", "euclidean"])
+def test_self_mode_equals_query_mode_with_duplicates(metric, N, D):
+    """Rows 3, 5 and N // 2 identical, row 7 zero.  vsom_knn_query(X, X) holds row i in its own list at exactly 0, among its
+    duplicates by index; moved to the front, the list is vsom_umap_knn's bit for bit.  A row without a duplicate is first
+    already."""
+    from vit_som_amd import ops
+    k = 15
+    X = _randn(1, N, D, seed=6)[1]
+    X[5] = X[3]
+    X[N // 2] = X[3]
+    X[7] = 0.0
+    X = X.to(DEV)
+    ar = torch.arange(N, device=DEV)
+    idx, dist = _query(X, X, k, metric)
+    own = idx == ar[:, None]
+    assert (own.sum(1) == 1).all() and (dist[own] == 0).all()
+    slot = torch.arange(k, device=DEV).expand(N, k)
+    order = torch.where(own, -1, slot).argsort(dim=1, stable=True)     # the row's own entry first, the rest as they were
+    qi, qd = idx.gather(1, order), dist.gather(1, order)
+    ui = torch.full((N, k), -7, dtype=torch.int64, device=DEV)
+    ud = torch.full((N, k), -7.0, dtype=torch.float32, device=DEV)
+    ops.umap_knn(X, k, METRIC[metric], ui, ud)
+    assert torch.equal(ui, qi) and torch.equal(ud, qd)
+    single = torch.ones(N, dtype=torch.bool, device=DEV)
+    single[[3, 5, N // 2]] = False
+    assert torch.equal(ui[single], idx[single]) and torch.equal(ud[single], dist[single])
+    assert ui[5, :3].tolist() == [5, 3, N // 2] and ud[5, :3].tolist() == [0.0, 0.0, 0.0]
 
 
 # ------------------------------------------------------------------ 6. reproducibility

@@ -60,6 +60,7 @@ inline void launch_or_record(F&& f, const char* what) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }       // workspace sections
 
 // ---------------------------------------------------------------- device helpers
 __device__ __forceinline__ float wave_sum(float v) {

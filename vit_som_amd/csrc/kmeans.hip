@@ -25,8 +25,6 @@ constexpr size_t KM_SLAB_BUDGET = size_t(128) << 20;
 constexpr int KM_COLVAR_CHUNKS = 64;
 constexpr int KM_RED_THREADS = 256;
 
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
-
 // Workgroups of the assign pass: one per CU, fewer when the [G, k, D] slabs would pass 128 MiB (large k * D).
 inline int km_groups(long N, int D, int k) {
     const size_t per = (size_t)k * (size_t)D * 4 + (size_t)k * 4;

@@ -1,22 +1,184 @@
-// k-nearest-neighbour probe (evaluate_knn; no counterpart in the reference): the neighbours of one set (queries) in
-// another (the bank), streamed bank chunk by bank chunk, and the weighted class vote over them.
+// Exact k nearest neighbours on the f32 matrix cores, one search path behind two entry points, and the class vote of the
+// kNN probe (evaluate_knn; no counterpart in the reference).
 //
-//   vsom_knn_query   exact k nearest bank rows of every query (euclidean or cosine): the Q X^T contraction on the f32
-//                    matrix cores (knn_common.h: the tile, the order and the distance vsom_umap_knn uses), a per-query
-//                    top-k kept across a workgroup's column chunk, then a fixed-order merge of the per-chunk lists that
-//                    also takes the list already in the output when `accumulate` is set.
+//   vsom_knn_query   the k nearest rows of a bank chunk for every query (euclidean or cosine), the bank streamed chunk by
+//                    chunk: a fixed-order merge of the per-chunk lists also takes the list already in the output when
+//                    `accumulate` is set.
+//   vsom_umap_knn    the same search of a set among itself (UMAP's kNN graph): the self mode of the same kernels, which
+//                    puts row i first in its own list at distance 0, before any duplicate of it with a lower index.
 //   vsom_knn_vote    one wave per query: fp64 class scores in neighbour order, first argmax.
 //
+// The contract both entry points keep, written once below:
+//   - the 128 x 64 tile of dot products (knn_tile_dots), every (row, row) pair summed over D in one fixed order that
+//     depends neither on where the two rows fall in a tile nor on the sizes of the two sets;
+//   - the squared norms summed in that same order (knn_sqnorm_kernel), so identical rows are at distance exactly 0;
+//   - the distance from (dot, norm, norm) (knn_distance);
+//   - the strict (distance, index) total order of the lists and the order-independent insertion (knn_less, knn_insert).
 // No floating-point atomics and every sum has one fixed order: results are bitwise reproducible, and folding a bank in
 // any number of pieces, in any order, gives bit for bit the lists of one call over the whole bank.
-#include "knn_common.h"
+#include "gemm_f32.h"
 
 namespace vsom {
 namespace {
 
+constexpr int KNN_BM = 128;                  // rows per workgroup (4 waves x 32)
+constexpr int KNN_BN = 64;                   // columns per tile (two 32 x 32 accumulators per wave)
+constexpr int KNN_THREADS = 256;
+constexpr int KNN_MAX_K = 64;                // one list entry per lane
+constexpr int KNN_TARGET_BLOCKS = 2048;      // workgroups wanted per launch (8 per CU): the column chunking stops there
+constexpr int KNN_MERGE_ROWS = 4;            // rows per merge workgroup (one wave each)
 constexpr int VOTE_WAVES = 4;                // queries per vote workgroup (one wave each)
 constexpr int VOTE_MAX_CLASSES = 1024;       // fp64 LDS score table per wave: 4 x 8 KB
 constexpr int64_t KNN_NO_INDEX = 0x7fffffffffffffffLL;      // sorts after every real ordinal; stored as -1
+
+// Squared row norms in the order in which the MFMA loop of knn_tile_dots sums a row's products with itself:
+// in groups of 8, k = kb + s then kb + 4 + s for s = 0..3 (lane half h feeds k = kb + 4h + s to MFMA step s; the
+// instruction is bitwise fma(a_k1 b_k1, fma(a_k0 b_k0, c))).  So sq[i] is <x_i, x_i> of the contraction bit for bit,
+// and the euclidean distance between two identical rows is exactly 0.
+__global__ __launch_bounds__(256) void knn_sqnorm_kernel(const float* __restrict__ X, long ldx, long N, int D,
+                                                        float* __restrict__ sq) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const float* x = X + i * ldx;
+    float s = 0.f;
+    for (int kb = 0; kb < D; kb += 8) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float a0 = kb + j < D ? x[kb + j] : 0.f;
+            const float a1 = kb + 4 + j < D ? x[kb + 4 + j] : 0.f;
+            s = fmaf(a0, a0, s);
+            s = fmaf(a1, a1, s);
+        }
+    }
+    sq[i] = s;
+}
+
+// Strict total order of the lists: (distance, index) lexicographic.  I is int (row of this launch) or int64_t (global ordinal).
+template <class I>
+__device__ __forceinline__ bool knn_less(float d0, I i0, float d1, I i1) { return d0 < d1 || (d0 == d1 && i0 < i1); }
+
+// Insert the wave's candidates (lane l offers (cd, ci)) into a row's sorted list (lane j < k holds entry j), lowest
+// lane first.  The result is the k smallest of list and candidates in (distance, index) order: it does not depend on
+// the order of insertion, hence neither on the tiling nor on the chunking.
+template <class I>
+__device__ __forceinline__ void knn_insert(float& ld, I& li, float cd, I ci, int k, int lane) {
+    const float kd = __shfl(ld, k - 1, 64);
+    const I ki = __shfl(li, k - 1, 64);
+    unsigned long long mask = __ballot(knn_less(cd, ci, kd, ki));
+    while (mask) {
+        const int s = __builtin_ctzll(mask);
+        mask &= mask - 1;
+        const float xd = __shfl(cd, s, 64);
+        const I xi = __shfl(ci, s, 64);
+        const int pos = __popcll(__ballot(lane < k && knn_less(ld, li, xd, xi)));
+        const float ud = __shfl_up(ld, 1, 64);
+        const I ui = __shfl_up(li, 1, 64);
+        if (pos < k) {
+            if (lane > pos) { ld = ud; li = ui; }
+            else if (lane == pos) { ld = xd; li = xi; }
+        }
+    }
+}
+
+// Distance from the dot product and the two squared norms (umap-learn's definitions; cosine of a zero row: 0 against
+// another zero row, 1 against any other row).
+__device__ __forceinline__ float knn_distance(float dot, float si, float sj, int metric) {
+    if (metric == VSOM_DIST_EUCLIDEAN) return sqrtf(fmaxf(si + sj - 2.f * dot, 0.f));
+    if (si == 0.f && sj == 0.f) return 0.f;
+    if (si == 0.f || sj == 0.f) return 1.f;
+    if (dot == si && dot == sj) return 0.f;                          // identical rows
+    return fmaxf(1.f - dot / (sqrtf(si) * sqrtf(sj)), 0.f);
+}
+
+// One operand of the contraction: rows [rows, D] with row stride ld.
+struct KnnOperand {
+    const float* base;
+    long ld;
+    int rows;
+    unsigned bytes;     // FAST path: extent for the bounds-checked buffer loads
+    int vec;            // generic path: 16-byte loads legal
+};
+
+// The operand staging of one workgroup: the row offsets of its 128 A rows are computed once, those of a 64-row B tile
+// once per tile (FAST path only; the generic path indexes from the pointers).
+template <bool FAST>
+struct KnnStage {
+    StageRegs<KNN_BM> sa;
+    StageRegs<KNN_BN> sb;
+    __amdgpu_buffer_rsrc_t rsA, rsB;
+    OffKC<KNN_BM> oa;
+    OffKC<KNN_BN> ob;
+};
+template <bool FAST>
+__device__ __forceinline__ void knn_stage_init(KnnStage<FAST>& st, const KnnOperand& A, int bm0, const KnnOperand& B, int t) {
+    if constexpr (FAST) {
+        st.rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A.base), 0, (int)A.bytes, 0x00020000);
+        st.rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(B.base), 0, (int)B.bytes, 0x00020000);
+        init_kc<KNN_BM>(st.oa, A.ld, bm0, A.rows, t);
+    }
+}
+
+// acc[j] <- the 128 x 64 block <A[bm0 + .], B[bn0 + .]> over K on the f32 matrix cores: wave w owns rows 32w..32w+31,
+// acc[j] columns 32j..32j+31 (register v of acc[j]: row (v & 3) + 8 (v >> 2) + 4h, column 32j + r).  Operand tiles are
+// staged global -> registers -> LDS as in gemm_f32_kernel (lds: (128 + 64) * 36 floats).  Every pair's products are
+// summed k-tile by k-tile, 8-group by 8-group, step s = 0..3 with k = kb + s before kb + 4 + s inside the instruction:
+// one order for every pair.  Rows outside either operand and k >= K contribute exact zeros.  All waves must call it;
+// the caller synchronises before the next call overwrites the LDS tiles.
+template <bool FAST>
+__device__ __forceinline__ void knn_tile_dots(KnnStage<FAST>& st, const KnnOperand& A, int bm0, const KnnOperand& B, int bn0,
+                                              int K, float* lds, int t, f32x16 (&acc)[2]) {
+    constexpr int BM = KNN_BM, BN = KNN_BN;
+    float* As = lds;
+    float* Bs = lds + BM * 36;
+    const int lane = t & 63, wave = t >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int wm0 = wave * 32;
+    const int ktiles = (K + 31) >> 5;
+    if constexpr (FAST) init_kc<BN>(st.ob, B.ld, bn0, B.rows, t);
+    auto gload = [&](int kt) {
+        const int k0 = kt << 5;
+        if constexpr (FAST) {
+            load_kc_fast<BM>(st.sa, st.rsA, st.oa, k0, K, t);
+            load_kc_fast<BN>(st.sb, st.rsB, st.ob, k0, K, t);
+        } else {
+            load_kc<BM>(st.sa, A.base, A.ld, bm0, A.rows, k0, K, A.vec, t);
+            load_kc<BN>(st.sb, B.base, B.ld, bn0, B.rows, k0, K, B.vec, t);
+        }
+    };
+    auto lstore = [&]() {
+        store_kc<BM>(st.sa, As, t);
+        store_kc<BN>(st.sb, Bs, t);
+    };
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[j][v] = 0.f;
+    auto mfma_tile = [&]() {
+#pragma unroll
+        for (int kb = 0; kb < 32; kb += 8) {
+            const f32x4 a = *reinterpret_cast<const f32x4*>(As + (wm0 + r) * 36 + kb + 4 * h);
+            f32x4 b[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) b[j] = *reinterpret_cast<const f32x4*>(Bs + (j * 32 + r) * 36 + kb + 4 * h);
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b[j][s], acc[j], 0, 0, 0);
+        }
+    };
+    gload(0);
+    lstore();
+    __syncthreads();
+    for (int kt = 0; kt + 1 < ktiles; ++kt) {
+        gload(kt + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        mfma_tile();
+        __syncthreads();
+        lstore();
+        __syncthreads();
+    }
+    mfma_tile();
+}
 
 // (query row blocks, bank column tiles, chunks): chunks split the bank's columns so that few queries still fill the GPU.
 struct QueryPlan {
@@ -32,8 +194,10 @@ inline QueryPlan query_plan(long Nq, long Nb) {
 }
 
 // Workspace: sqq f32 [Nq], sqx f32 [Nb], cand_d f32 [chunks][Nq][k], cand_i i32 [chunks][Nq][k], each 256-aligned.  The
-// slabs are sized by a bound on chunks * Nq that grows with Nq -- chunks * rb <= min(ct * rb, KNN_TARGET_BLOCKS - 1 + rb)
-// -- so that the size is monotone in every argument (chunks itself falls as Nq grows).
+// slabs are sized in whole row blocks (Nq <= rb * 128), by a bound on chunks * rb that grows with Nq -- chunks * rb <=
+// min(ct * rb, KNN_TARGET_BLOCKS - 1 + rb) -- so that the size is monotone in every argument (chunks itself falls as Nq
+// grows).  A self search (queries = bank) has the one norm array, sqx = sqq, and one size argument, so no such promise
+// to keep: its slabs hold chunks * rb row blocks exactly.
 inline size_t knn_min(size_t a, size_t b) { return a < b ? a : b; }
 struct QueryWs {
     float* sqq;
@@ -42,15 +206,15 @@ struct QueryWs {
     int* cand_i;
     size_t bytes;
 };
-inline QueryWs query_layout(void* ws, long Nq, long Nb, int k) {
+inline QueryWs query_layout(void* ws, long Nq, long Nb, int k, bool self) {
     const QueryPlan pl = query_plan(Nq, Nb);
-    const size_t blocks = knn_min((size_t)pl.ct * pl.rb, (size_t)KNN_TARGET_BLOCKS - 1 + pl.rb);
-    const size_t sqq = align256((size_t)Nq * 4), sqx = align256((size_t)Nb * 4);
+    const size_t blocks = self ? (size_t)pl.chunks * pl.rb : knn_min((size_t)pl.ct * pl.rb, (size_t)KNN_TARGET_BLOCKS - 1 + pl.rb);
+    const size_t sqq = align256((size_t)Nq * 4), sqx = self ? 0 : align256((size_t)Nb * 4);
     const size_t cand = align256(blocks * KNN_BM * (size_t)k * 4);
     char* p = static_cast<char*>(ws);
     QueryWs w;
     w.sqq = reinterpret_cast<float*>(p);
-    w.sqx = reinterpret_cast<float*>(p + sqq);
+    w.sqx = self ? w.sqq : reinterpret_cast<float*>(p + sqq);
     w.cand_d = reinterpret_cast<float*>(p + sqq + sqx);
     w.cand_i = reinterpret_cast<int*>(p + sqq + sqx + cand);
     w.bytes = sqq + sqx + 2 * cand;
@@ -58,7 +222,7 @@ inline QueryWs query_layout(void* ws, long Nq, long Nb, int k) {
 }
 
 struct QueryP {
-    KnnOperand Q, X;
+    KnnOperand Q, X;            // a self search reads Q and sqq alone
     int D, k, metric;
     const float* sqq;
     const float* sqx;
@@ -73,8 +237,11 @@ struct QueryP {
 // (knn_tile_dots), the distances into LDS, then every wave folds each of its 32 queries' 64 candidates into that
 // query's list (registers: lane j holds entry j).  A column outside the bank, or the one a query excludes, is offered
 // as (+inf, no index): it is never inserted.  At the end the lists go to the chunk's candidate slab.
-template <bool FAST>
-__global__ __launch_bounds__(KNN_THREADS) void knn_query_tile_kernel(const QueryP p) {
+// SELF: the bank is the queries (both operands and both norms are read through Q's pointers), nothing is excluded, and
+// row i against itself gets distance -1: it sorts before every real distance (>= 0) and the merge writes it out as 0, so
+// row i comes first even when a duplicate of it has a lower index.  What SELF turns off is compiled out.
+template <bool FAST, bool SELF>
+__global__ __launch_bounds__(KNN_THREADS) void knn_tile_kernel(const QueryP p) {
     constexpr int BM = KNN_BM, BN = KNN_BN;
     __shared__ __attribute__((aligned(16))) float lds[(BM + BN) * 36];
     __shared__ float sd[BM][BN + 1];
@@ -85,7 +252,9 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_query_tile_kernel(const Query
     const int bm0 = blockIdx.x * BM;
     const int chunk = blockIdx.y;
     const int ct0 = (int)((long)chunk * p.ct / p.chunks), ct1 = (int)((long)(chunk + 1) * p.ct / p.chunks);
-    const int Nq = p.Q.rows, Nb = p.X.rows;
+    const KnnOperand& X = SELF ? p.Q : p.X;
+    const float* sqx = SELF ? p.sqq : p.sqx;
+    const int Nq = p.Q.rows, Nb = X.rows;
 
     float ld_[32];
     int li_[32];
@@ -94,29 +263,31 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_query_tile_kernel(const Query
 
     // the bank row (of this call) each of the wave's queries must not receive: lane rr holds query wm0 + rr's, -1 = none
     int excl = -1;
-    if (p.exclude && lane < 32 && bm0 + wm0 + lane < Nq) {
-        const int64_t e = p.exclude[bm0 + wm0 + lane] - p.index_base;
-        if (e >= 0 && e < Nb) excl = (int)e;
+    if constexpr (!SELF) {
+        if (p.exclude && lane < 32 && bm0 + wm0 + lane < Nq) {
+            const int64_t e = p.exclude[bm0 + wm0 + lane] - p.index_base;
+            if (e >= 0 && e < Nb) excl = (int)e;
+        }
     }
 
     KnnStage<FAST> st;
-    knn_stage_init<FAST>(st, p.Q, bm0, p.X, t);
+    knn_stage_init<FAST>(st, p.Q, bm0, X, t);
 
     for (int ctile = ct0; ctile < ct1; ++ctile) {
         const int bn0 = ctile * BN;
         f32x16 acc[2];
-        knn_tile_dots<FAST>(st, p.Q, bm0, p.X, bn0, p.D, lds, t, acc);
+        knn_tile_dots<FAST>(st, p.Q, bm0, X, bn0, p.D, lds, t, acc);
 
         // accumulator register v of tile j: row (v & 3) + 8 (v >> 2) + 4h, column 32j + r
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int col = j * 32 + r, gj = bn0 + col;
-            const float sj = gj < Nb ? p.sqx[gj] : 0.f;
+            const float sj = gj < Nb ? sqx[gj] : 0.f;
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
                 const int row = wm0 + (v & 3) + 8 * (v >> 2) + 4 * h, gi = bm0 + row;
                 float d = INFINITY;
-                if (gi < Nq && gj < Nb) d = knn_distance(acc[j][v], p.sqq[gi], sj, p.metric);
+                if (gi < Nq && gj < Nb) d = SELF && gi == gj ? -1.f : knn_distance(acc[j][v], p.sqq[gi], sj, p.metric);
                 sd[row][col] = d;
             }
         }
@@ -124,8 +295,9 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_query_tile_kernel(const Query
         const int gj = bn0 + lane;
 #pragma unroll
         for (int rr = 0; rr < 32; ++rr) {
-            const int ex = __shfl(excl, rr, 64);        // by every lane: a shuffle under `gj < Nb` would read inactive lanes as 0
-            const bool ok = gj < Nb && gj != ex;
+            bool ok = gj < Nb;
+            // by every lane, never under a run-time branch: a shuffle under `gj < Nb` would read inactive lanes as 0
+            if constexpr (!SELF) ok &= gj != __shfl(excl, rr, 64);
             knn_insert(ld_[rr], li_[rr], ok ? sd[wm0 + rr][lane] : INFINITY, ok ? gj : 0x7fffffff, p.k, lane);
         }
     }
@@ -142,12 +314,12 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_query_tile_kernel(const Query
 
 // One wave per query: the list already in (idx, dist) when `accumulate` (an entry with idx < 0 is an empty slot), then
 // the per-chunk lists in chunk order, folded into the k smallest by (distance, global ordinal).  Empty slots leave as
-// (+inf, -1).
-__global__ __launch_bounds__(KNN_MERGE_ROWS * 64) void knn_query_merge_kernel(const float* __restrict__ cand_d,
-                                                                              const int* __restrict__ cand_i, int Nq, int k,
-                                                                              int chunks, int64_t index_base, int accumulate,
-                                                                              int64_t* __restrict__ idx,
-                                                                              float* __restrict__ dist) {
+// (+inf, -1).  `self`: the tile kernel's -1 of row i against itself leaves as 0.
+__global__ __launch_bounds__(KNN_MERGE_ROWS * 64) void knn_merge_kernel(const float* __restrict__ cand_d,
+                                                                        const int* __restrict__ cand_i, int Nq, int k,
+                                                                        int chunks, int64_t index_base, int accumulate,
+                                                                        int self, int64_t* __restrict__ idx,
+                                                                        float* __restrict__ dist) {
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * KNN_MERGE_ROWS + (threadIdx.x >> 6);
     if (i >= Nq) return;
@@ -175,8 +347,40 @@ __global__ __launch_bounds__(KNN_MERGE_ROWS * 64) void knn_query_merge_kernel(co
     if (lane < k) {
         const bool empty = li == KNN_NO_INDEX;
         idx[(size_t)i * k + lane] = empty ? -1 : li;
-        dist[(size_t)i * k + lane] = empty ? INFINITY : ld;
+        dist[(size_t)i * k + lane] = empty ? INFINITY : self ? fmaxf(ld, 0.f) : ld;
     }
+}
+
+// The search behind both entry points, arguments already checked: the norms, the tile kernel over (row blocks, chunks),
+// the merge.  self: X is Q.  The 16-byte buffer loads (FAST) need D, both strides and both pointers 16-byte aligned and
+// both extents under the buffer limit; anything else takes the element-wise loads, which feed the same values.
+int knn_search(const char* name, bool self, const float* Q, long ldq, long Nq, const float* X, long ldx, long Nb, int D, int k,
+               int metric, int64_t index_base, int accumulate, const int64_t* exclude, int64_t* idx, float* dist, void* ws,
+               vsom_stream_t stream) {
+    const QueryPlan pl = query_plan(Nq, Nb);
+    const QueryWs w = query_layout(ws, Nq, Nb, k, self);
+    VSOM_LAUNCH(knn_sqnorm_kernel, dim3(cdiv(Nq, 256)), dim3(256), 0, stream, Q, ldq, Nq, D, w.sqq);
+    if (!self) VSOM_LAUNCH(knn_sqnorm_kernel, dim3(cdiv(Nb, 256)), dim3(256), 0, stream, X, ldx, Nb, D, w.sqx);
+    const bool qvec = D % 4 == 0 && ldq % 4 == 0 && aligned16(Q), xvec = D % 4 == 0 && ldx % 4 == 0 && aligned16(X);
+    const size_t qext = (size_t)Nq * ldq * 4, xext = (size_t)Nb * ldx * 4;
+    QueryP p = {};
+    p.Q = {Q, ldq, (int)Nq, (unsigned)qext, qvec};
+    p.X = {X, ldx, (int)Nb, (unsigned)xext, xvec};
+    p.D = D; p.k = k; p.metric = metric; p.sqq = w.sqq; p.sqx = w.sqx; p.exclude = exclude; p.index_base = index_base;
+    p.cand_d = w.cand_d; p.cand_i = w.cand_i; p.ct = pl.ct; p.chunks = pl.chunks;
+    const bool fast = qvec && xvec && qext < (size_t)OOB - 256 && xext < (size_t)OOB - 256;
+    const dim3 grid(pl.rb, pl.chunks), block(KNN_THREADS);
+    if (self) {
+        if (fast) VSOM_LAUNCH((knn_tile_kernel<true, true>), grid, block, 0, stream, p);
+        else VSOM_LAUNCH((knn_tile_kernel<false, true>), grid, block, 0, stream, p);
+    } else {
+        if (fast) VSOM_LAUNCH((knn_tile_kernel<true, false>), grid, block, 0, stream, p);
+        else VSOM_LAUNCH((knn_tile_kernel<false, false>), grid, block, 0, stream, p);
+    }
+    VSOM_LAUNCH(knn_merge_kernel, dim3(cdiv(Nq, KNN_MERGE_ROWS)), dim3(KNN_MERGE_ROWS * 64), 0, stream,
+                (const float*)w.cand_d, (const int*)w.cand_i, (int)Nq, k, pl.chunks, index_base, accumulate, (int)self, idx,
+                dist);
+    return launch_status(name);
 }
 
 struct VoteP {
@@ -266,7 +470,7 @@ extern "C" {
 
 size_t vsom_knn_query_workspace_bytes(long Nq, long Nb, int k) {
     if (Nq < 1 || Nb < 1 || k < 1) return 0;
-    return vsom::query_layout(nullptr, Nq, Nb, k).bytes;
+    return vsom::query_layout(nullptr, Nq, Nb, k, false).bytes;
 }
 
 int vsom_knn_query(const float* Q, long ldq, long Nq, const float* X, long ldx, long Nb, int D, int k, int metric,
@@ -284,25 +488,27 @@ int vsom_knn_query(const float* Q, long ldq, long Nq, const float* X, long ldx, 
                  "knn_query: metric %d (euclidean or cosine only)", metric);
     VSOM_REQUIRE(ws && aligned16(ws) && ws_bytes >= vsom_knn_query_workspace_bytes(Nq, Nb, k), VSOM_EWORKSPACE,
                  "knn_query: workspace too small or misaligned");
-    const QueryPlan pl = query_plan(Nq, Nb);
-    const QueryWs w = query_layout(ws, Nq, Nb, k);
-    VSOM_LAUNCH(knn_sqnorm_kernel, dim3(cdiv(Nq, 256)), dim3(256), 0, stream, Q, ldq, Nq, D, w.sqq);
-    VSOM_LAUNCH(knn_sqnorm_kernel, dim3(cdiv(Nb, 256)), dim3(256), 0, stream, X, ldx, Nb, D, w.sqx);
-    const bool qvec = D % 4 == 0 && ldq % 4 == 0 && aligned16(Q), xvec = D % 4 == 0 && ldx % 4 == 0 && aligned16(X);
-    const size_t qext = (size_t)Nq * ldq * 4, xext = (size_t)Nb * ldx * 4;
-    QueryP p = {};
-    p.Q = {Q, ldq, (int)Nq, (unsigned)qext, qvec};
-    p.X = {X, ldx, (int)Nb, (unsigned)xext, xvec};
-    p.D = D; p.k = k; p.metric = metric; p.sqq = w.sqq; p.sqx = w.sqx; p.exclude = exclude; p.index_base = index_base;
-    p.cand_d = w.cand_d; p.cand_i = w.cand_i; p.ct = pl.ct; p.chunks = pl.chunks;
-    if (qvec && xvec && qext < (size_t)OOB - 256 && xext < (size_t)OOB - 256) {
-        VSOM_LAUNCH(knn_query_tile_kernel<true>, dim3(pl.rb, pl.chunks), dim3(KNN_THREADS), 0, stream, p);
-    } else {
-        VSOM_LAUNCH(knn_query_tile_kernel<false>, dim3(pl.rb, pl.chunks), dim3(KNN_THREADS), 0, stream, p);
-    }
-    VSOM_LAUNCH(knn_query_merge_kernel, dim3(cdiv(Nq, KNN_MERGE_ROWS)), dim3(KNN_MERGE_ROWS * 64), 0, stream,
-                (const float*)w.cand_d, (const int*)w.cand_i, (int)Nq, k, pl.chunks, index_base, accumulate, idx, dist);
-    return launch_status("knn_query");
+    return knn_search("knn_query", false, Q, ldq, Nq, X, ldx, Nb, D, k, metric, index_base, accumulate, exclude, idx, dist, ws,
+                      stream);
+}
+
+size_t vsom_umap_knn_workspace_bytes(long N, int k) {
+    if (N < 1 || k < 1) return 0;
+    return vsom::query_layout(nullptr, N, N, k, true).bytes;
+}
+
+int vsom_umap_knn(const float* X, long ldx, long N, int D, int k, int metric, int64_t* knn_idx, float* knn_dist, void* ws,
+                  size_t ws_bytes, vsom_stream_t stream) {
+    using namespace vsom;
+    VSOM_REQUIRE(X && knn_idx && knn_dist, VSOM_EINVAL, "umap_knn: null pointer");
+    VSOM_REQUIRE(N >= 2 && D >= 1 && k >= 1 && k < N && ldx >= D && N <= 0x7fffffffL - KNN_BM, VSOM_EINVAL,
+                 "umap_knn: bad sizes N=%ld D=%d k=%d ldx=%ld", N, D, k, ldx);
+    VSOM_REQUIRE(k <= KNN_MAX_K, VSOM_EUNSUPPORTED, "umap_knn: k=%d > %d", k, KNN_MAX_K);
+    VSOM_REQUIRE(metric == VSOM_DIST_EUCLIDEAN || metric == VSOM_DIST_COSINE, VSOM_EUNSUPPORTED,
+                 "umap_knn: metric %d (euclidean or cosine only)", metric);
+    VSOM_REQUIRE(ws && aligned16(ws) && ws_bytes >= vsom_umap_knn_workspace_bytes(N, k), VSOM_EWORKSPACE,
+                 "umap_knn: workspace too small or misaligned");
+    return knn_search("umap_knn", true, X, ldx, N, X, ldx, N, D, k, metric, 0, 0, nullptr, knn_idx, knn_dist, ws, stream);
 }
 
 int vsom_knn_vote(const int64_t* idx, const float* dist, long Nq, int k, const int64_t* bank_labels, long n_bank,

@@ -1,51 +1,17 @@
-// UMAP for visualize_umap_progression (tools/evaluation.py:267-323): the two steps of umap-learn's fit that touch the
-// data or run once per epoch (vit_som_amd/umap.py states the whole algorithm step by step).
+// UMAP for visualize_umap_progression (tools/evaluation.py:267-323): the step of umap-learn's fit that runs once per
+// epoch (vit_som_amd/umap.py states the whole algorithm step by step).  The other step that touches the data, the
+// exact kNN graph (vsom_umap_knn), is the self mode of the search in knn.hip.
 //
-//   vsom_umap_knn     exact k nearest neighbours (euclidean or cosine): the X X^T contraction on the f32 matrix cores
-//                     (gemm_f32.h staging, v_mfma_f32_32x32x2_f32), a per-row top-k kept across a workgroup's column
-//                     chunk, then a fixed-order merge of the per-chunk lists.
-//   vsom_umap_epoch   one synchronous epoch of optimize_layout_euclidean: one thread per vertex, walking its CSR row.
+//   vsom_umap_epoch        one synchronous epoch of optimize_layout_euclidean: one thread per vertex, walking its CSR row.
+//   vsom_umap_neg_sample   the negative-sample hash the epoch evaluates, for the host.
 //
 // No floating-point atomics anywhere and every sum has one fixed order: a fit is bitwise reproducible.
-#include "knn_common.h"
+#include "common.h"
 
 namespace vsom {
 namespace {
 
-constexpr int EPOCH_THREADS = 256;            // the kNN tile, list and order definitions: knn_common.h
-
-// (row blocks, column tiles, chunks): chunks split every row's columns so that a small N still fills the GPU; the
-// candidate buffer holds chunks * N * k entries, at most about max(N, KNN_TARGET_BLOCKS * KNN_BM) * k.
-struct KnnPlan {
-    int rb, ct, chunks;
-};
-inline KnnPlan knn_plan(long N) {
-    KnnPlan p;
-    p.rb = cdiv(N, KNN_BM);
-    p.ct = cdiv(N, KNN_BN);
-    const int want = cdiv(KNN_TARGET_BLOCKS, p.rb);
-    p.chunks = want < 1 ? 1 : (want > p.ct ? p.ct : want);
-    return p;
-}
-
-// Workspace: sq f32 [N] (squared row norms), cand_d f32 [chunks][N][k], cand_i i32 [chunks][N][k], each 256-aligned
-struct KnnWs {
-    float* sq;
-    float* cand_d;
-    int* cand_i;
-    size_t bytes;
-};
-inline KnnWs knn_layout(void* ws, long N, int k) {
-    const KnnPlan pl = knn_plan(N);
-    const size_t sq = align256((size_t)N * 4), cand = align256((size_t)pl.chunks * N * k * 4);
-    char* p = static_cast<char*>(ws);
-    KnnWs w;
-    w.sq = reinterpret_cast<float*>(p);
-    w.cand_d = reinterpret_cast<float*>(p + sq);
-    w.cand_i = reinterpret_cast<int*>(p + sq + cand);
-    w.bytes = sq + 2 * cand;
-    return w;
-}
+constexpr int EPOCH_THREADS = 256;
 
 // The negative-sample hash (include/vitsom_hip.h): two splitmix64 rounds over (seed, edge) and (epoch, p).
 __host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
@@ -56,102 +22,6 @@ __host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
 }
 __host__ __device__ __forceinline__ uint64_t umap_neg_hash(uint64_t seed, int epoch, long edge, long p) {
     return splitmix64(splitmix64(seed ^ (uint64_t)edge) ^ (((uint64_t)(uint32_t)epoch << 32) | (uint64_t)(uint32_t)p));
-}
-
-struct KnnP {
-    const float* X;
-    long ldx;
-    int N, D, k, metric;
-    const float* sq;
-    float* cand_d;      // [chunks][N][k]
-    int* cand_i;
-    int ct, chunks;
-    unsigned x_bytes;   // FAST path: extent of X for the bounds-checked buffer loads
-    int vec;            // generic path: 16-byte loads legal
-};
-
-// One workgroup = 128 rows x one column chunk.  Per 64-column tile: the 128 x 64 block of X X^T on the f32 matrix
-// cores (knn_tile_dots in knn_common.h: wave w owns rows 32w..32w+31), the
-// distances into LDS, then every wave folds each of its 32 rows' 64 candidates into that row's list (registers: lane j
-// holds entry j).  Row i against itself gets distance -1: it sorts before every real distance (>= 0) and is written
-// out as 0, so row i comes first even when a duplicate of it has a lower index.  At the end the lists go to the
-// chunk's candidate slab.
-template <bool FAST>
-__global__ __launch_bounds__(KNN_THREADS) void umap_knn_tile_kernel(const KnnP p) {
-    constexpr int BM = KNN_BM, BN = KNN_BN;
-    __shared__ __attribute__((aligned(16))) float lds[(BM + BN) * 36];
-    __shared__ float sd[BM][BN + 1];
-
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int wm0 = wave * 32;
-    const int bm0 = blockIdx.x * BM;
-    const int chunk = blockIdx.y;
-    const int ct0 = (int)((long)chunk * p.ct / p.chunks), ct1 = (int)((long)(chunk + 1) * p.ct / p.chunks);
-
-    float ld_[32];
-    int li_[32];
-#pragma unroll
-    for (int rr = 0; rr < 32; ++rr) { ld_[rr] = INFINITY; li_[rr] = 0x7fffffff; }
-
-    const KnnOperand X = {p.X, p.ldx, p.N, p.x_bytes, p.vec};
-    KnnStage<FAST> st;
-    knn_stage_init<FAST>(st, X, bm0, X, t);
-
-    for (int ctile = ct0; ctile < ct1; ++ctile) {
-        const int bn0 = ctile * BN;
-        f32x16 acc[2];
-        knn_tile_dots<FAST>(st, X, bm0, X, bn0, p.D, lds, t, acc);
-
-        // accumulator register v of tile j: row (v & 3) + 8 (v >> 2) + 4h, column 32j + r
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = j * 32 + r, gj = bn0 + col;
-            const float sj = gj < p.N ? p.sq[gj] : 0.f;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int row = wm0 + (v & 3) + 8 * (v >> 2) + 4 * h, gi = bm0 + row;
-                float d = INFINITY;
-                if (gi < p.N && gj < p.N) d = gi == gj ? -1.f : knn_distance(acc[j][v], p.sq[gi], sj, p.metric);
-                sd[row][col] = d;
-            }
-        }
-        __syncthreads();        // also: every wave is past its last MFMA read of As / Bs before the next tile's lstore
-        const int gj = bn0 + lane;
-        const bool ok = gj < p.N;
-#pragma unroll
-        for (int rr = 0; rr < 32; ++rr)
-            knn_insert(ld_[rr], li_[rr], ok ? sd[wm0 + rr][lane] : INFINITY, ok ? gj : 0x7fffffff, p.k, lane);
-    }
-#pragma unroll
-    for (int rr = 0; rr < 32; ++rr) {
-        const int gi = bm0 + wm0 + rr;
-        if (gi < p.N && lane < p.k) {
-            const size_t o = ((size_t)chunk * p.N + gi) * p.k + lane;
-            p.cand_d[o] = ld_[rr];
-            p.cand_i[o] = li_[rr];
-        }
-    }
-}
-
-// The per-chunk lists of a row merged in chunk order (one wave per row): the k smallest in (distance, index) order.
-__global__ __launch_bounds__(KNN_MERGE_ROWS * 64) void umap_knn_merge_kernel(const float* __restrict__ cand_d,
-                                                                             const int* __restrict__ cand_i, int N, int k,
-                                                                             int chunks, int64_t* __restrict__ knn_idx,
-                                                                             float* __restrict__ knn_dist) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * KNN_MERGE_ROWS + (threadIdx.x >> 6);
-    if (i >= N) return;
-    float ld = INFINITY;
-    int li = 0x7fffffff;
-    for (int c = 0; c < chunks; ++c) {
-        const size_t o = ((size_t)c * N + i) * k + lane;
-        knn_insert(ld, li, lane < k ? cand_d[o] : INFINITY, lane < k ? cand_i[o] : 0x7fffffff, k, lane);
-    }
-    if (lane < k) {
-        knn_idx[(size_t)i * k + lane] = li;
-        knn_dist[(size_t)i * k + lane] = fmaxf(ld, 0.f);          // row i itself: -1 -> 0
-    }
 }
 
 // ---------------------------------------------------------------- layout epoch
@@ -225,42 +95,6 @@ __global__ __launch_bounds__(EPOCH_THREADS) void umap_epoch_kernel(const EpochP 
 }  // namespace vsom
 
 extern "C" {
-
-size_t vsom_umap_knn_workspace_bytes(long N, int k) {
-    if (N < 1 || k < 1) return 0;
-    return vsom::knn_layout(nullptr, N, k).bytes;
-}
-
-int vsom_umap_knn(const float* X, long ldx, long N, int D, int k, int metric, int64_t* knn_idx, float* knn_dist, void* ws,
-                  size_t ws_bytes, vsom_stream_t stream) {
-    using namespace vsom;
-    VSOM_REQUIRE(X && knn_idx && knn_dist, VSOM_EINVAL, "umap_knn: null pointer");
-    VSOM_REQUIRE(N >= 2 && D >= 1 && k >= 1 && k < N && ldx >= D && N <= 0x7fffffffL - KNN_BM, VSOM_EINVAL,
-                 "umap_knn: bad sizes N=%ld D=%d k=%d ldx=%ld", N, D, k, ldx);
-    VSOM_REQUIRE(k <= KNN_MAX_K, VSOM_EUNSUPPORTED, "umap_knn: k=%d > %d", k, KNN_MAX_K);
-    VSOM_REQUIRE(metric == VSOM_DIST_EUCLIDEAN || metric == VSOM_DIST_COSINE, VSOM_EUNSUPPORTED,
-                 "umap_knn: metric %d (euclidean or cosine only)", metric);
-    VSOM_REQUIRE(ws && aligned16(ws) && ws_bytes >= vsom_umap_knn_workspace_bytes(N, k), VSOM_EWORKSPACE,
-                 "umap_knn: workspace too small or misaligned");
-    const KnnPlan pl = knn_plan(N);
-    const KnnWs w = knn_layout(ws, N, k);
-    VSOM_LAUNCH(knn_sqnorm_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, X, ldx, N, D, w.sq);
-    KnnP p = {};
-    p.X = X; p.ldx = ldx; p.N = (int)N; p.D = D; p.k = k; p.metric = metric; p.sq = w.sq;
-    p.cand_d = w.cand_d; p.cand_i = w.cand_i; p.ct = pl.ct; p.chunks = pl.chunks;
-    const bool vec = D % 4 == 0 && ldx % 4 == 0 && aligned16(X);
-    const size_t extent = (size_t)N * ldx * 4;
-    p.vec = vec;
-    p.x_bytes = (unsigned)extent;
-    if (vec && extent < (size_t)OOB - 256) {
-        VSOM_LAUNCH(umap_knn_tile_kernel<true>, dim3(pl.rb, pl.chunks), dim3(KNN_THREADS), 0, stream, p);
-    } else {
-        VSOM_LAUNCH(umap_knn_tile_kernel<false>, dim3(pl.rb, pl.chunks), dim3(KNN_THREADS), 0, stream, p);
-    }
-    VSOM_LAUNCH(umap_knn_merge_kernel, dim3(cdiv(N, KNN_MERGE_ROWS)), dim3(KNN_MERGE_ROWS * 64), 0, stream,
-                (const float*)w.cand_d, (const int*)w.cand_i, (int)N, k, pl.chunks, knn_idx, knn_dist);
-    return launch_status("umap_knn");
-}
 
 long vsom_umap_neg_sample(uint64_t seed, int epoch, long edge, long p, long N) {
     if (N < 1 || epoch < 0 || edge < 0 || p < 0) return -1;

@@ -930,7 +930,7 @@ def kmeans_colvar(X, k, out, ws):
 
 
 # ---------------------------------------------------------------- UMAP (visualize_umap_progression)
-UMAP_MAX_K = 64                                                  # csrc/umap.hip: one list entry per lane
+UMAP_MAX_K = 64                                                  # csrc/knn.hip (KNN_MAX_K): one list entry per lane
 
 
 def umap_knn(X, k, metric, knn_idx, knn_dist):
@@ -967,7 +967,7 @@ def umap_epoch(indptr, indices, eps, next_s, eps_neg, next_neg, Y_in, Y_out, a, 
 
 
 # ---------------------------------------------------------------- kNN probe (evaluate_knn)
-KNN_MAX_K = 64                                                   # csrc/knn_common.h: one list entry per lane
+KNN_MAX_K = UMAP_MAX_K                                           # the same search (csrc/knn.hip), the same limit
 KNN_MAX_CLASSES = 1024                                           # csrc/knn.hip: the vote's LDS score table
 KNN_UNIFORM, KNN_DISTANCE, KNN_SOFTMAX = 0, 1, 2                 # VSOM_KNN_*
 

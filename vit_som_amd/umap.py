@@ -1,8 +1,8 @@
 """umap-learn's ``umap.UMAP`` (0.5: umap_.py) on the device, for visualize_umap_progression
 (tools/evaluation.py:267-323).
 
-As in kmeans.py, the steps that touch the data are HIP kernels (umap.hip): the exact k-nearest-neighbour search on the
-f32 matrix cores and one launch per layout epoch.  The host keeps the O(N k) decisions, vectorised numpy / scipy as
+As in kmeans.py, the steps that touch the data are HIP kernels: the exact k-nearest-neighbour search on the f32 matrix
+cores (knn.hip, the search of the kNN probe with the set as its own bank) and one launch per layout epoch (umap.hip).  The host keeps the O(N k) decisions, vectorised numpy / scipy as
 umap-learn itself does them: sigma / rho, the membership strengths, the set operations, the pruning, the a / b curve
 fit and the spectral initialisation.  The kNN table and the graph are copied to the host once; the input never leaves
 the device.  Everything is bitwise reproducible for a given ``random_state``.
