@@ -509,6 +509,34 @@ int vsom_umap_epoch(const int64_t* indptr, const int64_t* indices, const double*
                     double* epoch_of_next_sample, const double* epochs_per_negative_sample,
                     double* epoch_of_next_negative_sample, const float* Y_in, float* Y_out, long N, int dim, float a,
                     float b, float gamma, float alpha, int epoch, uint64_t seed, vsom_stream_t stream);
+/* The layout of UMAP.transform (optimize_layout_euclidean, move_other=False): M new points against the fixed training
+ * embedding Y_train [N, dim] f32, epochs epoch_begin .. epoch_end - 1 of an n_epochs schedule in ONE launch, one thread
+ * per new point (the points never interact).  knn_idx int64 [M, k] are ordinals of training rows, weights fp64 [M, k]
+ * the row-normalised memberships, epochs_per_sample fp64 [M, k] (+inf = a pruned edge, never sampled); Y [M, dim] f32 is
+ * read (epoch_begin > 0) and written.  The schedule state lives in ws: epoch_of_next_sample fp64 [k][M] at offset 0 and
+ * epoch_of_next_negative_sample fp64 [k][M] at offset round_up(8 M k, 256), and persists there between calls.
+ * epoch_begin == 0 first writes Y[i] = sum_j weights[i,j] Y_train[knn_idx[i,j]] (fp64, j = 0 .. k-1 in order, rounded once)
+ * and resets the state to next = eps, next_neg = eps / negative_sample_rate.  Then for n = epoch_begin .. epoch_end - 1
+ * and j = 0 .. k-1 in order, when next[j] <= n:
+ *   attraction  to u = knn_idx[i,j]: d2 = |y - y_u|^2, c = -2ab d2^(b-1) / (a d2^b + 1) (0 if d2 == 0),
+ *               y += alpha_n clip(c (y - y_u), -4, 4), applied at once and once;
+ *   next[j] += eps[j]; n_neg = floor((n - next_neg[j]) / (eps[j] / negative_sample_rate));
+ *   repulsion   for p < n_neg, each applied at once: s = vsom_umap_neg_sample(seed, n, i k + j, p, N), d2 = |y - y_s|^2,
+ *               c = 2 gamma b / ((0.001 + d2)(a d2^b + 1)), y += alpha_n clip(c (y - y_s), -4, 4); nothing when d2 == 0;
+ *   next_neg[j] += n_neg * (eps[j] / negative_sample_rate).
+ * alpha_0 = initial_alpha, alpha_n = initial_alpha (1 - (n-1) / n_epochs), computed in fp64 and rounded to f32.  So
+ * [0, e) followed by [e, n) on the same ws and Y is [0, n) bit for bit.  transform_graph (vit_som_amd/umap.py) gives
+ * eps >= 1; a call's run time grows with n_epochs negative_sample_rate / eps.
+ * An edge with an ordinal outside [0, N), a NaN or negative weight, or a NaN or non-positive eps is never followed (not
+ * in the initial sum either; its state is +inf) and counted in status[0] (int32 [1], zeroed by the caller) once per call.
+ * 1 <= k <= 64 (more: VSOM_EUNSUPPORTED), 1 <= dim <= 4, M, N >= 1, 0 <= epoch_begin <= epoch_end <= n_epochs,
+ * negative_sample_rate >= 1.  Workspace: vsom_umap_transform_workspace_bytes(M, k) (host arithmetic; 0 for a non-positive
+ * size); too small or NULL: VSOM_EWORKSPACE. */
+size_t vsom_umap_transform_workspace_bytes(long M, int k);
+int vsom_umap_transform_layout(const int64_t* knn_idx, const double* weights, const double* epochs_per_sample,
+                               const float* Y_train, long N, float* Y, long M, int k, int dim, float a, float b, float gamma,
+                               double initial_alpha, int n_epochs, int epoch_begin, int epoch_end, int negative_sample_rate,
+                               uint64_t seed, int32_t* status, void* ws, size_t ws_bytes, vsom_stream_t stream);
 
 /* k-nearest-neighbour probe of evaluate_knn (no counterpart in the reference).  No floating-point atomics, every sum in
  * one fixed order: two runs are bitwise equal.

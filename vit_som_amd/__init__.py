@@ -15,7 +15,7 @@ from .model import ViTSOM  # noqa: F401,E402
 from .desom import DESOM, Autoencoder  # noqa: F401,E402
 from .classifier import ViTClassifier  # noqa: F401,E402
 from . import evaluation  # noqa: F401,E402
-from .evaluation import KNNReport, MapQuality, evaluate_knn, evaluate_map_quality  # noqa: F401,E402
+from .evaluation import KNNReport, MapQuality, evaluate_knn, evaluate_map_quality, visualize_umap_map  # noqa: F401,E402
 from .kmeans import KMeans, kmeans_plusplus  # noqa: F401,E402
 from .umap import UMAP  # noqa: F401,E402
 from .knn import KNNClassifier  # noqa: F401,E402

@@ -149,6 +149,10 @@ SIGNATURES = {
     "vsom_umap_neg_sample": (C.c_long, [C.c_uint64, C.c_int, C.c_long, C.c_long, C.c_long]),
     "vsom_umap_epoch": (C.c_int, [c_fp] * 8 + [C.c_long, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
                                                C.c_uint64, c_stream]),
+    "vsom_umap_transform_workspace_bytes": (C.c_size_t, [C.c_long, C.c_int]),
+    "vsom_umap_transform_layout": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_long, c_fp, C.c_long, C.c_int, C.c_int, C.c_float,
+                                             C.c_float, C.c_float, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64,
+                                             c_fp, c_fp, C.c_size_t, c_stream]),
     "vsom_knn_query_workspace_bytes": (C.c_size_t, [C.c_long, C.c_long, C.c_int]),
     "vsom_knn_query": (C.c_int, [c_fp, C.c_long, C.c_long, c_fp, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int,
                                  c_fp, c_fp, c_fp, c_fp, C.c_size_t, c_stream]),

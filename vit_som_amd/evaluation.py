@@ -7,7 +7,8 @@ atomics), so the only device->host traffic of a whole evaluation pass is that ta
 (sklearn's arithmetic-mean normalisation) and the macro precision / recall / F1 are O(classes^2)
 host arithmetic on the table.  evaluate_kmeans keeps the model outputs in one device buffer and clusters them with
 the HIP k-means (kmeans.py); visualize_umap_progression (:267-323) embeds the latent representations with the HIP
-UMAP (umap.py).  The two pictures of the map itself: visualize_decoded_prototypes / decode_prototype (:153-222) push the
+UMAP (umap.py), and visualize_umap_map (no counterpart) places the SOM's prototypes into that embedding with
+UMAP.transform and draws the unit grid over it.  The two pictures of the map itself: visualize_decoded_prototypes / decode_prototype (:153-222) push the
 prototypes through the ViT decoder in batches and assemble the mosaic on the device (`vsom_proto_mosaic`);
 visualize_label_heatmap (:224-265) folds (BMU, label) pairs into a last-label-per-cell table (`vsom_last_label`).
 Map quality has no counterpart in the reference: evaluate_map_quality folds the distances and BMUs every predict() leaves
@@ -199,12 +200,9 @@ def evaluate_kmeans(model, config, dataloader, num_labels=None):
     return purity, nmi, inference_time
 
 
-def visualize_umap_progression(model, config, dataloader, epoch=0, output_dir="experiments/plots/vit_som/umap"):
-    """evaluation.py:267-323: UMAP(n_neighbors=15, min_dist=0.1, metric='cosine', random_state=42) of
-    model.get_latent_representation(x) over the whole set, fitted on the device (umap.py), drawn as the reference's
-    scatter plot into output_dir/som_umap_epoch_{epoch}.png (rank 0 only; skipped with a warning when matplotlib is
-    missing).  With model.world_size > 1 every rank gathers all rows and runs the same deterministic fit.  Returns
-    (embedding [N, 2] float32, labels [N]) as host arrays (the reference returns None)."""
+def _umap_latents(model, config, dataloader, feats):
+    """feats(x, C, S) of every batch (copied: the model's buffers are reused by the next batch) and the labels, as device
+    tensors over the whole set: with model.world_size > 1 every rank gathers all rows, rank 0's first."""
     model.eval()
     d = config["data"]
     C, S = d["num_channels"], d["input_size"]
@@ -212,38 +210,101 @@ def visualize_umap_progression(model, config, dataloader, epoch=0, output_dir="e
     lat, labels = [], []
     with torch.no_grad():
         for x, y in dataloader:
-            x = x.to(dev, non_blocking=True).reshape(-1, C, S, S)
+            x = x.to(dev, non_blocking=True)
             y = y.to(dev, non_blocking=True)
-            z = model.get_latent_representation(x)
-            lat.append(z.reshape(z.shape[0], -1).float().clone())     # the model's buffers are reused by the next batch
+            z = feats(x, C, S)
+            lat.append(z.reshape(z.shape[0], -1).float().clone())
             labels.append(y.reshape(-1).long())
     X, y = torch.cat(lat), torch.cat(labels)
     world = _world(model)
     if world > 1:
         X, y = _gather_rows(X, world), _gather_rows(y, world)
+    return X.contiguous(), y
+
+
+def _umap_embed(X, fit_rows=None):
+    """-> (the fitted UMAP(n_neighbors=15, min_dist=0.1, metric='cosine', random_state=42), the embedding of every row
+    of X as a device tensor).  fit_rows None, or not below the row count: one fit of all rows.  Otherwise the fit sees a
+    fixed subset -- the first fit_rows entries of RandomState(42).permutation(N), sorted -- and the other rows are
+    placed into it by transform(); the rows come back in their original order."""
     reducer = UMAP(n_neighbors=15, min_dist=0.1, metric="cosine", random_state=42)
-    embedding = reducer.fit_transform(X.contiguous()).cpu().numpy()
+    N = X.shape[0]
+    if fit_rows is None or N <= int(fit_rows):
+        return reducer, reducer.fit_transform(X)
+    chosen = np.zeros(N, dtype=bool)
+    chosen[np.random.RandomState(42).permutation(N)[:int(fit_rows)]] = True
+    sub = torch.from_numpy(np.flatnonzero(chosen)).to(X.device)
+    rest = torch.from_numpy(np.flatnonzero(~chosen)).to(X.device)
+    fitted = reducer.fit_transform(X.index_select(0, sub))
+    embedding = torch.empty(N, fitted.shape[1], dtype=torch.float32, device=X.device)
+    embedding[sub] = fitted
+    embedding[rest] = reducer.transform(X.index_select(0, rest))
+    return reducer, embedding
+
+
+def _umap_scatter(plt, embedding, all_labels):
+    """The reference's scatter plot of an embedding, on a new figure."""
+    plt.figure(figsize=(10, 8), dpi=300)
+    plt.axis("off")
+    scatter = plt.scatter(embedding[:, 0], embedding[:, 1], c=all_labels, cmap="tab10", s=3, alpha=0.7,
+                          edgecolor="none", rasterized=True)
+    cbar = plt.colorbar(scatter, ticks=range(10), drawedges=True)
+    cbar.set_ticklabels([str(i) for i in range(10)])
+    cbar.ax.tick_params(labelsize=10, width=0.5)
+    cbar.outline.set_linewidth(0.5)
+
+
+def visualize_umap_progression(model, config, dataloader, epoch=0, output_dir="experiments/plots/vit_som/umap", fit_rows=None):
+    """evaluation.py:267-323: UMAP(n_neighbors=15, min_dist=0.1, metric='cosine', random_state=42) of
+    model.get_latent_representation(x) over the whole set, fitted on the device (umap.py), drawn as the reference's
+    scatter plot into output_dir/som_umap_epoch_{epoch}.png (rank 0 only; skipped with a warning when matplotlib is
+    missing).  With model.world_size > 1 every rank gathers all rows and runs the same deterministic fit.  fit_rows (not in
+    the reference): fit on a fixed subset of that many rows and transform() the others into it (_umap_embed), for sets
+    whose host-side graph and spectral initialisation would take too long.  Returns (embedding [N, 2] float32, labels [N])
+    as host arrays (the reference returns None)."""
+    X, y = _umap_latents(model, config, dataloader, lambda x, C, S: model.get_latent_representation(x.reshape(-1, C, S, S)))
+    embedding = _umap_embed(X, fit_rows)[1].cpu().numpy()
     all_labels = y.cpu().numpy()
     if int(getattr(model, "rank", 0)) == 0:
-        try:
-            import matplotlib.pyplot as plt
-        except ImportError:
-            import warnings
-            warnings.warn("visualize_umap_progression: matplotlib is not installed; no plot written")
+        plt = _pyplot("visualize_umap_progression")
+        if plt is None:
             return embedding, all_labels
         os.makedirs(output_dir, exist_ok=True)
-        plt.figure(figsize=(10, 8), dpi=300)
-        plt.axis("off")
-        scatter = plt.scatter(embedding[:, 0], embedding[:, 1], c=all_labels, cmap="tab10", s=3, alpha=0.7,
-                              edgecolor="none", rasterized=True)
-        cbar = plt.colorbar(scatter, ticks=range(10), drawedges=True)
-        cbar.set_ticklabels([str(i) for i in range(10)])
-        cbar.ax.tick_params(labelsize=10, width=0.5)
-        cbar.outline.set_linewidth(0.5)
+        _umap_scatter(plt, embedding, all_labels)
         plt.savefig(os.path.join(output_dir, f"som_umap_epoch_{epoch}.png"), bbox_inches="tight", pad_inches=0,
                     transparent=False, dpi=400)
         plt.close()
     return embedding, all_labels
+
+
+def visualize_umap_map(model, config, dataloader, epoch=0, output_dir="experiments/plots/vit_som/umap", fit_rows=None):
+    """The map in data space (no counterpart in the reference): the embedding of visualize_umap_progression (same
+    latents, same UMAP, same fit_rows) with the SOM's K prototypes placed INTO it by UMAP.transform -- they live in the
+    space of the latents -- and the unit grid drawn over the scatter plot: a marker per unit and a line between units the
+    layer's topology makes adjacent (umatrix's neighbour table, square and hexagonal) ->
+    output_dir/som_umap_map_epoch_{epoch}.png (rank 0 only; skipped with a warning when matplotlib is missing).  Latents:
+    model.get_latent_representation(x) for vit_som, x_encoded for desom, as evaluate_knn chooses them; any other model
+    raises ValueError.  Returns (embedding [N, 2] float32, labels [N], prototype_embedding [K, 2] float32) as host arrays."""
+    feats = _knn_features(model, config["hyperparameters"]["model_arch"], "visualize_umap_map")
+    X, y = _umap_latents(model, config, dataloader, feats)
+    reducer, embedding = _umap_embed(X, fit_rows)
+    protos = reducer.transform(model.som_layer.prototypes.detach().float().contiguous()).cpu().numpy()
+    embedding, all_labels = embedding.cpu().numpy(), y.cpu().numpy()
+    nbr_idx = umatrix(model)[1]
+    if int(getattr(model, "rank", 0)) == 0:
+        plt = _pyplot("visualize_umap_map")
+        if plt is None:
+            return embedding, all_labels, protos
+        os.makedirs(output_dir, exist_ok=True)
+        _umap_scatter(plt, embedding, all_labels)
+        for u, row in enumerate(nbr_idx):
+            for v in row[row > u]:                               # every grid edge once
+                plt.plot(protos[[u, v], 0], protos[[u, v], 1], color="black", linewidth=0.4, alpha=0.8)
+        plt.scatter(protos[:, 0], protos[:, 1], c="black", s=8, marker="o", edgecolor="white", linewidth=0.3, zorder=3)
+        plt.savefig(os.path.join(output_dir, f"som_umap_map_epoch_{epoch}.png"), bbox_inches="tight", pad_inches=0,
+                    transparent=False, dpi=400)
+        plt.close()
+    return embedding, all_labels, protos
 
 
 def _pyplot(who):
@@ -556,13 +617,13 @@ class KNNReport:
     inference_time: float
 
 
-def _knn_features(model, arch):
+def _knn_features(model, arch, who="evaluate_knn"):
     """x -> the [B, D] float32 features the probe compares (views of the model's buffers: copy before the next batch)."""
     if arch == "vit_som" and hasattr(model, "get_latent_representation"):
         return lambda x, C, S: model.get_latent_representation(x.reshape(-1, C, S, S))
     if arch == "desom" and hasattr(model, "autoencoder"):
         return lambda x, C, S: model(x.reshape(x.shape[0], -1))[1]
-    raise ValueError(f"evaluate_knn: needs a vit_som model (get_latent_representation) or a desom model (x_encoded); got "
+    raise ValueError(f"{who}: needs a vit_som model (get_latent_representation) or a desom model (x_encoded); got "
                      f"{type(model).__name__} with model_arch {arch!r}")
 
 

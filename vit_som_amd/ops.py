@@ -966,6 +966,39 @@ def umap_epoch(indptr, indices, eps, next_s, eps_neg, next_neg, Y_in, Y_out, a, 
     return Y_out
 
 
+def umap_transform_workspace(M, k, device) -> torch.Tensor:
+    """The byte buffer that holds the schedule state of one transform layout (it persists between sliced calls)."""
+    return torch.empty(max(int(lib.vsom_umap_transform_workspace_bytes(int(M), int(k))), 16), dtype=torch.uint8, device=device)
+
+
+def umap_transform_state(ws, M, k):
+    """(epoch_of_next_sample, epoch_of_next_negative_sample): fp64 [k, M] views of such a buffer."""
+    n = 8 * int(M) * int(k)
+    off = (n + 255) // 256 * 256
+    return ws[:n].view(torch.float64).view(k, M), ws[off:off + n].view(torch.float64).view(k, M)
+
+
+def umap_transform_layout(knn_idx, weights, eps, Y_train, Y, a, b, gamma, initial_alpha, n_epochs, epoch_begin, epoch_end,
+                          negative_sample_rate, seed, status, ws):
+    """Epochs [epoch_begin, epoch_end) of the transform layout of Y [M, dim] against the fixed Y_train [N, dim] in one launch
+    (epoch_begin == 0 writes the weighted-mean init first); knn_idx int64 / weights fp64 / eps fp64 [M, k]; status int32 [1]
+    (zeroed by the caller) counts refused edges; ws from umap_transform_workspace(M, k)."""
+    M, k = knn_idx.shape
+    N, dim = Y_train.shape
+    _f32(Y_train, "Y_train"); _f32(Y, "Y")
+    assert Y_train.is_contiguous() and Y.is_contiguous() and Y.shape == (M, dim)
+    assert knn_idx.dtype == torch.int64 and knn_idx.is_contiguous() and knn_idx.is_cuda
+    for t in (weights, eps):
+        assert t.dtype == torch.float64 and t.is_contiguous() and t.shape == (M, k) and t.is_cuda
+    assert status.dtype == torch.int32 and status.numel() == 1 and status.is_cuda
+    assert ws.dtype == torch.uint8 and ws.is_cuda and ws.is_contiguous()
+    check(lib.vsom_umap_transform_layout(ptr(knn_idx), ptr(weights), ptr(eps), ptr(Y_train), N, ptr(Y), M, k, dim, float(a),
+                                         float(b), float(gamma), float(initial_alpha), int(n_epochs), int(epoch_begin),
+                                         int(epoch_end), int(negative_sample_rate), int(seed), ptr(status), ptr(ws), ws.numel(),
+                                         stream()), "vsom_umap_transform_layout")
+    return Y
+
+
 # ---------------------------------------------------------------- kNN probe (evaluate_knn)
 KNN_MAX_K = UMAP_MAX_K                                           # the same search (csrc/knn.hip), the same limit
 KNN_MAX_CLASSES = 1024                                           # csrc/knn.hip: the vote's LDS score table

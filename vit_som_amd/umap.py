@@ -54,7 +54,31 @@ The algorithm (umap-learn 0.5, restated; the departures are marked):
    nothing is scattered.
    Departure -- negative samples: a counter-based hash of (seed, epoch, edge index, p) instead of umap-learn's
    sequential Tausworthe draws: two splitmix64 rounds (include/vitsom_hip.h, vsom_umap_neg_sample) mod N.
-Not covered: transform() of new points, supervised / parametric UMAP, densMAP, sparse input, other metrics.
+
+transform(X) of M new rows into a fitted map (umap-learn 0.5's ``transform``, restated from memory like the steps above:
+umap-learn is not a dependency and the restatement has not been run against it):
+
+9.  X is the very tensor the model was fitted on: ``embedding_`` is returned.
+10. Search: the k = n_neighbors nearest training rows of every new row, ascending by (distance, ordinal), nothing
+    excluded and nothing put first (vsom_knn_query against the kept training tensor ``_raw_data``).
+11. Graph (transform_graph, host, fp64): sigma / rho of step 2 over the [M, k] table with local_connectivity
+    max(0, lc - 1) -- the sum still skips j = 0, which umap-learn's transform inherits from the fit although column 0
+    is no longer the row itself; w_ij = 1 if d_ij - rho_i <= 0 or sigma_i = 0, else exp(-(d_ij - rho_i) / sigma_i),
+    with no "self" column; every row divided by its sum (added in the order j = 0 .. k-1).  Edges with
+    w < max(w) / n_epochs (max over the whole table) are pruned, epochs_per_sample = +inf; the others max(w) / w.
+12. n_epochs = 100 if M <= 10000 else 30 when ``n_epochs`` is None, else n_epochs // 3; 0 returns the init.
+13. Init and layout (vsom_umap_transform_layout, one launch): y_i = sum_j w_ij Y_train[idx_ij] in fp64, rounded once;
+    then optimize_layout_euclidean with move_other=False: alpha_0 = learning_rate / 4, alpha_n = alpha_0
+    (1 - (n-1) / n_epochs), gamma = repulsion_strength, the fit's a and b, the schedule of step 8 per (i, j) with
+    next = eps and next_neg = eps / negative_sample_rate at the start.  Only the new point moves, and new points meet
+    training points only, so each is laid out on its own, all epochs in one thread, and every term is applied at once
+    in the order (epoch, j, attraction, negative samples) as umap-learn's loop applies them: step 8's synchronous
+    departure is not needed here.  The attraction counts once.  A negative sample that coincides with the point adds
+    nothing (umap-learn adds 4 per component there unless it is the point itself).
+    Departure -- negative samples: step 8's hash with edge index i k + j (the position in the [M, k] table, so pruning
+    does not shift it), drawn among the N training rows.  The seed is the first 8 bytes of a fresh
+    RandomState(random_state), as in fit: transform does not depend on how often it was called before.
+Not covered: supervised / parametric / inverse transform, densMAP, sparse input, other metrics.
 """
 import warnings
 
@@ -183,6 +207,36 @@ def make_schedule(graph, n_epochs, negative_sample_rate):
     return G, eps, eps / float(negative_sample_rate)
 
 
+def transform_n_epochs(n_epochs, M):
+    """Step 12: the layout epochs of a transform of M rows by a model made with ``n_epochs``."""
+    if n_epochs is None:
+        return 100 if M <= 10000 else 30
+    return int(n_epochs) // 3
+
+
+def transform_graph(knn_idx, knn_dist, local_connectivity=1.0, n_epochs=100):
+    """Step 11 -> (weights, epochs_per_sample), float64 [M, k]: the row-normalised memberships of the new rows in their
+    k nearest training rows, and max(w) / w with +inf on the edges pruned for an n_epochs layout (n_epochs = 0 prunes
+    them all).  Entry (i, j) belongs to the edge from new row i to training row knn_idx[i, j]: the graph keeps the
+    table's layout, so the ordinals are only checked for their shape."""
+    d = np.asarray(knn_dist, dtype=np.float64)
+    if np.shape(knn_idx) != d.shape or d.ndim != 2:
+        raise ValueError(f"transform_graph: knn_idx {np.shape(knn_idx)} and knn_dist {d.shape} must be the same [M, k]")
+    sigma, rho = smooth_knn_dist(d, max(0.0, float(local_connectivity) - 1.0))
+    x = d - rho[:, None]
+    s = sigma[:, None]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        w = np.where((x <= 0.0) | (s == 0.0), 1.0, np.exp(-(x / s)))
+    total = np.zeros(d.shape[0])
+    for j in range(d.shape[1]):                                  # the scalar loop's order
+        total += w[:, j]
+    w = w / total[:, None]
+    top = w.max()
+    with np.errstate(divide="ignore"):
+        eps = np.where(w < top / np.float64(n_epochs), np.inf, top / w)
+    return w, eps
+
+
 def _eigenmap(G, dim):
     """The eigenvectors of eigenvalues 2..dim+1 of I - D^-1/2 G D^-1/2 (one connected graph)."""
     from scipy.sparse.linalg import eigsh
@@ -242,9 +296,12 @@ def spectral_init(G, dim, rs, centroids):
 
 
 def _check_x(X, n_neighbors):
+    """n_neighbors None: the rows of a transform, of which one is enough."""
     if not isinstance(X, torch.Tensor) or X.dim() != 2:
         raise ValueError("UMAP: X must be a float32 [N, D] tensor on the GPU")
-    if X.shape[0] <= n_neighbors:
+    if n_neighbors is None and X.shape[0] < 1:
+        raise ValueError("UMAP: X has no rows")
+    if n_neighbors is not None and X.shape[0] <= n_neighbors:
         raise ValueError(f"UMAP: N={X.shape[0]} rows must exceed n_neighbors={n_neighbors}")
     if X.shape[1] < 1:
         raise ValueError("UMAP: X has no columns")
@@ -264,7 +321,9 @@ def _is_int(v):
 class UMAP:
     """umap.UMAP for a float32 [N, D] device tensor, with umap-learn's parameter names and defaults (the subset
     listed; module docstring for the algorithm and its departures).  After ``fit``: ``embedding_`` float32
-    [N, n_components] on the device, ``graph_`` (scipy CSR, float32, the unpruned fuzzy graph), ``_a``, ``_b``."""
+    [N, n_components] on the device, ``graph_`` (scipy CSR, float32, the unpruned fuzzy graph), ``_a``, ``_b``, and
+    ``_raw_data``: the training tensor itself, a reference and not a copy, which ``transform`` searches -- the caller
+    must not overwrite it while the model is in use."""
 
     def __init__(self, n_neighbors=15, n_components=2, metric="euclidean", n_epochs=None, learning_rate=1.0,
                  init="spectral", min_dist=0.1, spread=1.0, set_op_mix_ratio=1.0, local_connectivity=1.0,
@@ -368,7 +427,45 @@ class UMAP:
             Y.reverse()
         self.embedding_ = Y[0]
         self._n_epochs, self._layout_seed = n_epochs, seed
+        self._raw_data = X                                       # a reference: transform() searches it
         return self
 
     def fit_transform(self, X):
         return self.fit(X).embedding_
+
+    def transform(self, X):
+        """Steps 9-13: float32 [M, D] device tensor -> float32 [M, n_components] device tensor, the new rows placed in
+        the fitted embedding, which does not move.  Reproducible: the result depends on X, the fit and ``random_state``
+        only."""
+        if not hasattr(self, "embedding_"):
+            raise ValueError("UMAP: transform() needs a fitted model; call fit() first")
+        self._validate()
+        train = self._raw_data
+        if X is train:
+            return self.embedding_
+        if isinstance(X, torch.Tensor) and X.dim() == 2 and X.shape[1] != train.shape[1]:
+            raise ValueError(f"UMAP: X has {X.shape[1]} columns, the model was fitted on {train.shape[1]}")
+        X = _check_x(X, None)
+        if X.device != train.device:
+            raise ValueError(f"UMAP: X is on {X.device}, the model was fitted on {train.device}")
+        M, N, k, dim = X.shape[0], train.shape[0], self.n_neighbors, self.n_components
+        if N < k:
+            raise ValueError(f"UMAP: the {N} training rows are fewer than n_neighbors={k}")
+        dev = X.device
+        idx = torch.empty(M, k, dtype=torch.int64, device=dev)
+        dist = torch.empty(M, k, dtype=torch.float32, device=dev)
+        ops.knn_query(X, train, k, METRICS[self.metric], idx, dist)
+        n_epochs = transform_n_epochs(self.n_epochs, M)
+        weights, eps = transform_graph(idx.cpu().numpy(), dist.cpu().numpy(), self.local_connectivity, n_epochs)
+        seed = int(np.frombuffer(_random_state(self.random_state).bytes(8), dtype="<u8")[0])
+        Y = torch.empty(M, dim, dtype=torch.float32, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        ops.umap_transform_layout(idx, torch.from_numpy(weights).to(dev), torch.from_numpy(eps).to(dev), self.embedding_, Y,
+                                  self._a, self._b, self.repulsion_strength, float(self.learning_rate) / 4.0, n_epochs, 0,
+                                  n_epochs, self.negative_sample_rate, seed, status,
+                                  ops.umap_transform_workspace(M, k, dev))
+        refused = int(status.item())
+        if refused:
+            raise ValueError(f"UMAP: the transform layout refused {refused} edges (a neighbour outside the training set, or "
+                             f"a weight or schedule entry that is not a number)")
+        return Y
