@@ -560,6 +560,26 @@ size_t vsom_knn_query_workspace_bytes(long Nq, long Nb, int k);
 int vsom_knn_query(const float* Q, long ldq, long Nq, const float* X, long ldx, long Nb, int D, int k, int metric,
                    int64_t index_base, int accumulate, const int64_t* exclude, int64_t* idx, float* dist, void* ws,
                    size_t ws_bytes, vsom_stream_t stream);
+/* Neighbour ranks (trustworthiness / continuity of an embedding, vit_som_amd/embedding_quality.py; no counterpart in the
+ * reference).  d(i, l) is the distance of vsom_umap_knn between rows i and l of A [N, D] (row stride lda), computed by
+ * the same contraction in the same summation order.  nbr int64 [N, k] lists, for every row, k rows of the same set (the
+ * neighbours it has in ANOTHER space); for every slot with n = nbr[i][j] in [0, N), n != i:
+ *   less[i][j] = #{ l : l != i, l != n, d(i, l) <  d(i, n) }      (int32 [N, k])
+ *   tied[i][j] = #{ l : l != i, l != n, d(i, l) == d(i, n) }      (int32 [N, k])
+ * so that n has rank 1 + less (ties to the lowest rank) .. 1 + less + tied among the N - 1 other rows.  A slot holding
+ * -1 (empty) or i itself gets less = tied = -1.  The threshold d(i, n) is summed by a gather launch in the order of the
+ * tile contraction, so it is bit for bit the value the tile pass produces for that pair: a row never counts its
+ * neighbour's own rounding as a tie, and the k nearest rows in A itself get less = 0 .. k - 1 exactly (ties apart).
+ * Counts are combined over the column chunks with integer atomics: bitwise reproducible, independent of the chunking.
+ * An index outside [0, N) other than -1 is NOT an error of this entry: no row is read for it and the slot leaves as an
+ * empty one (-1, -1); the host wrapper ops.knn_ranks refuses such a table with ValueError before the call.
+ * Both outputs are written in full (no need to clear them).  1 <= k <= 64 (more: VSOM_EUNSUPPORTED), 2 <= N <= 2^31 - 129,
+ * lda >= D >= 1, metric as vsom_umap_knn; 16-byte row loads under the conditions of vsom_knn_query, element-wise
+ * otherwise.  Workspace: vsom_knn_ranks_workspace_bytes(N, k) (host arithmetic; 0 for a non-positive size): the N squared
+ * norms, the N k thresholds and the N k neighbours as int32, each rounded up to 256 bytes. */
+size_t vsom_knn_ranks_workspace_bytes(long N, int k);
+int vsom_knn_ranks(const float* A, long lda, long N, int D, int metric, const int64_t* nbr, int k, int32_t* less, int32_t* tied,
+                   void* ws, size_t ws_bytes, vsom_stream_t stream);
 /* The class vote over such lists, one wave per query: scores[i, c] (fp64) = the weights of query i's neighbours j with
  * bank_labels[idx[i, j]] == c, added in neighbour order j = 0 .. k-1; pred[i] = the first argmax (ties go to the
  * lowest class, as vsom_argmax_rows).  weights:

@@ -16,6 +16,8 @@ from .desom import DESOM, Autoencoder  # noqa: F401,E402
 from .classifier import ViTClassifier  # noqa: F401,E402
 from . import evaluation  # noqa: F401,E402
 from .evaluation import KNNReport, MapQuality, evaluate_knn, evaluate_map_quality, visualize_umap_map  # noqa: F401,E402
+from .evaluation import EmbeddingQualityReport, MapNeighbourhood, evaluate_embedding_quality, map_neighbourhood  # noqa: F401,E402
+from .embedding_quality import EmbeddingQuality, continuity, embedding_quality, rank_penalties, trustworthiness  # noqa: F401,E402
 from .kmeans import KMeans, kmeans_plusplus  # noqa: F401,E402
 from .umap import UMAP  # noqa: F401,E402
 from .knn import KNNClassifier  # noqa: F401,E402

@@ -156,6 +156,8 @@ SIGNATURES = {
     "vsom_knn_query_workspace_bytes": (C.c_size_t, [C.c_long, C.c_long, C.c_int]),
     "vsom_knn_query": (C.c_int, [c_fp, C.c_long, C.c_long, c_fp, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int,
                                  c_fp, c_fp, c_fp, c_fp, C.c_size_t, c_stream]),
+    "vsom_knn_ranks_workspace_bytes": (C.c_size_t, [C.c_long, C.c_int]),
+    "vsom_knn_ranks": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, C.c_int, c_fp, C.c_int, c_fp, c_fp, c_fp, C.c_size_t, c_stream]),
     "vsom_knn_vote": (C.c_int, [c_fp, c_fp, C.c_long, C.c_int, c_fp, C.c_long, C.c_int, C.c_int, C.c_float, c_fp, c_fp, c_fp,
                                 c_stream]),
     "vsom_fill": (C.c_int, [c_fp, C.c_long, C.c_float, c_stream]),

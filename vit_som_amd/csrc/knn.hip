@@ -7,8 +7,11 @@
 //   vsom_umap_knn    the same search of a set among itself (UMAP's kNN graph): the self mode of the same kernels, which
 //                    puts row i first in its own list at distance 0, before any duplicate of it with a lower index.
 //   vsom_knn_vote    one wave per query: fp64 class scores in neighbour order, first argmax.
+//   vsom_knn_ranks   the same contraction of a set with itself, counting instead of selecting: for every row and each
+//                    row listed for it, how many other rows lie closer and how many exactly as far (trustworthiness and
+//                    continuity of an embedding).  Integer atomics only.
 //
-// The contract both entry points keep, written once below:
+// The contract the search entry points keep (the rank pass takes its distances from the same four), written once below:
 //   - the 128 x 64 tile of dot products (knn_tile_dots), every (row, row) pair summed over D in one fixed order that
 //     depends neither on where the two rows fall in a tile nor on the sizes of the two sets;
 //   - the squared norms summed in that same order (knn_sqnorm_kernel), so identical rows are at distance exactly 0;
@@ -383,6 +386,186 @@ int knn_search(const char* name, bool self, const float* Q, long ldq, long Nq, c
     return launch_status(name);
 }
 
+// ---------------------------------------------------------------------------------------------- neighbour ranks
+// A slot as the tile kernel reads it: the threshold d(i, n) and the neighbour n as a row of this launch (-1: nothing to count).
+struct RankSlot {
+    float thr;
+    int nb;
+};
+// Workspace of vsom_knn_ranks: sq f32 [N], slot RankSlot [N][k], each 256-aligned.
+struct RankWs {
+    float* sq;
+    RankSlot* slot;
+    size_t bytes;
+};
+inline RankWs rank_layout(void* ws, long N, int k) {
+    const size_t sq = align256((size_t)N * 4), slots = align256((size_t)N * k * sizeof(RankSlot));
+    char* p = static_cast<char*>(ws);
+    RankWs w;
+    w.sq = reinterpret_cast<float*>(p);
+    w.slot = reinterpret_cast<RankSlot*>(p + sq);
+    w.bytes = sq + slots;
+    return w;
+}
+
+// <x, y> over D in the order in which knn_tile_dots sums that pair (see knn_sqnorm_kernel): bit for bit the tile's value.
+template <bool VEC>
+__device__ __forceinline__ float knn_pair_dot(const float* __restrict__ x, const float* __restrict__ y, int D) {
+    float s = 0.f;
+#pragma unroll 2
+    for (int kb = 0; kb < D; kb += 8) {
+        float a[8], b[8];
+        if constexpr (VEC) {                                         // D % 4 == 0: a group is whole or its upper half is missing
+            const bool hi = kb + 4 < D;
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(x + kb), b0 = *reinterpret_cast<const f32x4*>(y + kb);
+            const f32x4 a1 = hi ? *reinterpret_cast<const f32x4*>(x + kb + 4) : z;
+            const f32x4 b1 = hi ? *reinterpret_cast<const f32x4*>(y + kb + 4) : z;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { a[j] = a0[j]; b[j] = b0[j]; a[4 + j] = a1[j]; b[4 + j] = b1[j]; }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                a[j] = kb + j < D ? x[kb + j] : 0.f;
+                b[j] = kb + j < D ? y[kb + j] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            s = fmaf(a[j], b[j], s);
+            s = fmaf(a[4 + j], b[4 + j], s);
+        }
+    }
+    return s;
+}
+
+// One thread per slot (i, j): the threshold d(i, nbr[i][j]) exactly as the tile kernel will compute that pair, the
+// neighbour as a row of this launch, and the slot's two counters at their start value.  A slot that is empty (-1),
+// names row i itself or lies outside [0, N) never reads A: threshold NaN (no distance is below or equal to it),
+// neighbour -1, counters -1 for good.
+template <bool VEC>
+__global__ __launch_bounds__(256) void knn_rank_threshold_kernel(const float* __restrict__ A, long lda, long N, int D, int k,
+                                                                int metric, const int64_t* __restrict__ nbr,
+                                                                const float* __restrict__ sq, RankSlot* __restrict__ out,
+                                                                int* __restrict__ less, int* __restrict__ tied) {
+    const size_t slot = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (slot >= (size_t)N * k) return;
+    const long i = (long)(slot / k);
+    const int64_t n = nbr[slot];
+    if (n < 0 || n >= N || n == i) {
+        out[slot] = {__builtin_nanf(""), -1};
+        less[slot] = -1;
+        tied[slot] = -1;
+        return;
+    }
+    const float dot = knn_pair_dot<VEC>(A + i * lda, A + n * lda, D);
+    out[slot] = {knn_distance(dot, sq[i], sq[n], metric), (int)n};
+    less[slot] = 0;
+    tied[slot] = 0;
+}
+
+struct RankP {
+    KnnOperand A;
+    int D, k, metric;
+    const float* sq;
+    const RankSlot* slot;       // [N][k]
+    int* less;                  // [N][k], 0 (or -1) on entry
+    int* tied;
+    int ct, chunks;
+};
+
+// One workgroup = 128 rows x one chunk of column tiles, built like knn_tile_kernel<., SELF>.  Per 64-column tile: the
+// 128 x 64 block of A A^T (knn_tile_dots), the distances into LDS -- NaN for a column outside the set and for row i
+// against itself, so neither is ever counted -- then every wave walks each of its 32 rows' 64 distances: lane j < k
+// holds slot j's threshold and neighbour, all lanes read the same LDS word (a broadcast), and two integer counters per
+// lane take d < threshold and d == threshold; the neighbour's own column is walked with the others and taken out again
+// by one read of its word when it falls into the tile.  At the end the counters are added into less / tied with integer
+// atomics: the result does not depend on the chunking or on the order of arrival.
+template <bool FAST>
+__global__ __launch_bounds__(KNN_THREADS, 2) void knn_rank_tile_kernel(const RankP p) {
+    constexpr int BM = KNN_BM, BN = KNN_BN;
+    __shared__ __attribute__((aligned(16))) float lds[(BM + BN) * 36];
+    __shared__ float sd[BM][BN + 1];
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int wm0 = wave * 32;
+    const int bm0 = blockIdx.x * BM;
+    const int chunk = blockIdx.y;
+    const int ct0 = (int)((long)chunk * p.ct / p.chunks), ct1 = (int)((long)(chunk + 1) * p.ct / p.chunks);
+    const int N = p.A.rows;
+
+    // lane j < k of the wave holds slot j of each of its 32 rows: the two counters stay in registers over the chunk, the
+    // threshold and the neighbour are read again for every tile (keeping them too would cost the second workgroup per CU)
+    int ls_[32], td_[32];
+#pragma unroll
+    for (int rr = 0; rr < 32; ++rr) { ls_[rr] = 0; td_[rr] = 0; }
+    const bool mine = lane < p.k;
+    const int wrow0 = __builtin_amdgcn_readfirstlane(bm0 + wm0);     // the wave's first row, known to be wave-uniform
+    const RankSlot* slots = p.slot + (size_t)wrow0 * p.k;
+
+    KnnStage<FAST> st;
+    knn_stage_init<FAST>(st, p.A, bm0, p.A, t);
+
+    for (int ctile = ct0; ctile < ct1; ++ctile) {
+        const int bn0 = ctile * BN;
+        f32x16 acc[2];
+        knn_tile_dots<FAST>(st, p.A, bm0, p.A, bn0, p.D, lds, t, acc);
+
+        // accumulator register v of tile j: row (v & 3) + 8 (v >> 2) + 4h, column 32j + r
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int col = j * 32 + r, gj = bn0 + col;
+            const float sj = gj < N ? p.sq[gj] : 0.f;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int row = wm0 + (v & 3) + 8 * (v >> 2) + 4 * h, gi = bm0 + row;
+                float d = __builtin_nanf("");
+                if (gi < N && gj < N && gi != gj) d = knn_distance(acc[j][v], p.sq[gi], sj, p.metric);
+                sd[row][col] = d;
+            }
+        }
+        __syncthreads();        // also: every wave is past its last MFMA read of the LDS tiles before the next tile's stores
+        RankSlot sl_[32];
+        int off = lane;
+        asm volatile("" : "+v"(off));                                // computed per tile: 32 hoisted addresses cost the occupancy
+#pragma unroll
+        for (int rr = 0; rr < 32; ++rr) {
+            const bool ok = mine && wrow0 + rr < N;
+            sl_[rr] = ok ? slots[rr * p.k + off] : RankSlot{__builtin_nanf(""), -1};
+        }
+#pragma unroll
+        for (int rr = 0; rr < 32; ++rr) {
+            const float* row = sd[wm0 + rr];
+            const float th = sl_[rr].thr;
+            const int skip = sl_[rr].nb - bn0;                          // the neighbour's column of this tile, if it is one
+            int ls = 0, td = 0;
+#pragma unroll 8
+            for (int c = 0; c < BN; ++c) {
+                const float d = row[c];
+                ls += d < th;
+                td += d == th;
+            }
+            if (skip >= 0 && skip < BN) {                            // the neighbour's own column was walked too: take it out
+                const float d = row[skip];
+                ls -= d < th;
+                td -= d == th;
+            }
+            ls_[rr] += ls;
+            td_[rr] += td;
+        }
+    }
+#pragma unroll
+    for (int rr = 0; rr < 32; ++rr) {
+        // a slot with nothing to count (threshold NaN) has counted nothing: its -1 stays
+        if (wrow0 + rr < N && mine) {
+            const size_t o = (size_t)(wrow0 + rr) * p.k + lane;
+            if (ls_[rr]) atomicAdd(&p.less[o], ls_[rr]);
+            if (td_[rr]) atomicAdd(&p.tied[o], td_[rr]);
+        }
+    }
+}
+
 struct VoteP {
     const int64_t* idx;
     const float* dist;
@@ -509,6 +692,44 @@ int vsom_umap_knn(const float* X, long ldx, long N, int D, int k, int metric, in
     VSOM_REQUIRE(ws && aligned16(ws) && ws_bytes >= vsom_umap_knn_workspace_bytes(N, k), VSOM_EWORKSPACE,
                  "umap_knn: workspace too small or misaligned");
     return knn_search("umap_knn", true, X, ldx, N, X, ldx, N, D, k, metric, 0, 0, nullptr, knn_idx, knn_dist, ws, stream);
+}
+
+size_t vsom_knn_ranks_workspace_bytes(long N, int k) {
+    if (N < 1 || k < 1) return 0;
+    return vsom::rank_layout(nullptr, N, k).bytes;
+}
+
+int vsom_knn_ranks(const float* A, long lda, long N, int D, int metric, const int64_t* nbr, int k, int32_t* less, int32_t* tied,
+                   void* ws, size_t ws_bytes, vsom_stream_t stream) {
+    using namespace vsom;
+    VSOM_REQUIRE(A && nbr && less && tied, VSOM_EINVAL, "knn_ranks: null pointer");
+    VSOM_REQUIRE(N >= 2 && D >= 1 && k >= 1 && lda >= D && N <= 0x7fffffffL - KNN_BM, VSOM_EINVAL,
+                 "knn_ranks: bad sizes N=%ld D=%d k=%d lda=%ld", N, D, k, lda);
+    VSOM_REQUIRE(k <= KNN_MAX_K, VSOM_EUNSUPPORTED, "knn_ranks: k=%d > %d", k, KNN_MAX_K);
+    VSOM_REQUIRE(metric == VSOM_DIST_EUCLIDEAN || metric == VSOM_DIST_COSINE, VSOM_EUNSUPPORTED,
+                 "knn_ranks: metric %d (euclidean or cosine only)", metric);
+    VSOM_REQUIRE(ws && aligned16(ws) && ws_bytes >= vsom_knn_ranks_workspace_bytes(N, k), VSOM_EWORKSPACE,
+                 "knn_ranks: workspace too small or misaligned");
+    const RankWs w = rank_layout(ws, N, k);
+    const QueryPlan pl = query_plan(N, N);
+    const bool vec = D % 4 == 0 && lda % 4 == 0 && aligned16(A);
+    const size_t ext = (size_t)N * lda * 4;
+    VSOM_LAUNCH(knn_sqnorm_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, A, lda, N, D, w.sq);
+    const dim3 slots((unsigned)(((size_t)N * k + 255) / 256));
+    if (vec)
+        VSOM_LAUNCH(knn_rank_threshold_kernel<true>, slots, dim3(256), 0, stream, A, lda, N, D, k, metric, nbr,
+                    (const float*)w.sq, w.slot, less, tied);
+    else
+        VSOM_LAUNCH(knn_rank_threshold_kernel<false>, slots, dim3(256), 0, stream, A, lda, N, D, k, metric, nbr,
+                    (const float*)w.sq, w.slot, less, tied);
+    RankP p = {};
+    p.A = {A, lda, (int)N, (unsigned)ext, vec};
+    p.D = D; p.k = k; p.metric = metric; p.sq = w.sq; p.slot = w.slot; p.less = less; p.tied = tied;
+    p.ct = pl.ct; p.chunks = pl.chunks;
+    const dim3 grid(pl.rb, pl.chunks), block(KNN_THREADS);
+    if (vec && ext < (size_t)OOB - 256) VSOM_LAUNCH(knn_rank_tile_kernel<true>, grid, block, 0, stream, p);
+    else VSOM_LAUNCH(knn_rank_tile_kernel<false>, grid, block, 0, stream, p);
+    return launch_status("knn_ranks");
 }
 
 int vsom_knn_vote(const int64_t* idx, const float* dist, long Nq, int k, const int64_t* bank_labels, long n_bank,

@@ -17,6 +17,9 @@ in the SOM layer's buffers into quantization error, topographic error, hit map a
 evaluate_knn (no counterpart either) asks how much class information the latents carry: every test sample is classified by
 a weighted vote of its k nearest training samples in latent space (knn.py: `vsom_knn_query` / `vsom_knn_vote`), the training
 set streamed through a fixed-size device buffer.
+evaluate_embedding_quality (no counterpart either) says how far the UMAP pictures can be believed: trustworthiness and
+continuity of the embedding against the latents (embedding_quality.py: `vsom_umap_knn` / `vsom_knn_ranks`); map_neighbourhood
+asks the same of the map itself, the prototypes against their grid.
 """
 import os
 import time
@@ -26,6 +29,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .embedding_quality import EmbeddingQuality, embedding_quality, subset_scores
 from .kmeans import KMeans
 from .knn import KNNClassifier
 from .umap import UMAP
@@ -222,6 +226,15 @@ def _umap_latents(model, config, dataloader, feats):
     return X.contiguous(), y
 
 
+def _umap_fit_subset(N, fit_rows):
+    """The rows _umap_embed fits on, as a boolean mask [N]; None when it fits all of them."""
+    if fit_rows is None or N <= int(fit_rows):
+        return None
+    chosen = np.zeros(N, dtype=bool)
+    chosen[np.random.RandomState(42).permutation(N)[:int(fit_rows)]] = True
+    return chosen
+
+
 def _umap_embed(X, fit_rows=None):
     """-> (the fitted UMAP(n_neighbors=15, min_dist=0.1, metric='cosine', random_state=42), the embedding of every row
     of X as a device tensor).  fit_rows None, or not below the row count: one fit of all rows.  Otherwise the fit sees a
@@ -229,10 +242,9 @@ def _umap_embed(X, fit_rows=None):
     placed into it by transform(); the rows come back in their original order."""
     reducer = UMAP(n_neighbors=15, min_dist=0.1, metric="cosine", random_state=42)
     N = X.shape[0]
-    if fit_rows is None or N <= int(fit_rows):
+    chosen = _umap_fit_subset(N, fit_rows)
+    if chosen is None:
         return reducer, reducer.fit_transform(X)
-    chosen = np.zeros(N, dtype=bool)
-    chosen[np.random.RandomState(42).permutation(N)[:int(fit_rows)]] = True
     sub = torch.from_numpy(np.flatnonzero(chosen)).to(X.device)
     rest = torch.from_numpy(np.flatnonzero(~chosen)).to(X.device)
     fitted = reducer.fit_transform(X.index_select(0, sub))
@@ -305,6 +317,42 @@ def visualize_umap_map(model, config, dataloader, epoch=0, output_dir="experimen
                     transparent=False, dpi=400)
         plt.close()
     return embedding, all_labels, protos
+
+
+@dataclass
+class EmbeddingQualityReport(EmbeddingQuality):
+    """evaluate_embedding_quality's result: EmbeddingQuality of the UMAP embedding against the latents, the embedding
+    itself, and with fit_rows the two measures over the fitted and over the transformed rows alone."""
+    embedding: np.ndarray = None         # float32 [N, 2], host
+    fitted_rows: np.ndarray = None       # bool [N]: the rows the UMAP was fitted on; None when it was fitted on all
+    fitted: tuple = None                 # (trustworthiness, continuity) over the fitted rows
+    transformed: tuple = None            # ... over the rows placed by transform()
+    inference_time: float = 0.0
+
+
+def evaluate_embedding_quality(model, config, dataloader, n_neighbors=15, fit_rows=None):
+    """Trustworthiness and continuity (embedding_quality.py) of the picture visualize_umap_map draws -> EmbeddingQualityReport.
+    Same latents (_knn_features: get_latent_representation for vit_som, x_encoded for desom), same UMAP(n_neighbors=15,
+    min_dist=0.1, metric='cosine', random_state=42) and same fit_rows subset; the latents are compared by cosine distance,
+    the embedding by euclidean, ties take the lowest rank.  With fit_rows the measures are also given over the fitted rows
+    and over the transformed rows alone -- what the shortcut costs; every neighbour list is still taken over all rows.
+    With model.world_size > 1 every rank gathers the rows and computes the same numbers."""
+    feats = _knn_features(model, config["hyperparameters"]["model_arch"], "evaluate_embedding_quality")
+    start = time.time()
+    X, _ = _umap_latents(model, config, dataloader, feats)
+    _, embedding = _umap_embed(X, fit_rows)
+    q = embedding_quality(X, embedding.contiguous(), n_neighbors=n_neighbors, metric="cosine")
+    chosen = _umap_fit_subset(X.shape[0], fit_rows)
+    report = EmbeddingQualityReport(**vars(q), embedding=embedding.cpu().numpy(), fitted_rows=chosen,
+                                    fitted=None if chosen is None else subset_scores(q, chosen),
+                                    transformed=None if chosen is None else subset_scores(q, ~chosen))
+    report.inference_time = time.time() - start
+    line = f"Trustworthiness: {report.trustworthiness:.4f}, Continuity: {report.continuity:.4f} (k={report.n_neighbors}, {report.n_samples} samples)"
+    if chosen is not None:
+        line += (f"; fitted rows {report.fitted[0]:.4f} / {report.fitted[1]:.4f}, transformed rows "
+                 f"{report.transformed[0]:.4f} / {report.transformed[1]:.4f}")
+    print(line + f", Inference Time: {report.inference_time:.3f}")
+    return report
 
 
 def _pyplot(who):
@@ -560,6 +608,40 @@ def umatrix(model):
     rows, cols = som.map_size
     u, nbr_idx, nbr_dist = ops.umatrix(som.prototypes.detach().contiguous(), som.grid_positions, som.adjacency_radius2(), som._dist_mode)
     return u.view(rows, cols).cpu().numpy(), nbr_idx.cpu().numpy(), nbr_dist.cpu().numpy()
+
+
+@dataclass
+class MapNeighbourhood:
+    """Host values of map_neighbourhood.  Unit u is row u; its grid neighbours in umatrix's order, -1 padding."""
+    neighbours: np.ndarray               # int32 [K, 8]: umatrix(model)[1]
+    ranks: np.ndarray                    # int64 [K, 8]: rank of the grid neighbour among the other K - 1 prototypes (1 = nearest), -1 padding
+    mean_rank: float                     # over all grid edges (each seen from both ends)
+    within_degree: float                 # share of grid neighbours among the unit's deg(u) nearest prototypes
+
+
+def map_neighbourhood(model):
+    """Is the map folded?  For every unit, where its grid neighbours rank among all prototypes by prototype distance ->
+    MapNeighbourhood.  Needs no data and no labels, like umatrix: the neighbour table is umatrix's (the layer's topology,
+    square or hexagonal), the ranks are one `vsom_knn_ranks` call on the prototypes in the layer's distance function
+    (cosine or euclidean; anything else raises ValueError); tied prototypes share the lowest rank.  On a well-ordered map
+    a unit's deg(u) grid neighbours ARE its deg(u) nearest prototypes: mean_rank near (deg + 1) / 2 and within_degree near 1."""
+    som = model.som_layer
+    if som._dist_mode not in (ops.DIST_COSINE, ops.DIST_EUCLIDEAN):
+        raise ValueError(f"map_neighbourhood: the layer's distance {som.distance_fcn!r} is not one the rank kernel has (cosine, euclidean)")
+    protos = som.prototypes.detach().float().contiguous()
+    nbr_idx = umatrix(model)[1]
+    nbr = torch.from_numpy(nbr_idx.astype(np.int64)).to(protos.device)
+    less = torch.empty(nbr.shape, dtype=torch.int32, device=protos.device)
+    tied = torch.empty(nbr.shape, dtype=torch.int32, device=protos.device)
+    ops.knn_ranks(protos, nbr, som._dist_mode, less, tied)
+    less = less.cpu().numpy().astype(np.int64)
+    valid = less >= 0
+    ranks = np.where(valid, 1 + less, -1)
+    deg = valid.sum(axis=1, keepdims=True)
+    n = int(valid.sum())
+    return MapNeighbourhood(neighbours=nbr_idx, ranks=ranks,
+                            mean_rank=float(ranks[valid].sum() / n) if n else float("nan"),
+                            within_degree=float((valid & (ranks <= deg)).sum() / n) if n else float("nan"))
 
 
 def _draw_map(who, values, label, annotate, path):

@@ -1023,6 +1023,26 @@ def knn_query(Q, X, k, metric, idx, dist, index_base=0, accumulate=False, exclud
     return idx, dist
 
 
+def knn_ranks(A, nbr, metric, less, tied):
+    """less / tied int32 [N, k]: for every row i of A [N, D] and every slot n = nbr[i, j] (int64 [N, k]; rows of A, -1 = an
+    empty slot) the number of rows other than i and n that lie closer to i than n does / exactly as far, in the distances
+    of umap_knn (same contraction, same order); -1 in both for an empty slot and for n == i.  An index outside [0, N) other
+    than -1 is refused HERE, on the host (one device reduction and one synchronisation): the C entry has no status word
+    and would treat it as an empty slot."""
+    N, D, lda = _kmeans_x(A)
+    assert nbr.dtype == torch.int64 and nbr.is_cuda and nbr.is_contiguous() and nbr.dim() == 2 and nbr.shape[0] == N
+    k = nbr.shape[1]
+    for t in (less, tied):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.shape == (N, k)
+    n_bad = int(((nbr < -1) | (nbr >= N)).sum())
+    if n_bad:
+        raise ValueError(f"knn_ranks: {n_bad} neighbour indices outside [0, {N}) (-1 marks an empty slot)")
+    ws = scratch(lib.vsom_knn_ranks_workspace_bytes(N, k), A.device)
+    check(lib.vsom_knn_ranks(ptr(A), lda, N, D, int(metric), ptr(nbr), int(k), ptr(less), ptr(tied), ptr(ws), ws.numel(),
+                             stream()), "vsom_knn_ranks")
+    return less, tied
+
+
 def knn_vote(idx, dist, bank_labels, n_classes, weights, temperature, pred, status, scores=None):
     """pred int64 [Nq] = first argmax of the fp64 class scores of each query's neighbour list (weights KNN_UNIFORM /
     KNN_DISTANCE / KNN_SOFTMAX); scores fp64 [Nq, n_classes] optionally; status int32 [2] (zeroed by the caller) counts

@@ -27,7 +27,8 @@ import numpy as np
 import torch
 import yaml
 
-from .evaluation import evaluate_classification, evaluate_clustering, evaluate_knn, evaluate_map_quality
+from .evaluation import (evaluate_classification, evaluate_clustering, evaluate_embedding_quality, evaluate_knn,
+                         evaluate_map_quality)
 from .classifier import ViTClassifier
 from .model import ViTSOM
 
@@ -275,13 +276,15 @@ def main_vit(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, 
 
 
 def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print, map_quality=False,
-         knn_eval=False):
+         knn_eval=False, embedding_quality=False):
     """train_vit_som.py:27-130; a config with hyperparameters.model_arch == "vit" runs main_vit (train_vit.py) instead.
     model_states_dir defaults to experiments/states/vit_som (experiments/states/vit for the ViT baseline).
     map_quality: after each run's final evaluation also run evaluate_map_quality on the training loader with the model that
     was evaluated, and report quantization_error / topographic_error next to the other metrics (ViT-SOM only).
     knn_eval: likewise run evaluate_knn with that model (bank = the training loader, queries = the test loader) and report
-    knn_accuracy."""
+    knn_accuracy.
+    embedding_quality: likewise run evaluate_embedding_quality with that model on the training loader (as map_quality does)
+    and report trustworthiness / continuity of the UMAP embedding of its latents."""
     if config["hyperparameters"].get("model_arch") == "vit":
         return main_vit(config, n_runs=n_runs, max_epochs=max_epochs, make_loaders=make_loaders,
                         model_states_dir=model_states_dir or "experiments/states/vit", log=log)
@@ -303,6 +306,8 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
         all_metrics.update(quantization_error=[], topographic_error=[])
     if knn_eval:
         all_metrics.update(knn_accuracy=[])
+    if embedding_quality:
+        all_metrics.update(trustworthiness=[], continuity=[])
     for run in range(n_runs):
         log(f"Starting run {run + 1} for {dataset_name}...")
         start = time.time()
@@ -344,6 +349,12 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
             kr = evaluate_knn(evaluated, config, train_loader, test_loader)
             log(f"kNN probe: accuracy {kr.accuracy:.4f} (k={kr.k}, {kr.n_train} training / {kr.n_test} test samples)")
             all_metrics["knn_accuracy"].append(kr.accuracy)
+        if embedding_quality:
+            eq = evaluate_embedding_quality(evaluated, config, train_loader)
+            log(f"Embedding quality: trustworthiness {eq.trustworthiness:.4f}, continuity {eq.continuity:.4f} "
+                f"(k={eq.n_neighbors}, {eq.n_samples} samples)")
+            all_metrics["trustworthiness"].append(eq.trustworthiness)
+            all_metrics["continuity"].append(eq.continuity)
         all_metrics["run_duration"].append(run_duration)
         all_metrics["inference_time"].append(inf_t)
     if n_runs > 1:
@@ -364,6 +375,8 @@ def _parser():
                     help="after each run also report the map's quantization and topographic error on the training set")
     ap.add_argument("--knn-eval", action="store_true",
                     help="after each run also report the k-nearest-neighbour accuracy of the latents (bank: training set, queries: test set)")
+    ap.add_argument("--embedding-quality", action="store_true",
+                    help="after each run also report trustworthiness and continuity of the UMAP embedding of the training set's latents")
     return ap
 
 
@@ -373,4 +386,4 @@ if __name__ == "__main__":
     if a.device_data or a.data_npz or a.device_randaug:
         loaders = lambda c, r, w: device_loaders(c, r, w, npz=a.data_npz, auto_augment=a.device_randaug)     # noqa: E731
     main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs, make_loaders=loaders, map_quality=a.map_quality,
-         knn_eval=a.knn_eval)
+         knn_eval=a.knn_eval, embedding_quality=a.embedding_quality)
