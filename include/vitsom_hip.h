@@ -580,6 +580,33 @@ int vsom_knn_query(const float* Q, long ldq, long Nq, const float* X, long ldx, 
 size_t vsom_knn_ranks_workspace_bytes(long N, int k);
 int vsom_knn_ranks(const float* A, long lda, long N, int D, int metric, const int64_t* nbr, int k, int32_t* less, int32_t* tied,
                    void* ws, size_t ws_bytes, vsom_stream_t stream);
+/* Silhouette coefficient (Rousseeuw 1987; sklearn.metrics.silhouette_samples; vit_som_amd/silhouette.py; no counterpart
+ * in the reference) of the rows of X [N, D] (row stride ldx) under labels int64 [N] in [0, n_clusters): the contraction
+ * of vsom_knn_ranks with a summing epilogue.  Every distance d(i, j) is that of vsom_umap_knn, except that dot products
+ * and squared norms are summed in segments of 128 k-values (each in the search's order, the segment sums added in ascending
+ * order in fp32: shorter chains, a more accurate sum; for D <= 128 the value is bit for bit the search's, for every D
+ * identical rows are at distance exactly 0 and a pair's value does not depend on its place in a tile).  It is
+ * turned into fixed point, q = llrint((double)d * 2^(40 - e)), where 2^e is the smallest power of two > 4 sqrt(max
+ * squared norm) (cosine: 4), found on the device, and added into S[i][labels[j]] (uint64, integer atomics).  Then in fp64
+ *   a[i] = S[i][own] unit / (n_own - 1),  b[i] = min over the other non-empty clusters c of S[i][c] unit / n_c (the lowest
+ *   c on a tie; nearest[i] = that c),  sil[i] = (b - a) / max(a, b),  unit = 2^(e - 40);
+ * sil = 0 (a = 0) for a singleton cluster, sil = 0 where max(a, b) = 0, and with no other non-empty cluster sil = 0,
+ * b = NaN, nearest = -1.  counts[c] = members of cluster c; cluster_mean[c] = mean of sil over them (NaN when empty);
+ * score[0] = mean of sil over the counted rows; both means are exact integer sums of llrint(sil 2^40) divided once.
+ * A row whose label is outside [0, n_clusters) gets sil = a = b = NaN and nearest = -1, is part of no sum, no count and
+ * no bound: the other rows come out as if it were absent.  A pair adds nothing when one of its rows has a NaN or
+ * overflowed squared norm or its distance is not below 2^e.  status int64 [4]: [0] rows with a label out of range,
+ * [1] such refused distances (each ordered pair), [2] non-empty clusters, [3] singleton clusters.
+ * All integer sums: every output is bitwise reproducible and bit for bit independent of the order of the rows and of the
+ * launch's chunking.  a, b, nearest and cluster_mean may be NULL; every output given is written in full (no need to clear
+ * it).  2 <= N <= 2^22 - 1 (more: VSOM_EUNSUPPORTED -- a row's sum of N values below 2^40 must stay below 2^63),
+ * n_clusters >= 1, ldx >= D >= 1, metric VSOM_DIST_COSINE | VSOM_DIST_EUCLIDEAN; 16-byte row loads under the conditions of
+ * vsom_knn_query, element-wise otherwise.  Workspace: vsom_silhouette_workspace_bytes(N, n_clusters) (host arithmetic; 0
+ * for a non-positive size), 16-byte aligned; its first N * n_clusters uint64 words are S, left there for the caller. */
+size_t vsom_silhouette_workspace_bytes(long N, int n_clusters);
+int vsom_silhouette(const float* X, long ldx, long N, int D, int metric, const int64_t* labels, int n_clusters, double* sil,
+                    double* a, double* b, int64_t* nearest, int64_t* counts, double* cluster_mean, double* score,
+                    int64_t* status, void* ws, size_t ws_bytes, vsom_stream_t stream);
 /* The class vote over such lists, one wave per query: scores[i, c] (fp64) = the weights of query i's neighbours j with
  * bank_labels[idx[i, j]] == c, added in neighbour order j = 0 .. k-1; pred[i] = the first argmax (ties go to the
  * lowest class, as vsom_argmax_rows).  weights:

@@ -18,6 +18,8 @@ from . import evaluation  # noqa: F401,E402
 from .evaluation import KNNReport, MapQuality, evaluate_knn, evaluate_map_quality, visualize_umap_map  # noqa: F401,E402
 from .evaluation import EmbeddingQualityReport, MapNeighbourhood, evaluate_embedding_quality, map_neighbourhood  # noqa: F401,E402
 from .embedding_quality import EmbeddingQuality, continuity, embedding_quality, rank_penalties, trustworthiness  # noqa: F401,E402
+from .silhouette import SilhouetteReport, cluster_silhouette, silhouette_samples, silhouette_score  # noqa: F401,E402
+from .evaluation import evaluate_silhouette, visualize_silhouette_map  # noqa: F401,E402
 from .kmeans import KMeans, kmeans_plusplus  # noqa: F401,E402
 from .umap import UMAP  # noqa: F401,E402
 from .knn import KNNClassifier  # noqa: F401,E402

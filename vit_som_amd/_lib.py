@@ -158,6 +158,9 @@ SIGNATURES = {
                                  c_fp, c_fp, c_fp, c_fp, C.c_size_t, c_stream]),
     "vsom_knn_ranks_workspace_bytes": (C.c_size_t, [C.c_long, C.c_int]),
     "vsom_knn_ranks": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, C.c_int, c_fp, C.c_int, c_fp, c_fp, c_fp, C.c_size_t, c_stream]),
+    "vsom_silhouette_workspace_bytes": (C.c_size_t, [C.c_long, C.c_int]),
+    "vsom_silhouette": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, C.c_int, c_fp, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
+                                  c_fp, c_fp, C.c_size_t, c_stream]),
     "vsom_knn_vote": (C.c_int, [c_fp, c_fp, C.c_long, C.c_int, c_fp, C.c_long, C.c_int, C.c_int, C.c_float, c_fp, c_fp, c_fp,
                                 c_stream]),
     "vsom_fill": (C.c_int, [c_fp, C.c_long, C.c_float, c_stream]),

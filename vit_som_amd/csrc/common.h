@@ -74,6 +74,16 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Order-preserving map from fp32 bits to uint32: negative values (sign set) are flipped whole, so -1e-7 < -0.0 < +0.0 < 1e-30.
+// An integer atomic min / max on the key is a float min / max (mapquality.hip, knn.hip).
+__device__ __forceinline__ unsigned ordered_key(float v) {
+    const unsigned b = __float_as_uint(v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float ordered_key_value(unsigned key) {
+    return __uint_as_float((key & 0x80000000u) ? key ^ 0x80000000u : ~key);
+}
+
 // nn.GELU() (exact-erf form) and its derivative from ONE exponential:
 //   gelu(x) = x Phi(x),  gelu'(x) = Phi(x) + x phi(x),  Phi(x) = (1 + erf(x/sqrt2))/2,
 //   phi(x) = exp(-x^2/2)/sqrt(2 pi)  -- and erf(x/sqrt2) = 1 - poly(t) exp(-x^2/2) with the SAME

@@ -10,6 +10,8 @@
 //   vsom_knn_ranks   the same contraction of a set with itself, counting instead of selecting: for every row and each
 //                    row listed for it, how many other rows lie closer and how many exactly as far (trustworthiness and
 //                    continuity of an embedding).  Integer atomics only.
+//   vsom_silhouette  the same contraction once more, summing instead of counting: for every row the fixed-point sum of its
+//                    distances to each cluster's members, then the silhouette coefficient.  Integer atomics only.
 //
 // The contract the search entry points keep (the rank pass takes its distances from the same four), written once below:
 //   - the 128 x 64 tile of dot products (knn_tile_dots), every (row, row) pair summed over D in one fixed order that
@@ -38,11 +40,7 @@ constexpr int64_t KNN_NO_INDEX = 0x7fffffffffffffffLL;      // sorts after every
 // in groups of 8, k = kb + s then kb + 4 + s for s = 0..3 (lane half h feeds k = kb + 4h + s to MFMA step s; the
 // instruction is bitwise fma(a_k1 b_k1, fma(a_k0 b_k0, c))).  So sq[i] is <x_i, x_i> of the contraction bit for bit,
 // and the euclidean distance between two identical rows is exactly 0.
-__global__ __launch_bounds__(256) void knn_sqnorm_kernel(const float* __restrict__ X, long ldx, long N, int D,
-                                                        float* __restrict__ sq) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const float* x = X + i * ldx;
+__device__ __forceinline__ float knn_sqnorm_row(const float* __restrict__ x, int D) {
     float s = 0.f;
     for (int kb = 0; kb < D; kb += 8) {
 #pragma unroll
@@ -53,7 +51,13 @@ __global__ __launch_bounds__(256) void knn_sqnorm_kernel(const float* __restrict
             s = fmaf(a1, a1, s);
         }
     }
-    sq[i] = s;
+    return s;
+}
+__global__ __launch_bounds__(256) void knn_sqnorm_kernel(const float* __restrict__ X, long ldx, long N, int D,
+                                                        float* __restrict__ sq) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    sq[i] = knn_sqnorm_row(X + i * ldx, D);
 }
 
 // Strict total order of the lists: (distance, index) lexicographic.  I is int (row of this launch) or int64_t (global ordinal).
@@ -112,13 +116,18 @@ struct KnnStage {
     OffKC<KNN_BM> oa;
     OffKC<KNN_BN> ob;
 };
+// Point the staging at operands that begin elsewhere in the same rows (a later k-segment): the row offsets stay.
 template <bool FAST>
-__device__ __forceinline__ void knn_stage_init(KnnStage<FAST>& st, const KnnOperand& A, int bm0, const KnnOperand& B, int t) {
+__device__ __forceinline__ void knn_stage_rebase(KnnStage<FAST>& st, const KnnOperand& A, const KnnOperand& B) {
     if constexpr (FAST) {
         st.rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A.base), 0, (int)A.bytes, 0x00020000);
         st.rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(B.base), 0, (int)B.bytes, 0x00020000);
-        init_kc<KNN_BM>(st.oa, A.ld, bm0, A.rows, t);
     }
+}
+template <bool FAST>
+__device__ __forceinline__ void knn_stage_init(KnnStage<FAST>& st, const KnnOperand& A, int bm0, const KnnOperand& B, int t) {
+    knn_stage_rebase<FAST>(st, A, B);
+    if constexpr (FAST) init_kc<KNN_BM>(st.oa, A.ld, bm0, A.rows, t);
 }
 
 // acc[j] <- the 128 x 64 block <A[bm0 + .], B[bn0 + .]> over K on the f32 matrix cores: wave w owns rows 32w..32w+31,
@@ -566,6 +575,356 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void knn_rank_tile_kernel(const Ran
     }
 }
 
+// ---------------------------------------------------------------------------------------------- silhouette
+// The same contraction of a set with itself, summing instead of counting: S[i][c] = the sum over the members j != i of
+// cluster c of d(i, j), in fixed point.  Nothing of size N x N exists.
+//
+// The fixed-point unit.  With M the largest squared norm of the counted rows (an integer atomic max on ordered_key, read
+// back by the kernels: it never visits the host) the bound is 2^e, the smallest power of two with 2^e > 4 sqrt(M):
+// frexpf gives M < 2^x, so e = ceil((x + 4) / 2).  No euclidean distance of the set reaches it.  In exact arithmetic
+// d <= |x_i| + |x_j| <= 2 sqrt(M).  As computed, d^2 = fl(s_i + s_j - 2 dot) with s <= M, and the fp32 dot product is off
+// by at most g sum |a_k b_k| <= g |x_i| |x_j| with g = D u / (1 - D u), u = 2^-24, while the true squared norms are at
+// most M / (1 - g): |dot| <= M (1 + g) / (1 - g) <= 2 M for D <= 2^22 (g <= 1/3).  So d^2 <= 6 M (1 + u)^3 < 8 M and
+// d <= sqrtf(8 M) (1 + u) < 2.83 sqrt(M) (1 + u) < 4 sqrt(M): the factor 2 over the exact bound is the headroom, and the
+// rounding uses less than half of it.  The cosine distance is at most 2 up to a few ulp (1 - dot / (|x_i| |x_j|) with
+// the quotient within a few ulp of [-1, 1]); its bound is 4, e = 2, the same factor.  A distance becomes
+// q = llrint((double)d * 2^(40 - e)) < 2^40, so a row's sum over fewer than 2^22 columns stays below 2^62: no 64-bit sum
+// can wrap (SIL_MAX_N).  The proof is not what keeps the sums in range, though: a distance that is not below the bound
+// (D > 2^22, a NaN, an overflowed norm) is treated as non-finite -- it adds nothing and is counted in status[1].
+//
+// Integer sums do not depend on the order of their terms and a pair's distance does not depend on where it falls in a
+// tile (the contract above): every output is bit for bit independent of the chunking and of the order of the rows.
+constexpr long SIL_MAX_N = (1L << 22) - 1;      // N 2^41 < 2^63
+constexpr int SIL_FRAC = 40;                    // fractional bits of a distance relative to the bound 2^e
+constexpr int SIL_ROWS = 4;                     // rows per finishing workgroup (one wave each)
+constexpr int SIL_SEG = 128;                    // k-values per summation segment: four 32-wide k-tiles
+
+// Segmented sums.  One fp32 chain over D products leaves a squared norm off by about 0.6 sqrt(D) 2^-24 relative (4e-6 at
+// D = 12 288, 6e-7 at D = 256) -- one factor on every cosine of the row, a shift of all its distances that a mean over a
+// cluster does not average away: s was off by 5e-7 at D = 12 288 and, on latents whose cosine distances are 1e-4, by
+// 4.7e-5 at D = 256.  The silhouette therefore sums every pair, and every norm, segment by segment: SIL_SEG k-values in the
+// order of knn_tile_dots (one call of it per segment, on operands that begin at the segment), then the segment sums added
+// in ascending order, in fp32.  A chain's error grows with the root of its length and scales with its end value, so short
+// chains of small sums win: 3.8e-8 and 2.3e-5 on the same two sets (measured; a host emulation of both orders reproduces
+// all four figures).  Four k-tiles is the shortest segment in which knn_tile_dots still hides
+// three of its four loads behind the matrix cores.
+// What the contract gives carries over segment by segment: a pair's value does not depend on where it falls in a tile, and
+// <x, x> is bit for bit the row's norm, so identical rows are still at distance exactly 0.  For D <= SIL_SEG there is one
+// segment and the distance is bit for bit that of vsom_umap_knn.
+__global__ __launch_bounds__(256) void sil_sqnorm_kernel(const float* __restrict__ X, long ldx, long N, int D,
+                                                        float* __restrict__ sq) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const float* x = X + i * ldx;
+    float s = knn_sqnorm_row(x, D < SIL_SEG ? D : SIL_SEG);
+    for (int k0 = SIL_SEG; k0 < D; k0 += SIL_SEG) s += knn_sqnorm_row(x + k0, D - k0 < SIL_SEG ? D - k0 : SIL_SEG);
+    sq[i] = s;
+}
+
+// Workspace of vsom_silhouette, each section 256-aligned: S u64 [N][C] FIRST (a caller may read the sums there), acc i64
+// [C + 1] (the fixed-point silhouette sums per cluster, the total last), ctrl u32 [64] ([0]: key of the largest squared
+// norm), sq f32 [N].  S, acc and ctrl are cleared by one launch.
+struct SilWs {
+    unsigned long long* S;
+    unsigned long long* acc;
+    unsigned* ctrl;
+    float* sq;
+    size_t clear_words, bytes;
+};
+inline SilWs sil_layout(void* ws, long N, int C) {
+    const size_t s = align256((size_t)N * C * 8), acc = align256(((size_t)C + 1) * 8), ctrl = 256, sq = align256((size_t)N * 4);
+    char* p = static_cast<char*>(ws);
+    SilWs w;
+    w.S = reinterpret_cast<unsigned long long*>(p);
+    w.acc = reinterpret_cast<unsigned long long*>(p + s);
+    w.ctrl = reinterpret_cast<unsigned*>(p + s + acc);
+    w.sq = reinterpret_cast<float*>(p + s + acc + ctrl);
+    w.clear_words = (s + acc + ctrl) / 8;
+    w.bytes = s + acc + ctrl + sq;
+    return w;
+}
+
+__device__ __forceinline__ bool sil_label_ok(int64_t l, int C) { return l >= 0 && l < C; }
+
+// The exponent e of the bound 2^e (see above) from the key of the largest squared norm; key 0: no counted row.
+__device__ __forceinline__ int sil_bound_exp(unsigned key, int metric) {
+    if (metric == VSOM_DIST_COSINE) return 2;
+    const float M = key ? ordered_key_value(key) : 0.f;
+    if (!(M < INFINITY)) return 66;             // an overflowed or NaN norm: every distance to that row is refused anyway
+    if (M == 0.f) return 0;
+    int x;
+    frexpf(M, &x);                              // M = f 2^x, f in [0.5, 1)
+    return (x + 5) >> 1;                        // ceil((x + 4) / 2), x in [-148, 128]
+}
+
+__global__ __launch_bounds__(256) void sil_clear_kernel(unsigned long long* __restrict__ words, size_t n_words,
+                                                       unsigned long long* __restrict__ counts, int C,
+                                                       unsigned long long* __restrict__ status) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n_words; i += stride) words[i] = 0;
+    for (size_t c = (size_t)blockIdx.x * 256 + threadIdx.x; c < (size_t)C; c += stride) counts[c] = 0;
+    if (blockIdx.x == 0 && threadIdx.x < 4) status[threadIdx.x] = 0;
+}
+
+// One thread per row: the cluster sizes, the rows whose label is outside [0, C) (status[0]; they count for nothing, not
+// even for the bound), and the largest squared norm of the others: one integer atomic max per wave.
+__global__ __launch_bounds__(256) void sil_prepare_kernel(const int64_t* __restrict__ labels, const float* __restrict__ sq, long N,
+                                                         int C, unsigned long long* __restrict__ counts,
+                                                         unsigned* __restrict__ ctrl, unsigned long long* __restrict__ status) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    unsigned key = 0;
+    bool bad = false;
+    if (i < N) {
+        const int64_t l = labels[i];
+        if (sil_label_ok(l, C)) {
+            atomicAdd(&counts[l], 1ull);
+            const float s = sq[i];
+            key = ordered_key(s < INFINITY ? s : INFINITY);          // a NaN norm sorts as +inf
+        } else {
+            bad = true;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned other = __shfl_xor(key, o, 64);
+        key = other > key ? other : key;
+    }
+    const int n_bad = __popcll(__ballot(bad));
+    if ((threadIdx.x & 63) == 0) {
+        if (key) atomicMax(&ctrl[0], key);
+        if (n_bad) atomicAdd(&status[0], (unsigned long long)n_bad);
+    }
+}
+
+struct SilP {
+    KnnOperand A;
+    int D, metric, C;
+    const float* sq;
+    const int64_t* labels;
+    const unsigned* ctrl;
+    unsigned long long* S;          // [N][C]
+    unsigned long long* status;
+    int ct, chunks;
+};
+
+// One workgroup = 128 rows x one chunk of column tiles, built like knn_rank_tile_kernel.  Per 64-column tile: the labels
+// of its columns into LDS (once; -1 for a column outside the set or the range), the 128 x 64 block of A A^T
+// (knn_tile_dots), the distances into LDS -- 0 for a pair that adds nothing: (i, i), a row or column that is not
+// counted, a distance that is refused -- then every wave walks its 32 rows with lane = column: the distance becomes
+// fixed point, a segmented suffix sum over the runs of equal adjacent labels leaves each run's total in its first lane,
+// and only those lanes issue an atomic, S[i][label] += total.  Integer additions all the way: any tree, any order of
+// arrival and any chunking give the same sums.
+template <bool FAST>
+__global__ __launch_bounds__(KNN_THREADS, 2) void sil_tile_kernel(const SilP p) {
+    constexpr int BM = KNN_BM, BN = KNN_BN;
+    __shared__ __attribute__((aligned(16))) float lds[(BM + BN) * 36];
+    __shared__ float sd[BM][BN + 1];
+    __shared__ int collab[2][BN];           // by tile parity: wave 0 writes the next tile's while others still read this one's
+    __shared__ int rowlab[BM];
+    __shared__ float rowsq[BM];
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int wm0 = wave * 32;
+    const int bm0 = blockIdx.x * BM;
+    const int chunk = blockIdx.y;
+    const int ct0 = (int)((long)chunk * p.ct / p.chunks), ct1 = (int)((long)(chunk + 1) * p.ct / p.chunks);
+    const int N = p.A.rows;
+
+    const int e = sil_bound_exp(p.ctrl[0], p.metric);
+    const float bound = ldexpf(1.f, e);
+    const double scale = ldexp(1.0, SIL_FRAC - e);
+    if (t < BM) {
+        const int gi = bm0 + t;
+        int l = -1;
+        float s = 0.f;
+        if (gi < N) {
+            const int64_t v = p.labels[gi];
+            if (sil_label_ok(v, p.C)) l = (int)v;
+            s = p.sq[gi];
+        }
+        rowlab[t] = l;
+        rowsq[t] = s;
+    }
+    int refused = 0;
+
+    KnnStage<FAST> st;
+    knn_stage_init<FAST>(st, p.A, bm0, p.A, t);      // the row offsets of the 128 A rows: once per workgroup
+
+    for (int ctile = ct0; ctile < ct1; ++ctile) {
+        const int bn0 = ctile * BN;
+        const int par = (ctile - ct0) & 1;
+        if (t < BN) {
+            const int gj = bn0 + t;
+            int l = -1;
+            if (gj < N) {
+                const int64_t v = p.labels[gj];
+                if (sil_label_ok(v, p.C)) l = (int)v;
+            }
+            collab[par][t] = l;
+        }
+        f32x16 acc[2];
+        for (int k0 = 0; k0 < p.D; k0 += SIL_SEG) {                         // segment by segment, see SIL_SEG
+            const KnnOperand seg = {p.A.base + k0, p.A.ld, p.A.rows, p.A.bytes - 4u * (unsigned)k0, p.A.vec};
+            const int len = p.D - k0 < SIL_SEG ? p.D - k0 : SIL_SEG;
+            knn_stage_rebase<FAST>(st, seg, seg);
+            if (k0 == 0) {
+                knn_tile_dots<FAST>(st, seg, bm0, seg, bn0, len, lds, t, acc);  // its barriers publish collab (and rowlab, rowsq)
+            } else {
+                f32x16 part[2];
+                __syncthreads();                                            // every wave is past its reads of the LDS tiles
+                knn_tile_dots<FAST>(st, seg, bm0, seg, bn0, len, lds, t, part);
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) acc[j][v] += part[j][v];
+            }
+        }
+
+        // accumulator register v of tile j: row (v & 3) + 8 (v >> 2) + 4h, column 32j + r
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int col = j * 32 + r, gj = bn0 + col;
+            const bool colok = collab[par][col] >= 0;
+            const float sj = colok ? p.sq[gj] : 0.f;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int row = wm0 + (v & 3) + 8 * (v >> 2) + 4 * h, gi = bm0 + row;
+                float d = 0.f;
+                if (colok && rowlab[row] >= 0 && gi != gj) {
+                    const float si = rowsq[row];
+                    d = knn_distance(acc[j][v], si, sj, p.metric);
+                    // knn_distance clamps with fmaxf, which drops a NaN: the norms say whether a row is finite
+                    if (!(si < INFINITY && sj < INFINITY && d < bound)) { ++refused; d = 0.f; }
+                }
+                sd[row][col] = d;
+            }
+        }
+        __syncthreads();        // also: every wave is past its last MFMA read of the LDS tiles before the next tile's stores
+
+        const int lab = collab[par][lane];
+        const int prev = __shfl_up(lab, 1, 64);
+        const unsigned long long heads = __ballot(lane == 0 || lab != prev);
+        const unsigned long long above = heads & ~((2ull << lane) - 1ull);          // the run heads after this lane
+        const int last = above ? __builtin_ctzll(above) - 1 : 63;                    // the last lane of this lane's run
+        const bool issue = ((heads >> lane) & 1) && lab >= 0;
+#pragma unroll 4
+        for (int rr = 0; rr < 32; ++rr) {
+            // 2^52 + d 2^(40 - e) in one rounding (the product is exact: 24 bits times a power of two; it is below 2^40):
+            // round-to-nearest-even leaves llrint(d 2^(40 - e)) in the low mantissa bits
+            const double y = fma((double)sd[wm0 + rr][lane], scale, 0x1p52);
+            unsigned long long q = (unsigned long long)__double_as_longlong(y) & 0xFFFFFFFFFFFFFull;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned long long up = __shfl_down(q, o, 64);
+                if (lane + o <= last) q += up;
+            }
+            if (issue && q && rowlab[wm0 + rr] >= 0) atomicAdd(&p.S[(size_t)(bm0 + wm0 + rr) * p.C + lab], q);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) refused += __shfl_xor(refused, o, 64);
+    if (lane == 0 && refused) atomicAdd(&p.status[1], (unsigned long long)refused);
+}
+
+struct SilOut {
+    double* sil;
+    double* a;
+    double* b;
+    int64_t* nearest;
+};
+
+// One wave per row, from S and the cluster sizes, in fp64 with contraction off: each of a, b and s is an exact
+// conversion-and-scale followed by one correctly rounded division (s: a subtraction and a division).
+//   a = S[i][own] unit / (n_own - 1);  b = min over the other non-empty clusters of S[i][c] unit / n_c, the lowest
+//   cluster on a tie;  s = (b - a) / max(a, b), 0 for a singleton cluster and where max(a, b) = 0 (sklearn's nan_to_num),
+//   0 too with no other non-empty cluster (b NaN, nearest -1).  A row whose label is out of range: NaN, NaN, NaN, -1.
+// The row's s goes into its cluster's and the total's sum as llrint(s 2^40): integer sums again, so the means do not
+// depend on the order of the rows either (2^-41 per row, far below what fp32 distances resolve).
+__global__ __launch_bounds__(SIL_ROWS * 64) void sil_finish_kernel(const unsigned long long* __restrict__ S,
+                                                                   const unsigned long long* __restrict__ counts,
+                                                                   const int64_t* __restrict__ labels, long N, int C,
+                                                                   const unsigned* __restrict__ ctrl, int metric, SilOut out,
+                                                                   unsigned long long* __restrict__ acc) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const long i = (long)blockIdx.x * SIL_ROWS + (threadIdx.x >> 6);
+    if (i >= N) return;
+    const int64_t own = labels[i];
+    if (!sil_label_ok(own, C)) {
+        if (lane == 0) {
+            const double nan = __builtin_nan("");
+            out.sil[i] = nan;
+            if (out.a) out.a[i] = nan;
+            if (out.b) out.b[i] = nan;
+            if (out.nearest) out.nearest[i] = -1;
+        }
+        return;
+    }
+    const double unit = ldexp(1.0, sil_bound_exp(ctrl[0], metric) - SIL_FRAC);
+    const unsigned long long* row = S + (size_t)i * C;
+    double best = INFINITY;
+    int arg = 0x7fffffff;
+    for (int c = lane; c < C; c += 64) {
+        const unsigned long long n = counts[c];
+        if (c == own || n == 0) continue;
+        const double v = (double)row[c] * unit / (double)n;
+        if (v < best) { best = v; arg = c; }           // ascending c: the first minimum of this lane's clusters
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ob = __shfl_xor(best, o, 64);
+        const int oa = __shfl_xor(arg, o, 64);
+        if (ob < best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+    }
+    if (lane) return;
+    const unsigned long long n_own = counts[own];
+    const bool other = arg != 0x7fffffff;
+    const double a = n_own > 1 ? (double)row[own] * unit / (double)(n_own - 1) : 0.0;
+    const double b = other ? best : __builtin_nan("");
+    double s = 0.0;
+    if (n_own > 1 && other) {
+        const double m = a > b ? a : b;
+        if (m > 0.0) s = (b - a) / m;
+    }
+    out.sil[i] = s;
+    if (out.a) out.a[i] = a;
+    if (out.b) out.b[i] = b;
+    if (out.nearest) out.nearest[i] = other ? arg : -1;
+    const unsigned long long q = (unsigned long long)llrint(ldexp(s, SIL_FRAC));     // two's complement: the sums are signed
+    if (q) {
+        atomicAdd(&acc[own], q);
+        atomicAdd(&acc[C], q);
+    }
+}
+
+// One workgroup: the cluster means and the score from the integer sums, the two cluster counts of status.
+__global__ __launch_bounds__(256) void sil_means_kernel(const unsigned long long* __restrict__ acc,
+                                                       const unsigned long long* __restrict__ counts, long N, int C,
+                                                       double* __restrict__ cluster_mean, double* __restrict__ score,
+                                                       unsigned long long* __restrict__ status) {
+#pragma clang fp contract(off)
+    __shared__ unsigned tally[2];
+    if (threadIdx.x < 2) tally[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned present = 0, single = 0;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const unsigned long long n = counts[c];
+        present += n > 0;
+        single += n == 1;
+        if (cluster_mean) cluster_mean[c] = n ? ldexp((double)(long long)acc[c], -SIL_FRAC) / (double)n : __builtin_nan("");
+    }
+    if (present) atomicAdd(&tally[0], present);
+    if (single) atomicAdd(&tally[1], single);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long counted = (unsigned long long)N - status[0];
+        score[0] = counted ? ldexp((double)(long long)acc[C], -SIL_FRAC) / (double)counted : __builtin_nan("");
+        status[2] = tally[0];
+        status[3] = tally[1];
+    }
+}
+
 struct VoteP {
     const int64_t* idx;
     const float* dist;
@@ -730,6 +1089,51 @@ int vsom_knn_ranks(const float* A, long lda, long N, int D, int metric, const in
     if (vec && ext < (size_t)OOB - 256) VSOM_LAUNCH(knn_rank_tile_kernel<true>, grid, block, 0, stream, p);
     else VSOM_LAUNCH(knn_rank_tile_kernel<false>, grid, block, 0, stream, p);
     return launch_status("knn_ranks");
+}
+
+size_t vsom_silhouette_workspace_bytes(long N, int n_clusters) {
+    if (N < 1 || n_clusters < 1) return 0;
+    return vsom::sil_layout(nullptr, N, n_clusters).bytes;
+}
+
+int vsom_silhouette(const float* X, long ldx, long N, int D, int metric, const int64_t* labels, int n_clusters, double* sil,
+                    double* a, double* b, int64_t* nearest, int64_t* counts, double* cluster_mean, double* score,
+                    int64_t* status, void* ws, size_t ws_bytes, vsom_stream_t stream) {
+    using namespace vsom;
+    VSOM_REQUIRE(X && labels && sil && counts && score && status, VSOM_EINVAL, "silhouette: null pointer");
+    VSOM_REQUIRE(N >= 2 && D >= 1 && ldx >= D && n_clusters >= 1, VSOM_EINVAL, "silhouette: bad sizes N=%ld D=%d ldx=%ld n_clusters=%d",
+                 N, D, ldx, n_clusters);
+    VSOM_REQUIRE(N <= SIL_MAX_N, VSOM_EUNSUPPORTED, "silhouette: N=%ld > %ld (a row's fixed-point sum must stay below 2^63)", N,
+                 SIL_MAX_N);
+    VSOM_REQUIRE(metric == VSOM_DIST_EUCLIDEAN || metric == VSOM_DIST_COSINE, VSOM_EUNSUPPORTED,
+                 "silhouette: metric %d (euclidean or cosine only)", metric);
+    VSOM_REQUIRE(ws && aligned16(ws) && ws_bytes >= vsom_silhouette_workspace_bytes(N, n_clusters), VSOM_EWORKSPACE,
+                 "silhouette: workspace too small or misaligned");
+    const SilWs w = sil_layout(ws, N, n_clusters);
+    const QueryPlan pl = query_plan(N, N);
+    const bool vec = D % 4 == 0 && ldx % 4 == 0 && aligned16(X);
+    const size_t ext = (size_t)N * ldx * 4;
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
+    unsigned long long* stat = reinterpret_cast<unsigned long long*>(status);
+    const size_t clear_blocks = (w.clear_words + 255) / 256;
+    VSOM_LAUNCH(sil_clear_kernel, dim3((unsigned)(clear_blocks < 4096 ? clear_blocks : 4096)), dim3(256), 0, stream, w.S,
+                w.clear_words, cnt, n_clusters, stat);
+    VSOM_LAUNCH(sil_sqnorm_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, X, ldx, N, D, w.sq);
+    VSOM_LAUNCH(sil_prepare_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, labels, (const float*)w.sq, N, n_clusters, cnt, w.ctrl,
+                stat);
+    SilP p = {};
+    p.A = {X, ldx, (int)N, (unsigned)ext, vec};
+    p.D = D; p.metric = metric; p.C = n_clusters; p.sq = w.sq; p.labels = labels; p.ctrl = w.ctrl; p.S = w.S; p.status = stat;
+    p.ct = pl.ct; p.chunks = pl.chunks;
+    const dim3 grid(pl.rb, pl.chunks), block(KNN_THREADS);
+    if (vec && ext < (size_t)OOB - 256) VSOM_LAUNCH(sil_tile_kernel<true>, grid, block, 0, stream, p);
+    else VSOM_LAUNCH(sil_tile_kernel<false>, grid, block, 0, stream, p);
+    const SilOut out = {sil, a, b, nearest};
+    VSOM_LAUNCH(sil_finish_kernel, dim3(cdiv(N, SIL_ROWS)), dim3(SIL_ROWS * 64), 0, stream, (const unsigned long long*)w.S,
+                (const unsigned long long*)cnt, labels, N, n_clusters, (const unsigned*)w.ctrl, metric, out, w.acc);
+    VSOM_LAUNCH(sil_means_kernel, dim3(1), dim3(256), 0, stream, (const unsigned long long*)w.acc, (const unsigned long long*)cnt, N,
+                n_clusters, cluster_mean, score, stat);
+    return launch_status("silhouette");
 }
 
 int vsom_knn_vote(const int64_t* idx, const float* dist, long Nq, int k, const int64_t* bank_labels, long n_bank,

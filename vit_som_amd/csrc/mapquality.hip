@@ -8,12 +8,6 @@ namespace vsom {
 constexpr int MQ_ROWS = 8;        // rows of dist per workgroup (two per wave)
 constexpr int MQ_NBR = 8;         // neighbour slots per unit
 
-// Order-preserving map from fp32 bits to uint32: negative values (sign set) are flipped whole, so -1e-7 < -0.0 < +0.0 < 1e-30.
-__device__ __forceinline__ unsigned ordered_key(float v) {
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 // (value, index) lexicographic minimum over the wave; every lane ends with the result.
 __device__ __forceinline__ void wave_argmin(float& v, int& i) {
 #pragma unroll

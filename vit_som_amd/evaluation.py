@@ -20,6 +20,8 @@ set streamed through a fixed-size device buffer.
 evaluate_embedding_quality (no counterpart either) says how far the UMAP pictures can be believed: trustworthiness and
 continuity of the embedding against the latents (embedding_quality.py: `vsom_umap_knn` / `vsom_knn_ranks`); map_neighbourhood
 asks the same of the map itself, the prototypes against their grid.
+evaluate_silhouette (no counterpart either) says whether the clusters -- the SOM's units, or k-means' -- are compact and
+separated in latent space, without labels (silhouette.py: `vsom_silhouette`); visualize_silhouette_map draws it per unit.
 """
 import os
 import time
@@ -32,6 +34,7 @@ from . import ops
 from .embedding_quality import EmbeddingQuality, embedding_quality, subset_scores
 from .kmeans import KMeans
 from .knn import KNNClassifier
+from .silhouette import cluster_silhouette
 from .umap import UMAP
 
 
@@ -684,6 +687,89 @@ def visualize_hit_map(model, config, dataloader, output_dir="experiments/plots")
         if _draw_map("visualize_hit_map", hits, "samples", True, path) is not None:
             print(f"Saved hit map visualization to {output_dir}")
     return hits
+
+
+# ------------------------------------------------------------------------------------ silhouette
+def _som_latents(model, config, dataloader, who):
+    """(X [N, D] float32, bmu [N] int64) over the loader, on the device: the rows the SOM layer was given and the unit
+    each of them won.  vit_som: predict() leaves the BMUs in the SOM layer's buffers and the encoder output in the ViT's;
+    both are copied before the next batch overwrites them.  desom: forward() returns both.  With model.world_size > 1
+    every rank gathers all rows, rank 0's first."""
+    model.eval()
+    d = config["data"]
+    C, S = d["num_channels"], d["input_size"]
+    arch = config["hyperparameters"]["model_arch"]
+    dev = model.arena.device
+    lat, units = [], []
+    with torch.no_grad():
+        for x, _ in dataloader:
+            x = x.to(dev, non_blocking=True)
+            if arch == "vit_som" and hasattr(model, "_som_input"):
+                x = x.reshape(-1, C, S, S)
+                bmu, _ = model.predict(x)
+                z = model._som_input(model.vit._buffers_for(x.shape[0], x.device))
+            elif arch == "desom" and hasattr(model, "autoencoder"):
+                _, z, _, bmu = model(x.reshape(x.shape[0], -1))
+            else:
+                raise ValueError(f"{who}: needs a vit_som or a desom model; got {type(model).__name__} with model_arch {arch!r}")
+            lat.append(z.reshape(z.shape[0], -1).float().clone())
+            units.append(bmu.reshape(-1).long().clone())
+    if not lat:
+        raise ValueError(f"{who}: the loader is empty")
+    X, u = torch.cat(lat), torch.cat(units)
+    world = _world(model)
+    if world > 1:
+        X, u = _gather_rows(X, world), _gather_rows(u, world)
+    return X.contiguous(), u.contiguous()
+
+
+def evaluate_silhouette(model, config, dataloader, clusters="bmu", metric=None, n_clusters=None, sample_size=None):
+    """Silhouette coefficient (silhouette.py: `vsom_silhouette`) of the latents the SOM layer sees -> SilhouetteReport.  No
+    labels are read.
+    clusters="bmu": every sample's cluster is the unit it won; the report has one cluster per unit of the map
+        (per_cluster / counts indexed by unit, NaN / 0 for a dead unit), so per_cluster shows which cells are clusters of
+        their own and which only split a continuum.
+    clusters="kmeans": the clusters of the project's KMeans(n_clusters, random_state=0, n_init=10) on those latents
+        (n_clusters defaults to data.num_classes).
+    metric: "cosine" or "euclidean"; None takes the SOM's distance_fcn when it is one of the two and "euclidean"
+        otherwise -- a manhattan map is scored with EUCLIDEAN distances, the kernel has no manhattan contraction.
+    sample_size: score a subset only, numpy.random.RandomState(0).permutation(N)[:sample_size], gathered on the device.
+    With model.world_size > 1 every rank gathers the rows (as evaluate_kmeans does) and computes the same report."""
+    who = "evaluate_silhouette"
+    if clusters not in ("bmu", "kmeans"):
+        raise ValueError(f"{who}: clusters must be 'bmu' or 'kmeans', got {clusters!r}")
+    som = model.som_layer
+    if metric is None:
+        metric = som.distance_fcn if som.distance_fcn in ("cosine", "euclidean") else "euclidean"
+    start = time.time()
+    X, units = _som_latents(model, config, dataloader, who)
+    if sample_size is not None:
+        rows = torch.from_numpy(np.random.RandomState(0).permutation(X.shape[0])[:int(sample_size)]).to(X.device)
+        X, units = X[rows].contiguous(), units[rows].contiguous()
+    if clusters == "bmu":
+        report = cluster_silhouette(X, units, metric=metric, n_clusters=som.n_prototypes)
+    else:
+        k = int(n_clusters) if n_clusters else int(config["data"]["num_classes"])
+        report = cluster_silhouette(X, KMeans(n_clusters=k, random_state=0, n_init=10).fit_predict(X).long(), metric=metric)
+    report.inference_time = time.time() - start
+    print(f"Silhouette ({clusters}, {metric}): {report.score:.4f} over {report.n_samples} samples in "
+          f"{int((report.counts > 0).sum())} clusters, Inference Time: {report.inference_time:.3f}")
+    return report
+
+
+def visualize_silhouette_map(model, config, dataloader, output_dir="experiments/plots", metric=None):
+    """The mean silhouette of every unit's samples (evaluate_silhouette, clusters="bmu") on the grid ->
+    {output_dir}/{model_arch}_epoch_{epoch}_silhouette_map.png (rank 0; skipped with a warning when matplotlib is
+    missing).  Dead units are left blank.  Returns the values [rows, cols] float64, NaN for a dead unit."""
+    model_arch = config["hyperparameters"]["model_arch"]
+    rows, cols = model.som_layer.map_size
+    values = evaluate_silhouette(model, config, dataloader, clusters="bmu", metric=metric).per_cluster.reshape(rows, cols)
+    if int(getattr(model, "rank", 0)) == 0:
+        path = os.path.join(output_dir, f"{model_arch}_epoch_{_epoch(model)}_silhouette_map.png")
+        if _draw_map("visualize_silhouette_map", np.ma.masked_invalid(values), "mean silhouette of the unit's samples", False,
+                     path) is not None:
+            print(f"Saved silhouette map visualization to {output_dir}")
+    return values
 
 
 # ------------------------------------------------------------------------------------ kNN probe

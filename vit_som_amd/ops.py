@@ -1043,6 +1043,54 @@ def knn_ranks(A, nbr, metric, less, tied):
     return less, tied
 
 
+SILHOUETTE_MAX_N = (1 << 22) - 1                                 # csrc/knn.hip: a row's fixed-point sum stays below 2^63
+
+
+class Silhouette:
+    """What one vsom_silhouette call wrote: device tensors, except `status`, the four counts on the host."""
+    __slots__ = ("sil", "a", "b", "nearest", "counts", "cluster_mean", "score", "status", "sums")
+
+
+def silhouette_workspace(N, C, device) -> torch.Tensor:
+    """A workspace of the caller's own for `silhouette`; afterwards `silhouette(...).sums` is a view of it."""
+    return torch.empty(max(lib.vsom_silhouette_workspace_bytes(int(N), int(C)), 1), dtype=torch.uint8, device=device)
+
+
+def silhouette(X, labels, metric, n_clusters, ws=None, details=True):
+    """Silhouette coefficient of the rows of X [N, D] (f32) under labels int64 [N] in [0, n_clusters) -> Silhouette:
+    sil f64 [N], a / b f64 [N] and nearest int64 [N] (None without `details`), counts int64 [C], cluster_mean f64 [C],
+    score f64 [1], status (host ints: rows with a label out of range, refused distances, non-empty clusters, singleton
+    clusters) and, with a workspace from silhouette_workspace, sums int64 [N, C]: the fixed-point distance sums.
+    One synchronisation, to read status.  A NaN or infinite input (status[1] != 0) raises ValueError; a label outside the
+    range does not: that row gets NaN, counts for nothing and is reported in status[0]."""
+    N, D, ldx = _kmeans_x(X)
+    C = int(n_clusters)
+    assert labels.dtype == torch.int64 and labels.is_cuda and labels.is_contiguous() and labels.shape == (N,)
+    dev = X.device
+    r = Silhouette()
+    f64 = lambda n: torch.empty(n, dtype=torch.float64, device=dev)      # noqa: E731
+    r.sil, r.a, r.b = f64(N), f64(N) if details else None, f64(N) if details else None
+    r.nearest = torch.empty(N, dtype=torch.int64, device=dev) if details else None
+    r.counts = torch.empty(max(C, 0), dtype=torch.int64, device=dev)
+    r.cluster_mean, r.score = f64(max(C, 0)), f64(1)
+    status = torch.empty(4, dtype=torch.int64, device=dev)
+    need = lib.vsom_silhouette_workspace_bytes(N, C)
+    own = ws is not None
+    if own:
+        assert ws.dtype == torch.uint8 and ws.is_cuda and ws.is_contiguous()
+    else:
+        ws = scratch(need, dev)
+    check(lib.vsom_silhouette(ptr(X), ldx, N, D, int(metric), ptr(labels), C, ptr(r.sil), ptr(r.a), ptr(r.b), ptr(r.nearest),
+                              ptr(r.counts), ptr(r.cluster_mean), ptr(r.score), ptr(status), ptr(ws), ws.numel(), stream()),
+          "vsom_silhouette")
+    r.sums = ws[:N * C * 8].view(torch.int64).view(N, C) if own else None
+    r.status = [int(v) for v in status.cpu()]
+    if r.status[1]:
+        raise ValueError(f"silhouette: {r.status[1]} distances were not finite: the input contains NaN or infinity, or a "
+                         f"row's squared norm overflows float32")
+    return r
+
+
 def knn_vote(idx, dist, bank_labels, n_classes, weights, temperature, pred, status, scores=None):
     """pred int64 [Nq] = first argmax of the fp64 class scores of each query's neighbour list (weights KNN_UNIFORM /
     KNN_DISTANCE / KNN_SOFTMAX); scores fp64 [Nq, n_classes] optionally; status int32 [2] (zeroed by the caller) counts

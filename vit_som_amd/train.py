@@ -28,7 +28,7 @@ import torch
 import yaml
 
 from .evaluation import (evaluate_classification, evaluate_clustering, evaluate_embedding_quality, evaluate_knn,
-                         evaluate_map_quality)
+                         evaluate_map_quality, evaluate_silhouette)
 from .classifier import ViTClassifier
 from .model import ViTSOM
 
@@ -276,7 +276,7 @@ def main_vit(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, 
 
 
 def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print, map_quality=False,
-         knn_eval=False, embedding_quality=False):
+         knn_eval=False, embedding_quality=False, silhouette=False):
     """train_vit_som.py:27-130; a config with hyperparameters.model_arch == "vit" runs main_vit (train_vit.py) instead.
     model_states_dir defaults to experiments/states/vit_som (experiments/states/vit for the ViT baseline).
     map_quality: after each run's final evaluation also run evaluate_map_quality on the training loader with the model that
@@ -284,7 +284,9 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
     knn_eval: likewise run evaluate_knn with that model (bank = the training loader, queries = the test loader) and report
     knn_accuracy.
     embedding_quality: likewise run evaluate_embedding_quality with that model on the training loader (as map_quality does)
-    and report trustworthiness / continuity of the UMAP embedding of its latents."""
+    and report trustworthiness / continuity of the UMAP embedding of its latents.
+    silhouette: likewise run evaluate_silhouette with that model on the training loader, the samples clustered by their
+    BMU, and report silhouette_bmu (NaN, with the reason logged, when fewer than two units or every sample alone won)."""
     if config["hyperparameters"].get("model_arch") == "vit":
         return main_vit(config, n_runs=n_runs, max_epochs=max_epochs, make_loaders=make_loaders,
                         model_states_dir=model_states_dir or "experiments/states/vit", log=log)
@@ -308,6 +310,8 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
         all_metrics.update(knn_accuracy=[])
     if embedding_quality:
         all_metrics.update(trustworthiness=[], continuity=[])
+    if silhouette:
+        all_metrics.update(silhouette_bmu=[])
     for run in range(n_runs):
         log(f"Starting run {run + 1} for {dataset_name}...")
         start = time.time()
@@ -355,6 +359,17 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
                 f"(k={eq.n_neighbors}, {eq.n_samples} samples)")
             all_metrics["trustworthiness"].append(eq.trustworthiness)
             all_metrics["continuity"].append(eq.continuity)
+        if silhouette:
+            try:
+                sr = evaluate_silhouette(evaluated, config, train_loader, clusters="bmu")
+                log(f"Silhouette: silhouette_bmu {sr.score:.4f} ({sr.metric}, {int((sr.counts > 0).sum())} of {sr.n_clusters} units "
+                    f"hit, {sr.n_samples} samples)")
+                all_metrics["silhouette_bmu"].append(sr.score)
+            except ValueError as err:
+                if "Number of labels" not in str(err):     # sklearn's rule: 2 .. n_samples - 1 clusters; anything else is an error
+                    raise
+                log(f"Silhouette: silhouette_bmu undefined ({err})")
+                all_metrics["silhouette_bmu"].append(float("nan"))
         all_metrics["run_duration"].append(run_duration)
         all_metrics["inference_time"].append(inf_t)
     if n_runs > 1:
@@ -377,6 +392,8 @@ def _parser():
                     help="after each run also report the k-nearest-neighbour accuracy of the latents (bank: training set, queries: test set)")
     ap.add_argument("--embedding-quality", action="store_true",
                     help="after each run also report trustworthiness and continuity of the UMAP embedding of the training set's latents")
+    ap.add_argument("--silhouette", action="store_true",
+                    help="after each run also report the silhouette coefficient of the training set's latents clustered by their BMU")
     return ap
 
 
@@ -386,4 +403,4 @@ if __name__ == "__main__":
     if a.device_data or a.data_npz or a.device_randaug:
         loaders = lambda c, r, w: device_loaders(c, r, w, npz=a.data_npz, auto_augment=a.device_randaug)     # noqa: E731
     main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs, make_loaders=loaders, map_quality=a.map_quality,
-         knn_eval=a.knn_eval, embedding_quality=a.embedding_quality)
+         knn_eval=a.knn_eval, embedding_quality=a.embedding_quality, silhouette=a.silhouette)
