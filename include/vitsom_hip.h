@@ -625,6 +625,49 @@ int vsom_knn_vote(const int64_t* idx, const float* dist, long Nq, int k, const i
                   int n_classes, int weights, float temperature, int64_t* pred, double* scores, int* status,
                   vsom_stream_t stream);
 
+/* ------------------------------------------------------------------ principal component analysis (pca.hip)
+ * The kernels of a block subspace iteration on the covariance operator of X [N, D] (row stride ldx) with a basis kept as
+ * ROWS, B [l, D] (sklearn's components_ layout); vit_som_amd/pca.py drives them, DESIGN.md section 4 has the algorithm;
+ * no counterpart in the reference.  Limits of every entry: l <= 256 and l <= D, N >= 2 where N is given (else
+ * VSOM_EUNSUPPORTED).  Scratch is a TYPED array with an element count, sized by a host-only query (0 for a non-positive
+ * size); a count below the query or a null array is VSOM_EWORKSPACE, an array that is not 16-byte aligned VSOM_EALIGN,
+ * both before any launch.  No floating-point atomics; every sum has one fixed order: all outputs are bitwise reproducible.
+ *
+ * vsom_pca_colstats: mean[c] (f32) = the column mean, summed in fp64 and rounded once; var[c] (fp64) = sum (x - mean[c])^2
+ * / (N - 1) about that ROUNDED mean, in a second sweep.  The rows are split over vsom_pca_colstats_parts(N, D) / D
+ * workgroup rows (at least two workgroups per CU at the benchmark's shape), the per-split fp64 partials added in split
+ * order.  part: vsom_pca_colstats_parts(N, D) doubles. */
+long vsom_pca_colstats_parts(long N, int D);
+int vsom_pca_colstats(const float* X, long ldx, long N, int D, float* mean, double* var, double* part, long n_part,
+                      vsom_stream_t stream);
+/* Floats of slab space of vsom_pca_project (which = 0) and vsom_pca_backproject (which = 1): the reduction splits (a
+ * function of the shape alone) times the output size. */
+long vsom_pca_slabs(long N, int D, int l, int which);
+/* Y [N, l] (row stride ldy) = (X - mean) B^T diag(scale): the hot kernel of transform and half of a pass.  mean [D] and
+ * scale [l] may be NULL (no centring / no scaling; scale carries 1 / sqrt(explained variance) for whitening).  Exact-f32
+ * matrix cores (v_mfma_f32_32x32x2_f32), both operands k-contiguous; the mean is subtracted from each X tile between the
+ * global load and the LDS store, and only from elements inside the matrix.  The reduction over D is split, per-split
+ * slabs are added in split order.  16-byte loads when D % 4 == 0 and X, B, mean and their strides are 16-byte aligned,
+ * element-wise otherwise. */
+int vsom_pca_project(const float* X, long ldx, long N, int D, const float* mean, const float* B, long ldb, int l,
+                     const float* scale, float* Y, long ldy, float* slabs, long n_slabs, vsom_stream_t stream);
+/* Zt [l, D] (row stride ldz) = Y^T (X - mean): the other half of a pass; both operands k-strided (the shape of a weight
+ * gradient), the reduction over the N rows split the same way.  16-byte loads additionally want ldy % 4 == 0. */
+int vsom_pca_backproject(const float* Y, long ldy, const float* X, long ldx, long N, int D, const float* mean, int l, float* Zt,
+                         long ldz, float* slabs, long n_slabs, vsom_stream_t stream);
+/* G [l, l] = Zt Zt^T and, when B (and H) are given, H [l, l] = B Zt^T: products and sums in fp64, each entry one
+ * fixed-order sum over D (G is symmetric bit for bit); dense row-major outputs, no workspace. */
+int vsom_pca_gram(const float* Zt, long ldz, const float* B, long ldb, int l, int D, double* G, double* H, vsom_stream_t stream);
+/* Bout [l_out, D] (row stride ldo) = T Zt with T fp64 [l_out, l_in] dense on the device: fp64 accumulation over the rows
+ * of Zt in ascending order, one rounding to f32.  Bout may not overlap Zt (VSOM_EINVAL). */
+int vsom_pca_rotate(const double* T, int l_out, int l_in, const float* Zt, long ldz, int D, float* Bout, long ldo,
+                    vsom_stream_t stream);
+/* Xout [M, D] (row stride ldo) = (Y diag(scale)) B + mean, Y [M, l]; scale and mean may be NULL: inverse_transform and the
+ * linear initialisation of the SOM.  f32 fma chain over the l components in ascending order; bound by the output store.
+ * M <= 262140 rows per call. */
+int vsom_pca_reconstruct(const float* Y, long ldy, long M, int l, const float* scale, const float* B, long ldb, int D,
+                         const float* mean, float* Xout, long ldo, vsom_stream_t stream);
+
 /* SOMLayer.som_loss(weights, distances) = mean(weights * distances) for ARBITRARY weights (som_layer.py:137-142):
    loss_sum <- sum_ik weights[i,k] dist[i,k]; with coef/row_dot/col_dot given, also the backward coefficients of
    grad_scale * that sum w.r.t. the distances' inputs (what vsom_som_bwd consumes) -- with weights = an upstream

@@ -20,6 +20,8 @@ from .evaluation import EmbeddingQualityReport, MapNeighbourhood, evaluate_embed
 from .embedding_quality import EmbeddingQuality, continuity, embedding_quality, rank_penalties, trustworthiness  # noqa: F401,E402
 from .silhouette import SilhouetteReport, cluster_silhouette, silhouette_samples, silhouette_score  # noqa: F401,E402
 from .evaluation import evaluate_silhouette, visualize_silhouette_map  # noqa: F401,E402
+from .pca import PCA  # noqa: F401,E402
+from .evaluation import LatentSpectrum, evaluate_latent_spectrum, init_som_from_data, visualize_pca_map  # noqa: F401,E402
 from .kmeans import KMeans, kmeans_plusplus  # noqa: F401,E402
 from .umap import UMAP  # noqa: F401,E402
 from .knn import KNNClassifier  # noqa: F401,E402

@@ -163,6 +163,17 @@ SIGNATURES = {
                                   c_fp, c_fp, C.c_size_t, c_stream]),
     "vsom_knn_vote": (C.c_int, [c_fp, c_fp, C.c_long, C.c_int, c_fp, C.c_long, C.c_int, C.c_int, C.c_float, c_fp, c_fp, c_fp,
                                 c_stream]),
+    "vsom_pca_colstats_parts": (C.c_long, [C.c_long, C.c_int]),
+    "vsom_pca_colstats": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, c_fp, c_fp, C.c_long, c_stream]),
+    "vsom_pca_slabs": (C.c_long, [C.c_long, C.c_int, C.c_int, C.c_int]),
+    "vsom_pca_project": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, c_fp, C.c_long, C.c_int, c_fp, c_fp, C.c_long, c_fp,
+                                   C.c_long, c_stream]),
+    "vsom_pca_backproject": (C.c_int, [c_fp, C.c_long, c_fp, C.c_long, C.c_long, C.c_int, c_fp, C.c_int, c_fp, C.c_long, c_fp,
+                                       C.c_long, c_stream]),
+    "vsom_pca_gram": (C.c_int, [c_fp, C.c_long, c_fp, C.c_long, C.c_int, C.c_int, c_fp, c_fp, c_stream]),
+    "vsom_pca_rotate": (C.c_int, [c_fp, C.c_int, C.c_int, c_fp, C.c_long, C.c_int, c_fp, C.c_long, c_stream]),
+    "vsom_pca_reconstruct": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, c_fp, C.c_long, C.c_int, c_fp, c_fp, C.c_long,
+                                       c_stream]),
     "vsom_fill": (C.c_int, [c_fp, C.c_long, C.c_float, c_stream]),
     "vsom_scaled_mul": (C.c_int, [c_fp, c_fp, c_fp, C.c_long, c_fp, C.c_float, c_stream]),
     "vsom_som_weighted_loss": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_float, c_fp, c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_int,

@@ -22,6 +22,9 @@ continuity of the embedding against the latents (embedding_quality.py: `vsom_uma
 asks the same of the map itself, the prototypes against their grid.
 evaluate_silhouette (no counterpart either) says whether the clusters -- the SOM's units, or k-means' -- are compact and
 separated in latent space, without labels (silhouette.py: `vsom_silhouette`); visualize_silhouette_map draws it per unit.
+Principal components (pca.py: `vsom_pca_*`; no counterpart either): evaluate_latent_spectrum says how many directions the
+encoder uses, visualize_pca_map is the linear, deterministic counterpart of visualize_umap_map, and init_som_from_data
+starts the map on the plane of the latents' first two principal components (SOMLayer.init_prototypes).
 """
 import os
 import time
@@ -257,6 +260,14 @@ def _umap_embed(X, fit_rows=None):
     return reducer, embedding
 
 
+def _draw_grid(plt, protos, nbr_idx):
+    """The unit grid over a scatter plot: a line between units the topology makes adjacent, a marker per unit."""
+    for u, row in enumerate(nbr_idx):
+        for v in row[row > u]:                               # every grid edge once
+            plt.plot(protos[[u, v], 0], protos[[u, v], 1], color="black", linewidth=0.4, alpha=0.8)
+    plt.scatter(protos[:, 0], protos[:, 1], c="black", s=8, marker="o", edgecolor="white", linewidth=0.3, zorder=3)
+
+
 def _umap_scatter(plt, embedding, all_labels):
     """The reference's scatter plot of an embedding, on a new figure."""
     plt.figure(figsize=(10, 8), dpi=300)
@@ -312,10 +323,7 @@ def visualize_umap_map(model, config, dataloader, epoch=0, output_dir="experimen
             return embedding, all_labels, protos
         os.makedirs(output_dir, exist_ok=True)
         _umap_scatter(plt, embedding, all_labels)
-        for u, row in enumerate(nbr_idx):
-            for v in row[row > u]:                               # every grid edge once
-                plt.plot(protos[[u, v], 0], protos[[u, v], 1], color="black", linewidth=0.4, alpha=0.8)
-        plt.scatter(protos[:, 0], protos[:, 1], c="black", s=8, marker="o", edgecolor="white", linewidth=0.3, zorder=3)
+        _draw_grid(plt, protos, nbr_idx)
         plt.savefig(os.path.join(output_dir, f"som_umap_map_epoch_{epoch}.png"), bbox_inches="tight", pad_inches=0,
                     transparent=False, dpi=400)
         plt.close()
@@ -770,6 +778,101 @@ def visualize_silhouette_map(model, config, dataloader, output_dir="experiments/
                      path) is not None:
             print(f"Saved silhouette map visualization to {output_dir}")
     return values
+
+
+# ------------------------------------------------------------------------------------ principal components
+SPECTRUM_SHARES = (0.5, 0.9, 0.95, 0.99)
+
+
+def components_for(cumulative_ratio, shares=SPECTRUM_SHARES):
+    """{share: the first k (counted from 1) whose cumulative explained-variance ratio reaches it, or None}."""
+    c = np.asarray(cumulative_ratio, np.float64)
+    return {s: (int(np.argmax(c >= s)) + 1 if bool((c >= s).any()) else None) for s in shares}
+
+
+def effective_rank(eigenvalues) -> float:
+    """exp of the entropy of the given eigenvalues renormalised to sum 1 (Roy & Vetterli 2007) -- of the top-k spectrum
+    when only the top k are given: m equal eigenvalues give m, one dominant eigenvalue gives 1."""
+    lam = np.maximum(np.asarray(eigenvalues, np.float64), 0.0)
+    total = lam.sum()
+    if total <= 0:
+        return 0.0
+    p = lam[lam > 0] / total
+    return float(np.exp(-(p * np.log(p)).sum()))
+
+
+@dataclass
+class LatentSpectrum:
+    """Host values of one evaluate_latent_spectrum pass: the top of the spectrum of the latents' covariance."""
+    explained_variance: np.ndarray           # float64 [k], descending
+    explained_variance_ratio: np.ndarray     # float64 [k]: over total_variance
+    cumulative_ratio: np.ndarray             # float64 [k]
+    total_variance: float                    # the sum of the D column variances
+    components_for: dict                     # {0.5, 0.9, 0.95, 0.99} -> first k reaching that share of the variance, or None
+    effective_rank: float                    # of the top-k spectrum: exp(entropy of the k eigenvalues renormalised to sum 1)
+    residuals: np.ndarray                    # float64 [k]: PCA.residuals_
+    n_samples: int
+    inference_time: float = 0.0
+
+
+def evaluate_latent_spectrum(model, config, dataloader, n_components=64):
+    """The spectrum of the latents the SOM layer sees (pca.py, on the device) -> LatentSpectrum: how many directions the
+    encoder uses, whether it collapses, how much of the variance a 2-D picture shows.  n_components is cut to
+    min(N, D).  With model.world_size > 1 every rank gathers the rows and computes the same report."""
+    from .pca import PCA
+    start = time.time()
+    X, _ = _som_latents(model, config, dataloader, "evaluate_latent_spectrum")
+    k = max(1, min(int(n_components), X.shape[0], X.shape[1]))
+    p = PCA(n_components=k).fit(X)
+    ev = p.explained_variance_.cpu().numpy()
+    ratio = p.explained_variance_ratio_.cpu().numpy()
+    cum = np.cumsum(ratio)
+    report = LatentSpectrum(ev, ratio, cum, p.total_variance_, components_for(cum), effective_rank(ev), p.residuals_.cpu().numpy(),
+                            int(X.shape[0]), time.time() - start)
+    print(f"Latent spectrum: effective rank {report.effective_rank:.2f} of the top {k}, {report.components_for[0.9]} components "
+          f"for 90% of the variance, PC1+PC2 {float(ratio[:2].sum()):.3f}, Inference Time: {report.inference_time:.3f}")
+    return report
+
+
+def visualize_pca_map(model, config, dataloader, epoch=0, output_dir="experiments/plots/vit_som/pca"):
+    """The linear counterpart of visualize_umap_map: the latents projected on their first two principal components
+    (pca.py), coloured by label, with the SOM's prototypes `transform`ed into the same plane and the unit grid drawn over
+    them -> output_dir/som_pca_map_epoch_{epoch}.png (rank 0 only; skipped with a warning when matplotlib is missing).
+    Deterministic and without hyper-parameters, so comparable from epoch to epoch; the axis labels carry the
+    explained-variance ratios.  Returns (projection [N, 2] float32, labels [N], prototype_projection [K, 2] float32,
+    explained_variance_ratio [2]) as host arrays."""
+    from .pca import PCA
+    feats = _knn_features(model, config["hyperparameters"]["model_arch"], "visualize_pca_map")
+    X, y = _umap_latents(model, config, dataloader, feats)
+    p = PCA(n_components=2).fit(X)
+    proj = p.transform(X).cpu().numpy()
+    protos = p.transform(model.som_layer.prototypes.detach().float().contiguous()).cpu().numpy()
+    ratio, all_labels = p.explained_variance_ratio_.cpu().numpy(), y.cpu().numpy()
+    nbr_idx = umatrix(model)[1]
+    if int(getattr(model, "rank", 0)) == 0:
+        plt = _pyplot("visualize_pca_map")
+        if plt is None:
+            return proj, all_labels, protos, ratio
+        os.makedirs(output_dir, exist_ok=True)
+        _umap_scatter(plt, proj, all_labels)
+        plt.axis("on")
+        plt.xlabel(f"PC1 ({100 * ratio[0]:.1f}% of the variance)")
+        plt.ylabel(f"PC2 ({100 * ratio[1]:.1f}% of the variance)")
+        _draw_grid(plt, protos, nbr_idx)
+        plt.savefig(os.path.join(output_dir, f"som_pca_map_epoch_{epoch}.png"), bbox_inches="tight", dpi=400)
+        plt.close()
+    return proj, all_labels, protos, ratio
+
+
+def init_som_from_data(model, config, dataloader, method="pca", max_rows=None):
+    """Start the SOM's prototypes from the data (SOMLayer.init_prototypes): the latents of the loader through the CURRENT
+    encoder, at most max_rows of them (the first ones), method "pca" or "sample".  Returns the fitted PCA or None."""
+    training = model.training
+    X, _ = _som_latents(model, config, dataloader, "init_som_from_data")
+    model.train(training)
+    if max_rows is not None:
+        X = X[:int(max_rows)]
+    return model.som_layer.init_prototypes(X, method=method)
 
 
 # ------------------------------------------------------------------------------------ kNN probe

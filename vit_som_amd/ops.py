@@ -1109,6 +1109,108 @@ def knn_vote(idx, dist, bank_labels, n_classes, weights, temperature, pred, stat
     return pred
 
 
+# ---------------------------------------------------------------- principal component analysis (pca.py)
+PCA_MAX_WIDTH = 256                                              # csrc/pca.hip: PCA_MAX_L
+PCA_PROJECT, PCA_BACKPROJECT = 0, 1                              # `which` of vsom_pca_slabs
+
+
+def _pca_vec(t, n, name):
+    """An optional contiguous f32 device vector of n elements (mean [D], scale [l])."""
+    if t is not None:
+        _f32(t, name)
+        assert t.dim() == 1 and t.numel() == n and t.is_contiguous(), f"{name} must be a contiguous vector of {n}"
+    return t
+
+
+def _pca_f64(t, shape, name):
+    assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == tuple(shape), \
+        f"{name} must be a contiguous float64 device tensor of shape {tuple(shape)}"
+    return t
+
+
+def pca_slabs(N, D, l, which) -> int:
+    """Floats of slab space pca_project (which = PCA_PROJECT) / pca_backproject (PCA_BACKPROJECT) take: host arithmetic."""
+    return int(lib.vsom_pca_slabs(int(N), int(D), int(l), int(which)))
+
+
+def pca_colstats(X, mean=None, var=None):
+    """(mean f32 [D], var f64 [D]) of the columns of X [N, D]: fp64 sums in a fixed order, the mean rounded once, the
+    unbiased variance about that rounded mean."""
+    N, D, ldx = _kmeans_x(X)
+    mean = torch.empty(D, dtype=torch.float32, device=X.device) if mean is None else _pca_vec(mean, D, "mean")
+    var = torch.empty(D, dtype=torch.float64, device=X.device) if var is None else _pca_f64(var, (D,), "var")
+    n_part = int(lib.vsom_pca_colstats_parts(N, D))
+    part = scratch(8 * n_part, X.device)
+    check(lib.vsom_pca_colstats(ptr(X), ldx, N, D, ptr(mean), ptr(var), ptr(part), part.numel() // 8, stream()), "vsom_pca_colstats")
+    return mean, var
+
+
+def pca_project(X, mean, B, scale, Y):
+    """Y [N, l] = (X - mean) B^T diag(scale); mean [D] and scale [l] optional."""
+    N, D, ldx = _kmeans_x(X)
+    _f32(B, "B"); _f32(Y, "Y")
+    assert B.dim() == 2 and B.shape[1] == D, "B must be [l, D]"
+    l = B.shape[0]
+    assert Y.dim() == 2 and Y.shape == (N, l), "Y must be [N, l]"
+    _pca_vec(mean, D, "mean"); _pca_vec(scale, l, "scale")
+    slabs = scratch(4 * pca_slabs(N, D, l, PCA_PROJECT), X.device)
+    check(lib.vsom_pca_project(ptr(X), ldx, N, D, ptr(mean), ptr(B), _rows(B), l, ptr(scale), ptr(Y), _rows(Y), ptr(slabs),
+                               slabs.numel() // 4, stream()), "vsom_pca_project")
+    return Y
+
+
+def pca_backproject(Y, X, mean, Zt):
+    """Zt [l, D] = Y^T (X - mean); Y [N, l], mean [D] optional."""
+    N, D, ldx = _kmeans_x(X)
+    _f32(Y, "Y"); _f32(Zt, "Zt")
+    assert Y.dim() == 2 and Y.shape[0] == N, "Y must be [N, l]"
+    l = Y.shape[1]
+    assert Zt.dim() == 2 and Zt.shape == (l, D), "Zt must be [l, D]"
+    _pca_vec(mean, D, "mean")
+    slabs = scratch(4 * pca_slabs(N, D, l, PCA_BACKPROJECT), X.device)
+    check(lib.vsom_pca_backproject(ptr(Y), _rows(Y), ptr(X), ldx, N, D, ptr(mean), l, ptr(Zt), _rows(Zt), ptr(slabs),
+                                   slabs.numel() // 4, stream()), "vsom_pca_backproject")
+    return Zt
+
+
+def pca_gram(Zt, G, B=None, H=None):
+    """G f64 [l, l] = Zt Zt^T and, with B [l, D] and H f64 [l, l], H = B Zt^T: fp64 products and sums."""
+    l, D, ldz = _kmeans_x(Zt)
+    _pca_f64(G, (l, l), "G")
+    assert (B is None) == (H is None), "B and H go together"
+    if B is not None:
+        _f32(B, "B")
+        assert B.dim() == 2 and B.shape == (l, D), "B must have the shape of Zt"
+        _pca_f64(H, (l, l), "H")
+    check(lib.vsom_pca_gram(ptr(Zt), ldz, ptr(B), _rows(B) if B is not None else 0, l, D, ptr(G), ptr(H), stream()), "vsom_pca_gram")
+    return G, H
+
+
+def pca_rotate(T, Zt, Bout):
+    """Bout [l_out, D] = T Zt, T f64 [l_out, l_in] on the device: fp64 accumulation, one rounding.  Bout may not overlap Zt."""
+    l_in, D, ldz = _kmeans_x(Zt)
+    assert T.dim() == 2 and T.shape[1] == l_in, "T must be [l_out, l_in]"
+    l_out = T.shape[0]
+    _pca_f64(T, (l_out, l_in), "T")
+    _f32(Bout, "Bout")
+    assert Bout.dim() == 2 and Bout.shape == (l_out, D), "Bout must be [l_out, D]"
+    check(lib.vsom_pca_rotate(ptr(T), l_out, l_in, ptr(Zt), ldz, D, ptr(Bout), _rows(Bout), stream()), "vsom_pca_rotate")
+    return Bout
+
+
+def pca_reconstruct(Y, scale, B, mean, Xout):
+    """Xout [M, D] = (Y diag(scale)) B + mean; Y [M, l], B [l, D], scale [l] and mean [D] optional."""
+    M, l, ldy = _kmeans_x(Y)
+    _f32(B, "B"); _f32(Xout, "Xout")
+    assert B.dim() == 2 and B.shape[0] == l, "B must be [l, D]"
+    D = B.shape[1]
+    assert Xout.dim() == 2 and Xout.shape == (M, D), "Xout must be [M, D]"
+    _pca_vec(scale, l, "scale"); _pca_vec(mean, D, "mean")
+    check(lib.vsom_pca_reconstruct(ptr(Y), ldy, M, l, ptr(scale), ptr(B), _rows(B), D, ptr(mean), ptr(Xout), _rows(Xout), stream()),
+          "vsom_pca_reconstruct")
+    return Xout
+
+
 # ---------------------------------------------------------------- data-parallel exchange (RCCL)
 COMM_ID_BYTES = 128
 

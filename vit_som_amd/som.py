@@ -173,6 +173,55 @@ class SOMLayer(_Base):
             raise ValueError(f"Unsupported topology: {self.topology}")
         self.register_buffer("grid_positions", positions)
 
+    # ---- initialisation from data ---------------------------------------------------------
+    def pca_grid_coordinates(self) -> torch.Tensor:
+        """(u, v) in [-1, 1] per unit, float64 [K, 2], for the linear initialisation: the two grid_positions coordinates,
+        each axis rescaled to [-1, 1] (0 on an axis of one line), the axis with the larger extent first -- it carries the
+        first principal component.  Covers the hexagonal topology: its positions are plain plane coordinates too."""
+        pos = self.grid_positions.detach().double().cpu()
+        lo, hi = pos.min(dim=0).values, pos.max(dim=0).values
+        extent = hi - lo
+        uv = torch.where(extent > 0, 2.0 * (pos - lo) / torch.where(extent > 0, extent, torch.ones_like(extent)) - 1.0,
+                         torch.zeros_like(pos))
+        return uv if extent[0] >= extent[1] else uv.flip(1)
+
+    @torch.no_grad()
+    def init_prototypes(self, latents, method="pca", span=2.0, seed=0):
+        """Start the map from data instead of torch.rand (som_layer.py:44-56), which at a large latent width puts every
+        prototype in a corner of the positive orthant, far from the data.
+        method="pca": Kohonen's linear initialisation (SOM Toolbox som_lininit, MiniSom pca_weights_init): the grid spread
+        over the plane of the first two principal components of `latents` [N, D] (a device tensor; pca.py),
+        W = mean + span (u sqrt(lambda_1) c_1 + v sqrt(lambda_2) c_2) with (u, v) = pca_grid_coordinates().
+        method="sample": latents[RandomState(seed).choice(N, K, replace=N < K)].
+        With the cosine distance the rows are L2-normalised afterwards, as the random start is.  The existing Parameter is
+        written in place.  Returns the fitted PCA (None for "sample")."""
+        W = self.prototypes
+        X = latents.flatten(start_dim=1) if latents.dim() > 2 else latents
+        if X.dim() != 2 or X.shape[1] != W.shape[1]:
+            raise ValueError(f"init_prototypes: latents must be [N, {W.shape[1]}], got {tuple(latents.shape)}")
+        X = X.detach().to(device=W.device, dtype=torch.float32)
+        if X.stride(-1) != 1:
+            X = X.contiguous()
+        K, D = W.shape
+        fitted = None
+        if method == "pca":
+            from .pca import PCA
+            fitted = PCA(n_components=2, random_state=seed).fit(X)
+            uv = (self.pca_grid_coordinates() * float(span)).to(device=W.device, dtype=torch.float32).contiguous()
+            new = torch.empty(K, D, dtype=torch.float32, device=W.device)
+            ops.pca_reconstruct(uv, fitted.explained_variance_.sqrt().float(), fitted.components_, fitted.mean_, new)
+        elif method == "sample":
+            N = X.shape[0]
+            idx = np.random.RandomState(seed).choice(N, K, replace=N < K)
+            new = X[torch.from_numpy(idx).to(W.device)]
+        else:
+            raise ValueError(f"init_prototypes: unknown method {method!r} (pca or sample)")
+        if self.distance_fcn == "cosine":
+            new = torch.nn.functional.normalize(new, p=2, dim=1)
+        W.copy_(new)
+        self.invalidate_planes()
+        return fitted
+
     def adjacency_radius2(self) -> float:
         """Two units are grid neighbours when their grid_positions lie within this squared distance: square lattice
         distances^2 are 1, 2, 4, ... (2.25 takes the 8 around a cell), hexagonal ones 1, 3, ... (1.5 takes the 6)."""

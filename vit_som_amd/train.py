@@ -28,7 +28,7 @@ import torch
 import yaml
 
 from .evaluation import (evaluate_classification, evaluate_clustering, evaluate_embedding_quality, evaluate_knn,
-                         evaluate_map_quality, evaluate_silhouette)
+                         evaluate_map_quality, evaluate_silhouette, evaluate_latent_spectrum, init_som_from_data)
 from .classifier import ViTClassifier
 from .model import ViTSOM
 
@@ -276,7 +276,7 @@ def main_vit(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, 
 
 
 def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print, map_quality=False,
-         knn_eval=False, embedding_quality=False, silhouette=False):
+         knn_eval=False, embedding_quality=False, silhouette=False, som_init=None, latent_spectrum=False):
     """train_vit_som.py:27-130; a config with hyperparameters.model_arch == "vit" runs main_vit (train_vit.py) instead.
     model_states_dir defaults to experiments/states/vit_som (experiments/states/vit for the ViT baseline).
     map_quality: after each run's final evaluation also run evaluate_map_quality on the training loader with the model that
@@ -286,7 +286,13 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
     embedding_quality: likewise run evaluate_embedding_quality with that model on the training loader (as map_quality does)
     and report trustworthiness / continuity of the UMAP embedding of its latents.
     silhouette: likewise run evaluate_silhouette with that model on the training loader, the samples clustered by their
-    BMU, and report silhouette_bmu (NaN, with the reason logged, when fewer than two units or every sample alone won)."""
+    BMU, and report silhouette_bmu (NaN, with the reason logged, when fewer than two units or every sample alone won).
+    som_init: "pca" or "sample": before the first step of each run start the SOM's prototypes from the training loader's
+    latents under the fresh encoder (evaluation.init_som_from_data) instead of the uniform random start.
+    latent_spectrum: after each run also run evaluate_latent_spectrum with the evaluated model on the training loader and
+    report effective_rank and components_90 (the components that carry 90% of the variance; NaN when the top 64 do not)."""
+    if som_init not in (None, "pca", "sample"):
+        raise ValueError(f"som_init must be None, 'pca' or 'sample', got {som_init!r}")
     if config["hyperparameters"].get("model_arch") == "vit":
         return main_vit(config, n_runs=n_runs, max_epochs=max_epochs, make_loaders=make_loaders,
                         model_states_dir=model_states_dir or "experiments/states/vit", log=log)
@@ -312,6 +318,8 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
         all_metrics.update(trustworthiness=[], continuity=[])
     if silhouette:
         all_metrics.update(silhouette_bmu=[])
+    if latent_spectrum:
+        all_metrics.update(effective_rank=[], components_90=[])
     for run in range(n_runs):
         log(f"Starting run {run + 1} for {dataset_name}...")
         start = time.time()
@@ -321,6 +329,10 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
         model = ViTSOM(copy.deepcopy(config))
         model.set_distributed(world, rank)
         model.broadcast_parameters()                                      # DDP broadcasts rank 0's weights at construction
+        if som_init:
+            fitted = init_som_from_data(model, config, train_loader, method=som_init)
+            log(f"SOM initialised from the training latents ({som_init}"
+                + (f", PC1+PC2 carry {float(fitted.explained_variance_ratio_.sum()):.3f} of the variance)" if fitted is not None else ")"))
         out = fit(model, config, train_loader, val_loader, model_states_dir, dataset_name, use_validation, max_epochs, log)
         torch.cuda.synchronize()
         run_duration = time.time() - start
@@ -370,6 +382,13 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
                     raise
                 log(f"Silhouette: silhouette_bmu undefined ({err})")
                 all_metrics["silhouette_bmu"].append(float("nan"))
+        if latent_spectrum:
+            ls = evaluate_latent_spectrum(evaluated, config, train_loader)
+            c90 = ls.components_for[0.9]
+            log(f"Latent spectrum: effective_rank {ls.effective_rank:.2f} of the top {len(ls.explained_variance)}, "
+                f"components_90 {c90} ({ls.n_samples} samples)")
+            all_metrics["effective_rank"].append(ls.effective_rank)
+            all_metrics["components_90"].append(float("nan") if c90 is None else float(c90))
         all_metrics["run_duration"].append(run_duration)
         all_metrics["inference_time"].append(inf_t)
     if n_runs > 1:
@@ -394,6 +413,12 @@ def _parser():
                     help="after each run also report trustworthiness and continuity of the UMAP embedding of the training set's latents")
     ap.add_argument("--silhouette", action="store_true",
                     help="after each run also report the silhouette coefficient of the training set's latents clustered by their BMU")
+    ap.add_argument("--som-init", choices=("pca", "sample"), default=None,
+                    help="start the SOM's prototypes from the training set's latents: the plane of their first two principal "
+                         "components (pca) or random samples (sample), instead of the uniform random start")
+    ap.add_argument("--latent-spectrum", action="store_true",
+                    help="after each run also report the effective rank of the training set's latents and the number of principal "
+                         "components that carry 90%% of their variance")
     return ap
 
 
@@ -403,4 +428,5 @@ if __name__ == "__main__":
     if a.device_data or a.data_npz or a.device_randaug:
         loaders = lambda c, r, w: device_loaders(c, r, w, npz=a.data_npz, auto_augment=a.device_randaug)     # noqa: E731
     main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs, make_loaders=loaders, map_quality=a.map_quality,
-         knn_eval=a.knn_eval, embedding_quality=a.embedding_quality, silhouette=a.silhouette)
+         knn_eval=a.knn_eval, embedding_quality=a.embedding_quality, silhouette=a.silhouette, som_init=a.som_init,
+         latent_spectrum=a.latent_spectrum)
