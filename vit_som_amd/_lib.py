@@ -269,7 +269,9 @@ def stream():
 class Event:
     """A library-owned HIP event (vsom_event_record / vsom_stream_wait_event): an ordering edge between two of the step's
     streams that a launch tape can hold (torch.cuda.Event records would be invisible to it).  Ids come from a process-wide
-    pool of 512; `Event.pooled()` hands out round-robin events for record-then-wait edges that are consumed at once."""
+    supply of 512.  `Event.pooled()` hands out POOL events round-robin -- a new one per call until POOL exist, then the
+    oldest again -- for edges whose wait is enqueued before POOL - 1 further pooled calls: a record-then-wait pair, or a
+    join deferred by a block or two.  An edge whose wait may come later than that owns an `Event()` of its own."""
     _next_id = 0
     _pool, _pool_pos = [], 0
     POOL = 192
@@ -282,10 +284,11 @@ class Event:
 
     @classmethod
     def pooled(cls):
-        if len(cls._pool) < cls.POOL:
+        i = cls._pool_pos
+        cls._pool_pos = (i + 1) % cls.POOL
+        if i == len(cls._pool):                  # the pool is still filling: the event just made, not an older one
             cls._pool.append(cls())
-        cls._pool_pos = (cls._pool_pos + 1) % cls.POOL
-        return cls._pool[cls._pool_pos % len(cls._pool)]
+        return cls._pool[i]
 
     def record(self, torch_stream=None):
         """Record on `torch_stream` (default: the stream launches currently go to)."""

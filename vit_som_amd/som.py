@@ -111,6 +111,7 @@ class SOMLayer(_Base):
         self._wplanes_stamp = None
         self._raw_updates = 0           # updates of the prototypes that bypass torch (raw-pointer kernels)
         self._planes_used = False       # a forward took the planes path: the optimizer keeps the image current
+        self._w_ready_ev = None         # the event of _w_planes_async (a dedicated one: its wait comes a whole encoder later)
 
     # ---- plane image of the prototypes ---------------------------------------------------
     def _w_stamp(self):
@@ -141,7 +142,8 @@ class SOMLayer(_Base):
         """Bring the prototypes' image up to date on `side_stream`, behind everything the launch stream holds so far
         (the optimizer step that wrote the prototypes, the last contraction that read the image) -- when it is stale,
         or always with `force` (a recorded training step must contain the launch whatever the state it was recorded
-        in).  Returns the event the consumer has to wait for, or None when nothing was launched."""
+        in).  Returns the event the consumer has to wait for, or None when nothing was launched.  The event is the layer's
+        own: the consumer waits a whole encoder later, by which time a pooled event could have been recorded again."""
         W = self.prototypes
         if self._wplanes is None or self._wplanes.device != W.device or self._wplanes.numel() != ops.lib.vsom_bmu_planes_bytes(*W.shape):
             self._wplanes = ops.bmu_planes_alloc(W.shape[0], W.shape[1], W.device)
@@ -152,7 +154,9 @@ class SOMLayer(_Base):
         with on_stream(side_stream):
             ops.bmu_planes_from(W.detach(), self._wplanes)
         self._wplanes_stamp = self._w_stamp()
-        return Event.pooled().record(side_stream)
+        if self._w_ready_ev is None:
+            self._w_ready_ev = Event()
+        return self._w_ready_ev.record(side_stream)
 
     def _load_from_state_dict(self, *args, **kwargs):
         super()._load_from_state_dict(*args, **kwargs)

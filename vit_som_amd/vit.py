@@ -108,8 +108,9 @@ class _BackwardSchedule:
         self.pending = []
 
     def _event(self):
-        """Pooled library events (re-recording one is safe once the waits on its previous record are enqueued; the pool is
-        far longer than the few events whose wait is deferred by a block or two)."""
+        """A pooled library event: the next of Event.POOL in turn, so each record of a pass has an event of its own until
+        POOL - 1 further pooled calls have been made.  Re-recording one is safe once the waits on its previous record are
+        enqueued; the pool is far longer than the few events whose wait is deferred by a block or two (_side_join)."""
         return Event.pooled()
 
     def _dx(self, dy, weight, dx, **kw):
