@@ -668,6 +668,37 @@ int vsom_pca_rotate(const double* T, int l_out, int l_in, const float* Zt, long 
 int vsom_pca_reconstruct(const float* Y, long ldy, long M, int l, const float* scale, const float* B, long ldb, int D,
                          const float* mean, float* Xout, long ldo, vsom_stream_t stream);
 
+/* ------------------------------------------------------------------ Kohonen's batch map (batch_som.hip)
+ * One epoch of the batch SOM at radius sigma (SOMLayer.fit_batch drives it, DESIGN.md section 4 has the algorithm; no
+ * counterpart in the reference): the per-unit sums of the rows each unit won, then every prototype as the neighbourhood-
+ * weighted mean of those sums.  Scratch is a typed array with an element count, sized by a host-only query (0 for a size
+ * the entry refuses); a count below the query or a null array is VSOM_EWORKSPACE before any launch.  No floating-point
+ * atomics; every sum has one fixed order: all outputs are bitwise reproducible.
+ *
+ * vsom_som_batch_accumulate: counts[c] (int64) = the rows whose bmu is c, sums[c][d] (fp64, dense [K, D]) = the sum over
+ * those rows, in ASCENDING ROW INDEX, of (double)X[i][d] * (double)inv_norm[i] (inv_norm may be NULL: the rows themselves).
+ * `order` [N] is the stable sort permutation of bmu (order[j] = the row at sorted position j; torch.sort(stable=True)
+ * gives it).  accumulate = 0 overwrites sums and counts (units without rows get zeros), accumulate = 1 continues every
+ * chain from what they hold: cutting the rows into several calls changes no bit, and the result equals a sequential fp64
+ * loop over the rows.  A bmu outside [0, K) or an order entry outside [0, N) adds one to *bad (int, zeroed by the caller)
+ * and is never dereferenced; its row is left out.  16-byte loads when D % 4 == 0, ldx % 4 == 0 and X is 16-byte aligned,
+ * element-wise otherwise.  seg: vsom_som_batch_accumulate_parts(K) = K + 1 int64.  K <= 65535 (else VSOM_EUNSUPPORTED). */
+long vsom_som_batch_accumulate_parts(int K);
+int vsom_som_batch_accumulate(const float* X, long ldx, long N, int D, const int64_t* bmu, const int64_t* order,
+                              const float* inv_norm, int K, double* sums, int64_t* counts, int accumulate, int* bad, int64_t* seg,
+                              long n_seg, vsom_stream_t stream);
+/* vsom_som_batch_update: W_out[k] (f32, row stride ldw) = sum_c h(k,c) sums[c] / sum_c h(k,c) counts[c] over the units with
+ * counts[c] > 0, h(k,c) = exp(-(d2(k,c) - m_k) / (2 sigma^2)), d2 the squared distance of grid_positions [K, 2], m_k the
+ * smallest d2(k,c) among the units with hits: the largest weight of every row is exactly 1, so a unit far from every hit
+ * at a small radius is the mean of its nearest hit units instead of 0 / 0.  m_k and the denominators in fp64 (pre-pass);
+ * the numerator on the exact-f32 matrix cores, the weights generated from the positions (exponent in fp64, rounded once),
+ * sums rounded to f32 as loaded, the reduction over c in ascending order inside one workgroup.  normalize != 0: every row
+ * is L2-normalised afterwards (x / max(|x|, 1e-12)).  No unit with hits at all: W_out = 0.  sigma <= 0, not finite, or so
+ * extreme that 1 / (2 sigma^2) is 0 or infinite: VSOM_EINVAL.  part: vsom_som_batch_update_parts(K) = 4 K doubles. */
+long vsom_som_batch_update_parts(int K);
+int vsom_som_batch_update(const double* sums, const int64_t* counts, const float* grid_positions, int K, int D, double sigma,
+                          int normalize, float* W_out, long ldw, double* part, long n_part, vsom_stream_t stream);
+
 /* SOMLayer.som_loss(weights, distances) = mean(weights * distances) for ARBITRARY weights (som_layer.py:137-142):
    loss_sum <- sum_ik weights[i,k] dist[i,k]; with coef/row_dot/col_dot given, also the backward coefficients of
    grad_scale * that sum w.r.t. the distances' inputs (what vsom_som_bwd consumes) -- with weights = an upstream

@@ -9,7 +9,7 @@ three peers."""
 from . import _lib  # noqa: F401  (fails loudly when libvitsom_hip.so is absent)
 from . import ops  # noqa: F401
 from .vit import ViTAutoencoder  # noqa: F401,E402
-from .som import SOMLayer  # noqa: F401,E402
+from .som import BatchSOMReport, SOMLayer  # noqa: F401,E402
 from .optim import FusedAdamW, param_groups_lrd  # noqa: F401,E402
 from .model import ViTSOM  # noqa: F401,E402
 from .desom import DESOM, Autoencoder  # noqa: F401,E402
@@ -22,6 +22,7 @@ from .silhouette import SilhouetteReport, cluster_silhouette, silhouette_samples
 from .evaluation import evaluate_silhouette, visualize_silhouette_map  # noqa: F401,E402
 from .pca import PCA  # noqa: F401,E402
 from .evaluation import LatentSpectrum, evaluate_latent_spectrum, init_som_from_data, visualize_pca_map  # noqa: F401,E402
+from .evaluation import fit_som_batch  # noqa: F401,E402
 from .kmeans import KMeans, kmeans_plusplus  # noqa: F401,E402
 from .umap import UMAP  # noqa: F401,E402
 from .knn import KNNClassifier  # noqa: F401,E402

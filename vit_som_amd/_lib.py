@@ -174,6 +174,12 @@ SIGNATURES = {
     "vsom_pca_rotate": (C.c_int, [c_fp, C.c_int, C.c_int, c_fp, C.c_long, C.c_int, c_fp, C.c_long, c_stream]),
     "vsom_pca_reconstruct": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, c_fp, C.c_long, C.c_int, c_fp, c_fp, C.c_long,
                                        c_stream]),
+    "vsom_som_batch_accumulate_parts": (C.c_long, [C.c_int]),
+    "vsom_som_batch_accumulate": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, c_fp, c_fp, C.c_int, c_fp, c_fp, C.c_int, c_fp,
+                                            c_fp, C.c_long, c_stream]),
+    "vsom_som_batch_update_parts": (C.c_long, [C.c_int]),
+    "vsom_som_batch_update": (C.c_int, [c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_double, C.c_int, c_fp, C.c_long, c_fp, C.c_long,
+                                        c_stream]),
     "vsom_fill": (C.c_int, [c_fp, C.c_long, C.c_float, c_stream]),
     "vsom_scaled_mul": (C.c_int, [c_fp, c_fp, c_fp, C.c_long, c_fp, C.c_float, c_stream]),
     "vsom_som_weighted_loss": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_float, c_fp, c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_int,

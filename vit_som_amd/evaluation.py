@@ -875,6 +875,23 @@ def init_som_from_data(model, config, dataloader, method="pca", max_rows=None):
     return model.som_layer.init_prototypes(X, method=method)
 
 
+def fit_som_batch(model, config, dataloader, epochs=10, init=None, sigma=None, max_rows=None):
+    """Fit the SOM to the data with Kohonen's batch map (SOMLayer.fit_batch) -> BatchSOMReport: the latents of the loader
+    through the CURRENT encoder (a frozen or pretrained one is what this is for), at most max_rows of them (the first ones);
+    init "pca" or "sample" first starts the prototypes from those latents (SOMLayer.init_prototypes), None keeps them as
+    they are.  sigma as in fit_batch (None: Tmax down to Tmin).  For vit_som and desom; the model's training mode is
+    restored.  With model.world_size > 1 every rank holds all rows and computes the same map."""
+    training = model.training
+    X, _ = _som_latents(model, config, dataloader, "fit_som_batch")
+    model.train(training)
+    if max_rows is not None:
+        X = X[:int(max_rows)]
+    som = model.som_layer
+    if init is not None:
+        som.init_prototypes(X, method=init)
+    return som.fit_batch(X, epochs=epochs, sigma=sigma)
+
+
 # ------------------------------------------------------------------------------------ kNN probe
 @dataclass
 class KNNReport:

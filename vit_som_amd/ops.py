@@ -1211,6 +1211,57 @@ def pca_reconstruct(Y, scale, B, mean, Xout):
     return Xout
 
 
+# ---------------------------------------------------------------- Kohonen's batch map (SOMLayer.fit_batch)
+def som_batch_accumulate(X, bmu, sums, counts, inv_norm=None, accumulate=False, bad=None):
+    """counts [K] int64 = rows per unit, sums [K, D] float64 = per unit the sum of its rows of X [N, D] (times inv_norm [N]
+    when given), every (unit, column) one fp64 chain in ascending row index (see vsom_som_batch_accumulate).  accumulate=True
+    continues from what sums / counts hold: a row set cut into several calls gives the same bits as one call.
+    bad: an int32 [1] device counter of BMUs outside [0, K) the caller zeroes and reads later; None: checked here (one
+    host read) and raised as VsomError."""
+    N, D, ldx = _kmeans_x(X)
+    K = counts.numel()
+    assert bmu.dtype == torch.int64 and bmu.is_cuda and bmu.dim() == 1 and bmu.is_contiguous() and bmu.numel() == N, \
+        "bmu must be a contiguous int64 device vector of N"
+    _pca_f64(sums, (K, D), "sums")
+    assert counts.dtype == torch.int64 and counts.is_cuda and counts.dim() == 1 and counts.is_contiguous(), \
+        "counts must be a contiguous int64 device vector"
+    _pca_vec(inv_norm, N, "inv_norm")
+    own = bad is None
+    if own:
+        bad = torch.zeros(1, dtype=torch.int32, device=X.device)
+    assert bad.dtype == torch.int32 and bad.is_cuda and bad.numel() == 1
+    order = torch.sort(bmu, stable=True).indices              # the rows of a unit, ascending: what fixes every chain's order
+    n_seg = int(lib.vsom_som_batch_accumulate_parts(K))
+    seg = scratch(8 * n_seg, X.device)
+    check(lib.vsom_som_batch_accumulate(ptr(X), ldx, N, D, ptr(bmu), ptr(order), ptr(inv_norm), K, ptr(sums), ptr(counts),
+                                        int(bool(accumulate)), ptr(bad), ptr(seg), seg.numel() // 8, stream()),
+          "vsom_som_batch_accumulate")
+    if own:
+        n_bad = int(bad.item())
+        if n_bad:
+            raise _lib_mod.VsomError(f"vsom_som_batch_accumulate failed with status -1: {n_bad} rows have a BMU outside [0, {K})")
+    return sums, counts
+
+
+def som_batch_update(sums, counts, grid_positions, sigma, W_out, normalize=False):
+    """W_out [K, D] f32 = the batch-map update at radius sigma from sums [K, D] float64 and counts [K] int64 (see
+    vsom_som_batch_update); normalize=True L2-normalises every row afterwards (the cosine map)."""
+    K = counts.numel()
+    assert sums.dim() == 2, "sums must be [K, D]"
+    D = sums.shape[1]
+    _pca_f64(sums, (K, D), "sums")
+    assert counts.dtype == torch.int64 and counts.is_cuda and counts.dim() == 1 and counts.is_contiguous(), \
+        "counts must be a contiguous int64 device vector"
+    _f32(grid_positions, "grid_positions"); _f32(W_out, "W_out")
+    assert grid_positions.is_contiguous() and tuple(grid_positions.shape) == (K, 2), "grid_positions must be [K, 2]"
+    assert W_out.dim() == 2 and tuple(W_out.shape) == (K, D), "W_out must be [K, D]"
+    n_part = int(lib.vsom_som_batch_update_parts(K))
+    part = scratch(8 * n_part, sums.device)
+    check(lib.vsom_som_batch_update(ptr(sums), ptr(counts), ptr(grid_positions), K, D, float(sigma), int(bool(normalize)), ptr(W_out),
+                                    _rows(W_out), ptr(part), part.numel() // 8, stream()), "vsom_som_batch_update")
+    return W_out
+
+
 # ---------------------------------------------------------------- data-parallel exchange (RCCL)
 COMM_ID_BYTES = 128
 

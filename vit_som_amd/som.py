@@ -1,4 +1,5 @@
 """SOMLayer (models/som_layer.py:8-152) on the HIP kernels, with the autograd functions of its distances and loss."""
+from dataclasses import dataclass
 from typing import Dict, Optional
 
 import numpy as np
@@ -64,6 +65,18 @@ class _SomLossFn(torch.autograd.Function):
         gw = ops.scaled_mul(torch.empty_like(weights), distances, scale_dev=g, factor=inv) if ctx.needs_input_grad[0] else None
         gd = ops.scaled_mul(torch.empty_like(distances), weights, scale_dev=g, factor=inv) if ctx.needs_input_grad[1] else None
         return gw, gd
+
+
+@dataclass
+class BatchSOMReport:
+    """Host values of one SOMLayer.fit_batch run over T epochs (bmu stays on the device)."""
+    sigma: np.ndarray                    # float64 [T]: the radius of every epoch
+    quantization_error: np.ndarray       # float64 [T]: mean BMU distance (the layer's distance) BEFORE each update
+    final_quantization_error: float      # the same after the last update
+    moved: np.ndarray                    # int64 [T]: rows whose BMU differs from the previous epoch's (all rows in the first)
+    hits: np.ndarray                     # int64 [K]: rows per unit in the final search
+    dead_units: int                      # units no row hit in the final search
+    bmu: torch.Tensor                    # int64 [N] on the device: the final search
 
 
 # ------------------------------------------------------------------------------------ SOM layer
@@ -225,6 +238,100 @@ class SOMLayer(_Base):
         W.copy_(new)
         self.invalidate_planes()
         return fitted
+
+    # ---- Kohonen's batch map ----------------------------------------------------------------
+    def batch_sigma_schedule(self, epochs, sigma=None) -> np.ndarray:
+        """The radii of fit_batch, float64 [epochs].  None: the layer's own schedule Tmax (Tmin / Tmax)^(t / (T - 1)) (Tmax
+        when T = 1); a float: constant; a pair (hi, lo): the same geometric schedule between the two; a sequence of length
+        `epochs`: the radii themselves (for two epochs the two readings of a pair agree)."""
+        T = int(epochs)
+        if T < 1:
+            raise ValueError(f"fit_batch: epochs must be >= 1, got {epochs}")
+        if sigma is None:
+            sigma = (float(self.Tmax), float(self.Tmin))
+        if isinstance(sigma, (int, float, np.integer, np.floating)):
+            s = np.full(T, float(sigma), dtype=np.float64)
+        else:
+            seq = [float(v) for v in sigma]
+            if len(seq) == T:
+                s = np.asarray(seq, dtype=np.float64)
+            elif len(seq) == 2:
+                hi, lo = seq
+                if not (hi > 0 and lo > 0):
+                    raise ValueError(f"fit_batch: radii must be positive and finite, got {sigma!r}")
+                s = hi * (lo / hi) ** (np.arange(T, dtype=np.float64) / (T - 1)) if T > 1 else np.full(1, hi, dtype=np.float64)
+            else:
+                raise ValueError(f"fit_batch: sigma must be None, a number, a pair (hi, lo) or {T} radii, got {len(seq)} values")
+        if not (np.all(np.isfinite(s)) and np.all(s > 0)):
+            raise ValueError(f"fit_batch: radii must be positive and finite, got {s.tolist()}")
+        return s
+
+    def _bmu_search(self, X, bmu_out, chunk):
+        """BMU of every row of X into bmu_out [N], in chunks of rows through _distances_into; -> the sum of the BMU
+        distances as a float64 device scalar."""
+        total = torch.zeros((), dtype=torch.float64, device=X.device)
+        for i0 in range(0, X.shape[0], chunk):
+            xc = X[i0:i0 + chunk]
+            s = self._buffers_for(xc.shape[0], xc.device)
+            self._distances_into(xc, s)
+            bmu_out[i0:i0 + xc.shape[0]].copy_(s.bmu)
+            total += s.dist.gather(1, s.bmu.view(-1, 1)).sum(dtype=torch.float64)
+        return total
+
+    @torch.no_grad()
+    def fit_batch(self, latents, epochs=10, sigma=None, chunk=8192) -> "BatchSOMReport":
+        """Train the map on `latents` [N, D] (a device tensor) with Kohonen's batch rule (SOM Toolbox som_batchtrain,
+        somoclu): no learning rate, no optimizer state, one pass over the data per epoch.  Per epoch at radius sigma_t
+        (batch_sigma_schedule): the BMU of every row under the layer's own distance (the existing search, `chunk` rows
+        at a time), the per-unit sums and hit counts (ops.som_batch_accumulate; the rows times 1 / |row| for the cosine
+        distance), then every prototype as the neighbourhood-weighted mean of the sums (ops.som_batch_update; L2-normalised
+        for the cosine distance).  The prototypes are written in place; one more search follows the last update.
+        The manhattan distance is refused: its batch rule is a weighted median, not a mean.  Nothing N- or D-sized goes to
+        the host: the report's scalars are read once, at the end.  The searches run in a buffer set of their own ([chunk, K]
+        distances), dropped on return: the layer's training and validation buffers are neither evicted nor grown."""
+        W = self.prototypes
+        if self._dist_mode == ops.DIST_MANHATTAN:
+            raise NotImplementedError("fit_batch: the batch rule of the manhattan distance is a weighted median, not the weighted "
+                                      "mean implemented here; use the cosine or the euclidean distance")
+        X = latents.flatten(start_dim=1) if latents.dim() > 2 else latents
+        if X.dim() != 2 or X.shape[1] != W.shape[1]:
+            raise ValueError(f"fit_batch: latents must be [N, {W.shape[1]}], got {tuple(latents.shape)}")
+        if X.shape[0] < 1:
+            raise ValueError("fit_batch: latents is empty")
+        if int(chunk) < 1:
+            raise ValueError(f"fit_batch: chunk must be >= 1, got {chunk}")
+        radii = self.batch_sigma_schedule(epochs, sigma)
+        X = X.detach().to(device=W.device, dtype=torch.float32)
+        if X.stride(-1) != 1:
+            X = X.contiguous()
+        N, (K, D), T, dev = X.shape[0], W.shape, len(radii), W.device
+        cosine = self._dist_mode == ops.DIST_COSINE
+        inv_norm = ops.row_inv_norm(X, torch.empty(N, dtype=torch.float32, device=dev)) if cosine else None
+        pos = self.grid_positions.to(device=dev, dtype=torch.float32).contiguous()
+        sums = torch.empty(K, D, dtype=torch.float64, device=dev)
+        counts = torch.empty(K, dtype=torch.int64, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        bmu, prev = torch.empty(N, dtype=torch.int64, device=dev), torch.full((N,), -1, dtype=torch.int64, device=dev)
+        stats = torch.zeros(T + 1, 2, dtype=torch.float64, device=dev)          # per epoch: sum of BMU distances, rows moved
+        kept, self._bufs = self._bufs, {}
+        try:
+            for t in range(T):
+                stats[t, 0] = self._bmu_search(X, bmu, int(chunk))
+                stats[t, 1] = (bmu != prev).sum()
+                ops.som_batch_accumulate(X, bmu, sums, counts, inv_norm=inv_norm, bad=bad)
+                ops.som_batch_update(sums, counts, pos, float(radii[t]), W.data, normalize=cosine)
+                self.invalidate_planes()
+                bmu, prev = prev, bmu
+            stats[T, 0] = self._bmu_search(X, bmu, int(chunk))
+        finally:
+            self._bufs = kept
+        hits = torch.bincount(bmu, minlength=K)
+        host = stats.cpu().numpy()
+        if int(bad.item()):
+            raise RuntimeError(f"fit_batch: the BMU search returned {int(bad.item())} units outside the map")
+        hits = hits.cpu().numpy().astype(np.int64)
+        return BatchSOMReport(sigma=radii, quantization_error=host[:T, 0] / N, final_quantization_error=float(host[T, 0] / N),
+                              moved=host[:T, 1].astype(np.int64), hits=hits, dead_units=int((hits == 0).sum()), bmu=bmu)
 
     def adjacency_radius2(self) -> float:
         """Two units are grid neighbours when their grid_positions lie within this squared distance: square lattice

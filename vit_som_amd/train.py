@@ -28,7 +28,8 @@ import torch
 import yaml
 
 from .evaluation import (evaluate_classification, evaluate_clustering, evaluate_embedding_quality, evaluate_knn,
-                         evaluate_map_quality, evaluate_silhouette, evaluate_latent_spectrum, init_som_from_data)
+                         evaluate_map_quality, evaluate_silhouette, evaluate_latent_spectrum, fit_som_batch,
+                         init_som_from_data)
 from .classifier import ViTClassifier
 from .model import ViTSOM
 
@@ -276,7 +277,7 @@ def main_vit(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, 
 
 
 def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print, map_quality=False,
-         knn_eval=False, embedding_quality=False, silhouette=False, som_init=None, latent_spectrum=False):
+         knn_eval=False, embedding_quality=False, silhouette=False, som_init=None, latent_spectrum=False, som_batch_epochs=0):
     """train_vit_som.py:27-130; a config with hyperparameters.model_arch == "vit" runs main_vit (train_vit.py) instead.
     model_states_dir defaults to experiments/states/vit_som (experiments/states/vit for the ViT baseline).
     map_quality: after each run's final evaluation also run evaluate_map_quality on the training loader with the model that
@@ -289,10 +290,15 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
     BMU, and report silhouette_bmu (NaN, with the reason logged, when fewer than two units or every sample alone won).
     som_init: "pca" or "sample": before the first step of each run start the SOM's prototypes from the training loader's
     latents under the fresh encoder (evaluation.init_som_from_data) instead of the uniform random start.
+    som_batch_epochs: N > 0: after som_init and before the first step of each run fit the SOM to the training loader's
+    latents under the fresh encoder with N epochs of Kohonen's batch map (evaluation.fit_som_batch), and log the
+    quantization error before and after; 0 (the default) changes nothing.
     latent_spectrum: after each run also run evaluate_latent_spectrum with the evaluated model on the training loader and
     report effective_rank and components_90 (the components that carry 90% of the variance; NaN when the top 64 do not)."""
     if som_init not in (None, "pca", "sample"):
         raise ValueError(f"som_init must be None, 'pca' or 'sample', got {som_init!r}")
+    if int(som_batch_epochs) != som_batch_epochs or som_batch_epochs < 0:
+        raise ValueError(f"som_batch_epochs must be a non-negative integer, got {som_batch_epochs!r}")
     if config["hyperparameters"].get("model_arch") == "vit":
         return main_vit(config, n_runs=n_runs, max_epochs=max_epochs, make_loaders=make_loaders,
                         model_states_dir=model_states_dir or "experiments/states/vit", log=log)
@@ -333,6 +339,10 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
             fitted = init_som_from_data(model, config, train_loader, method=som_init)
             log(f"SOM initialised from the training latents ({som_init}"
                 + (f", PC1+PC2 carry {float(fitted.explained_variance_ratio_.sum()):.3f} of the variance)" if fitted is not None else ")"))
+        if som_batch_epochs:
+            br = fit_som_batch(model, config, train_loader, epochs=int(som_batch_epochs))
+            log(f"SOM batch map: {int(som_batch_epochs)} epochs, quantization error {float(br.quantization_error[0]):.4f} before, "
+                f"{br.final_quantization_error:.4f} after, dead units {br.dead_units}/{br.hits.size}")
         out = fit(model, config, train_loader, val_loader, model_states_dir, dataset_name, use_validation, max_epochs, log)
         torch.cuda.synchronize()
         run_duration = time.time() - start
@@ -416,6 +426,9 @@ def _parser():
     ap.add_argument("--som-init", choices=("pca", "sample"), default=None,
                     help="start the SOM's prototypes from the training set's latents: the plane of their first two principal "
                          "components (pca) or random samples (sample), instead of the uniform random start")
+    ap.add_argument("--som-batch-epochs", type=int, default=0, metavar="N",
+                    help="before the first step (after --som-init) fit the SOM to the training set's latents with N epochs of "
+                         "Kohonen's batch map")
     ap.add_argument("--latent-spectrum", action="store_true",
                     help="after each run also report the effective rank of the training set's latents and the number of principal "
                          "components that carry 90%% of their variance")
@@ -429,4 +442,4 @@ if __name__ == "__main__":
         loaders = lambda c, r, w: device_loaders(c, r, w, npz=a.data_npz, auto_augment=a.device_randaug)     # noqa: E731
     main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs, make_loaders=loaders, map_quality=a.map_quality,
          knn_eval=a.knn_eval, embedding_quality=a.embedding_quality, silhouette=a.silhouette, som_init=a.som_init,
-         latent_spectrum=a.latent_spectrum)
+         latent_spectrum=a.latent_spectrum, som_batch_epochs=a.som_batch_epochs)
