@@ -433,6 +433,69 @@ def test_evaluate_silhouette_two_ranks(tmp_path):
     assert np.array_equal(r0["sil"], single.per_sample.cpu().numpy()) and np.array_equal(r0["counts"], single.counts)
 
 
+def _whole_set_entries(m, cfg, loader):
+    """What the three entries that collect the whole set on every rank return on `loader`, as host arrays."""
+    from vit_som_amd.evaluation import evaluate_kmeans, evaluate_latent_spectrum, evaluate_silhouette
+    purity, nmi, _ = evaluate_kmeans(m, cfg, loader)
+    sil = evaluate_silhouette(m, cfg, loader)
+    spec = evaluate_latent_spectrum(m, cfg, loader)
+    return dict(kmeans=np.array([purity, nmi], dtype=np.float64), score=np.array([sil.score], dtype=np.float64),
+                per_cluster=sil.per_cluster, counts=sil.counts, explained_variance=spec.explained_variance,
+                total_variance=np.array([spec.total_variance], dtype=np.float64))
+
+
+def _whole_set_worker(rank, world, port, out):
+    import torch.distributed as dist
+    from test_knn_gpu import _loaders, _model
+    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+    m, cfg = _model("ref_cluster_tiny")
+    train, _ = _loaders(cfg, 4)
+    _spread_map(m, cfg, train)                                   # as one process: before the model learns of the ranks
+    m.world_size, m.rank = world, rank
+    np.savez(f"{out}.{rank}.npz", **_whole_set_entries(m, cfg, train[:5] if rank == 0 else train[5:]))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_whole_set_entries_two_ranks(tmp_path):
+    """evaluate_kmeans, evaluate_silhouette and evaluate_latent_spectrum share one collector: every rank gathers all rows,
+    rank 0's first.  The 96 samples are dealt in contiguous halves (batches 0-4: 50 rows, batches 5-9: 46 rows), so the
+    gathered rows are the single-process rows in the single-process order, and both ranks must return bit for bit what
+    one process returns on the whole loader."""
+    import torch.multiprocessing as mp
+    from test_distributed import _free_port
+    from test_knn_gpu import _loaders, _model
+    out = str(tmp_path / "whole")
+    mp.spawn(_whole_set_worker, args=(2, _free_port(), out), nprocs=2, join=True)
+    m, cfg = _model("ref_cluster_tiny")
+    train, _ = _loaders(cfg, 4)
+    assert len(train) == 10
+    _spread_map(m, cfg, train)
+    single = _whole_set_entries(m, cfg, train)
+    assert single["counts"].sum() == 96 and single["explained_variance"].size >= 2
+    for rank in (0, 1):
+        got = np.load(f"{out}.{rank}.npz")
+        assert set(got.files) == set(single)
+        for key, want in single.items():
+            assert got[key].dtype == want.dtype and got[key].shape == want.shape, (rank, key)
+            assert got[key].tobytes() == want.tobytes(), (rank, key)
+
+
+def test_an_empty_loader_is_a_value_error():
+    """Every entry that collects the whole set names itself and the empty loader, whatever it reads from the model."""
+    from test_knn_gpu import _model
+    from vit_som_amd import evaluation as ev
+    m, cfg = _model("ref_cluster_tiny")
+    for name in ("evaluate_kmeans", "evaluate_silhouette", "evaluate_latent_spectrum", "evaluate_embedding_quality",
+                 "visualize_umap_progression", "visualize_umap_map", "visualize_pca_map", "init_som_from_data", "fit_som_batch"):
+        with pytest.raises(ValueError, match=f"^{name}: the loader is empty$"):
+            getattr(ev, name)(m, cfg, [])
+    m.train()
+    with pytest.raises(ValueError, match="empty"):
+        ev.fit_som_batch(m, cfg, [])
+    assert m.training and torch.is_grad_enabled()                  # both modes are restored on the error path too
+
+
 def test_driver_reports_silhouette_bmu(tmp_path):
     from vit_som_amd.train import main, synthetic_loaders
     _, cfg = load_golden("ref_cluster_tiny")

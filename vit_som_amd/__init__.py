@@ -5,7 +5,7 @@ Layers, lowest first: ``_lib`` / ``ops`` (the C-ABI), ``arena``, ``tuning`` and 
 (ViTAutoencoder) and ``som`` (SOMLayer); ``optim`` (FusedAdamW) and ``step`` (the fused step's
 machinery shared by every arena-owning model); ``vit_owner`` (what the two ViT models share);
 ``model`` (ViTSOM), ``classifier`` (ViTClassifier, the plain ViT baseline) and ``desom`` (DESOM),
-three peers."""
+three peers; ``plots`` (host-only drawing) under ``evaluation``."""
 from . import _lib  # noqa: F401  (fails loudly when libvitsom_hip.so is absent)
 from . import ops  # noqa: F401
 from .vit import ViTAutoencoder  # noqa: F401,E402

@@ -1,31 +1,28 @@
-"""On-device evaluation mirroring the reference's tools/evaluation.py entry points
-(evaluate_clustering :18-52, evaluate_kmeans :54-91, evaluate_classification :93-128, calculate_purity :130-151).
+"""On-device evaluation behind the reference's tools/evaluation.py entry points, and what this project adds to them.
+The model forward runs on the HIP kernels; what an entry folds or collects stays on the device, and the host sees a table
+or a report at the end.  One rule holds for every entry: NO HOST SYNCHRONISATION INSIDE A LOADER LOOP.
 
-The model forward runs on the HIP kernels (encoder + SOM only: `ViTSOM.predict`); BMU / label
-pairs are folded into a contingency table ON DEVICE batch by batch (`vsom_contingency`, integer
-atomics), so the only device->host traffic of a whole evaluation pass is that table.  Purity, NMI
-(sklearn's arithmetic-mean normalisation) and the macro precision / recall / F1 are O(classes^2)
-host arithmetic on the table.  evaluate_kmeans keeps the model outputs in one device buffer and clusters them with
-the HIP k-means (kmeans.py); visualize_umap_progression (:267-323) embeds the latent representations with the HIP
-UMAP (umap.py), and visualize_umap_map (no counterpart) places the SOM's prototypes into that embedding with
-UMAP.transform and draws the unit grid over it.  The two pictures of the map itself: visualize_decoded_prototypes / decode_prototype (:153-222) push the
-prototypes through the ViT decoder in batches and assemble the mosaic on the device (`vsom_proto_mosaic`);
-visualize_label_heatmap (:224-265) folds (BMU, label) pairs into a last-label-per-cell table (`vsom_last_label`).
-Map quality has no counterpart in the reference: evaluate_map_quality folds the distances and BMUs every predict() leaves
-in the SOM layer's buffers into quantization error, topographic error, hit map and nearest sample per unit
-(`vsom_map_stats`), umatrix / visualize_umatrix / visualize_hit_map draw the map without labels (`vsom_umatrix`).
-evaluate_knn (no counterpart either) asks how much class information the latents carry: every test sample is classified by
-a weighted vote of its k nearest training samples in latent space (knn.py: `vsom_knn_query` / `vsom_knn_vote`), the training
-set streamed through a fixed-size device buffer.
-evaluate_embedding_quality (no counterpart either) says how far the UMAP pictures can be believed: trustworthiness and
-continuity of the embedding against the latents (embedding_quality.py: `vsom_umap_knn` / `vsom_knn_ranks`); map_neighbourhood
-asks the same of the map itself, the prototypes against their grid.
-evaluate_silhouette (no counterpart either) says whether the clusters -- the SOM's units, or k-means' -- are compact and
-separated in latent space, without labels (silhouette.py: `vsom_silhouette`); visualize_silhouette_map draws it per unit.
-Principal components (pca.py: `vsom_pca_*`; no counterpart either): evaluate_latent_spectrum says how many directions the
-encoder uses, visualize_pca_map is the linear, deterministic counterpart of visualize_umap_map, and init_som_from_data
-starts the map on the plane of the latents' first two principal components (SOMLayer.init_prototypes).
-"""
+Scaffolding, each written once:
+  _Arch         what a vit_som or a desom model is fed and what is read from it; the one unsupported-model error
+  _Arch.batches the loader loop: model.eval(), the batch moved to the model's device and shaped, labels flat int64
+  _whole_set    a reader's rows of every batch (copied), concatenated, all-gathered over the ranks (rank 0's first)
+  _rank_shift   where this rank's sample ordinals start among all ranks'
+  plots.py      the drawing, from host arrays
+
+Entries, by what they read from the model (every entry runs with grad mode off; with model.world_size > 1 every rank
+returns the whole set's result; figures are drawn by rank 0):
+  predict(), images for every arch     evaluate_clustering (BMUs -> `vsom_contingency`), evaluate_classification (logits)
+  predict(), the arch's own shape      visualize_label_heatmap (`vsom_last_label`), evaluate_map_quality / visualize_hit_map
+                                       (the SOM layer's buffers -> `vsom_map_stats`)
+  k-means feature, model(x)[1]         evaluate_kmeans (kmeans.py)
+  get_latent_representation, images    visualize_umap_progression (umap.py)
+  latent                               visualize_umap_map, evaluate_embedding_quality (embedding_quality.py),
+                                       visualize_pca_map (pca.py), evaluate_knn (knn.py)
+  SOM input and BMU                    evaluate_silhouette / visualize_silhouette_map (silhouette.py),
+                                       evaluate_latent_spectrum, init_som_from_data, fit_som_batch (SOMLayer.fit_batch)
+  the prototypes only, no data         visualize_decoded_prototypes / decoded_prototype_canvas / decode_prototype
+                                       (`vsom_proto_mosaic`), umatrix / visualize_umatrix (`vsom_umatrix`), map_neighbourhood
+Host arithmetic on a table: purity_from_table, nmi_from_table, classification_from_table, calculate_purity."""
 import os
 import time
 from dataclasses import dataclass
@@ -37,6 +34,7 @@ from . import ops
 from .embedding_quality import EmbeddingQuality, embedding_quality, subset_scores
 from .kmeans import KMeans
 from .knn import KNNClassifier
+from .plots import _draw_grid, _draw_map, _pyplot, _save_scatter, _umap_scatter, draw_decoded_prototypes, draw_label_heatmap  # noqa: F401
 from .silhouette import cluster_silhouette
 from .umap import UMAP
 
@@ -129,23 +127,147 @@ def _world(model):
     return int(getattr(model, "world_size", 1))
 
 
+def _rank(model):
+    return int(getattr(model, "rank", 0))
+
+
+def _label_count(config, num_labels, at_least_256):
+    """num_labels when given.  Else data.num_classes: raised to 256 (at_least_256, the tables of the clustering
+    entries), or 256 only when the config has none (the kNN probe, whose vote kernel takes at most 1024 classes)."""
+    if num_labels:
+        return int(num_labels)
+    n = int(config["data"].get("num_classes", 0))
+    return max(n, 256) if at_least_256 or n <= 0 else n
+
+
+class _Arch:
+    """What a vit_som or a desom model is fed and what is read from it, for the entry `who`.  The only place in this
+    module that knows the architectures.  Shapes take a batch on the device; readers take the shaped batch and may return
+    views of buffers that the model's next forward overwrites."""
+    _PROBES = {("vit_som", "latent"): "get_latent_representation", ("vit_som", "som_input"): "_som_input",
+               ("desom", "latent"): "autoencoder", ("desom", "som_input"): "autoencoder"}
+
+    def __init__(self, model, config, who):
+        d = config["data"]
+        self.model, self.who = model, who
+        self.C, self.S = d["num_channels"], d["input_size"]
+        self.name = config.get("hyperparameters", {}).get("model_arch")
+
+    @property
+    def device(self):
+        return self.model.arena.device
+
+    def require(self, reader=None):
+        """Refuse, before any batch is read, a model_arch that is neither vit_som nor desom and a model that lacks what
+        `reader` ("latent", "som_input") reads.  Returns self."""
+        probe = self._PROBES.get((self.name, reader))
+        if self.name not in ("vit_som", "desom") or (probe is not None and not hasattr(self.model, probe)):
+            raise ValueError(f"{self.who}: needs a vit_som or a desom model; got {type(self.model).__name__} with "
+                             f"model_arch {self.name!r}")
+        return self
+
+    @staticmethod
+    def is_vit_som(config):
+        """For an entry the reference has for vit_som alone, asked before anything of the model is touched."""
+        return config["hyperparameters"]["model_arch"] == "vit_som"
+
+    # ---- shapes
+    def images(self, x):
+        return x.reshape(-1, self.C, self.S, self.S)
+
+    @staticmethod
+    def flat(x):
+        return x.reshape(x.shape[0], -1)
+
+    def own(self, x):
+        """The shape the architecture's forward takes (after require())."""
+        return self.images(x) if self.name == "vit_som" else self.flat(x)
+
+    # ---- readers
+    def latent(self, x):
+        """[B, D] features: get_latent_representation for vit_som, x_encoded for desom (require("latent"))."""
+        return self.model.get_latent_representation(x) if self.name == "vit_som" else self.model(x)[1]
+
+    def som_input(self, x):
+        """(the rows the SOM layer was given, the unit each of them won) (require("som_input")).  vit_som: predict()
+        leaves the BMUs in the SOM layer's buffers and the encoder output in the ViT's.  desom: forward() returns both."""
+        m = self.model
+        if self.name == "vit_som":
+            bmu, _ = m.predict(x)
+            return m._som_input(m.vit._buffers_for(x.shape[0], x.device)), bmu
+        _, z, _, bmu = m(x)
+        return z, bmu
+
+    def kmeans_feature(self, x):
+        """The SECOND output of forward(): recon_img for vit_som (the reference calls it x_encoded, vit_som.py:67-78), the
+        encoder latent for desom (desom.py:50-54)."""
+        return self.model(x)[1]
+
+    # ---- the loader loop
+    def batches(self, loader, shape, labels=True):
+        """THE loop over a data loader: the model in eval mode, every batch moved to its device; yields (shape(x), y) with
+        y flat int64 on the device, or None -- the loader's labels untouched -- when labels is False.  Grad mode is the
+        caller's business (a generator cannot hold a no_grad across its yields): every entry is @torch.no_grad()."""
+        self.model.eval()
+        dev = self.device
+        for x, y in loader:
+            x = shape(x.to(dev, non_blocking=True))
+            yield x, (y.to(dev, non_blocking=True).reshape(-1).long().contiguous() if labels else None)
+
+
+def _rows(arch, loader, read, labels, shape=None, what="loader"):
+    """This rank's (X [N, D] float32, second [N] int64) over the loader, on the device.  labels True: read(x) gives the
+    rows and second is the labels.  labels False: read(x) gives (rows, units) and the labels are not touched.  What a
+    reader returns is copied: it may be a view of a buffer the next batch overwrites."""
+    first, second = [], []
+    batches = arch.batches(loader, shape or arch.own, labels)
+    for x, y in batches:
+        z, other = (read(x), None) if labels else read(x)
+        first.append(z.reshape(z.shape[0], -1).float().clone())
+        second.append(y if labels else other.reshape(-1).long().clone())
+    if not first:
+        raise ValueError(f"{arch.who}: the {what} is empty")
+    return torch.cat(first).contiguous(), torch.cat(second).contiguous()
+
+
+def _whole_set(arch, loader, read, labels, shape=None):
+    """_rows over the whole set on every rank: with model.world_size > 1 every rank gathers all rows, rank 0's first."""
+    X, second = _rows(arch, loader, read, labels, shape)
+    world = _world(arch.model)
+    if world > 1:
+        X, second = _gather_rows(X, world).contiguous(), _gather_rows(second, world).contiguous()
+    return X, second
+
+
+def _rank_shift(model, seen, who):
+    """-> (before, total): the samples the ranks before this one have seen, and all ranks' together; (0, seen) in a single
+    process.  Ordinals travel in 31 bits of a packed word: 2^31 samples or more raise ValueError."""
+    world = _world(model)
+    if world == 1:
+        return 0, seen
+    import torch.distributed as dist
+    dev = model.arena.device
+    counts = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(world)]
+    dist.all_gather(counts, torch.tensor([seen], dtype=torch.int64, device=dev))
+    counts = [int(c) for c in counts]
+    if sum(counts) >= 2 ** 31:
+        raise ValueError(f"{who}: more than 2^31 - 1 samples")
+    return sum(counts[:_rank(model)]), sum(counts)
+
+
+@torch.no_grad()
 def evaluate_clustering(model, config, dataloader, num_labels=None):
     """evaluation.py:18-52 -> (purity, nmi, inference_time) from the model's native BMU assignments.  No host
     synchronisation inside the loop: labels outside [0, num_labels) are counted on the device and reported once at the
     end (num_labels defaults to max(data.num_classes, 256)).  With model.world_size > 1 every rank folds its shard and
     the tables are summed, so all ranks return the metrics of the whole set."""
-    model.eval()
-    d = config["data"]
-    C, S = d["num_channels"], d["input_size"]
-    K = model.som_layer.n_prototypes
-    dev = model.arena.device
-    L = int(num_labels) if num_labels else max(int(d.get("num_classes", 0)), 256)
-    table, start = _Table(K, L, dev), time.time()
-    for x, y in dataloader:
-        x = x.to(dev, non_blocking=True).reshape(-1, C, S, S)
-        y = y.to(dev, non_blocking=True)
+    arch = _Arch(model, config, "evaluate_clustering")
+    table = _Table(model.som_layer.n_prototypes, _label_count(config, num_labels, True), arch.device)
+    start = time.time()
+    batches = arch.batches(dataloader, arch.images)
+    for x, y in batches:
         bmu, _ = model.predict(x)
-        table.add(bmu, y.view(-1))
+        table.add(bmu, y)
     w = table.numpy(_world(model))
     purity, nmi = purity_from_table(w), nmi_from_table(w)
     inference_time = time.time() - start
@@ -167,6 +289,7 @@ def _gather_rows(t, world_size):
     return torch.cat([p[:s] for p, s in zip(parts, sizes)])
 
 
+@torch.no_grad()
 def evaluate_kmeans(model, config, dataloader, num_labels=None):
     """evaluation.py:54-91 -> (purity, nmi, inference_time) of KMeans(n_clusters=len(unique(labels)), random_state=0,
     n_init=10) on the model's outputs.  The features are what the reference clusters: for vit_som the SECOND output of
@@ -174,29 +297,10 @@ def evaluate_kmeans(model, config, dataloader, num_labels=None):
     the encoder latent x_encoded (desom.py:50-54).  Features and labels stay on the device; the fit is the HIP k-means
     (kmeans.py).  Labels must lie in [0, num_labels) (default max(data.num_classes, 256)).  With model.world_size > 1
     every rank gathers the whole set and runs the same deterministic fit, so all ranks report the whole set's metrics."""
-    model.eval()
-    d = config["data"]
-    C, S = d["num_channels"], d["input_size"]
-    arch = config["hyperparameters"]["model_arch"]
-    dev = model.arena.device
-    L = int(num_labels) if num_labels else max(int(d.get("num_classes", 0)), 256)
-    feats, labels, start = [], [], time.time()
-    with torch.no_grad():                                  # evaluation.py:67
-        for x, y in dataloader:
-            x = x.to(dev, non_blocking=True)
-            y = y.to(dev, non_blocking=True)
-            if arch == "vit_som":
-                _, f, *_ = model(x.reshape(-1, C, S, S))
-            elif arch == "desom":
-                _, f, *_ = model(x.reshape(x.shape[0], -1))
-            else:
-                raise ValueError(f"evaluate_kmeans: unknown model_arch {arch!r}")
-            feats.append(f.reshape(f.shape[0], -1))
-            labels.append(y.reshape(-1).long())
-    X, y = torch.cat(feats), torch.cat(labels)
-    world = _world(model)
-    if world > 1:
-        X, y = _gather_rows(X, world), _gather_rows(y, world)
+    arch = _Arch(model, config, "evaluate_kmeans").require()
+    dev, L = arch.device, _label_count(config, num_labels, True)
+    start = time.time()
+    X, y = _whole_set(arch, dataloader, arch.kmeans_feature, labels=True)
     hist = _Table(1, L, dev)                               # len(np.unique(y_trues)), labels range-checked
     hist.add(torch.zeros_like(y), y)
     n_clusters = int((hist.numpy() > 0).sum())
@@ -208,28 +312,6 @@ def evaluate_kmeans(model, config, dataloader, num_labels=None):
     inference_time = time.time() - start
     print(f"Purity (KMeans): {purity:.3f}, NMI (KMeans): {nmi:.3f}, Inference Time: {inference_time:.3f}")
     return purity, nmi, inference_time
-
-
-def _umap_latents(model, config, dataloader, feats):
-    """feats(x, C, S) of every batch (copied: the model's buffers are reused by the next batch) and the labels, as device
-    tensors over the whole set: with model.world_size > 1 every rank gathers all rows, rank 0's first."""
-    model.eval()
-    d = config["data"]
-    C, S = d["num_channels"], d["input_size"]
-    dev = model.arena.device
-    lat, labels = [], []
-    with torch.no_grad():
-        for x, y in dataloader:
-            x = x.to(dev, non_blocking=True)
-            y = y.to(dev, non_blocking=True)
-            z = feats(x, C, S)
-            lat.append(z.reshape(z.shape[0], -1).float().clone())
-            labels.append(y.reshape(-1).long())
-    X, y = torch.cat(lat), torch.cat(labels)
-    world = _world(model)
-    if world > 1:
-        X, y = _gather_rows(X, world), _gather_rows(y, world)
-    return X.contiguous(), y
 
 
 def _umap_fit_subset(N, fit_rows):
@@ -260,26 +342,10 @@ def _umap_embed(X, fit_rows=None):
     return reducer, embedding
 
 
-def _draw_grid(plt, protos, nbr_idx):
-    """The unit grid over a scatter plot: a line between units the topology makes adjacent, a marker per unit."""
-    for u, row in enumerate(nbr_idx):
-        for v in row[row > u]:                               # every grid edge once
-            plt.plot(protos[[u, v], 0], protos[[u, v], 1], color="black", linewidth=0.4, alpha=0.8)
-    plt.scatter(protos[:, 0], protos[:, 1], c="black", s=8, marker="o", edgecolor="white", linewidth=0.3, zorder=3)
+_UMAP_SAVEFIG = dict(bbox_inches="tight", pad_inches=0, transparent=False, dpi=400)
 
 
-def _umap_scatter(plt, embedding, all_labels):
-    """The reference's scatter plot of an embedding, on a new figure."""
-    plt.figure(figsize=(10, 8), dpi=300)
-    plt.axis("off")
-    scatter = plt.scatter(embedding[:, 0], embedding[:, 1], c=all_labels, cmap="tab10", s=3, alpha=0.7,
-                          edgecolor="none", rasterized=True)
-    cbar = plt.colorbar(scatter, ticks=range(10), drawedges=True)
-    cbar.set_ticklabels([str(i) for i in range(10)])
-    cbar.ax.tick_params(labelsize=10, width=0.5)
-    cbar.outline.set_linewidth(0.5)
-
-
+@torch.no_grad()
 def visualize_umap_progression(model, config, dataloader, epoch=0, output_dir="experiments/plots/vit_som/umap", fit_rows=None):
     """evaluation.py:267-323: UMAP(n_neighbors=15, min_dist=0.1, metric='cosine', random_state=42) of
     model.get_latent_representation(x) over the whole set, fitted on the device (umap.py), drawn as the reference's
@@ -288,21 +354,17 @@ def visualize_umap_progression(model, config, dataloader, epoch=0, output_dir="e
     the reference): fit on a fixed subset of that many rows and transform() the others into it (_umap_embed), for sets
     whose host-side graph and spectral initialisation would take too long.  Returns (embedding [N, 2] float32, labels [N])
     as host arrays (the reference returns None)."""
-    X, y = _umap_latents(model, config, dataloader, lambda x, C, S: model.get_latent_representation(x.reshape(-1, C, S, S)))
+    who = "visualize_umap_progression"
+    arch = _Arch(model, config, who)
+    X, y = _whole_set(arch, dataloader, model.get_latent_representation, labels=True, shape=arch.images)
     embedding = _umap_embed(X, fit_rows)[1].cpu().numpy()
     all_labels = y.cpu().numpy()
-    if int(getattr(model, "rank", 0)) == 0:
-        plt = _pyplot("visualize_umap_progression")
-        if plt is None:
-            return embedding, all_labels
-        os.makedirs(output_dir, exist_ok=True)
-        _umap_scatter(plt, embedding, all_labels)
-        plt.savefig(os.path.join(output_dir, f"som_umap_epoch_{epoch}.png"), bbox_inches="tight", pad_inches=0,
-                    transparent=False, dpi=400)
-        plt.close()
+    if _rank(model) == 0:
+        _save_scatter(who, output_dir, f"som_umap_epoch_{epoch}.png", embedding, all_labels, **_UMAP_SAVEFIG)
     return embedding, all_labels
 
 
+@torch.no_grad()
 def visualize_umap_map(model, config, dataloader, epoch=0, output_dir="experiments/plots/vit_som/umap", fit_rows=None):
     """The map in data space (no counterpart in the reference): the embedding of visualize_umap_progression (same
     latents, same UMAP, same fit_rows) with the SOM's K prototypes placed INTO it by UMAP.transform -- they live in the
@@ -311,22 +373,16 @@ def visualize_umap_map(model, config, dataloader, epoch=0, output_dir="experimen
     output_dir/som_umap_map_epoch_{epoch}.png (rank 0 only; skipped with a warning when matplotlib is missing).  Latents:
     model.get_latent_representation(x) for vit_som, x_encoded for desom, as evaluate_knn chooses them; any other model
     raises ValueError.  Returns (embedding [N, 2] float32, labels [N], prototype_embedding [K, 2] float32) as host arrays."""
-    feats = _knn_features(model, config["hyperparameters"]["model_arch"], "visualize_umap_map")
-    X, y = _umap_latents(model, config, dataloader, feats)
+    who = "visualize_umap_map"
+    arch = _Arch(model, config, who).require("latent")
+    X, y = _whole_set(arch, dataloader, arch.latent, labels=True)
     reducer, embedding = _umap_embed(X, fit_rows)
     protos = reducer.transform(model.som_layer.prototypes.detach().float().contiguous()).cpu().numpy()
     embedding, all_labels = embedding.cpu().numpy(), y.cpu().numpy()
     nbr_idx = umatrix(model)[1]
-    if int(getattr(model, "rank", 0)) == 0:
-        plt = _pyplot("visualize_umap_map")
-        if plt is None:
-            return embedding, all_labels, protos
-        os.makedirs(output_dir, exist_ok=True)
-        _umap_scatter(plt, embedding, all_labels)
-        _draw_grid(plt, protos, nbr_idx)
-        plt.savefig(os.path.join(output_dir, f"som_umap_map_epoch_{epoch}.png"), bbox_inches="tight", pad_inches=0,
-                    transparent=False, dpi=400)
-        plt.close()
+    if _rank(model) == 0:
+        _save_scatter(who, output_dir, f"som_umap_map_epoch_{epoch}.png", embedding, all_labels, grid=(protos, nbr_idx),
+                      **_UMAP_SAVEFIG)
     return embedding, all_labels, protos
 
 
@@ -341,16 +397,17 @@ class EmbeddingQualityReport(EmbeddingQuality):
     inference_time: float = 0.0
 
 
+@torch.no_grad()
 def evaluate_embedding_quality(model, config, dataloader, n_neighbors=15, fit_rows=None):
     """Trustworthiness and continuity (embedding_quality.py) of the picture visualize_umap_map draws -> EmbeddingQualityReport.
-    Same latents (_knn_features: get_latent_representation for vit_som, x_encoded for desom), same UMAP(n_neighbors=15,
+    Same latents (_Arch.latent: get_latent_representation for vit_som, x_encoded for desom), same UMAP(n_neighbors=15,
     min_dist=0.1, metric='cosine', random_state=42) and same fit_rows subset; the latents are compared by cosine distance,
     the embedding by euclidean, ties take the lowest rank.  With fit_rows the measures are also given over the fitted rows
     and over the transformed rows alone -- what the shortcut costs; every neighbour list is still taken over all rows.
     With model.world_size > 1 every rank gathers the rows and computes the same numbers."""
-    feats = _knn_features(model, config["hyperparameters"]["model_arch"], "evaluate_embedding_quality")
+    arch = _Arch(model, config, "evaluate_embedding_quality").require("latent")
     start = time.time()
-    X, _ = _umap_latents(model, config, dataloader, feats)
+    X, _ = _whole_set(arch, dataloader, arch.latent, labels=True)
     _, embedding = _umap_embed(X, fit_rows)
     q = embedding_quality(X, embedding.contiguous(), n_neighbors=n_neighbors, metric="cosine")
     chosen = _umap_fit_subset(X.shape[0], fit_rows)
@@ -364,17 +421,6 @@ def evaluate_embedding_quality(model, config, dataloader, n_neighbors=15, fit_ro
                  f"{report.transformed[0]:.4f} / {report.transformed[1]:.4f}")
     print(line + f", Inference Time: {report.inference_time:.3f}")
     return report
-
-
-def _pyplot(who):
-    """matplotlib.pyplot, or None with a warning when matplotlib is not installed (no plot is written then)."""
-    try:
-        import matplotlib.pyplot as plt
-        return plt
-    except ImportError:
-        import warnings
-        warnings.warn(f"{who}: matplotlib is not installed; no plot written")
-        return None
 
 
 def _epoch(model):
@@ -402,22 +448,6 @@ def decoded_prototype_canvas(model, config, chunk=512, gap=1):
     return images.cpu().numpy(), canvas.cpu().numpy()
 
 
-def draw_decoded_prototypes(canvas, output_dir, model_arch, epoch):
-    """One imshow of the mosaic, axis off -> {output_dir}/{model_arch}_epoch_{epoch}_decoded_prototypes.png (host only).
-    Returns the path, or None when matplotlib is missing."""
-    plt = _pyplot("visualize_decoded_prototypes")
-    if plt is None:
-        return None
-    os.makedirs(output_dir, exist_ok=True)
-    fig = plt.figure(figsize=(10, 10 * canvas.shape[0] / canvas.shape[1]))
-    plt.imshow(canvas, interpolation="nearest")
-    plt.axis("off")
-    path = os.path.join(output_dir, f"{model_arch}_epoch_{epoch}_decoded_prototypes.png")
-    plt.savefig(path, bbox_inches="tight")
-    plt.close(fig)
-    return path
-
-
 def visualize_decoded_prototypes(model, config, output_dir="experiments/plots", return_decoded=False, chunk=512, gap=1):
     """evaluation.py:153-207: the SOM prototypes decoded into image space and drawn on the map grid.  The reference runs
     one decoder pass and one Axes per prototype; here the prototypes go through the decoder `chunk` at a time and the
@@ -425,39 +455,17 @@ def visualize_decoded_prototypes(model, config, output_dir="experiments/plots", 
     [K, C, S, S] array when return_decoded, else None."""
     model.eval()
     hp = config["hyperparameters"]
-    model_arch = hp["model_arch"]
-    if model_arch != "vit_som" or hp.get("som", {}).get("use_reduced", False):
+    if not _Arch.is_vit_som(config) or hp.get("som", {}).get("use_reduced", False):
         print("Visualization supported only for vit_som with use_reduced=False.")
         return None
     images, canvas = decoded_prototype_canvas(model, config, chunk=chunk, gap=gap)
-    if int(getattr(model, "rank", 0)) == 0:
-        if draw_decoded_prototypes(canvas, output_dir, model_arch, _epoch(model)) is not None:
+    if _rank(model) == 0:
+        if draw_decoded_prototypes(canvas, output_dir, hp["model_arch"], _epoch(model)) is not None:
             print(f"Saved decoded prototypes visualization to {output_dir}")
     return images if return_decoded else None
 
 
-def draw_label_heatmap(heatmap, output_dir, model_arch, epoch):
-    """The reference's sns.heatmap(annot=True, fmt="d", cmap="viridis") in plain matplotlib ->
-    {output_dir}/{model_arch}_epoch_{epoch}_label_heatmap.png (host only).  Returns the path, or None without matplotlib."""
-    plt = _pyplot("visualize_label_heatmap")
-    if plt is None:
-        return None
-    os.makedirs(output_dir, exist_ok=True)
-    fig = plt.figure(figsize=(10, 8))
-    im = plt.imshow(heatmap, cmap="viridis", aspect="auto")
-    plt.colorbar(im)
-    mid = 0.5 * (float(heatmap.min()) + float(heatmap.max()))
-    size = max(3.0, min(10.0, 200.0 / max(heatmap.shape)))
-    for (r, c), v in np.ndenumerate(heatmap):
-        plt.text(c, r, str(int(v)), ha="center", va="center", fontsize=size, color="white" if v <= mid else "black")
-    plt.xticks(range(heatmap.shape[1]))
-    plt.yticks(range(heatmap.shape[0]))
-    path = os.path.join(output_dir, f"{model_arch}_epoch_{epoch}_label_heatmap.png")
-    plt.savefig(path)
-    plt.close(fig)
-    return path
-
-
+@torch.no_grad()
 def visualize_label_heatmap(model, config, dataloader, output_dir="experiments/plots"):
     """evaluation.py:224-265: the ground-truth label that lands on each map cell, as an annotated heat-map.  Where several
     samples hit a cell the LAST one in loader order wins, as in the reference's loop; the fold runs on the device
@@ -465,32 +473,20 @@ def visualize_label_heatmap(model, config, dataloader, output_dir="experiments/p
     synchronisation in the loop.  With model.world_size > 1 every rank folds its shard, ordinals are shifted so that rank
     r's samples follow rank r - 1's, and one MAX all-reduce combines the tables.  Returns the int64 [rows, cols] array
     of the whole set (the reference returns None); a cell no sample hit holds 0."""
-    model.eval()
-    d = config["data"]
-    C, S = d["num_channels"], d["input_size"]
-    model_arch = config["hyperparameters"]["model_arch"]
-    if model_arch not in ("vit_som", "desom"):
-        raise ValueError(f"visualize_label_heatmap: unknown model_arch {model_arch!r}")
+    who = "visualize_label_heatmap"
+    arch = _Arch(model, config, who).require()
     rows, cols = model.som_layer.map_size
-    dev = model.arena.device
-    cells = torch.zeros(rows * cols, dtype=torch.int64, device=dev)
-    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    cells = torch.zeros(rows * cols, dtype=torch.int64, device=arch.device)
+    bad = torch.zeros(1, dtype=torch.int32, device=arch.device)
     seen = 0
-    for x, y in dataloader:
-        x = x.to(dev, non_blocking=True)
-        y = y.to(dev, non_blocking=True).reshape(-1).long().contiguous()
-        x = x.reshape(-1, C, S, S) if model_arch == "vit_som" else x.reshape(x.shape[0], -1)
+    batches = arch.batches(dataloader, arch.own)
+    for x, y in batches:
         bmu, _ = model.predict(x)
         ops.last_label(bmu.contiguous().view(-1), y, seen, cells, bad)
         seen += y.numel()
-    world = _world(model)
-    if world > 1:
+    before, _ = _rank_shift(model, seen, who)
+    if _world(model) > 1:
         import torch.distributed as dist
-        counts = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(world)]
-        dist.all_gather(counts, torch.tensor([seen], dtype=torch.int64, device=dev))
-        before = sum(int(c) for c in counts[:int(getattr(model, "rank", 0))])
-        if sum(int(c) for c in counts) >= 2 ** 31:
-            raise ValueError("visualize_label_heatmap: more than 2^31 - 1 samples")
         cells = torch.where(cells != 0, cells + (before << 32), cells)
         dist.all_reduce(cells, op=dist.ReduceOp.MAX)
         bad = bad.long()
@@ -499,8 +495,8 @@ def visualize_label_heatmap(model, config, dataloader, output_dir="experiments/p
     if nbad:
         raise ValueError(f"{nbad} BMU indices fell outside the {rows} x {cols} map or labels outside [0, 2^31)")
     heatmap = (cells & 0xFFFFFFFF).view(rows, cols).cpu().numpy()
-    if int(getattr(model, "rank", 0)) == 0:
-        if draw_label_heatmap(heatmap, output_dir, model_arch, _epoch(model)) is not None:
+    if _rank(model) == 0:
+        if draw_label_heatmap(heatmap, output_dir, arch.name, _epoch(model)) is not None:
             print(f"Saved label heatmap visualization to {output_dir}")
     return heatmap
 
@@ -530,6 +526,7 @@ def _key_to_float(key):
 _SIGN64 = -(1 << 63)
 
 
+@torch.no_grad()
 def evaluate_map_quality(model, config, dataloader):
     """Quantization error, topographic error, hit map and the nearest sample of every unit over the loader -> MapQuality.
     For vit_som and desom.  Every batch goes through predict(); the distances [B, K] and BMUs it leaves in the SOM layer's
@@ -542,40 +539,29 @@ def evaluate_map_quality(model, config, dataloader):
     that each carry the contraction's rounding error.  With model.world_size > 1 every rank folds its shard, ordinals are
     shifted so that rank r's samples follow rank r - 1's, and one SUM and one MIN all-reduce combine the tables: every
     rank returns the whole set's report."""
-    model.eval()
-    d = config["data"]
-    C, S = d["num_channels"], d["input_size"]
-    model_arch = config["hyperparameters"]["model_arch"]
-    if model_arch not in ("vit_som", "desom"):
-        raise ValueError(f"evaluate_map_quality: unknown model_arch {model_arch!r}")
+    who = "evaluate_map_quality"
+    arch = _Arch(model, config, who).require()
     som = model.som_layer
     rows, cols = som.map_size
     K = rows * cols
-    dev = model.arena.device
+    dev = arch.device
     adj_r2 = som.adjacency_radius2()
     sums = torch.zeros(2 * K + 1, dtype=torch.int64, device=dev)          # hits | qe_fix | te: one all-reduce
     hits, qe_fix, te = sums[:K], sums[K:2 * K], sums[2 * K:]
     nearest = torch.full((K,), -1, dtype=torch.int64, device=dev)
     bad = torch.zeros(1, dtype=torch.int32, device=dev)
     seen, start = 0, time.time()
-    for x, _ in dataloader:
-        x = x.to(dev, non_blocking=True)
-        x = x.reshape(-1, C, S, S) if model_arch == "vit_som" else x.reshape(x.shape[0], -1)
+    batches = arch.batches(dataloader, arch.own, labels=False)
+    for x, _ in batches:
         bmu, _ = model.predict(x)
         s = som._buffers_for(bmu.shape[0], bmu.device)                  # the set predict() has just written
         if s.bmu.data_ptr() != bmu.data_ptr():
             raise RuntimeError("evaluate_map_quality: predict() did not leave its distances in the SOM layer's buffers")
         ops.map_stats(s.dist, s.bmu, som.grid_positions, adj_r2, seen, hits, qe_fix, te, nearest, bad)
         seen += bmu.shape[0]
-    world = _world(model)
-    if world > 1:
+    before, seen = _rank_shift(model, seen, who)
+    if _world(model) > 1:
         import torch.distributed as dist
-        counts = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(world)]
-        dist.all_gather(counts, torch.tensor([seen], dtype=torch.int64, device=dev))
-        before = sum(int(c) for c in counts[:int(getattr(model, "rank", 0))])
-        seen = sum(int(c) for c in counts)
-        if seen >= 2 ** 31:
-            raise ValueError("evaluate_map_quality: more than 2^31 - 1 samples")
         both = torch.cat([sums, bad.long()])
         dist.all_reduce(both)
         sums, bad = both[:-1], both[-1:]
@@ -655,82 +641,43 @@ def map_neighbourhood(model):
                             within_degree=float((valid & (ranks <= deg)).sum() / n) if n else float("nan"))
 
 
-def _draw_map(who, values, label, annotate, path):
-    plt = _pyplot(who)
-    if plt is None:
-        return None
-    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-    fig = plt.figure(figsize=(10, 8))
-    im = plt.imshow(values, cmap="viridis", interpolation="nearest")
-    plt.colorbar(im, label=label)
-    if annotate and max(values.shape) <= 24:
-        mid = 0.5 * (float(values.min()) + float(values.max()))
-        for (r, c), v in np.ndenumerate(values):
-            plt.text(c, r, str(int(v)), ha="center", va="center", fontsize=7, color="white" if v <= mid else "black")
-    plt.axis("off")
-    plt.savefig(path, bbox_inches="tight")
-    plt.close(fig)
-    return path
+def _save_cell_map(model, config, output_dir, who, suffix, kind, values, label, annotate=False):
+    """Rank 0: one value per map cell as an image -> {output_dir}/{model_arch}_epoch_{epoch}_{suffix}.png."""
+    if _rank(model) == 0:
+        model_arch = config["hyperparameters"]["model_arch"]
+        path = os.path.join(output_dir, f"{model_arch}_epoch_{_epoch(model)}_{suffix}.png")
+        if _draw_map(who, values, label, annotate, path) is not None:
+            print(f"Saved {kind} visualization to {output_dir}")
 
 
 def visualize_umatrix(model, config, output_dir="experiments/plots"):
     """The U-matrix as one image -> {output_dir}/{model_arch}_epoch_{epoch}_umatrix.png (rank 0; skipped with a warning when
     matplotlib is missing).  Returns u [rows, cols] float32."""
-    model_arch = config["hyperparameters"]["model_arch"]
     u, _, _ = umatrix(model)
-    if int(getattr(model, "rank", 0)) == 0:
-        path = os.path.join(output_dir, f"{model_arch}_epoch_{_epoch(model)}_umatrix.png")
-        if _draw_map("visualize_umatrix", u, "mean distance to the grid neighbours", False, path) is not None:
-            print(f"Saved U-matrix visualization to {output_dir}")
+    _save_cell_map(model, config, output_dir, "visualize_umatrix", "umatrix", "U-matrix", u, "mean distance to the grid neighbours")
     return u
 
 
+@torch.no_grad()
 def visualize_hit_map(model, config, dataloader, output_dir="experiments/plots"):
     """Samples per unit (evaluate_map_quality's hits) as one image -> {output_dir}/{model_arch}_epoch_{epoch}_hit_map.png
     (rank 0; skipped with a warning when matplotlib is missing).  Returns hits [rows, cols] int64."""
-    model_arch = config["hyperparameters"]["model_arch"]
     hits = evaluate_map_quality(model, config, dataloader).hits
-    if int(getattr(model, "rank", 0)) == 0:
-        path = os.path.join(output_dir, f"{model_arch}_epoch_{_epoch(model)}_hit_map.png")
-        if _draw_map("visualize_hit_map", hits, "samples", True, path) is not None:
-            print(f"Saved hit map visualization to {output_dir}")
+    _save_cell_map(model, config, output_dir, "visualize_hit_map", "hit_map", "hit map", hits, "samples", annotate=True)
     return hits
 
 
 # ------------------------------------------------------------------------------------ silhouette
+@torch.no_grad()
 def _som_latents(model, config, dataloader, who):
     """(X [N, D] float32, bmu [N] int64) over the loader, on the device: the rows the SOM layer was given and the unit
-    each of them won.  vit_som: predict() leaves the BMUs in the SOM layer's buffers and the encoder output in the ViT's;
-    both are copied before the next batch overwrites them.  desom: forward() returns both.  With model.world_size > 1
-    every rank gathers all rows, rank 0's first."""
-    model.eval()
-    d = config["data"]
-    C, S = d["num_channels"], d["input_size"]
-    arch = config["hyperparameters"]["model_arch"]
-    dev = model.arena.device
-    lat, units = [], []
-    with torch.no_grad():
-        for x, _ in dataloader:
-            x = x.to(dev, non_blocking=True)
-            if arch == "vit_som" and hasattr(model, "_som_input"):
-                x = x.reshape(-1, C, S, S)
-                bmu, _ = model.predict(x)
-                z = model._som_input(model.vit._buffers_for(x.shape[0], x.device))
-            elif arch == "desom" and hasattr(model, "autoencoder"):
-                _, z, _, bmu = model(x.reshape(x.shape[0], -1))
-            else:
-                raise ValueError(f"{who}: needs a vit_som or a desom model; got {type(model).__name__} with model_arch {arch!r}")
-            lat.append(z.reshape(z.shape[0], -1).float().clone())
-            units.append(bmu.reshape(-1).long().clone())
-    if not lat:
-        raise ValueError(f"{who}: the loader is empty")
-    X, u = torch.cat(lat), torch.cat(units)
-    world = _world(model)
-    if world > 1:
-        X, u = _gather_rows(X, world), _gather_rows(u, world)
-    return X.contiguous(), u.contiguous()
+    each of them won (_Arch.som_input), copied before the next batch overwrites them.  With model.world_size > 1 every
+    rank gathers all rows, rank 0's first."""
+    arch = _Arch(model, config, who).require("som_input")
+    return _whole_set(arch, dataloader, arch.som_input, labels=False)
 
 
+@torch.no_grad()
 def evaluate_silhouette(model, config, dataloader, clusters="bmu", metric=None, n_clusters=None, sample_size=None):
     """Silhouette coefficient (silhouette.py: `vsom_silhouette`) of the latents the SOM layer sees -> SilhouetteReport.  No
     labels are read.
@@ -765,18 +712,15 @@ def evaluate_silhouette(model, config, dataloader, clusters="bmu", metric=None, 
     return report
 
 
+@torch.no_grad()
 def visualize_silhouette_map(model, config, dataloader, output_dir="experiments/plots", metric=None):
     """The mean silhouette of every unit's samples (evaluate_silhouette, clusters="bmu") on the grid ->
     {output_dir}/{model_arch}_epoch_{epoch}_silhouette_map.png (rank 0; skipped with a warning when matplotlib is
     missing).  Dead units are left blank.  Returns the values [rows, cols] float64, NaN for a dead unit."""
-    model_arch = config["hyperparameters"]["model_arch"]
     rows, cols = model.som_layer.map_size
     values = evaluate_silhouette(model, config, dataloader, clusters="bmu", metric=metric).per_cluster.reshape(rows, cols)
-    if int(getattr(model, "rank", 0)) == 0:
-        path = os.path.join(output_dir, f"{model_arch}_epoch_{_epoch(model)}_silhouette_map.png")
-        if _draw_map("visualize_silhouette_map", np.ma.masked_invalid(values), "mean silhouette of the unit's samples", False,
-                     path) is not None:
-            print(f"Saved silhouette map visualization to {output_dir}")
+    _save_cell_map(model, config, output_dir, "visualize_silhouette_map", "silhouette_map", "silhouette map",
+                   np.ma.masked_invalid(values), "mean silhouette of the unit's samples")
     return values
 
 
@@ -815,6 +759,7 @@ class LatentSpectrum:
     inference_time: float = 0.0
 
 
+@torch.no_grad()
 def evaluate_latent_spectrum(model, config, dataloader, n_components=64):
     """The spectrum of the latents the SOM layer sees (pca.py, on the device) -> LatentSpectrum: how many directions the
     encoder uses, whether it collapses, how much of the variance a 2-D picture shows.  n_components is cut to
@@ -834,6 +779,7 @@ def evaluate_latent_spectrum(model, config, dataloader, n_components=64):
     return report
 
 
+@torch.no_grad()
 def visualize_pca_map(model, config, dataloader, epoch=0, output_dir="experiments/plots/vit_som/pca"):
     """The linear counterpart of visualize_umap_map: the latents projected on their first two principal components
     (pca.py), coloured by label, with the SOM's prototypes `transform`ed into the same plane and the unit grid drawn over
@@ -842,50 +788,48 @@ def visualize_pca_map(model, config, dataloader, epoch=0, output_dir="experiment
     explained-variance ratios.  Returns (projection [N, 2] float32, labels [N], prototype_projection [K, 2] float32,
     explained_variance_ratio [2]) as host arrays."""
     from .pca import PCA
-    feats = _knn_features(model, config["hyperparameters"]["model_arch"], "visualize_pca_map")
-    X, y = _umap_latents(model, config, dataloader, feats)
+    who = "visualize_pca_map"
+    arch = _Arch(model, config, who).require("latent")
+    X, y = _whole_set(arch, dataloader, arch.latent, labels=True)
     p = PCA(n_components=2).fit(X)
     proj = p.transform(X).cpu().numpy()
     protos = p.transform(model.som_layer.prototypes.detach().float().contiguous()).cpu().numpy()
     ratio, all_labels = p.explained_variance_ratio_.cpu().numpy(), y.cpu().numpy()
     nbr_idx = umatrix(model)[1]
-    if int(getattr(model, "rank", 0)) == 0:
-        plt = _pyplot("visualize_pca_map")
-        if plt is None:
-            return proj, all_labels, protos, ratio
-        os.makedirs(output_dir, exist_ok=True)
-        _umap_scatter(plt, proj, all_labels)
-        plt.axis("on")
-        plt.xlabel(f"PC1 ({100 * ratio[0]:.1f}% of the variance)")
-        plt.ylabel(f"PC2 ({100 * ratio[1]:.1f}% of the variance)")
-        _draw_grid(plt, protos, nbr_idx)
-        plt.savefig(os.path.join(output_dir, f"som_pca_map_epoch_{epoch}.png"), bbox_inches="tight", dpi=400)
-        plt.close()
+    if _rank(model) == 0:
+        axes = (f"PC1 ({100 * ratio[0]:.1f}% of the variance)", f"PC2 ({100 * ratio[1]:.1f}% of the variance)")
+        _save_scatter(who, output_dir, f"som_pca_map_epoch_{epoch}.png", proj, all_labels, grid=(protos, nbr_idx),
+                      axis_labels=axes, bbox_inches="tight", dpi=400)
     return proj, all_labels, protos, ratio
 
 
+def _latents_keeping_mode(model, config, dataloader, who, max_rows):
+    """_som_latents' rows, at most max_rows of them (the first ones), with the model back in the training or eval mode it
+    was in."""
+    training = model.training
+    try:
+        X, _ = _som_latents(model, config, dataloader, who)
+    finally:
+        model.train(training)
+    return X if max_rows is None else X[:int(max_rows)]
+
+
+@torch.no_grad()
 def init_som_from_data(model, config, dataloader, method="pca", max_rows=None):
     """Start the SOM's prototypes from the data (SOMLayer.init_prototypes): the latents of the loader through the CURRENT
     encoder, at most max_rows of them (the first ones), method "pca" or "sample".  Returns the fitted PCA or None."""
-    training = model.training
-    X, _ = _som_latents(model, config, dataloader, "init_som_from_data")
-    model.train(training)
-    if max_rows is not None:
-        X = X[:int(max_rows)]
+    X = _latents_keeping_mode(model, config, dataloader, "init_som_from_data", max_rows)
     return model.som_layer.init_prototypes(X, method=method)
 
 
+@torch.no_grad()
 def fit_som_batch(model, config, dataloader, epochs=10, init=None, sigma=None, max_rows=None):
     """Fit the SOM to the data with Kohonen's batch map (SOMLayer.fit_batch) -> BatchSOMReport: the latents of the loader
     through the CURRENT encoder (a frozen or pretrained one is what this is for), at most max_rows of them (the first ones);
     init "pca" or "sample" first starts the prototypes from those latents (SOMLayer.init_prototypes), None keeps them as
     they are.  sigma as in fit_batch (None: Tmax down to Tmin).  For vit_som and desom; the model's training mode is
     restored.  With model.world_size > 1 every rank holds all rows and computes the same map."""
-    training = model.training
-    X, _ = _som_latents(model, config, dataloader, "fit_som_batch")
-    model.train(training)
-    if max_rows is not None:
-        X = X[:int(max_rows)]
+    X = _latents_keeping_mode(model, config, dataloader, "fit_som_batch", max_rows)
     som = model.som_layer
     if init is not None:
         som.init_prototypes(X, method=init)
@@ -905,16 +849,7 @@ class KNNReport:
     inference_time: float
 
 
-def _knn_features(model, arch, who="evaluate_knn"):
-    """x -> the [B, D] float32 features the probe compares (views of the model's buffers: copy before the next batch)."""
-    if arch == "vit_som" and hasattr(model, "get_latent_representation"):
-        return lambda x, C, S: model.get_latent_representation(x.reshape(-1, C, S, S))
-    if arch == "desom" and hasattr(model, "autoencoder"):
-        return lambda x, C, S: model(x.reshape(x.shape[0], -1))[1]
-    raise ValueError(f"{who}: needs a vit_som model (get_latent_representation) or a desom model (x_encoded); got "
-                     f"{type(model).__name__} with model_arch {arch!r}")
-
-
+@torch.no_grad()
 def evaluate_knn(model, config, train_loader, test_loader, k=20, weights="softmax", metric="cosine", temperature=0.07,
                  bank_rows=4096, num_labels=None):
     """k-nearest-neighbour probe of the latents -> KNNReport: every sample of test_loader is classified by the weighted vote
@@ -930,54 +865,42 @@ def evaluate_knn(model, config, train_loader, test_loader, k=20, weights="softma
     With model.world_size > 1 each rank keeps its own shard of the test queries and every bank buffer is all-gathered
     (rank 0's rows first) before it is folded, so every rank must see the same number of training rows; the confusion
     counts are summed over the ranks and every rank returns the whole set's report."""
-    model.eval()
-    d = config["data"]
-    C, S = d["num_channels"], d["input_size"]
-    feats = _knn_features(model, config["hyperparameters"]["model_arch"])
-    dev = model.arena.device
-    L = int(num_labels) if num_labels else (int(d.get("num_classes", 0)) if int(d.get("num_classes", 0)) > 0 else 256)
+    arch = _Arch(model, config, "evaluate_knn").require("latent")
+    dev, L = arch.device, _label_count(config, num_labels, False)
     bank_rows = int(bank_rows)
     if bank_rows < 1:
         raise ValueError(f"evaluate_knn: bank_rows must be positive, got {bank_rows}")
     clf = KNNClassifier(n_neighbors=k, weights=weights, metric=metric, temperature=temperature, n_classes=L)
     clf._validate()
     world, start = _world(model), time.time()
-    queries, labels = [], []
-    with torch.no_grad():
-        for x, y in test_loader:
-            f = feats(x.to(dev, non_blocking=True), C, S)
-            queries.append(f.reshape(f.shape[0], -1).float().clone())
-            labels.append(y.to(dev, non_blocking=True).reshape(-1).long())
-        if not queries:
-            raise ValueError("evaluate_knn: the test loader is empty")
-        Q, yq = torch.cat(queries).contiguous(), torch.cat(labels).contiguous()
-        clf.partial_fit_query(Q)
-        buf = torch.empty(bank_rows, Q.shape[1], dtype=torch.float32, device=dev)
-        ybuf = torch.empty(bank_rows, dtype=torch.int64, device=dev)
-        fill = 0
+    Q, yq = _rows(arch, test_loader, arch.latent, labels=True, what="test loader")
+    clf.partial_fit_query(Q)
+    buf = torch.empty(bank_rows, Q.shape[1], dtype=torch.float32, device=dev)
+    ybuf = torch.empty(bank_rows, dtype=torch.int64, device=dev)
+    fill = 0
 
-        def fold(n):
-            bx, by = buf[:n], ybuf[:n]
-            if world > 1:
-                bx, by = _gather_rows(bx, world).contiguous(), _gather_rows(by, world).contiguous()
-            if bx.shape[0]:
-                clf.update(bx, by)
+    def fold(n):
+        bx, by = buf[:n], ybuf[:n]
+        if world > 1:
+            bx, by = _gather_rows(bx, world).contiguous(), _gather_rows(by, world).contiguous()
+        if bx.shape[0]:
+            clf.update(bx, by)
 
-        for x, y in train_loader:
-            f = feats(x.to(dev, non_blocking=True), C, S)
-            f = f.reshape(f.shape[0], -1)
-            y = y.to(dev, non_blocking=True).reshape(-1)
-            off = 0
-            while off < f.shape[0]:
-                n = min(f.shape[0] - off, bank_rows - fill)
-                buf[fill:fill + n].copy_(f[off:off + n])
-                ybuf[fill:fill + n].copy_(y[off:off + n])
-                fill, off = fill + n, off + n
-                if fill == bank_rows:
-                    fold(fill)
-                    fill = 0
-        if fill or world > 1:
-            fold(fill)
+    batches = arch.batches(train_loader, arch.own)
+    for x, y in batches:
+        f = arch.latent(x)
+        f = f.reshape(f.shape[0], -1)
+        off = 0
+        while off < f.shape[0]:
+            n = min(f.shape[0] - off, bank_rows - fill)
+            buf[fill:fill + n].copy_(f[off:off + n])
+            ybuf[fill:fill + n].copy_(y[off:off + n])
+            fill, off = fill + n, off + n
+            if fill == bank_rows:
+                fold(fill)
+                fill = 0
+    if fill or world > 1:
+        fold(fill)
     n_train = clf._seen
     if n_train < clf.n_neighbors:
         raise ValueError(f"evaluate_knn: k={clf.n_neighbors} exceeds the {n_train} training samples")
@@ -1003,22 +926,20 @@ def evaluate_knn(model, config, train_loader, test_loader, k=20, weights="softma
     return report
 
 
+@torch.no_grad()
 def evaluate_classification(model, config, dataloader):
     """evaluation.py:93-128 -> (accuracy, precision, recall, f1, inference_time) (macro averages); summed over the
     ranks like evaluate_clustering."""
-    model.eval()
-    d = config["data"]
-    C, S, ncls = d["num_channels"], d["input_size"], d["num_classes"]
-    dev = model.arena.device
-    table, pred, start = _Table(ncls, ncls, dev), None, time.time()
-    for x, y in dataloader:
-        x = x.to(dev, non_blocking=True).reshape(-1, C, S, S)
-        y = y.to(dev, non_blocking=True)
+    arch = _Arch(model, config, "evaluate_classification")
+    ncls = config["data"]["num_classes"]
+    table, pred, start = _Table(ncls, ncls, arch.device), None, time.time()
+    batches = arch.batches(dataloader, arch.images)
+    for x, y in batches:
         _, logits = model.predict(x)
         if pred is None or pred.numel() != logits.shape[0]:
-            pred = torch.empty(logits.shape[0], dtype=torch.int64, device=dev)
+            pred = torch.empty(logits.shape[0], dtype=torch.int64, device=arch.device)
         ops.argmax_rows(logits, pred)
-        table.add(y.view(-1), pred)                       # cm[true, pred]
+        table.add(y, pred)                                # cm[true, pred]
     acc, precision, recall, f1 = classification_from_table(table.numpy(_world(model)))
     inference_time = time.time() - start
     print(f"Accuracy: {acc:.3f}, Precision: {precision:.3f}, Recall: {recall:.3f}, F1-score: {f1:.3f}, Inference Time: {inference_time:.3f}")
