@@ -18,7 +18,7 @@
 // reduction over c runs in ascending k-tiles inside one workgroup, in segments of 128 units whose sums are added in
 // order: one fixed order, bitwise reproducible.  m_k, the denominators and the hit units' positions come from a small
 // fp64 pre-pass.
-#include "common.h"
+#include "gemm_f32.h"
 
 #include <math.h>
 
@@ -31,6 +31,7 @@ constexpr int AV_LONG_SEGMENT = 256;         // 16-byte path: a unit with more r
 constexpr int BS_MAX_UNITS = 65535;          // the unit is a grid coordinate
 constexpr int UP_BM = 128, UP_BN = 128;      // update tile: 4 waves x (32 rows x 128 columns)
 constexpr int UP_ALD = 36, UP_BLD = 36;      // both LDS tiles are [row or column][k], 32 k-values in a pitch of 36 floats
+static_assert(f32_tile_floats<true, 1>() == UP_ALD && UP_BLD == UP_ALD, "mfma_tile reads the k-contiguous tile image of gemm_f32.h");
 constexpr int UP_SEG_KTILES = 4;            // k-tiles of 32 units per first-level sum
 
 // --------------------------------------------------------------------------------------------------- accumulate
@@ -310,17 +311,7 @@ __global__ __launch_bounds__(256, 2) void bs_update_kernel(const double* __restr
     __syncthreads();
     for (int kt = 0; kt < ktiles; ++kt) {
         const bool more = kt + 1 < ktiles;
-#pragma unroll
-        for (int kb = 0; kb < 32; kb += 8) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(As + (wm0 + r) * UP_ALD + kb + 4 * h);
-            f32x4 b[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = *reinterpret_cast<const f32x4*>(Bs + (j * 32 + r) * UP_BLD + kb + 4 * h);
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b[j][s], acc[j], 0, 0, 0);
-        }
+        mfma_tile<true, true, UP_BM, UP_BN>(As, Bs, wm0, 0, r, h, reinterpret_cast<f32x16 (&)[1][4]>(acc));
         if ((kt + 1) % UP_SEG_KTILES == 0 || !more) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {

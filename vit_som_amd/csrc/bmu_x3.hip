@@ -210,12 +210,6 @@ __global__ __launch_bounds__(512) void bmu_norms_wide_kernel(const float* __rest
     }
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // One workgroup per sample row: distances, approximate first minimum, exact re-rank of the candidates.
 constexpr int BMU_KPT = 8;           // prototypes per thread held in registers (K <= 2048)
 // V4: K % 4 == 0 and 16-byte aligned slabs / dist -- a thread owns two quads of consecutive columns (16-byte accesses,

@@ -19,8 +19,12 @@
 // 4 consecutive k per lane), k-strided tiles are [32][cols+4] (ds_read_b32 across 32 consecutive
 // columns).  Lane l = (r = l & 31, h = l >> 5) feeds MFMA step s of an 8-deep group with
 // k = kb + 4h + s for BOTH operands, so any consistent assignment is exact.
+// The tile contraction -- staging state, k-loop, fragment reads and MFMA order -- is written once below (F32Stage,
+// F32_KLOOP, mfma_tile) for this file's kernel and for the other users of the engine in pca.hip, knn.hip and batch_som.hip.
 #pragma once
 #include "common.h"
+
+#include <type_traits>
 
 namespace vsom {
 
@@ -187,6 +191,140 @@ __device__ __forceinline__ void store_ks(const StageRegs<COLS>& s, float* lds, i
         *reinterpret_cast<f32x4*>(lds + (p * KPP + t / TPR) * (COLS + 4) + ((t % TPR) << 2)) = s.v[p];
 }
 
+// ---- the tile contraction, written once ----------------------------------------------------
+// Its users: gemm_f32_kernel below, pca_gemm_kernel (pca.hip: the centring hooked in front of lstore), knn_tile_dots
+// (knn.hip: one call per column tile, re-pointed per k-segment by the silhouette) and, for mfma_tile alone,
+// bs_update_kernel (batch_som.hip).
+//
+// One operand: `rows` is the extent of the index that is NOT reduced (rows of a k-contiguous operand, columns of a
+// k-strided one); bytes = the extent for the bounds-checked buffer loads (FAST), vec = 16-byte loads legal (generic).
+struct F32Operand {
+    const float* base;
+    long ld;
+    int rows;
+    unsigned bytes;
+    int vec;
+};
+inline long operand_bytes(long rows, long ld, long cols) { return ((rows - 1) * ld + cols) * 4; }
+
+// The staging state of one workgroup for a layout pair: the staging registers and, on the FAST path, the buffer
+// resources and the per-thread offsets (the generic path indexes from the operands' pointers).  Set-up is point() for
+// the bases plus rows_a() / rows_b() for the offsets, separately: kNN computes A's offsets once per workgroup and B's
+// once per column tile, and re-points both at a later k-segment of the same rows without touching the offsets.
+template <bool A_KC, bool B_KC, int BM, int BN, bool FAST>
+struct F32Stage {
+    StageRegs<BM> sa;
+    StageRegs<BN> sb;
+    __amdgpu_buffer_rsrc_t rsA, rsB;
+    std::conditional_t<A_KC, OffKC<BM>, OffKS<BM>> oa;
+    std::conditional_t<B_KC, OffKC<BN>, OffKS<BN>> ob;
+
+    __device__ __forceinline__ void point(const F32Operand& A, const F32Operand& B) {
+        if constexpr (FAST) {
+            rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A.base), 0, (int)A.bytes, 0x00020000);
+            rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(B.base), 0, (int)B.bytes, 0x00020000);
+        }
+    }
+    __device__ __forceinline__ void rows_a(const F32Operand& A, int a0, int t) {
+        if constexpr (FAST) {
+            if constexpr (A_KC) init_kc<BM>(oa, A.ld, a0, A.rows, t); else init_ks<BM>(oa, A.ld, a0, A.rows, t);
+        }
+    }
+    __device__ __forceinline__ void rows_b(const F32Operand& B, int b0, int t) {
+        if constexpr (FAST) {
+            if constexpr (B_KC) init_kc<BN>(ob, B.ld, b0, B.rows, t); else init_ks<BN>(ob, B.ld, b0, B.rows, t);
+        }
+    }
+    // k-tile [k0, k0 + 32) of the rows a0.. of A and b0.. of B into the staging registers; (seg, stride, off) is GemmP's
+    // reduction-row map of a k-strided A.  A caller without one passes nothing: the zeros are then literals, which the
+    // k-strided loads need (fed the same zeros at run time, pca_gemm_kernel<TN> came out 16 % longer).
+    __device__ __forceinline__ void gload(const F32Operand& A, int a0, const F32Operand& B, int b0, int k0, int K, int t,
+                                          int seg = 0, int stride = 0, int off = 0) {
+        if constexpr (FAST) {
+            if constexpr (A_KC) load_kc_fast<BM>(sa, rsA, oa, k0, K, t);
+            else load_ks_fast<BM>(sa, rsA, oa, k0, K, t, seg, stride, off);
+            if constexpr (B_KC) load_kc_fast<BN>(sb, rsB, ob, k0, K, t);
+            else load_ks_fast<BN>(sb, rsB, ob, k0, K, t, 0, 0, 0);
+        } else {
+            if constexpr (A_KC) load_kc<BM>(sa, A.base, A.ld, a0, A.rows, k0, K, A.vec, t);
+            else load_ks<BM>(sa, A.base, A.ld, a0, A.rows, k0, K, A.vec, t, seg, stride, off);
+            if constexpr (B_KC) load_kc<BN>(sb, B.base, B.ld, b0, B.rows, k0, K, B.vec, t);
+            else load_ks<BN>(sb, B.base, B.ld, b0, B.rows, k0, K, B.vec, t, 0, 0, 0);
+        }
+    }
+    __device__ __forceinline__ void lstore(float* As, float* Bs, int t) const {
+        if constexpr (A_KC) store_kc<BM>(sa, As, t); else store_ks<BM>(sa, As, t);
+        if constexpr (B_KC) store_kc<BN>(sb, Bs, t); else store_ks<BN>(sb, Bs, t);
+    }
+};
+
+// LDS floats of an operand tile with ROWS rows (columns): [ROWS][36] k-contiguous, [32][ROWS + 4] k-strided
+template <bool KC, int ROWS>
+constexpr int f32_tile_floats() { return KC ? ROWS * 36 : 32 * (ROWS + 4); }
+
+// acc += the k-tile held in As / Bs, for the wave whose WM x WN accumulators begin at row wm0 / column wn0 of the block
+// tile.  THE summation order of the engine, spelled only here: 8-group by 8-group, MFMA step s = 0..3, lane half h
+// feeding k = kb + 4h + s of both operands -- the instruction is bitwise fma(a_k1 b_k1, fma(a_k0 b_k0, c)), so an output
+// element takes k = kb + s, then kb + 4 + s.  knn_sqnorm_row and knn_pair_dot (knn.hip) restate it on the VALU.
+template <bool A_KC, bool B_KC, int BM, int BN, int WM, int WN>
+__device__ __forceinline__ void mfma_tile(const float* As, const float* Bs, int wm0, int wn0, int r, int h,
+                                          f32x16 (&acc)[WM][WN]) {
+#pragma unroll
+    for (int kb = 0; kb < 32; kb += 8) {
+        f32x4 a[WM], b[WN];
+#pragma unroll
+        for (int i = 0; i < WM; ++i) {
+            if constexpr (A_KC) {
+                a[i] = *reinterpret_cast<const f32x4*>(As + (wm0 + i * 32 + r) * 36 + kb + 4 * h);
+            } else {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) a[i][s] = As[(kb + 4 * h + s) * (BM + 4) + wm0 + i * 32 + r];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < WN; ++j) {
+            if constexpr (B_KC) {
+                b[j] = *reinterpret_cast<const f32x4*>(Bs + (wn0 + j * 32 + r) * 36 + kb + 4 * h);
+            } else {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) b[j][s] = Bs[(kb + 4 * h + s) * (BN + 4) + wn0 + j * 32 + r];
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int i = 0; i < WM; ++i)
+#pragma unroll
+                for (int j = 0; j < WN; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][s], b[j][s], acc[i][j], 0, 0, 0);
+    }
+}
+
+// The k-loop over k-tiles [kt_begin, kt_end): gload(kt) loads k-tile kt into the staging registers, lstore() writes
+// them to the one LDS stage, mfma_tile() multiplies that stage.  Branch-free steady-state body with the last k-tile
+// peeled: a conditional prefetch inside the loop makes hipcc carry the accumulators through VGPRs (all of them copied
+// AGPR -> VGPR -> AGPR every iteration).  The next tile's global loads stay in flight under the MFMAs: the one
+// sched_barrier keeps them ABOVE the MFMAs (the scheduler otherwise sinks them to their use).  A macro for the reason
+// X6_KLOOP (gemm_x6.h) is one: as a function template taking the three lambdas, hipcc optimises the loop before inlining it.
+// NONEMPTY: a literal true where the range always holds a k-tile (kNN: D >= 1), so that the two guards are not compiled.
+#define F32_KLOOP(NONEMPTY, kt_begin, kt_end, gload, lstore, mfma_tile)                                                     \
+    do {                                                                                                                    \
+        if ((NONEMPTY) || (kt_begin) < (kt_end)) {                                                                          \
+            gload(kt_begin);                                                                                                \
+            lstore();                                                                                                       \
+        }                                                                                                                   \
+        __syncthreads();                                                                                                    \
+        for (int kt_ = (kt_begin); kt_ + 1 < (kt_end); ++kt_) {                                                             \
+            gload(kt_ + 1);                                                                                                 \
+            __builtin_amdgcn_sched_barrier(0);                                                                              \
+            mfma_tile();                                                                                                    \
+            __syncthreads();                                                                                                \
+            lstore();                                                                                                       \
+            __syncthreads();                                                                                                \
+        }                                                                                                                   \
+        if ((NONEMPTY) || (kt_begin) < (kt_end)) mfma_tile();                                                               \
+    } while (0)
+
 // ---- epilogue (shared by the exact-f32 and the split-bf16 kernels) ----------------------------
 // accumulator register v of a 32x32 tile holds row (v&3) + 8*(v>>2) + 4*h, column r: walk the
 // rows with pointer increments (no per-element index arithmetic); the rare output-row map
@@ -344,9 +482,8 @@ template <bool A_KC, bool B_KC, int WM, int WN, int WAVES_M, int WAVES_N, int EP
 __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmP g) {
     constexpr int BM = WAVES_M * WM * 32;
     constexpr int BN = WAVES_N * WN * 32;
-    constexpr int A_LDS = A_KC ? BM * 36 : 32 * (BM + 4);
-    constexpr int B_LDS = B_KC ? BN * 36 : 32 * (BN + 4);
-    __shared__ __attribute__((aligned(16))) float lds[A_LDS + B_LDS];
+    constexpr int A_LDS = f32_tile_floats<A_KC, BM>();
+    __shared__ __attribute__((aligned(16))) float lds[A_LDS + f32_tile_floats<B_KC, BN>()];
     float* As = lds;
     float* Bs = lds + A_LDS;
 
@@ -387,90 +524,23 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmP g) {
     float colsum = 0.f;                       // EPI_SLAB bias partial (thread t < BM owns A column t)
     const bool want_colsum = (EPI == EPI_SLAB) && !A_KC && g.slab_bias != nullptr && bn0 == 0;
 
-    StageRegs<BM> sa;
-    StageRegs<BN> sb;
-    __amdgpu_buffer_rsrc_t rsA, rsB;
-    OffKC<BM> oa_kc; OffKS<BM> oa_ks; OffKC<BN> ob_kc; OffKS<BN> ob_ks;
-    if constexpr (FAST) {
-        rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.A), 0, (int)g.a_bytes, 0x00020000);
-        rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.B), 0, (int)g.b_bytes, 0x00020000);
-        if constexpr (A_KC) init_kc<BM>(oa_kc, g.lda, bm0, g.M, t); else init_ks<BM>(oa_ks, g.lda, bm0, g.M, t);
-        if constexpr (B_KC) init_kc<BN>(ob_kc, g.ldb, bn0, g.N, t); else init_ks<BN>(ob_ks, g.ldb, bn0, g.N, t);
-    }
-    auto gload = [&](int kt) {
-        const int k0 = kt << 5;
-        if constexpr (FAST) {
-            if constexpr (A_KC) load_kc_fast<BM>(sa, rsA, oa_kc, k0, g.K, t);
-            else load_ks_fast<BM>(sa, rsA, oa_ks, k0, g.K, t, g.a_seg, g.a_stride, g.a_off);
-            if constexpr (B_KC) load_kc_fast<BN>(sb, rsB, ob_kc, k0, g.K, t);
-            else load_ks_fast<BN>(sb, rsB, ob_ks, k0, g.K, t, 0, 0, 0);
-        } else {
-            if constexpr (A_KC) load_kc<BM>(sa, g.A, g.lda, bm0, g.M, k0, g.K, g.a_vec, t);
-            else load_ks<BM>(sa, g.A, g.lda, bm0, g.M, k0, g.K, g.a_vec, t, g.a_seg, g.a_stride, g.a_off);
-            if constexpr (B_KC) load_kc<BN>(sb, g.B, g.ldb, bn0, g.N, k0, g.K, g.b_vec, t);
-            else load_ks<BN>(sb, g.B, g.ldb, bn0, g.N, k0, g.K, g.b_vec, t, 0, 0, 0);
-        }
-    };
-    auto lstore = [&]() {
-        if constexpr (A_KC) store_kc<BM>(sa, As, t); else store_ks<BM>(sa, As, t);
-        if constexpr (B_KC) store_kc<BN>(sb, Bs, t); else store_ks<BN>(sb, Bs, t);
-    };
-
-    if (kt_begin < kt_end) {
-        gload(kt_begin);
-        lstore();
-    }
-    __syncthreads();
-
-    auto mfma_tile = [&]() {
+    const F32Operand A = {g.A, g.lda, g.M, g.a_bytes, g.a_vec}, B = {g.B, g.ldb, g.N, g.b_bytes, g.b_vec};
+    F32Stage<A_KC, B_KC, BM, BN, FAST> st;
+    st.point(A, B);
+    st.rows_a(A, bm0, t);
+    st.rows_b(B, bn0, t);
+    auto gload = [&](int kt) { st.gload(A, bm0, B, bn0, kt << 5, g.K, t, g.a_seg, g.a_stride, g.a_off); };
+    auto lstore = [&]() { st.lstore(As, Bs, t); };
+    auto tile = [&]() {
         if (want_colsum && t < BM) {
             float s = 0.f;
 #pragma unroll
             for (int kk = 0; kk < 32; ++kk) s += As[kk * (BM + 4) + t];
             colsum += s;
         }
-#pragma unroll
-        for (int kb = 0; kb < 32; kb += 8) {
-            f32x4 a[WM], b[WN];
-#pragma unroll
-            for (int i = 0; i < WM; ++i) {
-                if constexpr (A_KC) {
-                    a[i] = *reinterpret_cast<const f32x4*>(As + (wm0 + i * 32 + r) * 36 + kb + 4 * h);
-                } else {
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) a[i][s] = As[(kb + 4 * h + s) * (BM + 4) + wm0 + i * 32 + r];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < WN; ++j) {
-                if constexpr (B_KC) {
-                    b[j] = *reinterpret_cast<const f32x4*>(Bs + (wn0 + j * 32 + r) * 36 + kb + 4 * h);
-                } else {
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) b[j][s] = Bs[(kb + 4 * h + s) * (BN + 4) + wn0 + j * 32 + r];
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int i = 0; i < WM; ++i)
-#pragma unroll
-                    for (int j = 0; j < WN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][s], b[j][s], acc[i][j], 0, 0, 0);
-        }
+        mfma_tile<A_KC, B_KC, BM, BN>(As, Bs, wm0, wn0, r, h, acc);
     };
-    // Branch-free steady-state body with the last k-tile peeled: a conditional prefetch inside the
-    // loop makes hipcc carry the accumulators through VGPRs (all of them copied AGPR -> VGPR ->
-    // AGPR every iteration).  The next tile's global loads stay in flight under the MFMAs.
-    for (int kt = kt_begin; kt + 1 < kt_end; ++kt) {
-        gload(kt + 1);
-        __builtin_amdgcn_sched_barrier(0);      // keep the loads ABOVE the MFMAs (the scheduler otherwise sinks them to their use)
-        mfma_tile();
-        __syncthreads();
-        lstore();
-        __syncthreads();
-    }
-    if (kt_begin < kt_end) mfma_tile();
+    F32_KLOOP(false, kt_begin, kt_end, gload, lstore, tile);
 
     if constexpr (EPI == EPI_SLAB) {
         if (want_colsum && t < BM && bm0 + t < g.M) g.slab_bias[(long)z * g.slab_bias_stride + bm0 + t] = colsum;

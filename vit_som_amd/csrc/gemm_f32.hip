@@ -29,8 +29,6 @@ int gemm_grad_products() { return gemm_mode() == VSOM_GEMM_SPLIT_BF16_GRAD3 ? 3 
 // One tile configuration: 128 x 64 (4 waves, each 32 x 64 = two 32x32 accumulators).  Measured
 // against 128 x 128 on every GEMM shape of the step (and 4096^3): faster everywhere -- three
 // workgroups per CU instead of two and half the epilogue per workgroup.
-static long operand_bytes(long rows, long ld, long cols) { return ((rows - 1) * ld + cols) * 4; }
-
 // ---- the launch plan ("Which kernel runs").
 // The kernels a (layout, epilogue) pair has beside the f32 128 x 64 pair that every one has.  gemm_plan() chooses among
 // them and dispatch_gemm() instantiates exactly them: a form that is false here is neither planned nor compiled.

@@ -14,8 +14,9 @@
 //                    distances to each cluster's members, then the silhouette coefficient.  Integer atomics only.
 //
 // The contract the search entry points keep (the rank pass takes its distances from the same four), written once below:
-//   - the 128 x 64 tile of dot products (knn_tile_dots), every (row, row) pair summed over D in one fixed order that
-//     depends neither on where the two rows fall in a tile nor on the sizes of the two sets;
+//   - the 128 x 64 tile of dot products (knn_tile_dots: the staging, the k-loop and the MFMA order of gemm_f32.h, shared
+//     with gemm_f32_kernel and pca_gemm_kernel), every (row, row) pair summed over D in one fixed order that depends
+//     neither on where the two rows fall in a tile nor on the sizes of the two sets;
 //   - the squared norms summed in that same order (knn_sqnorm_kernel), so identical rows are at distance exactly 0;
 //   - the distance from (dot, norm, norm) (knn_distance);
 //   - the strict (distance, index) total order of the lists and the order-independent insertion (knn_less, knn_insert).
@@ -36,9 +37,9 @@ constexpr int VOTE_WAVES = 4;                // queries per vote workgroup (one 
 constexpr int VOTE_MAX_CLASSES = 1024;       // fp64 LDS score table per wave: 4 x 8 KB
 constexpr int64_t KNN_NO_INDEX = 0x7fffffffffffffffLL;      // sorts after every real ordinal; stored as -1
 
-// Squared row norms in the order in which the MFMA loop of knn_tile_dots sums a row's products with itself:
-// in groups of 8, k = kb + s then kb + 4 + s for s = 0..3 (lane half h feeds k = kb + 4h + s to MFMA step s; the
-// instruction is bitwise fma(a_k1 b_k1, fma(a_k0 b_k0, c))).  So sq[i] is <x_i, x_i> of the contraction bit for bit,
+// Squared row norms in the order in which mfma_tile (gemm_f32.h: the one definition of the order) sums a row's products
+// with itself: in groups of 8, k = kb + s then kb + 4 + s for s = 0..3 (lane half h feeds k = kb + 4h + s to MFMA step s;
+// the instruction is bitwise fma(a_k1 b_k1, fma(a_k0 b_k0, c))).  So sq[i] is <x_i, x_i> of the contraction bit for bit,
 // and the euclidean distance between two identical rows is exactly 0.
 __device__ __forceinline__ float knn_sqnorm_row(const float* __restrict__ x, int D) {
     float s = 0.f;
@@ -98,44 +99,22 @@ __device__ __forceinline__ float knn_distance(float dot, float si, float sj, int
 }
 
 // One operand of the contraction: rows [rows, D] with row stride ld.
-struct KnnOperand {
-    const float* base;
-    long ld;
-    int rows;
-    unsigned bytes;     // FAST path: extent for the bounds-checked buffer loads
-    int vec;            // generic path: 16-byte loads legal
-};
+using KnnOperand = F32Operand;
 
-// The operand staging of one workgroup: the row offsets of its 128 A rows are computed once, those of a 64-row B tile
-// once per tile (FAST path only; the generic path indexes from the pointers).
+// The operand staging of one workgroup (gemm_f32.h, the NT form).  A kernel points it at its operands and computes the
+// row offsets of its 128 A rows once (point, rows_a), knn_tile_dots those of a 64-row B tile once per tile (FAST path
+// only; the generic path indexes from the pointers); point() alone moves it to operands that begin elsewhere in the
+// same rows (the silhouette's later k-segments): the row offsets stay.
 template <bool FAST>
-struct KnnStage {
-    StageRegs<KNN_BM> sa;
-    StageRegs<KNN_BN> sb;
-    __amdgpu_buffer_rsrc_t rsA, rsB;
-    OffKC<KNN_BM> oa;
-    OffKC<KNN_BN> ob;
-};
-// Point the staging at operands that begin elsewhere in the same rows (a later k-segment): the row offsets stay.
-template <bool FAST>
-__device__ __forceinline__ void knn_stage_rebase(KnnStage<FAST>& st, const KnnOperand& A, const KnnOperand& B) {
-    if constexpr (FAST) {
-        st.rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A.base), 0, (int)A.bytes, 0x00020000);
-        st.rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(B.base), 0, (int)B.bytes, 0x00020000);
-    }
-}
-template <bool FAST>
-__device__ __forceinline__ void knn_stage_init(KnnStage<FAST>& st, const KnnOperand& A, int bm0, const KnnOperand& B, int t) {
-    knn_stage_rebase<FAST>(st, A, B);
-    if constexpr (FAST) init_kc<KNN_BM>(st.oa, A.ld, bm0, A.rows, t);
-}
+using KnnStage = F32Stage<true, true, KNN_BM, KNN_BN, FAST>;
 
 // acc[j] <- the 128 x 64 block <A[bm0 + .], B[bn0 + .]> over K on the f32 matrix cores: wave w owns rows 32w..32w+31,
 // acc[j] columns 32j..32j+31 (register v of acc[j]: row (v & 3) + 8 (v >> 2) + 4h, column 32j + r).  Operand tiles are
-// staged global -> registers -> LDS as in gemm_f32_kernel (lds: (128 + 64) * 36 floats).  Every pair's products are
-// summed k-tile by k-tile, 8-group by 8-group, step s = 0..3 with k = kb + s before kb + 4 + s inside the instruction:
-// one order for every pair.  Rows outside either operand and k >= K contribute exact zeros.  All waves must call it;
-// the caller synchronises before the next call overwrites the LDS tiles.
+// staged global -> registers -> LDS by the staging, the k-loop and the MFMA order of gemm_f32_kernel, the same code
+// (gemm_f32.h; lds: (128 + 64) * 36 floats).  Every pair's products are summed k-tile by k-tile, 8-group by 8-group,
+// step s = 0..3 with k = kb + s before kb + 4 + s inside the instruction (mfma_tile): one order for every pair.  Rows
+// outside either operand and k >= K contribute exact zeros.  All waves must call it; the caller synchronises before the
+// next call overwrites the LDS tiles.
 template <bool FAST>
 __device__ __forceinline__ void knn_tile_dots(KnnStage<FAST>& st, const KnnOperand& A, int bm0, const KnnOperand& B, int bn0,
                                               int K, float* lds, int t, f32x16 (&acc)[2]) {
@@ -146,50 +125,15 @@ __device__ __forceinline__ void knn_tile_dots(KnnStage<FAST>& st, const KnnOpera
     const int r = lane & 31, h = lane >> 5;
     const int wm0 = wave * 32;
     const int ktiles = (K + 31) >> 5;
-    if constexpr (FAST) init_kc<BN>(st.ob, B.ld, bn0, B.rows, t);
-    auto gload = [&](int kt) {
-        const int k0 = kt << 5;
-        if constexpr (FAST) {
-            load_kc_fast<BM>(st.sa, st.rsA, st.oa, k0, K, t);
-            load_kc_fast<BN>(st.sb, st.rsB, st.ob, k0, K, t);
-        } else {
-            load_kc<BM>(st.sa, A.base, A.ld, bm0, A.rows, k0, K, A.vec, t);
-            load_kc<BN>(st.sb, B.base, B.ld, bn0, B.rows, k0, K, B.vec, t);
-        }
-    };
-    auto lstore = [&]() {
-        store_kc<BM>(st.sa, As, t);
-        store_kc<BN>(st.sb, Bs, t);
-    };
+    st.rows_b(B, bn0, t);
+    auto gload = [&](int kt) { st.gload(A, bm0, B, bn0, kt << 5, K, t); };
+    auto lstore = [&]() { st.lstore(As, Bs, t); };
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int v = 0; v < 16; ++v) acc[j][v] = 0.f;
-    auto mfma_tile = [&]() {
-#pragma unroll
-        for (int kb = 0; kb < 32; kb += 8) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(As + (wm0 + r) * 36 + kb + 4 * h);
-            f32x4 b[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) b[j] = *reinterpret_cast<const f32x4*>(Bs + (j * 32 + r) * 36 + kb + 4 * h);
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b[j][s], acc[j], 0, 0, 0);
-        }
-    };
-    gload(0);
-    lstore();
-    __syncthreads();
-    for (int kt = 0; kt + 1 < ktiles; ++kt) {
-        gload(kt + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_tile();
-        __syncthreads();
-        lstore();
-        __syncthreads();
-    }
-    mfma_tile();
+    auto tile = [&]() { mfma_tile<true, true, BM, BN>(As, Bs, wm0, 0, r, h, reinterpret_cast<f32x16 (&)[1][2]>(acc)); };
+    F32_KLOOP(true, 0, ktiles, gload, lstore, tile);       // K >= 1: every entry refuses D < 1
 }
 
 // (query row blocks, bank column tiles, chunks): chunks split the bank's columns so that few queries still fill the GPU.
@@ -283,7 +227,8 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_tile_kernel(const QueryP p) {
     }
 
     KnnStage<FAST> st;
-    knn_stage_init<FAST>(st, p.Q, bm0, X, t);
+    st.point(p.Q, X);
+    st.rows_a(p.Q, bm0, t);
 
     for (int ctile = ct0; ctile < ct1; ++ctile) {
         const int bn0 = ctile * BN;
@@ -417,7 +362,7 @@ inline RankWs rank_layout(void* ws, long N, int k) {
     return w;
 }
 
-// <x, y> over D in the order in which knn_tile_dots sums that pair (see knn_sqnorm_kernel): bit for bit the tile's value.
+// <x, y> over D in the order in which mfma_tile sums that pair (see knn_sqnorm_row): bit for bit the tile's value.
 template <bool VEC>
 __device__ __forceinline__ float knn_pair_dot(const float* __restrict__ x, const float* __restrict__ y, int D) {
     float s = 0.f;
@@ -514,7 +459,8 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void knn_rank_tile_kernel(const Ran
     const RankSlot* slots = p.slot + (size_t)wrow0 * p.k;
 
     KnnStage<FAST> st;
-    knn_stage_init<FAST>(st, p.A, bm0, p.A, t);
+    st.point(p.A, p.A);
+    st.rows_a(p.A, bm0, t);
 
     for (int ctile = ct0; ctile < ct1; ++ctile) {
         const int bn0 = ctile * BN;
@@ -749,7 +695,8 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void sil_tile_kernel(const SilP p) 
     int refused = 0;
 
     KnnStage<FAST> st;
-    knn_stage_init<FAST>(st, p.A, bm0, p.A, t);      // the row offsets of the 128 A rows: once per workgroup
+    st.point(p.A, p.A);
+    st.rows_a(p.A, bm0, t);      // the row offsets of the 128 A rows: once per workgroup
 
     for (int ctile = ct0; ctile < ct1; ++ctile) {
         const int bn0 = ctile * BN;
@@ -767,7 +714,7 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void sil_tile_kernel(const SilP p) 
         for (int k0 = 0; k0 < p.D; k0 += SIL_SEG) {                         // segment by segment, see SIL_SEG
             const KnnOperand seg = {p.A.base + k0, p.A.ld, p.A.rows, p.A.bytes - 4u * (unsigned)k0, p.A.vec};
             const int len = p.D - k0 < SIL_SEG ? p.D - k0 : SIL_SEG;
-            knn_stage_rebase<FAST>(st, seg, seg);
+            st.point(seg, seg);
             if (k0 == 0) {
                 knn_tile_dots<FAST>(st, seg, bm0, seg, bn0, len, lds, t, acc);  // its barriers publish collab (and rowlab, rowsq)
             } else {

@@ -107,12 +107,6 @@ __global__ __launch_bounds__(256) void map_stats_kernel(const float* __restrict_
     }
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // One workgroup per unit.  Wave 0 lists the unit's grid neighbours in ascending index order (ballot + prefix count); then the
 // unit's row and the neighbours' rows are streamed once, every thread keeping fp64 partial sums per neighbour (exact fp64
 // products / differences of the fp32 values); a butterfly per wave and the four waves in order give the row sums.

@@ -9,8 +9,9 @@
 //   vsom_pca_rotate       Bout = T Zt, T fp64 [l_out, l_in]: fp64 accumulation, one rounding to f32.
 //   vsom_pca_reconstruct  Xout = (Y diag(scale)) B + mean.
 //
-// The two contractions run on the exact-f32 matrix cores with the staging, the LDS images and the slab epilogue of
-// gemm_f32.h.  What they add is the CENTRING ON LOAD: the mean is subtracted from an X tile between the global load and
+// The two contractions run on the exact-f32 matrix cores and are the shared tile contraction of gemm_f32.h -- its staging
+// (F32Stage), its k-loop (F32_KLOOP), its MFMA order (mfma_tile), its LDS images and its slab epilogue: the same code as
+// gemm_f32_kernel's, not a copy.  What pca_gemm_kernel adds is the CENTRING ON LOAD: the mean is subtracted from an X tile between the global load and
 // the LDS store, never algebraically after the contraction -- latents have column means that are large against their
 // spread, and X B^T - 1 (mean^T B^T) cancels in f32.  A tile element outside the matrix (a row >= N, a column >= D, the
 // zero an out-of-range buffer load returns) must stay zero AFTER centring: the mean vector a thread subtracts is zero
@@ -116,14 +117,13 @@ __global__ __launch_bounds__(256) void pca_colfinish_kernel(const double* __rest
 
 // ---------------------------------------------------------------------------------------------- the two contractions
 // gemm_f32_kernel<NT ? (A_KC, B_KC) : (!A_KC, !B_KC), 1, 2, 4, 1, EPI_SLAB, FAST> with the centring step between the
-// global load and the LDS store.  NT: A = X (rows = output rows, centred along k = the columns of X), B = the basis.
+// global load and the LDS store: its own are the mean's buffer resource, mean4, centre() in front of lstore, and k_loaded.  NT: A = X (rows = output rows, centred along k = the columns of X), B = the basis.
 // TN: A = Y (k-strided; rows of Y are reduction indices), B = X (k-strided, centred along its columns = output columns).
 template <bool NT, bool FAST>
 __global__ __launch_bounds__(256) void pca_gemm_kernel(const GemmP g, const float* __restrict__ mean) {
     constexpr int BM = PCA_BM, BN = PCA_BN, WM = 1, WN = 2;
-    constexpr int A_LDS = NT ? BM * 36 : 32 * (BM + 4);
-    constexpr int B_LDS = NT ? BN * 36 : 32 * (BN + 4);
-    __shared__ __attribute__((aligned(16))) float lds[A_LDS + B_LDS];
+    constexpr int A_LDS = f32_tile_floats<NT, BM>();
+    __shared__ __attribute__((aligned(16))) float lds[A_LDS + f32_tile_floats<NT, BN>()];
     float* As = lds;
     float* Bs = lds + A_LDS;
 
@@ -133,6 +133,8 @@ __global__ __launch_bounds__(256) void pca_gemm_kernel(const GemmP g, const floa
     const int wm0 = wave * (WM * 32);
     const int wn0 = 0;
 
+    // gemm_f32_kernel's tile and split arithmetic, as text: behind a helper shared with it, every instantiation of both
+    // kernels came out rescheduled (same length and registers), and these four are byte for byte their hand-written form
     const int tiles_n = (g.N + BN - 1) / BN;
     const int tiles_m = (g.M + BM - 1) / BM;
     const int ntiles = tiles_m * tiles_n;
@@ -155,19 +157,17 @@ __global__ __launch_bounds__(256) void pca_gemm_kernel(const GemmP g, const floa
 #pragma unroll
         for (int v = 0; v < 16; ++v) acc[0][j][v] = 0.f;
 
-    StageRegs<BM> sa;
-    StageRegs<BN> sb;
-    __amdgpu_buffer_rsrc_t rsA, rsB, rsM;
-    OffKC<BM> oa_kc; OffKS<BM> oa_ks; OffKC<BN> ob_kc; OffKS<BN> ob_ks;
+    const F32Operand A = {g.A, g.lda, g.M, g.a_bytes, g.a_vec}, B = {g.B, g.ldb, g.N, g.b_bytes, g.b_vec};
+    F32Stage<NT, NT, BM, BN, FAST> st;
+    st.point(A, B);
+    // the mean as a bounds-checked buffer of its own: a load at a column >= D returns the zero the centring needs there
+    __amdgpu_buffer_rsrc_t rsM;
     if constexpr (FAST) {
-        rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.A), 0, (int)g.a_bytes, 0x00020000);
-        rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.B), 0, (int)g.b_bytes, 0x00020000);
-        // the mean as a bounds-checked buffer of its own: a load at a column >= D returns the zero the centring needs there
         const int mcols = NT ? g.K : g.N;
         rsM = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(mean), 0, mean ? mcols * 4 : 0, 0x00020000);
-        if constexpr (NT) { init_kc<BM>(oa_kc, g.lda, bm0, g.M, t); init_kc<BN>(ob_kc, g.ldb, bn0, g.N, t); }
-        else { init_ks<BM>(oa_ks, g.lda, bm0, g.M, t); init_ks<BN>(ob_ks, g.ldb, bn0, g.N, t); }
     }
+    st.rows_a(A, bm0, t);
+    st.rows_b(B, bn0, t);
     // the four mean values this thread subtracts: columns c .. c + 3 of X, zero outside [0, D)
     auto mean4 = [&](int c, int ncols) {
         f32x4 m = {0.f, 0.f, 0.f, 0.f};
@@ -188,13 +188,7 @@ __global__ __launch_bounds__(256) void pca_gemm_kernel(const GemmP g, const floa
     auto gload = [&](int kt) {
         const int k0 = kt << 5;
         k_loaded = k0;
-        if constexpr (FAST) {
-            if constexpr (NT) { load_kc_fast<BM>(sa, rsA, oa_kc, k0, g.K, t); load_kc_fast<BN>(sb, rsB, ob_kc, k0, g.K, t); }
-            else { load_ks_fast<BM>(sa, rsA, oa_ks, k0, g.K, t, 0, 0, 0); load_ks_fast<BN>(sb, rsB, ob_ks, k0, g.K, t, 0, 0, 0); }
-        } else {
-            if constexpr (NT) { load_kc<BM>(sa, g.A, g.lda, bm0, g.M, k0, g.K, g.a_vec, t); load_kc<BN>(sb, g.B, g.ldb, bn0, g.N, k0, g.K, g.b_vec, t); }
-            else { load_ks<BM>(sa, g.A, g.lda, bm0, g.M, k0, g.K, g.a_vec, t, 0, 0, 0); load_ks<BN>(sb, g.B, g.ldb, bn0, g.N, k0, g.K, g.b_vec, t, 0, 0, 0); }
-        }
+        st.gload(A, bm0, B, bn0, k0, g.K, t);                              // no reduction-row map: literal zeros
         if constexpr (NT) m4 = mean4(k0 + ((t & 7) << 2), g.K);            // NT: the thread's columns move with the k-tile
     };
     // Centring, between the global load and the LDS store.  Only elements whose ROW is inside the matrix are touched (m4 is
@@ -203,62 +197,20 @@ __global__ __launch_bounds__(256) void pca_gemm_kernel(const GemmP g, const floa
         if constexpr (NT) {
 #pragma unroll
             for (int p = 0; p < BM / 32; ++p)
-                if (bm0 + p * 32 + (t >> 3) < g.M) sa.v[p] -= m4;
+                if (bm0 + p * 32 + (t >> 3) < g.M) st.sa.v[p] -= m4;
         } else {
             constexpr int TPR = BN / 4, KPP = 256 / TPR;
 #pragma unroll
             for (int p = 0; p < BN / 32; ++p)
-                if (k_loaded + p * KPP + t / TPR < g.K) sb.v[p] -= m4;
+                if (k_loaded + p * KPP + t / TPR < g.K) st.sb.v[p] -= m4;
         }
     };
     auto lstore = [&]() {
         centre();
-        if constexpr (NT) { store_kc<BM>(sa, As, t); store_kc<BN>(sb, Bs, t); }
-        else { store_ks<BM>(sa, As, t); store_ks<BN>(sb, Bs, t); }
+        st.lstore(As, Bs, t);
     };
-
-    if (kt_begin < kt_end) {
-        gload(kt_begin);
-        lstore();
-    }
-    __syncthreads();
-
-    auto mfma_tile = [&]() {
-#pragma unroll
-        for (int kb = 0; kb < 32; kb += 8) {
-            f32x4 a, b[WN];
-            if constexpr (NT) {
-                a = *reinterpret_cast<const f32x4*>(As + (wm0 + r) * 36 + kb + 4 * h);
-            } else {
-#pragma unroll
-                for (int s = 0; s < 4; ++s) a[s] = As[(kb + 4 * h + s) * (BM + 4) + wm0 + r];
-            }
-#pragma unroll
-            for (int j = 0; j < WN; ++j) {
-                if constexpr (NT) {
-                    b[j] = *reinterpret_cast<const f32x4*>(Bs + (wn0 + j * 32 + r) * 36 + kb + 4 * h);
-                } else {
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) b[j][s] = Bs[(kb + 4 * h + s) * (BN + 4) + wn0 + j * 32 + r];
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int j = 0; j < WN; ++j)
-                    acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b[j][s], acc[0][j], 0, 0, 0);
-        }
-    };
-    // the k-loop of gemm_f32_kernel: last tile peeled, the next tile's global loads in flight under the MFMAs
-    for (int kt = kt_begin; kt + 1 < kt_end; ++kt) {
-        gload(kt + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_tile();
-        __syncthreads();
-        lstore();
-        __syncthreads();
-    }
-    if (kt_begin < kt_end) mfma_tile();
+    auto tile = [&]() { mfma_tile<NT, NT, BM, BN>(As, Bs, wm0, wn0, r, h, acc); };
+    F32_KLOOP(false, kt_begin, kt_end, gload, lstore, tile);
 
     gemm_epilogue<WM, WN, EPI_SLAB>(g, acc, bm0 + wm0, bn0 + wn0, r, h, z);
 }
@@ -276,8 +228,6 @@ __global__ __launch_bounds__(256) void pca_reduce_kernel(const float* __restrict
     out[m * ldo + n] = t;
 }
 
-inline long operand_extent_bytes(long rows, long ld, long cols) { return ((rows - 1) * ld + cols) * 4; }
-
 // NT / TN launch over the slabs, then the reduction into out (row stride ldo)
 int pca_contract(bool nt, GemmP g, const float* mean, const float* scale, float* out, long ldo, const PcaPlan& p,
                  float* slabs, hipStream_t stream) {
@@ -289,7 +239,7 @@ int pca_contract(bool nt, GemmP g, const float* mean, const float* scale, float*
     // what it reads past column l lands in tile rows >= l, which the epilogue never stores.
     const long a_rows = nt ? g.M : g.K, a_cols = nt ? g.K : (g.a_vec ? (g.M + 3L) / 4 * 4 : g.M);
     const long b_rows = nt ? g.N : g.K, b_cols = nt ? g.K : g.N;
-    const long ab = operand_extent_bytes(a_rows, g.lda, a_cols), bb = operand_extent_bytes(b_rows, g.ldb, b_cols);
+    const long ab = operand_bytes(a_rows, g.lda, a_cols), bb = operand_bytes(b_rows, g.ldb, b_cols);
     const int xcols = nt ? g.K : g.N;                  // D: the width of X, whichever operand it is
     const bool fast = g.a_vec && g.b_vec && xcols % 4 == 0 && (!mean || aligned16(mean)) && ab < 0xFFFF0000L && bb < 0xFFFF0000L;
     g.a_bytes = (unsigned)ab; g.b_bytes = (unsigned)bb;
@@ -317,11 +267,6 @@ int pca_contract(bool nt, GemmP g, const float* mean, const float* scale, float*
 // A workgroup owns a 4 x 4 patch of G (and of H).  Thread t sums the products at d = t, t + 1024, ... in fp64, the 64 lanes
 // of a wave are combined by a butterfly, the sixteen waves in wave order: one fixed order per entry, and G comes out
 // symmetric bit for bit (the patch (j, i) adds the same products in the same order).
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __global__ __launch_bounds__(GRAM_THREADS) void pca_gram_kernel(const float* __restrict__ Zt, long ldz, const float* __restrict__ B, long ldb,
                                                        int l, int D, double* __restrict__ G, double* __restrict__ H) {
     __shared__ double sh[GRAM_WAVES][32];
