@@ -117,7 +117,7 @@ int vsom_set_ln_tiles(int mode);
 /* Which kernel an entry point would launch ("Which kernel runs"), as one line of text in `out`:
  *     engine=<name> tile=<rows>x<cols> planes=<n> fast=<0|1> threads=<n> splits=<n> workgroups=<n>
  * engine: f32 | x6 (the generic GEMM kernels), x6_tn (weight-gradient tiles), x6_ln (LayerNorm-fused tiles), attn_two_launch
- * | attn_fused | attn_shared | attn_shared_bf16x3; planes = bf16 pieces per operand (0: fp32 products); fast = 16-byte
+ * | attn_fused | attn_shared | attn_shared_bf16x3, bmu_x3 | bmu_x3_planes (the three-product BMU forms); planes = bf16 pieces per operand (0: fp32 products); fast = 16-byte
  * buffer loads.  Pure host arithmetic under the current GEMM mode and hooks: nothing is launched and no GPU is needed; the
  * library itself never calls it.  M, N, K are the entry point's own shape arguments in its own order ((B, K, L) for the SOM
  * entries; (N tokens, H, hd) for VSOM_PLAN_ATTENTION_BWD, workgroups per image).  flags bit 0: every operand is 16-byte
@@ -137,6 +137,10 @@ int vsom_set_ln_tiles(int mode);
 #define VSOM_PLAN_SOM_BWD_GX 11
 #define VSOM_PLAN_BMU_COSINE_DOTS 12
 #define VSOM_PLAN_ATTENTION_BWD 13
+/* the cosine BMU pass as a whole, shape (B, K, L): engine = bmu_x3_planes | bmu_x3 | f32, the form vsom_bmu_cosine_form names
+   for dense rows (ldx = L); flags bit 1: plane images are available.  VSOM_PLAN_BMU_COSINE_DOTS describes the exact entry
+   point vsom_bmu_cosine_dots whatever the mode. */
+#define VSOM_PLAN_BMU_COSINE 14
 int vsom_describe_plan(int op, int M, int N, int K, int flags, char* out, size_t out_bytes);
 
 /* dW[N,K] = dY[M,N]^T * X[M,K] ;  db[N] = column sums of dY (db may be NULL)
@@ -744,6 +748,17 @@ int vsom_bmu_cosine_x3_planes_dots(const void* xplanes, const void* wplanes, int
 int vsom_bmu_cosine_x3_planes_finalize(const float* X, long ldx, const float* W, const void* xplanes, const void* wplanes,
                                        const void* ws, size_t ws_bytes, float* dist, int64_t* bmu, float* inv_nx, float* inv_nw,
                                        int* reranked, int B, int K, int L, vsom_stream_t stream);
+
+/* Which of the three forms above a caller of the cosine BMU pass should run for B sample rows of stride ldx against K
+   prototypes of L elements, under the current GEMM mode ("Which kernel runs": Cosine BMU pass):
+   VSOM_BMU_EXACT (vsom_bmu_cosine_*, after the two row-norm passes), VSOM_BMU_X3 (vsom_bmu_cosine_x3_*) or VSOM_BMU_X3_PLANES
+   (vsom_bmu_cosine_x3_planes_*).  flags bit 0: X is 16-byte aligned; bit 1: the caller can supply plane images.  Pure host
+   arithmetic, the same plan the entry points take their grids and workspace sizes from.  VSOM_EINVAL on a non-positive
+   shape. */
+#define VSOM_BMU_EXACT 0
+#define VSOM_BMU_X3 1
+#define VSOM_BMU_X3_PLANES 2
+int vsom_bmu_cosine_form(int B, int K, int L, long ldx, int flags);
 
 /* ------------------------------------------------------------------ data: the input side of a step (augment.hip)
  * A data set lives on the device as uint8 [N, C, H, W] (C 1 or 3, square, H <= 64).  vsom_augment_plan writes one row of

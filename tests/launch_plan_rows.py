@@ -5,7 +5,7 @@ from collections import namedtuple
 
 # include/vitsom_hip.h: VSOM_PLAN_*
 (LINEAR_FWD, LINEAR_GELU_FWD, LINEAR_RELU_FWD, LINEAR_RESIDUAL_FWD, BWD_INPUT, BWD_INPUT_GELU, BWD_INPUT_T, BWD_INPUT_T_GELU,
- BWD_WEIGHT, BWD_INPUT_LN, SOM_BWD_GW, SOM_BWD_GX, BMU_COSINE_DOTS, ATTENTION_BWD) = range(14)
+ BWD_WEIGHT, BWD_INPUT_LN, SOM_BWD_GW, SOM_BWD_GX, BMU_COSINE_DOTS, ATTENTION_BWD, BMU_COSINE) = range(15)
 
 F32, SPLIT, GRAD3 = 0, 1, 2                     # VSOM_GEMM_*
 MODES = (F32, SPLIT, GRAD3)
@@ -31,9 +31,11 @@ def ln(tile, planes):
 
 TWO_LAUNCH, FUSED, SHARED = (("attn_" + n, "16x16", 0, 1) for n in ("two_launch", "fused", "shared"))
 SHARED_BF16X3 = ("attn_shared_bf16x3", "16x16", 2, 1)
+BMU_X3_SMALL, BMU_X3_BIG = ("bmu_x3", "128x128", 2, 1), ("bmu_x3", "256x192", 2, 1)
+BMU_X3_PLANES = ("bmu_x3_planes", "256x192", 2, 1)
 
-# row: label of the table row; op, shape: vsom_describe_plan's arguments (the entry point's own M, N, K); aligned: flags
-# bit 0; expect[gemm mode] = the outcome, or {hook value: outcome} where the family's hook matters (hook = "wgrad_tiles",
+# row: label of the table row; op, shape: vsom_describe_plan's arguments (the entry point's own M, N, K); aligned: the
+# flags (bit 0: aligned operands; bit 1, BMU_COSINE only: plane images are available); expect[gemm mode] = the outcome, or {hook value: outcome} where the family's hook matters (hook = "wgrad_tiles",
 # "ln_tiles" or "attention_fused"); ld_pad: extra floats on the first operand's row stride in the GPU run
 Row = namedtuple("Row", "row op shape aligned expect hook ld_pad", defaults=(None, 0))
 
@@ -93,6 +95,13 @@ PLAN_ROWS = [
     Row("attn.fused", ATTENTION_BWD, (65, 2, 32), 1, every({0: TWO_LAUNCH, 1: FUSED, 2: FUSED, 3: FUSED}), "attention_fused"),
     Row("attn.two_launch.lds", ATTENTION_BWD, (197, 2, 64), 1, every({h: TWO_LAUNCH for h in range(4)}), "attention_fused"),
     Row("attn.two_launch.novec", ATTENTION_BWD, (17, 2, 8), 1, every({h: TWO_LAUNCH for h in range(4)}), "attention_fused"),
+    # ---- cosine BMU pass: shape = (B, K, L); in VSOM_GEMM_F32 mode every row is the exact form
+    Row("bmu.x3.small", BMU_COSINE, (70, 15, 256), 1, by_mode(F32_128, BMU_X3_SMALL, BMU_X3_SMALL)),
+    Row("bmu.x3.big", BMU_COSINE, (192, 15, 256), 1, by_mode(F32_128, BMU_X3_BIG, BMU_X3_BIG)),
+    Row("bmu.x3.planes", BMU_COSINE, (192, 15, 256), 3, by_mode(F32_128, BMU_X3_PLANES, BMU_X3_PLANES)),
+    Row("bmu.x3.l%8", BMU_COSINE, (192, 15, 252), 3, by_mode(F32_128, BMU_X3_BIG, BMU_X3_BIG)),
+    Row("bmu.exact.k", BMU_COSINE, (8, 2049, 8), 3, every(F32_128)),                        # 2049 > 256 * 8 prototypes
+    Row("bmu.exact.stride", BMU_COSINE, (70, 15, 256), 0, every(F32_128_SLOW), ld_pad=1),   # row stride 257: unaligned
 ]
 
 # every row of the table; test_launch_plan_cpu.py asserts that PLAN_ROWS hits each one
@@ -103,6 +112,7 @@ TABLE_ROWS = {
     "wgrad.192x64", "wgrad.96x96", "wgrad.192x192", "wgrad.unaligned",
     "ln.192", "ln.96", "ln.few_tiles", "ln.width",
     "attn.shared", "attn.shared.hd32", "attn.fused", "attn.two_launch.lds", "attn.two_launch.novec",
+    "bmu.x3.small", "bmu.x3.big", "bmu.x3.planes", "bmu.x3.l%8", "bmu.exact.k", "bmu.exact.stride",
 }
 
 HOOK_VALUES = {"wgrad_tiles": (0, 1, 2), "ln_tiles": (0, 1), "attention_fused": (0, 1, 2, 3)}

@@ -6,7 +6,7 @@ import re
 
 import pytest
 
-from launch_plan_rows import ATTENTION_BWD, GRAD3, HOOK_DEFAULTS, HOOK_VALUES, MODES, PLAN_ROWS, TABLE_ROWS, UNSUPPORTED
+from launch_plan_rows import ATTENTION_BWD, F32, GRAD3, HOOK_DEFAULTS, HOOK_VALUES, MODES, PLAN_ROWS, TABLE_ROWS, UNSUPPORTED
 
 LINE = re.compile(r"engine=(\S+) tile=(\d+x\d+) planes=(\d+) fast=([01]) threads=(\d+) splits=(\d+) workgroups=(\d+)$")
 
@@ -104,6 +104,46 @@ def test_attention_backward_plan_over_the_whole_range(ops, lib):
     assert not bad, (len(bad), bad[:8])
 
 
+def bmu_cosine_form(B, K, L, ldx, flags, mode):
+    """0 exact, 1 in-loop three-product, 2 planes: the "Cosine BMU pass" table of DESIGN.md restated (not from the C++)."""
+    aligned, planes = bool(flags & 1), bool(flags & 2)
+    x3 = mode != F32 and K <= 256 * 8 and L % 4 == 0 and ldx % 4 == 0 and aligned
+    if not x3:
+        return 0
+
+    def image(R):                       # bytes of an operand's fragment image: 2 planes of 32 x 32 bf16 blocks
+        return 2 * -(-L // 32) * -(-R // 32) * 2048
+    if planes and B >= 192 and L % 8 == 0 and image(B) < 2 ** 31 and image(K) < 2 ** 31:
+        return 2
+    return 1
+
+
+def test_bmu_cosine_form_over_the_whole_range(ops, lib):
+    """vsom_bmu_cosine_form against the table on both sides of every clause: the batch threshold of the big tile and the
+    planes, the prototype limit, L % 4 and L % 8, the row stride, both flags, the three modes, and the 2 GiB image bound
+    (1365 resp. 1366 row blocks of 384 x 2 x 2048 = 1 572 864 bytes)."""
+    prev = ops.get_gemm_mode()
+    bad = []
+    try:
+        for mode in MODES:
+            ops.set_gemm_mode(mode)
+            shapes = [(B, K, L) for B in (1, 64, 191, 192, 193, 512) for K in (1, 15, 2048, 2049)
+                      for L in (4, 8, 12, 250, 252, 256, 12288)] + [(43680, 16, 12288), (43681, 16, 12288)]
+            for B, K, L in shapes:
+                for ldx in (L, L + 1, L + 4):
+                    for flags in range(4):
+                        got, want = lib.vsom_bmu_cosine_form(B, K, L, ldx, flags), bmu_cosine_form(B, K, L, ldx, flags, mode)
+                        if got != want:
+                            bad.append((mode, B, K, L, ldx, flags, got, want))
+            if mode != F32:
+                assert lib.vsom_bmu_cosine_form(43680, 16, 12288, 12288, 3) == 2
+                assert lib.vsom_bmu_cosine_form(43681, 16, 12288, 12288, 3) == 1
+    finally:
+        ops.set_gemm_mode(prev)
+    assert not bad, (len(bad), bad[:8])
+    assert lib.vsom_bmu_cosine_form(0, 16, 8, 8, 3) == -1
+
+
 def test_describe_plan_grid_arithmetic(lib):
     """Workgroups = tiles x splits, the split count canonical (every split owns a k-tile of 32)."""
     got = describe(lib, 0, (300, 200, 64), 1)                       # 3 x 4 tiles of 128 x 64, one split
@@ -112,6 +152,8 @@ def test_describe_plan_grid_arithmetic(lib):
     assert got[6] == 100 * got[5] and -(-384 // -(-384 // got[5])) == got[5]
     got = describe(lib, 8, (70, 12, 24), 1)                         # generic dW: 3 k-tiles bound the splits
     assert got[5] <= 3 and got[6] == got[5]
+    got = describe(lib, 14, (512, 1600, 12288), 3)                  # BMU planes: 2 x 9 tiles of 256 x 192, 256 // 18 = 14 splits
+    assert got[4:] == (512, 14, 252)                                # ... of 28 k-tiles each
 
 
 def test_describe_plan_rejects_bad_calls(lib):

@@ -1,7 +1,9 @@
 """Every row of the launch-plan table (launch_plan_rows.PLAN_ROWS) run through its ops wrapper, in every GEMM mode and
 every setting of the family's hook, against an fp64 torch reference.  Bounds are the suite's own (test_ops_gpu.py):
-GEMM_TOL, GRAD3_TOL where the row runs three products, and the per-entry bounds of test_linear_gelu_fwd, test_bmu_cosine
-and test_attention.  The references are computed once per row and shared by the modes."""
+GEMM_TOL, GRAD3_TOL where the row runs three products, and the per-entry bounds of test_linear_gelu_fwd, test_bmu_cosine,
+test_bmu_cosine_x3_rerank and test_attention.  The rows of the cosine BMU pass run the package's dispatcher
+(SOMLayer._distances_into) and hold it, bit for bit, to the wrapper of the form the plan names.  The references are
+computed once per row and shared by the modes."""
 import functools
 
 import pytest
@@ -67,9 +69,10 @@ def case(i):
         da = c["dy"].double() @ c["Wt"].double().T
         y.backward(da)
         c["dx"], c["dbeta"] = x.grad, da.sum(0)
-    elif row.op in (R.SOM_BWD_GW, R.SOM_BWD_GX, R.BMU_COSINE_DOTS):
+    elif row.op in (R.SOM_BWD_GW, R.SOM_BWD_GX, R.BMU_COSINE_DOTS, R.BMU_COSINE):
         B, Kp, L = row.shape
-        c["x"], c["W"] = rnd(B, L, seed=1), F.normalize(torch.rand(Kp, L, generator=torch.Generator().manual_seed(2)), dim=1)
+        c["x"], c["xd"] = padded(B, L, row.ld_pad, 1)
+        c["W"] = F.normalize(torch.rand(Kp, L, generator=torch.Generator().manual_seed(2)), dim=1)
         c["coef"], c["rd"], c["cd"], c["gx0"] = rnd(B, Kp, seed=3), rnd(B, seed=4), rnd(Kp, seed=5), rnd(B, L, seed=6)
         x, W, coef = c["x"].double(), c["W"].double(), c["coef"].double()
         c["gW"] = coef.T @ x + c["cd"].double()[:, None] * W
@@ -85,6 +88,15 @@ def case(i):
         out.backward(c["dout"].double())
         c["dqkv"] = q64.grad
     return c
+
+
+def cosine_layer(K, L):
+    """A SOMLayer of K cosine prototypes of L elements: the package's dispatcher of the BMU pass."""
+    from vit_som_amd import SOMLayer
+    cfg = {"hyperparameters": {"model_arch": "desom", "total_epochs": 1, "batch_size": 8, "ae": {"encoder_dims": [L]},
+                               "som": {"map_size": [K, 1], "Tmax": 2.0, "Tmin": 0.5, "distance_fcn": "cosine", "topology": "square"}},
+           "data": {"dataset": "synthetic"}}
+    return SOMLayer(cfg).to(DEV)
 
 
 def run(ops, row, c, tol):
@@ -133,6 +145,41 @@ def run(ops, row, c, tol):
         dist, bmu = new(M, N), torch.empty(M, dtype=torch.int64, device=DEV)
         ops.bmu_cosine_fwd(xd, Wd, inx, inw, dist, bmu)
         assert float((dist.cpu().double() - c["d64"]).abs().max()) < 2e-6
+        assert torch.equal(bmu.cpu(), dist.cpu().argmin(1))
+    elif row.op == R.BMU_COSINE:
+        from vit_som_amd.tuning import hooks
+        engine = describe(ops.lib, row.op, row.shape, row.aligned)[0]
+        form = {"f32": ops.BMU_EXACT, "bmu_x3": ops.BMU_X3, "bmu_x3_planes": ops.BMU_X3_PLANES}[engine]
+        xd, Wd = c["xd"], d("W")
+        # 1. the form the plan names is the form the package's dispatcher runs: its outputs are, bit for bit, those of the
+        #    named form's own wrapper (the three forms differ in dist or in the last bits of the norms)
+        som = cosine_layer(N, K)
+        som.prototypes.data.copy_(Wd)
+        som.invalidate_planes()
+        s = som._buffers_for(M, xd.device)
+        planes_hook = hooks.bmu_planes
+        hooks.set(bmu_planes=bool(row.aligned & 2))
+        try:
+            assert som._bmu_form(M, xd.stride(0), xd.data_ptr() % 16 == 0) == form
+            som._distances_into(xd, s)
+        finally:
+            hooks.set(bmu_planes=planes_hook)
+        dist, bmu = new(M, N), torch.empty(M, dtype=torch.int64, device=DEV)
+        inx, inw = torch.empty(M, device=DEV), torch.empty(N, device=DEV)
+        if form == ops.BMU_EXACT:
+            ops.row_inv_norm(xd, inx); ops.row_inv_norm(Wd, inw)
+            ops.bmu_cosine_fwd(xd, Wd, inx, inw, dist, bmu)
+        elif form == ops.BMU_X3:
+            ops.bmu_cosine_x3_fwd(xd, Wd, dist, bmu, inx, inw)
+        else:
+            xp, wp = ops.bmu_planes_alloc(M, K, DEV), ops.bmu_planes_alloc(N, K, DEV)
+            ops.bmu_planes_from(xd, xp); ops.bmu_planes_from(Wd, wp)
+            ops.bmu_cosine_x3_planes_fwd(xd, Wd, xp, wp, dist, bmu, inx, inw)
+        for name, got, own in (("dist", s.dist, dist), ("bmu", s.bmu, bmu), ("inx", s.inx, inx), ("inw", s.inw, inw)):
+            assert torch.equal(got, own), (engine, name)
+        # 2. against fp64: 1e-5 for the three-product forms (test_bmu_cosine_x3_rerank), 2e-6 for the exact one (nt.slab)
+        assert float((dist.cpu().double() - c["d64"]).abs().max()) < (2e-6 if form == ops.BMU_EXACT else 1e-5)
+        # 3.
         assert torch.equal(bmu.cpu(), dist.cpu().argmin(1))
     elif row.op == R.ATTENTION_BWD:
         Nt, H, hd, B = M, N, K, 2

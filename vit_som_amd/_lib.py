@@ -98,6 +98,7 @@ SIGNATURES = {
     "vsom_adamw_step_planes": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, C.c_long, C.c_float, C.c_float, C.c_float, C.c_float,
                                          C.c_int, C.c_float, C.c_int, C.c_long, C.c_int, C.c_int, c_fp, C.c_size_t, c_stream]),
     "vsom_bmu_cosine_x3_planes_supported": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "vsom_bmu_cosine_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_long, C.c_int]),
     "vsom_bmu_cosine_x3_planes_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "vsom_bmu_cosine_x3_planes_dots": (C.c_int, [c_fp, c_fp, C.c_int, C.c_int, C.c_int, c_fp, C.c_size_t, c_stream]),
     "vsom_bmu_cosine_x3_planes_finalize": (C.c_int, [c_fp, C.c_long, c_fp, c_fp, c_fp, c_fp, C.c_size_t, c_fp, c_fp, c_fp, c_fp,

@@ -212,6 +212,7 @@ __global__ __launch_bounds__(512) void bmu_norms_wide_kernel(const float* __rest
 
 // One workgroup per sample row: distances, approximate first minimum, exact re-rank of the candidates.
 constexpr int BMU_KPT = 8;           // prototypes per thread held in registers (K <= 2048)
+constexpr int BMU_X3_MAX_K = 256 * BMU_KPT;
 // V4: K % 4 == 0 and 16-byte aligned slabs / dist -- a thread owns two quads of consecutive columns (16-byte accesses,
 // two slabs of loads in flight) instead of eight columns 256 apart (4-byte accesses behind a bounds branch each)
 template <bool V4>
@@ -610,38 +611,96 @@ __global__ __launch_bounds__(512) void bmu_x3_planes_kernel(const BmuPlP g) {
         }
 }
 
-// tile configuration: 256 x 192 with 8 waves (one workgroup per CU) for batches of >= 192 rows, else 128 x 128 / 4 waves
+// ---- the launch plan of the pass ("Which kernel runs": Cosine BMU pass) -- the rule, written once
+static size_t planes_image_bytes(int R, int L) { return (size_t)2 * cdiv(L, 32) * cdiv(R, 32) * 2048; }
+static bool planes_image_fits(int R, int L) { return planes_image_bytes(R, L) < 0x80000000UL; }     // one buffer resource: below 2 GB
+// three-product tile: 256 x 192 with 8 waves (one workgroup per CU) for batches of >= 192 rows, else 128 x 128 / 4 waves
 static bool bmu_x3_big(int B) { return B >= 192; }
-static int bmu_x3_tiles(int B, int K) { return bmu_x3_big(B) ? cdiv(B, 256) * cdiv(K, 192) : cdiv(B, 128) * cdiv(K, 128); }
-static int bmu_x3_splits(int B, int K, int L) {
-    const int tiles = bmu_x3_tiles(B, K), ktiles = cdiv(L, 32);
-    int s = (bmu_x3_big(B) ? 256 : 512) / tiles;     // one full round of resident workgroups
-    if (s > ktiles) s = ktiles;
-    if (s > 64) s = 64;
-    if (s < 1) s = 1;
-    const int per = cdiv(ktiles, s);
-    return cdiv(ktiles, per);
+
+// `form` at (B, K, L): its tile, grid and workspace -- whether or not bmu_plan would choose it
+static BmuPlan bmu_form_plan(int form, int B, int K, int L) {
+    BmuPlan p = {};
+    p.form = form;
+    const int ktiles = cdiv(L, 32);
+    int s;
+    if (form == VSOM_BMU_EXACT) {       // launch_gemm's f32 SLAB kernel; its tile count depends on neither alignment nor GEMM mode
+        p.tile_m = 128; p.tile_n = 64; p.threads = 256;
+        p.tiles = gemm_plan(true, true, EPI_SLAB, B, K, L, true, VSOM_GEMM_F32, 0, 1).tiles;
+        s = choose_splits(p.tiles, ktiles, 32, true);
+    } else {
+        const bool big = bmu_x3_big(B);
+        p.tile_m = big ? 256 : 128; p.tile_n = big ? 192 : 128; p.threads = big ? 512 : 256;
+        p.tiles = cdiv(B, p.tile_m) * cdiv(K, p.tile_n);
+        s = (big ? 256 : 512) / p.tiles;                 // one full round of resident workgroups
+        if (s > ktiles) s = ktiles;
+        if (s > 64) s = 64;
+        if (s < 1) s = 1;
+    }
+    p.ktiles_per_split = cdiv(ktiles, s);
+    p.splits = cdiv(ktiles, p.ktiles_per_split);
+    // slabs [splits][B * K]; the in-loop form adds its squared-norm partials [splits][B + K]; both three-product forms 4 spare floats
+    const size_t per_split = (size_t)B * K + (form == VSOM_BMU_X3 ? (size_t)B + K : 0);
+    p.ws_bytes = ((size_t)p.splits * per_split + (form == VSOM_BMU_EXACT ? 0 : 4)) * sizeof(float);
+    return p;
+}
+
+BmuPlan bmu_plan(int B, int K, int L, long ldx, bool aligned, int mode, bool planes) {
+    int x3 = VSOM_OK;
+    if (K > BMU_X3_MAX_K) x3 = VSOM_EUNSUPPORTED;                                   // the finalize kernel holds a row in registers
+    else if (L % 4 != 0 || ldx % 4 != 0 || !aligned) x3 = VSOM_EALIGN;              // 16-byte loads of whole rows
+    int form = VSOM_BMU_EXACT;
+    if (mode != VSOM_GEMM_F32 && x3 == VSOM_OK)
+        form = (planes && bmu_x3_big(B) && L % 8 == 0 && planes_image_fits(B, L) && planes_image_fits(K, L)) ? VSOM_BMU_X3_PLANES
+                                                                                                              : VSOM_BMU_X3;
+    BmuPlan p = bmu_form_plan(form, B, K, L);
+    p.x3_status = x3;
+    return p;
+}
+// What the entry points of the three-product family run: the GEMM mode chooses between the families, not inside one.
+static BmuPlan x3_plan(int B, int K, int L, long ldx, bool aligned, bool planes) {
+    return bmu_plan(B, K, L, ldx, aligned, VSOM_GEMM_SPLIT_BF16, planes);
 }
 
 }  // namespace vsom
 
 using namespace vsom;
 
+// stage 2 of both three-product forms: inv_nx / inv_nw from `nparts` squared-norm partials per row (the in-loop form's one
+// per split, or the plane images' one per PL_CHUNK), then the finalize kernel over the plan's slabs
+static int x3_finalize_launch(const BmuPlan& p, const float* slab, const float* xsq, const float* wsq, int nparts, bool wide,
+                              const float* X, long ldx, const float* W, float* dist, int64_t* bmu, float* inv_nx, float* inv_nw,
+                              int* reranked, int B, int K, int L, hipStream_t stream) {
+    if (wide) VSOM_LAUNCH(bmu_norms_wide_kernel, dim3(cdiv(B + K, 64)), dim3(512), 0, stream, xsq, wsq, nparts, B, K, inv_nx, inv_nw);
+    else VSOM_LAUNCH(bmu_norms_kernel, dim3(cdiv(B + K, 256)), dim3(256), 0, stream, xsq, wsq, nparts, B, K, inv_nx, inv_nw);
+    const int rc = hip_status(hipGetLastError(), wide ? "bmu_norms_wide_kernel" : "bmu_norms_kernel");
+    if (rc) return rc;
+    const long slab_stride = (long)B * K;
+    if (K % 4 == 0 && aligned16(slab))
+        VSOM_LAUNCH(bmu_x3_finalize_kernel<true>, dim3(B), dim3(256), 0, stream, slab, slab_stride, p.splits, X, ldx, W, inv_nx,
+                    inv_nw, dist, bmu, K, L, reranked);
+    else
+        VSOM_LAUNCH(bmu_x3_finalize_kernel<false>, dim3(B), dim3(256), 0, stream, slab, slab_stride, p.splits, X, ldx, W, inv_nx,
+                    inv_nw, dist, bmu, K, L, reranked);
+    return launch_status("bmu_x3_finalize_kernel");
+}
+
 extern "C" {
+
+int vsom_bmu_cosine_form(int B, int K, int L, long ldx, int flags) {
+    VSOM_REQUIRE(B > 0 && K > 0 && L > 0, VSOM_EINVAL, "bmu_cosine_form: non-positive shape %d %d %d", B, K, L);
+    return bmu_plan(B, K, L, ldx, flags & 1, gemm_mode(), flags & 2).form;
+}
 
 size_t vsom_bmu_cosine_x3_workspace_bytes(int B, int K, int L) {
     if (B <= 0 || K <= 0 || L <= 0) return 0;
-    const size_t s = (size_t)bmu_x3_splits(B, K, L);
-    return (s * ((size_t)B * K + B + K) + 4) * sizeof(float);
+    return bmu_form_plan(VSOM_BMU_X3, B, K, L).ws_bytes;
 }
 
-static int x3_layout(int B, int K, int L, void* ws, BmuP& g, int& splits, int** counter) {
-    splits = bmu_x3_splits(B, K, L);
+// the in-loop form's workspace: slabs, then the squared-norm partials of X and of W
+static void x3_layout(const BmuPlan& p, int B, int K, void* ws, BmuP& g) {
     float* f = static_cast<float*>(ws);
     g.slab = f; g.slab_stride = (long)B * K;
-    g.xsq = f + (size_t)splits * B * K; g.wsq = g.xsq + (size_t)splits * B;
-    *counter = reinterpret_cast<int*>(g.wsq + (size_t)splits * K);
-    return VSOM_OK;
+    g.xsq = f + (size_t)p.splits * B * K; g.wsq = g.xsq + (size_t)p.splits * B;
 }
 
 /* stage 1: partial dots (three-product bf16 contraction) + partial squared norms into the workspace */
@@ -649,21 +708,19 @@ int vsom_bmu_cosine_x3_dots(const float* X, long ldx, const float* W, int B, int
                             vsom_stream_t stream) {
     VSOM_REQUIRE(X && W, VSOM_EINVAL, "bmu_cosine_x3_dots: null pointer");
     VSOM_REQUIRE(B > 0 && K > 0 && L > 0 && ldx >= L, VSOM_EINVAL, "bmu_cosine_x3_dots: bad shape B=%d K=%d L=%d ldx=%ld", B, K, L, ldx);
-    VSOM_REQUIRE(K <= 256 * BMU_KPT, VSOM_EUNSUPPORTED, "bmu_cosine_x3: more than %d prototypes", 256 * BMU_KPT);
-    VSOM_REQUIRE(L % 4 == 0 && ldx % 4 == 0 && aligned16(X) && aligned16(W), VSOM_EALIGN,
-                 "bmu_cosine_x3: rows must be 16-byte aligned (L, ldx multiples of 4)");
-    VSOM_REQUIRE(ws && ws_bytes >= vsom_bmu_cosine_x3_workspace_bytes(B, K, L) && aligned16(ws), VSOM_EWORKSPACE,
-                 "bmu_cosine_x3: workspace too small or misaligned");
+    const BmuPlan p = x3_plan(B, K, L, ldx, aligned16(X) && aligned16(W), false);
+    VSOM_REQUIRE(p.x3_status != VSOM_EUNSUPPORTED, VSOM_EUNSUPPORTED, "bmu_cosine_x3: more than %d prototypes", BMU_X3_MAX_K);
+    VSOM_REQUIRE(p.x3_status == VSOM_OK, VSOM_EALIGN, "bmu_cosine_x3: rows must be 16-byte aligned (L, ldx multiples of 4)");
+    VSOM_REQUIRE(ws && ws_bytes >= p.ws_bytes && aligned16(ws), VSOM_EWORKSPACE, "bmu_cosine_x3: workspace too small or misaligned");
     const long xb = ((long)(B - 1) * ldx + L) * 4, wb = (long)K * L * 4;
     VSOM_REQUIRE(xb < 0xFFFF0000L && wb < 0xFFFF0000L, VSOM_EUNSUPPORTED, "bmu_cosine_x3: operand larger than 4 GB");
     BmuP g = {};
-    int splits; int* counter;
-    x3_layout(B, K, L, ws, g, splits, &counter);
+    x3_layout(p, B, K, ws, g);
     g.X = X; g.ldx = ldx; g.W = W; g.B = B; g.K = K; g.L = L;
-    g.ktiles_per_split = cdiv(cdiv(L, 32), splits);
+    g.ktiles_per_split = p.ktiles_per_split;
     g.x_bytes = (unsigned)xb; g.w_bytes = (unsigned)wb;
-    if (bmu_x3_big(B)) VSOM_LAUNCH((bmu_x3_kernel<2, 3, 4, 2>), dim3(bmu_x3_tiles(B, K) * splits), dim3(512), 0, stream, g);
-    else VSOM_LAUNCH((bmu_x3_kernel<2, 2, 2, 2>), dim3(bmu_x3_tiles(B, K) * splits), dim3(256), 0, stream, g);
+    if (p.tile_m == 256) VSOM_LAUNCH((bmu_x3_kernel<2, 3, 4, 2>), dim3(p.tiles * p.splits), dim3(p.threads), 0, stream, g);
+    else VSOM_LAUNCH((bmu_x3_kernel<2, 2, 2, 2>), dim3(p.tiles * p.splits), dim3(p.threads), 0, stream, g);
     return launch_status("bmu_x3_kernel");
 }
 
@@ -673,27 +730,16 @@ int vsom_bmu_cosine_x3_finalize(const float* X, long ldx, const float* W, const 
                                 int64_t* bmu, float* inv_nx, float* inv_nw, int* reranked, int B, int K, int L,
                                 vsom_stream_t stream) {
     VSOM_REQUIRE(X && W && bmu && inv_nx && inv_nw, VSOM_EINVAL, "bmu_cosine_x3_finalize: null pointer");
-    VSOM_REQUIRE(B > 0 && K > 0 && K <= 256 * BMU_KPT && L > 0 && L % 4 == 0 && ldx % 4 == 0, VSOM_EINVAL, "bmu_cosine_x3_finalize: bad shape");
-    VSOM_REQUIRE(ws && ws_bytes >= vsom_bmu_cosine_x3_workspace_bytes(B, K, L), VSOM_EWORKSPACE, "bmu_cosine_x3_finalize: workspace too small");
+    VSOM_REQUIRE(B > 0 && K > 0 && L > 0, VSOM_EINVAL, "bmu_cosine_x3_finalize: bad shape");
+    const BmuPlan p = x3_plan(B, K, L, ldx, true, false);
+    VSOM_REQUIRE(p.x3_status == VSOM_OK, VSOM_EINVAL, "bmu_cosine_x3_finalize: bad shape");
+    VSOM_REQUIRE(ws && ws_bytes >= p.ws_bytes, VSOM_EWORKSPACE, "bmu_cosine_x3_finalize: workspace too small");
     BmuP g = {};
-    int splits; int* counter;
-    x3_layout(B, K, L, const_cast<void*>(ws), g, splits, &counter);
-    VSOM_LAUNCH(bmu_norms_kernel, dim3(cdiv(B + K, 256)), dim3(256), 0, stream, g.xsq, g.wsq, splits, B, K, inv_nx, inv_nw);
-    int rc = hip_status(hipGetLastError(), "bmu_norms_kernel");
-    if (rc) return rc;
-    const bool v4 = K % 4 == 0 && aligned16(g.slab) && g.slab_stride % 4 == 0;
-    if (v4)
-        VSOM_LAUNCH(bmu_x3_finalize_kernel<true>, dim3(B), dim3(256), 0, stream, g.slab, g.slab_stride, splits, X, ldx, W, inv_nx,
-                           inv_nw, dist, bmu, K, L, reranked);
-    else
-    VSOM_LAUNCH(bmu_x3_finalize_kernel<false>, dim3(B), dim3(256), 0, stream, g.slab, g.slab_stride, splits, X, ldx, W, inv_nx,
-                       inv_nw, dist, bmu, K, L, reranked);
-    return launch_status("bmu_x3_finalize_kernel");
+    x3_layout(p, B, K, const_cast<void*>(ws), g);
+    return x3_finalize_launch(p, g.slab, g.xsq, g.wsq, p.splits, false, X, ldx, W, dist, bmu, inv_nx, inv_nw, reranked, B, K, L, stream);
 }
 
 /* ---------------------------------------------------------------- pre-split plane images (see planes_kernel above) */
-static size_t planes_image_bytes(int R, int L) { return (size_t)2 * cdiv(L, 32) * cdiv(R, 32) * 2048; }
-
 size_t vsom_bmu_planes_bytes(int R, int L) {
     if (R <= 0 || L <= 0) return 0;
     return planes_image_bytes(R, L) + (((size_t)cdiv(L, PL_CHUNK) * R * sizeof(float) + 15) & ~(size_t)15);
@@ -703,7 +749,7 @@ static int planes_params(PlanesP& q, int R, int L, void* planes, size_t planes_b
     VSOM_REQUIRE(R > 0 && L > 0 && L % 8 == 0, VSOM_EINVAL, "%s: bad shape R=%d L=%d (L must be a multiple of 8)", who, R, L);
     VSOM_REQUIRE(planes && aligned16(planes) && planes_bytes >= vsom_bmu_planes_bytes(R, L), VSOM_EWORKSPACE,
                  "%s: plane buffer too small or misaligned", who);
-    VSOM_REQUIRE(planes_image_bytes(R, L) < 0x80000000UL, VSOM_EUNSUPPORTED, "%s: image of 2 GB or more", who);
+    VSOM_REQUIRE(planes_image_fits(R, L), VSOM_EUNSUPPORTED, "%s: image of 2 GB or more", who);
     q.R = R; q.L = L; q.nrb = cdiv(R, 32); q.nst = 2 * cdiv(L, 32);
     q.img = static_cast<uint4*>(planes);
     q.sq = reinterpret_cast<float*>(static_cast<char*>(planes) + planes_image_bytes(R, L));
@@ -744,14 +790,15 @@ int vsom_adamw_step_planes(float* p, const float* g, float* m, float* v, const f
     return launch_status("planes_kernel<adamw>");
 }
 
+/* independent of the GEMM mode: the planes form's own entry points run in every mode */
 int vsom_bmu_cosine_x3_planes_supported(int B, int K, int L) {
-    return B > 0 && K > 0 && L > 0 && bmu_x3_big(B) && L % 8 == 0 && K <= 256 * BMU_KPT && planes_image_bytes(K, L) < 0x80000000UL &&
-           planes_image_bytes(B, L) < 0x80000000UL;
+    return B > 0 && K > 0 && L > 0 && x3_plan(B, K, L, L, true, true).form == VSOM_BMU_X3_PLANES;
 }
 
 size_t vsom_bmu_cosine_x3_planes_workspace_bytes(int B, int K, int L) {
-    if (!vsom_bmu_cosine_x3_planes_supported(B, K, L)) return 0;
-    return ((size_t)bmu_x3_splits(B, K, L) * B * K + 4) * sizeof(float);
+    if (B <= 0 || K <= 0 || L <= 0) return 0;
+    const BmuPlan p = x3_plan(B, K, L, L, true, true);
+    return p.form == VSOM_BMU_X3_PLANES ? p.ws_bytes : 0;
 }
 
 /* stage 1 on pre-split operands: partial dots into the workspace's slabs (bit-identical to vsom_bmu_cosine_x3_dots') */
@@ -760,20 +807,20 @@ int vsom_bmu_cosine_x3_planes_dots(const void* xplanes, const void* wplanes, int
     VSOM_REQUIRE(xplanes && wplanes && aligned16(xplanes) && aligned16(wplanes), VSOM_EINVAL, "bmu_cosine_x3_planes_dots: null or misaligned planes");
     VSOM_REQUIRE(vsom_bmu_cosine_x3_planes_supported(B, K, L), VSOM_EUNSUPPORTED,
                  "bmu_cosine_x3_planes_dots: shape B=%d K=%d L=%d not covered (B >= 192, L %% 8 == 0)", B, K, L);
-    VSOM_REQUIRE(ws && aligned16(ws) && ws_bytes >= vsom_bmu_cosine_x3_planes_workspace_bytes(B, K, L), VSOM_EWORKSPACE,
+    const BmuPlan p = x3_plan(B, K, L, L, true, true);
+    VSOM_REQUIRE(ws && aligned16(ws) && ws_bytes >= p.ws_bytes, VSOM_EWORKSPACE,
                  "bmu_cosine_x3_planes_dots: workspace too small or misaligned");
     static const int attr_rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(bmu_x3_planes_kernel),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, PL_LDS);
     VSOM_REQUIRE(attr_rc == 0, VSOM_EUNSUPPORTED, "bmu_cosine_x3_planes_dots: cannot reserve %d bytes of LDS", PL_LDS);
-    const int splits = bmu_x3_splits(B, K, L);
     BmuPlP g = {};
     g.ximg = xplanes; g.wimg = wplanes;
     g.ximg_bytes = (unsigned)planes_image_bytes(B, L); g.wimg_bytes = (unsigned)planes_image_bytes(K, L);
     g.nrb_x = cdiv(B, 32); g.nrb_w = cdiv(K, 32);
     g.B = B; g.K = K; g.nst = 2 * cdiv(L, 32);
-    g.stages_per_split = 2 * cdiv(cdiv(L, 32), splits);
+    g.stages_per_split = 2 * p.ktiles_per_split;
     g.slab = static_cast<float*>(ws); g.slab_stride = (long)B * K;
-    VSOM_LAUNCH(bmu_x3_planes_kernel, dim3(bmu_x3_tiles(B, K) * splits), dim3(512), PL_LDS, stream, g);
+    VSOM_LAUNCH(bmu_x3_planes_kernel, dim3(p.tiles * p.splits), dim3(p.threads), PL_LDS, stream, g);
     return launch_status("bmu_x3_planes_kernel");
 }
 
@@ -782,24 +829,14 @@ int vsom_bmu_cosine_x3_planes_finalize(const float* X, long ldx, const float* W,
                                        const void* ws, size_t ws_bytes, float* dist, int64_t* bmu, float* inv_nx, float* inv_nw,
                                        int* reranked, int B, int K, int L, vsom_stream_t stream) {
     VSOM_REQUIRE(X && W && xplanes && wplanes && bmu && inv_nx && inv_nw, VSOM_EINVAL, "bmu_cosine_x3_planes_finalize: null pointer");
-    VSOM_REQUIRE(vsom_bmu_cosine_x3_planes_supported(B, K, L) && ldx % 4 == 0 && ldx >= L, VSOM_EINVAL, "bmu_cosine_x3_planes_finalize: bad shape");
-    VSOM_REQUIRE(ws && ws_bytes >= vsom_bmu_cosine_x3_planes_workspace_bytes(B, K, L), VSOM_EWORKSPACE,
-                 "bmu_cosine_x3_planes_finalize: workspace too small");
-    const int splits = bmu_x3_splits(B, K, L);
+    VSOM_REQUIRE(B > 0 && K > 0 && L > 0 && ldx >= L, VSOM_EINVAL, "bmu_cosine_x3_planes_finalize: bad shape");
+    const BmuPlan p = x3_plan(B, K, L, ldx, true, true);
+    VSOM_REQUIRE(p.form == VSOM_BMU_X3_PLANES, VSOM_EINVAL, "bmu_cosine_x3_planes_finalize: bad shape");
+    VSOM_REQUIRE(ws && ws_bytes >= p.ws_bytes, VSOM_EWORKSPACE, "bmu_cosine_x3_planes_finalize: workspace too small");
     const float* xsq = reinterpret_cast<const float*>(static_cast<const char*>(xplanes) + planes_image_bytes(B, L));
     const float* wsq = reinterpret_cast<const float*>(static_cast<const char*>(wplanes) + planes_image_bytes(K, L));
-    VSOM_LAUNCH(bmu_norms_wide_kernel, dim3(cdiv(B + K, 64)), dim3(512), 0, stream, xsq, wsq, cdiv(L, PL_CHUNK), B, K, inv_nx, inv_nw);
-    int rc = hip_status(hipGetLastError(), "bmu_norms_wide_kernel");
-    if (rc) return rc;
-    const float* slab = static_cast<const float*>(ws);
-    const long slab_stride = (long)B * K;
-    if (K % 4 == 0 && aligned16(slab))
-        VSOM_LAUNCH(bmu_x3_finalize_kernel<true>, dim3(B), dim3(256), 0, stream, slab, slab_stride, splits, X, ldx, W, inv_nx,
-                    inv_nw, dist, bmu, K, L, reranked);
-    else
-        VSOM_LAUNCH(bmu_x3_finalize_kernel<false>, dim3(B), dim3(256), 0, stream, slab, slab_stride, splits, X, ldx, W, inv_nx,
-                    inv_nw, dist, bmu, K, L, reranked);
-    return launch_status("bmu_x3_finalize_kernel");
+    return x3_finalize_launch(p, static_cast<const float*>(ws), xsq, wsq, cdiv(L, PL_CHUNK), true, X, ldx, W, dist, bmu, inv_nx,
+                              inv_nw, reranked, B, K, L, stream);
 }
 
 }  // extern "C"

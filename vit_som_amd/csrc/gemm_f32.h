@@ -632,7 +632,18 @@ int reduce_slabs2_internal(const float* slabs, long stride, int nslabs, float* o
                            long n2, hipStream_t stream);
 int sum_partials(const float* part, int n, float* out, hipStream_t stream);
 int choose_splits(int tiles, int ktiles, int max_splits, bool prefer_xcd_multiple = false);
-int bmu_splits(int B, int K, int L);                          // som.hip
+// The cosine BMU pass (bmu_x3.hip; DESIGN.md, "Which kernel runs": Cosine BMU pass): which of its three forms runs, and that
+// form's launch.  Every entry point, size query and support query of the pass reads this and computes none of it again.
+struct BmuPlan {
+    int form;                   // VSOM_BMU_EXACT (the f32 SLAB GEMM of launch_gemm), VSOM_BMU_X3 or VSOM_BMU_X3_PLANES
+    int x3_status;              // what an entry point of the three-product family answers: VSOM_OK, or why it does not apply
+    int tile_m, tile_n, threads;
+    int tiles, splits, ktiles_per_split;      // grid = tiles * splits; the split count is canonical
+    size_t ws_bytes;
+};
+// Pure: `aligned` = X and W 16-byte aligned, `mode` the GEMM mode (VSOM_GEMM_*), `planes` = plane images can be had.
+// VSOM_GEMM_F32 as the mode asks for the exact form whatever the shape (the euclidean pass shares its contraction).
+BmuPlan bmu_plan(int B, int K, int L, long ldx, bool aligned, int mode, bool planes);
 int attn_bwd_threads(int N);                                  // attention.hip
 int attn_bwd_plan_now(int N, int hd);                         // attention.hip: AttnBwd under the current hook and mode, -1: hd unsupported
 int gemm_grad_products();     // 3 in VSOM_GEMM_SPLIT_BF16_GRAD3 mode (gradient GEMMs on the two-piece split), else 6

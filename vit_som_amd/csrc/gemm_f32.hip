@@ -592,7 +592,15 @@ int vsom_describe_plan(int op, int M, int N, int K, int flags, char* out, size_t
         // (B, K, L): gW[K,L] reduces over the batch, gX[B,L] over the prototypes, the dots [B,K] over L
         case VSOM_PLAN_SOM_BWD_GW: return describe_gemm(false, false, EPI_ROWAXPY, N, K, M, vec, g3, 1, out, out_bytes);
         case VSOM_PLAN_SOM_BWD_GX: return describe_gemm(true, false, EPI_ROWAXPY, M, K, N, vec, g3, 1, out, out_bytes);
-        case VSOM_PLAN_BMU_COSINE_DOTS: return describe_gemm(true, true, EPI_SLAB, M, N, K, vec, 0, bmu_splits(M, N, K), out, out_bytes);
+        case VSOM_PLAN_BMU_COSINE_DOTS:
+        case VSOM_PLAN_BMU_COSINE: {
+            const BmuPlan p = bmu_plan(M, N, K, K, vec, op == VSOM_PLAN_BMU_COSINE ? gemm_mode() : VSOM_GEMM_F32, flags & 2);
+            if (p.form == VSOM_BMU_EXACT) return describe_gemm(true, true, EPI_SLAB, M, N, K, vec, 0, p.splits, out, out_bytes);
+            n = snprintf(out, out_bytes, "engine=%s tile=%dx%d planes=2 fast=1 threads=%d splits=%d workgroups=%d",
+                         p.form == VSOM_BMU_X3_PLANES ? "bmu_x3_planes" : "bmu_x3", p.tile_m, p.tile_n, p.threads, p.splits,
+                         p.tiles * p.splits);
+            break;
+        }
         case VSOM_PLAN_LINEAR_BWD_WEIGHT: {
             const TnPlan p = bwd_weight_plan(M, N, K, gemm_mode(), g_wgrad_tiles.load(std::memory_order_relaxed));
             if (!bwd_weight_tiled(p, gemm_mode(), vec, M, 0))

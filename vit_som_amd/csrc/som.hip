@@ -122,10 +122,8 @@ __global__ __launch_bounds__(256) void bmu_finalize_kernel(const float* __restri
     }
 }
 
-// reduction splits of the X.W^T launch (vsom_bmu_cosine_dots); its tile count depends on neither alignment nor GEMM mode
-int bmu_splits(int B, int K, int L) {
-    return choose_splits(gemm_plan(true, true, EPI_SLAB, B, K, L, true, gemm_mode(), 0, 1).tiles, cdiv(L, 32), 32, true);
-}
+// the plan of the exact X.W^T launch (vsom_bmu_cosine_dots): reduction splits and workspace come from the BMU pass's one plan
+static BmuPlan bmu_exact_plan(int B, int K, int L) { return bmu_plan(B, K, L, L, true, VSOM_GEMM_F32, false); }
 
 // ------------------------------------------------------------------ neighbourhood / loss / coefficients
 // block per sample row i
@@ -279,7 +277,7 @@ int vsom_row_sqnorm(const float* X, long ldx, int rows, int cols, float* sqnorm,
 
 size_t vsom_bmu_cosine_workspace_bytes(int B, int K, int L) {
     if (B <= 0 || K <= 0 || L <= 0) return 0;
-    return (size_t)bmu_splits(B, K, L) * (size_t)B * K * sizeof(float);
+    return bmu_exact_plan(B, K, L).ws_bytes;
 }
 
 int vsom_bmu_cosine_dots(const float* X, long ldx, const float* W, int B, int K, int L, void* ws, size_t ws_bytes,
@@ -292,7 +290,7 @@ int vsom_bmu_cosine_dots(const float* X, long ldx, const float* W, int B, int K,
     g.A = X; g.lda = ldx; g.B = W; g.ldb = L;
     g.M = B; g.N = K; g.K = L;
     g.slab = static_cast<float*>(ws); g.slab_stride = (long)B * K;
-    return launch_gemm(true, true, EPI_SLAB, g, bmu_splits(B, K, L), stream);
+    return launch_gemm(true, true, EPI_SLAB, g, bmu_exact_plan(B, K, L).splits, stream);
 }
 
 int vsom_bmu_cosine_finalize(const void* ws, size_t ws_bytes, const float* inv_nx, const float* inv_nw, float* dist,
@@ -302,7 +300,7 @@ int vsom_bmu_cosine_finalize(const void* ws, size_t ws_bytes, const float* inv_n
     VSOM_REQUIRE(ws && ws_bytes >= vsom_bmu_cosine_workspace_bytes(B, K, L), VSOM_EWORKSPACE,
                  "bmu_cosine_finalize: workspace too small");
     VSOM_LAUNCH(bmu_finalize_kernel, dim3(B), dim3(256), 0, stream, (const float*)ws, (long)B * K,
-                       bmu_splits(B, K, L), inv_nx, inv_nw, dist, bmu, K, 0);
+                       bmu_exact_plan(B, K, L).splits, inv_nx, inv_nw, dist, bmu, K, 0);
     return launch_status("bmu_finalize_kernel");
 }
 
@@ -312,7 +310,7 @@ int vsom_bmu_euclid_fwd(const float* X, long ldx, const float* W, const float* s
     int rc = vsom_bmu_cosine_dots(X, ldx, W, B, K, L, ws, ws_bytes, stream);      // the same X.W^T contraction
     if (rc) return rc;
     VSOM_LAUNCH(bmu_finalize_kernel, dim3(B), dim3(256), 0, stream, (const float*)ws, (long)B * K,
-                       bmu_splits(B, K, L), sq_x, sq_w, dist, bmu, K, 1);
+                       bmu_exact_plan(B, K, L).splits, sq_x, sq_w, dist, bmu, K, 1);
     return launch_status("bmu_finalize_kernel");
 }
 

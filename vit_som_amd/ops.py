@@ -435,11 +435,21 @@ def row_sqnorm(x, out):
     return out
 
 
-def bmu_euclid_fwd(x, W, sq_x, sq_w, dist: Optional[torch.Tensor], bmu):
+def _bmu_args(x, W, dist, bmu, inv_nx=None, inv_nw=None, reranked=None):
+    """The argument checks every BMU wrapper shares -> (B, K, L).  inv_nx / inv_nw / reranked: what the three-product forms
+    write beside dist and bmu."""
     B, L = x.shape
     K = W.shape[0]
     _f32(x, "x"); _f32(W, "W")
     assert W.is_contiguous() and W.shape[1] == L and bmu.dtype == torch.int64 and (dist is None or dist.is_contiguous())
+    if inv_nx is not None:
+        _f32(inv_nx, "inv_nx"); _f32(inv_nw, "inv_nw")
+        assert reranked is None or (reranked.dtype == torch.int32 and reranked.is_cuda)
+    return B, K, L
+
+
+def bmu_euclid_fwd(x, W, sq_x, sq_w, dist: Optional[torch.Tensor], bmu):
+    B, K, L = _bmu_args(x, W, dist, bmu)
     nbytes = lib.vsom_bmu_cosine_workspace_bytes(B, K, L)
     ws = scratch(nbytes, x.device)
     check(lib.vsom_bmu_euclid_fwd(ptr(x), _rows(x), ptr(W), ptr(sq_x), ptr(sq_w), ptr(dist), ptr(bmu), B, K, L, ptr(ws),
@@ -448,10 +458,7 @@ def bmu_euclid_fwd(x, W, sq_x, sq_w, dist: Optional[torch.Tensor], bmu):
 
 
 def bmu_manhattan_fwd(x, W, dist: Optional[torch.Tensor], bmu):
-    B, L = x.shape
-    K = W.shape[0]
-    _f32(x, "x"); _f32(W, "W")
-    assert W.is_contiguous() and W.shape[1] == L and bmu.dtype == torch.int64 and (dist is None or dist.is_contiguous())
+    B, K, L = _bmu_args(x, W, dist, bmu)
     ws = scratch(lib.vsom_bmu_manhattan_workspace_bytes(B, K, L), x.device)
     check(lib.vsom_bmu_manhattan_fwd(ptr(x), _rows(x), ptr(W), ptr(dist), ptr(bmu), B, K, L, ptr(ws), ws.numel(), stream()),
           "vsom_bmu_manhattan_fwd")
@@ -466,14 +473,15 @@ def som_bwd_manhattan(x, W, coef, gW, gX, accumulate_gx=True):
                                      B, K, L, stream()), "vsom_som_bwd_manhattan")
 
 
+# The cosine BMU pass has three forms (include/vitsom_hip.h: VSOM_BMU_*); vsom_bmu_cosine_form names the one the library's
+# launch plan chooses for a shape (SOMLayer._bmu_form asks), the three wrappers below run one each.
+BMU_EXACT, BMU_X3, BMU_X3_PLANES = 0, 1, 2
+
+
 def bmu_cosine_x3_fwd(x, W, dist: Optional[torch.Tensor], bmu, inv_nx, inv_nw, reranked: Optional[torch.Tensor] = None):
     """Cosine BMU pass (norms + three-product bf16 contraction + exact re-rank) -> dist, bmu, inv_nx, inv_nw.
     `reranked`: optional int32 device scalar counting the rows whose minimum had to be re-ranked."""
-    B, L = x.shape
-    K = W.shape[0]
-    _f32(x, "x"); _f32(W, "W"); _f32(inv_nx, "inv_nx"); _f32(inv_nw, "inv_nw")
-    assert W.is_contiguous() and W.shape[1] == L and bmu.dtype == torch.int64 and (dist is None or dist.is_contiguous())
-    assert reranked is None or (reranked.dtype == torch.int32 and reranked.is_cuda)
+    B, K, L = _bmu_args(x, W, dist, bmu, inv_nx, inv_nw, reranked)
     nbytes = lib.vsom_bmu_cosine_x3_workspace_bytes(B, K, L)
     ws = scratch(nbytes, x.device)
     with _timed("bmu_cosine_dots"):
@@ -506,11 +514,7 @@ def bmu_cosine_x3_planes_fwd(x, W, xplanes, wplanes, dist: Optional[torch.Tensor
                              reranked: Optional[torch.Tensor] = None):
     """bmu_cosine_x3_fwd on pre-split operands: `xplanes` / `wplanes` must describe `x` / `W` as they are now (x and W
     themselves feed the exact re-rank)."""
-    B, L = x.shape
-    K = W.shape[0]
-    _f32(x, "x"); _f32(W, "W"); _f32(inv_nx, "inv_nx"); _f32(inv_nw, "inv_nw")
-    assert W.is_contiguous() and W.shape[1] == L and bmu.dtype == torch.int64 and (dist is None or dist.is_contiguous())
-    assert reranked is None or (reranked.dtype == torch.int32 and reranked.is_cuda)
+    B, K, L = _bmu_args(x, W, dist, bmu, inv_nx, inv_nw, reranked)
     nbytes = lib.vsom_bmu_cosine_x3_planes_workspace_bytes(B, K, L)
     if nbytes == 0:
         raise ValueError(f"bmu_cosine_x3_planes_fwd: shape B={B} K={K} L={L} is not covered by the planes form")
@@ -525,10 +529,7 @@ def bmu_cosine_x3_planes_fwd(x, W, xplanes, wplanes, dist: Optional[torch.Tensor
 
 
 def bmu_cosine_fwd(x, W, inv_nx, inv_nw, dist: Optional[torch.Tensor], bmu):
-    B, L = x.shape
-    K = W.shape[0]
-    _f32(x, "x"); _f32(W, "W")
-    assert W.is_contiguous() and W.shape[1] == L and bmu.dtype == torch.int64 and (dist is None or dist.is_contiguous())
+    B, K, L = _bmu_args(x, W, dist, bmu)
     nbytes = lib.vsom_bmu_cosine_workspace_bytes(B, K, L)
     ws = scratch(nbytes, x.device)
     with _timed("bmu_cosine_dots"):

@@ -79,14 +79,12 @@ class FusedAdamW(torch.optim.Optimizer):
         b1, b2 = g0["betas"]
         som = getattr(m, "som_layer", None)
         planes = None
-        if som is not None and som._planes_used and hooks.bmu_planes and hooks.adamw_planes:
-            # the prototypes' plane image for the next BMU pass leaves the same kernel that updates them
+        if som is not None and hooks.adamw_planes and som._planes_used and som._planes_shape_ok(som._planes_rows):
+            # the batch that last took the planes form would take it again: the prototypes' plane image for the next BMU
+            # pass leaves the same kernel that updates them
             name = next((n for n, q in m._named_trainable() if q is som.prototypes), None)
-            W = som.prototypes
-            if name is not None and W.dim() == 2 and W.shape[1] % 8 == 0 and ops.get_gemm_mode() != ops.GEMM_F32:
-                if som._wplanes is None or som._wplanes.device != W.device:
-                    som._wplanes = ops.bmu_planes_alloc(W.shape[0], W.shape[1], W.device)
-                planes = (m.arena.offsets[name][0], W.shape[0], W.shape[1], som._wplanes)
+            if name is not None:
+                planes = (m.arena.offsets[name][0], *som.prototypes.shape, som._w_planes_buffer())
         ops.adamw_step(m.arena.params, m.arena.grads, m.arena.exp_avg, m.arena.exp_avg_sq, m.arena.wd_chunk,
                        float(g0["lr"]), b1, b2, g0["eps"], self._step, grad_scale=1.0 / m.world_size, adamw=self._adamw,
                        planes=planes)

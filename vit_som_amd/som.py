@@ -124,6 +124,7 @@ class SOMLayer(_Base):
         self._wplanes_stamp = None
         self._raw_updates = 0           # updates of the prototypes that bypass torch (raw-pointer kernels)
         self._planes_used = False       # a forward took the planes path: the optimizer keeps the image current
+        self._planes_rows = 0           # ... with this many sample rows
         self._w_ready_ev = None         # the event of _w_planes_async (a dedicated one: its wait comes a whole encoder later)
 
     # ---- plane image of the prototypes ---------------------------------------------------
@@ -135,21 +136,33 @@ class SOMLayer(_Base):
         """Call after changing the prototypes behind torch's back (writes through ``.data`` or a raw pointer)."""
         self._wplanes_stamp = None
 
-    def _planes_shape_ok(self, B: int) -> bool:
-        W = self.prototypes
-        return bool(hooks.bmu_planes and self._dist_mode == ops.DIST_COSINE and W.is_cuda and ops.get_gemm_mode() != ops.GEMM_F32
-                    and ops.bmu_planes_supported(B, W.shape[0], W.shape[1]))
+    def _bmu_form(self, B: int, ldx: Optional[int] = None, aligned: bool = True) -> int:
+        """Which form of the cosine BMU pass runs for B sample rows of stride `ldx` floats (default: dense rows): ops.BMU_EXACT,
+        BMU_X3 or BMU_X3_PLANES.  The rule is the library's launch plan ("Which kernel runs"); this is the one place
+        of the package that asks it."""
+        K, L = self.prototypes.shape
+        return ops.lib.vsom_bmu_cosine_form(B, K, L, L if ldx is None else ldx, int(aligned) | (2 if hooks.bmu_planes else 0))
 
-    def _w_planes(self) -> torch.Tensor:
-        """The prototypes' plane buffer, re-split here if it does not describe them any more."""
+    def _planes_shape_ok(self, B: int) -> bool:
+        """Would a batch of B dense, aligned rows take the planes form?"""
+        return self._dist_mode == ops.DIST_COSINE and self.prototypes.is_cuda and self._bmu_form(B) == ops.BMU_X3_PLANES
+
+    def _w_planes_buffer(self) -> torch.Tensor:
+        """The prototypes' plane buffer, allocated here (and nowhere else) when there is none or it is on another device or of
+        another size.  A new buffer describes nothing yet."""
         W = self.prototypes
         if self._wplanes is None or self._wplanes.device != W.device or self._wplanes.numel() != ops.lib.vsom_bmu_planes_bytes(*W.shape):
             self._wplanes = ops.bmu_planes_alloc(W.shape[0], W.shape[1], W.device)
             self._wplanes_stamp = None
-        if self._wplanes_stamp != self._w_stamp():
-            ops.bmu_planes_from(W.detach(), self._wplanes)
-            self._wplanes_stamp = self._w_stamp()
         return self._wplanes
+
+    def _w_planes(self) -> torch.Tensor:
+        """The prototypes' plane buffer, re-split here if it does not describe them any more."""
+        planes = self._w_planes_buffer()
+        if self._wplanes_stamp != self._w_stamp():
+            ops.bmu_planes_from(self.prototypes.detach(), planes)
+            self._wplanes_stamp = self._w_stamp()
+        return planes
 
     def _w_planes_async(self, side_stream, force: bool):
         """Bring the prototypes' image up to date on `side_stream`, behind everything the launch stream holds so far
@@ -157,15 +170,12 @@ class SOMLayer(_Base):
         or always with `force` (a recorded training step must contain the launch whatever the state it was recorded
         in).  Returns the event the consumer has to wait for, or None when nothing was launched.  The event is the layer's
         own: the consumer waits a whole encoder later, by which time a pooled event could have been recorded again."""
-        W = self.prototypes
-        if self._wplanes is None or self._wplanes.device != W.device or self._wplanes.numel() != ops.lib.vsom_bmu_planes_bytes(*W.shape):
-            self._wplanes = ops.bmu_planes_alloc(W.shape[0], W.shape[1], W.device)
-            self._wplanes_stamp = None
+        planes = self._w_planes_buffer()
         if not force and self._wplanes_stamp == self._w_stamp():
             return None
         Event.pooled().record().wait(side_stream)
         with on_stream(side_stream):
-            ops.bmu_planes_from(W.detach(), self._wplanes)
+            ops.bmu_planes_from(self.prototypes.detach(), planes)
         self._wplanes_stamp = self._w_stamp()
         if self._w_ready_ev is None:
             self._w_ready_ev = Event()
@@ -367,19 +377,18 @@ class SOMLayer(_Base):
     def _distances_into(self, x2d, s: _Acts):
         if self._dist_mode == ops.DIST_COSINE:
             W = self.prototypes
-            if (ops.get_gemm_mode() != ops.GEMM_F32 and W.shape[0] <= 2048 and W.shape[1] % 4 == 0
-                    and x2d.stride(0) % 4 == 0 and x2d.data_ptr() % 16 == 0):
-                # norms + reduced-precision contraction + exact re-rank in one pass over X and W
-                if self._planes_shape_ok(x2d.shape[0]):
-                    # ... on pre-split operands: the prototypes' image is kept by the optimizer, the samples' written here
-                    self._planes_used = True
-                    if getattr(s, "xplanes", None) is None:
-                        s.xplanes = ops.bmu_planes_alloc(x2d.shape[0], x2d.shape[1], x2d.device)
-                    wplanes = self._w_planes()
-                    ops.bmu_planes_from(x2d, s.xplanes)
-                    ops.bmu_cosine_x3_planes_fwd(x2d, W, s.xplanes, wplanes, s.dist, s.bmu, s.inx, s.inw, s.reranked)
-                else:
-                    ops.bmu_cosine_x3_fwd(x2d, W, s.dist, s.bmu, s.inx, s.inw, s.reranked)
+            form = self._bmu_form(x2d.shape[0], x2d.stride(0), x2d.data_ptr() % 16 == 0)
+            if form == ops.BMU_X3_PLANES:
+                # norms + reduced-precision contraction + exact re-rank in one pass over X and W, on pre-split operands: the
+                # prototypes' image is kept by the optimizer, the samples' written here
+                self._planes_used, self._planes_rows = True, x2d.shape[0]
+                if getattr(s, "xplanes", None) is None:
+                    s.xplanes = ops.bmu_planes_alloc(x2d.shape[0], x2d.shape[1], x2d.device)
+                wplanes = self._w_planes()
+                ops.bmu_planes_from(x2d, s.xplanes)
+                ops.bmu_cosine_x3_planes_fwd(x2d, W, s.xplanes, wplanes, s.dist, s.bmu, s.inx, s.inw, s.reranked)
+            elif form == ops.BMU_X3:                # the same pass with the split inside the contraction
+                ops.bmu_cosine_x3_fwd(x2d, W, s.dist, s.bmu, s.inx, s.inw, s.reranked)
             else:
                 ops.row_inv_norm(x2d, s.inx)
                 ops.row_inv_norm(W, s.inw)
