@@ -703,6 +703,78 @@ long vsom_som_batch_update_parts(int K);
 int vsom_som_batch_update(const double* sums, const int64_t* counts, const float* grid_positions, int K, int D, double sigma,
                           int normalize, float* W_out, long ldw, double* part, long n_part, vsom_stream_t stream);
 
+/* ------------------------------------------------------------------ linear probe (linear_probe.hip)
+ * Multinomial logistic regression on frozen features (vit_som_amd/linear_probe.py drives it, DESIGN.md section 4 has the
+ * algorithm; no counterpart in the reference).  The two passes over X of an iteration are vsom_pca_project (the logits) and
+ * vsom_pca_backproject (the gradient); the entries below never touch X.  Parameters are one fp64 vector theta = W [C, D]
+ * row-major, then b [C] when there is an intercept.  2 <= C <= min(256, D) and N >= 2 (the contraction's limits), else
+ * VSOM_EUNSUPPORTED.  Every sum has one fixed order (per-workgroup fp64 partials added in workgroup order), no
+ * floating-point atomics: results are bitwise reproducible.  `part` buffers are scratch, sized by the matching query in
+ * doubles; one that is NULL or too small is refused with VSOM_EWORKSPACE before any launch.
+ *
+ * vsom_probe_fold: B[c][d] (f32, row stride ldb) = A[c][d] * invstd[d], fp64 product rounded once -- the standardisation
+ * folded into the weights (A = W) or into a search direction (A = P).  With W (fp64 [C, D], dense) also pen[3] =
+ * {W.W, W.A, A.A} in fp64: the penalty along A is a quadratic in the step.  W and pen go together; part:
+ * vsom_probe_fold_parts(C, D) doubles, needed with W only. */
+long vsom_probe_fold_parts(int C, int D);
+int vsom_probe_fold(const double* A, const double* invstd, int C, int D, float* B, long ldb, const double* W, double* pen,
+                    double* part, long n_part, vsom_stream_t stream);
+/* Doubles of scratch of vsom_probe_residual and vsom_probe_linesearch at this shape (host arithmetic; 0 outside the limits). */
+long vsom_probe_parts(long N, int C);
+/* vsom_probe_residual: for the logits Z [N, C] (f32, row stride ldz), the intercept b (fp64 [C], nullable = 0) and labels
+ * y (int64 [N]): R[i] (f32, row stride ldr) = softmax(Z[i] + b) - onehot(y[i]), computed in fp64 with the row maximum
+ * subtracted and rounded once; loss[0] (fp64) = sum_i CE_i = sum_i log sum_c exp(z_ic) - z_i,y[i]; gb[c] (fp64) = the column
+ * sums of the ROUNDED R.  pred (int64 [N], nullable): the first index of the row maximum; prob (fp64 [N, C] dense, nullable):
+ * the softmax.  A label outside [0, C) is counted in status[0] (int32, the caller zeroes it) and never used as an index:
+ * its row of R is zero and it adds nothing to loss and gb (pred and prob are written all the same). */
+int vsom_probe_residual(const float* Z, long ldz, long N, int C, const double* b, const int64_t* y, float* R, long ldr, double* loss,
+                        double* gb, int64_t* pred, double* prob, int* status, double* part, long n_part, vsom_stream_t stream);
+/* vsom_probe_linesearch: phi[j] (fp64, j < nsteps <= 16) = sum_i CE(Z[i] + a_j Zp[i] + b + a_j pb, y[i]) with
+ * a_j = alpha0[0] * 2^-j (alpha0 on the device), every logit fma(a_j, Zp, Z) + fma(a_j, pb, b) in fp64: the whole ladder in
+ * one launch, no pass over X.  Z and Zp share the row stride ldz; b and pb go together (nullable).  Rows whose label is
+ * outside [0, C) add nothing. */
+int vsom_probe_linesearch(const float* Z, const float* Zp, long ldz, long N, int C, const double* b, const double* pb,
+                          const int64_t* y, const double* alpha0, int nsteps, double* phi, double* part, long n_part,
+                          vsom_stream_t stream);
+/* vsom_probe_step: the Armijo choice, made on the device, and the move.  F(a) = phi(a) / N + lam / 2 (pen[0] + 2 a pen[1] +
+ * a^2 pen[2]), F(0) likewise from f0[0] (the summed CE at Z); the largest a_j = alpha0[0] 2^-j with
+ * F(a_j) <= F(0) + c1 a_j gtp[0] is alpha.  Then Z += alpha Zp (fp64 fma, rounded once), theta += alpha p, s_new = alpha p
+ * (n elements each).  rec[12 .. 15] = {alpha, status, F(alpha), j}; status 1: no step of the ladder passes, 2: gtp >= 0 --
+ * alpha = 0, Z and theta stay, s_new = 0.  phi, alpha0, f0, pen, gtp, rec: fp64 on the device; rec may be the state record
+ * of the L-BFGS pieces (alpha0 = rec, gtp = rec + 1). */
+int vsom_probe_step(const double* phi, int nsteps, const double* alpha0, const double* f0, const double* pen, const double* gtp,
+                    double lam, double c1, float* Z, const float* Zp, long ldz, long N, int C, double* theta, const double* p,
+                    double* s_new, long n, double* rec, vsom_stream_t stream);
+/* vsom_probe_gradient: g[c D + d] = Zt[c][d] invstd[d] / N + lam theta[c D + d] from Zt = R^T (X - mean) (f32 [C, D], row
+ * stride ldz), and with intercept != 0 g[C D + c] = gb[c] / N; y_new = g - g_prev (both nullable, together).  fp64. */
+int vsom_probe_gradient(const float* Zt, long ldz, const double* invstd, const double* theta, const double* gb, int C, int D,
+                        int intercept, long N, double lam, const double* g_prev, double* g, double* y_new, vsom_stream_t stream);
+
+/* ------------------------------------------------------------------ L-BFGS pieces (linear_probe.hip)
+ * The limited-memory BFGS direction in dot-product-matrix form, for any smooth objective over fp64 vectors of length n:
+ * the pieces know nothing of the probe.  The caller holds S [m, n] and Y [m, n] (ring slots, dense), the gradient g, the
+ * newest pair s_new = x_k+1 - x_k, y_new = g_k+1 - g_k, and `state`: vsom_lbfgs_state_doubles(m) doubles, ZEROED before
+ * the first call.  m <= 16.  state[0 .. 16) is the record
+ *   {alpha0, g.p, g.g, max |g|, pairs held, pairs skipped, pair accepted, its slot, next slot, -, -, -, 4 words for the caller},
+ * then the Gram matrix of the 2 m + 1 vectors (S slots, Y slots, g) and the 2 m + 1 coefficients of the direction.
+ * Per iteration:
+ *   vsom_lbfgs_dots     dots[k (2 m + 3) + v] = (s_new, y_new, g)[k] . v over the vectors (S slots held, Y slots held, g,
+ *                       s_new, y_new), dots[3 (2 m + 3)] = max |g|: ONE pass over the vectors, fp64 per-workgroup partials added
+ *                       in workgroup order.  has_new = 0: no pair (the first iteration, or a restart): g.g and max |g| only.
+ *                       dots: 3 (2 m + 3) + 1 doubles; part: vsom_lbfgs_parts(n, m) doubles.
+ *   vsom_lbfgs_coeff    one small workgroup: the pair is accepted into the next ring slot when s.y > 0 (else counted as skipped),
+ *                       its dot products enter the Gram matrix, and the two-loop recursion runs on coefficients.
+ *                       has_new = 0 empties the history (p = -g).  alpha0 = 1, or min(1, 1 / |g|) without history.
+ *   vsom_lbfgs_combine  an accepted pair is copied into its slot, and p = sum_j coefficient_j vector_j (one fma chain per
+ *                       element: S slots, Y slots, g). */
+long vsom_lbfgs_state_doubles(int m);
+long vsom_lbfgs_parts(long n, int m);
+int vsom_lbfgs_dots(const double* S, const double* Y, const double* g, const double* s_new, const double* y_new, long n, int m,
+                    int has_new, const double* state, double* dots, double* part, long n_part, vsom_stream_t stream);
+int vsom_lbfgs_coeff(const double* dots, int m, int has_new, double* state, vsom_stream_t stream);
+int vsom_lbfgs_combine(double* S, double* Y, const double* g, const double* s_new, const double* y_new, long n, int m,
+                       const double* state, double* p, vsom_stream_t stream);
+
 /* SOMLayer.som_loss(weights, distances) = mean(weights * distances) for ARBITRARY weights (som_layer.py:137-142):
    loss_sum <- sum_ik weights[i,k] dist[i,k]; with coef/row_dot/col_dot given, also the backward coefficients of
    grad_scale * that sum w.r.t. the distances' inputs (what vsom_som_bwd consumes) -- with weights = an upstream

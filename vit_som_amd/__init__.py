@@ -26,4 +26,5 @@ from .evaluation import fit_som_batch  # noqa: F401,E402
 from .kmeans import KMeans, kmeans_plusplus  # noqa: F401,E402
 from .umap import UMAP  # noqa: F401,E402
 from .knn import KNNClassifier  # noqa: F401,E402
+from .linear_probe import LinearProbeReport, LogisticRegression, evaluate_linear_probe  # noqa: F401,E402
 from .data import DeviceDataset, DeviceLoader, DeviceTransform  # noqa: F401,E402

@@ -181,6 +181,22 @@ SIGNATURES = {
     "vsom_som_batch_update_parts": (C.c_long, [C.c_int]),
     "vsom_som_batch_update": (C.c_int, [c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_double, C.c_int, c_fp, C.c_long, c_fp, C.c_long,
                                         c_stream]),
+    "vsom_probe_fold_parts": (C.c_long, [C.c_int, C.c_int]),
+    "vsom_probe_fold": (C.c_int, [c_fp, c_fp, C.c_int, C.c_int, c_fp, C.c_long, c_fp, c_fp, c_fp, C.c_long, c_stream]),
+    "vsom_probe_parts": (C.c_long, [C.c_long, C.c_int]),
+    "vsom_probe_residual": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, c_fp, c_fp, C.c_long, c_fp, c_fp, c_fp, c_fp, c_fp,
+                                      c_fp, C.c_long, c_stream]),
+    "vsom_probe_linesearch": (C.c_int, [c_fp, c_fp, C.c_long, C.c_long, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_int, c_fp, c_fp,
+                                        C.c_long, c_stream]),
+    "vsom_probe_step": (C.c_int, [c_fp, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_double, C.c_double, c_fp, c_fp, C.c_long, C.c_long,
+                                  C.c_int, c_fp, c_fp, c_fp, C.c_long, c_fp, c_stream]),
+    "vsom_probe_gradient": (C.c_int, [c_fp, C.c_long, c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_double, c_fp, c_fp,
+                                      c_fp, c_stream]),
+    "vsom_lbfgs_state_doubles": (C.c_long, [C.c_int]),
+    "vsom_lbfgs_parts": (C.c_long, [C.c_long, C.c_int]),
+    "vsom_lbfgs_dots": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, C.c_long, C.c_int, C.c_int, c_fp, c_fp, c_fp, C.c_long, c_stream]),
+    "vsom_lbfgs_coeff": (C.c_int, [c_fp, C.c_int, C.c_int, c_fp, c_stream]),
+    "vsom_lbfgs_combine": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, C.c_long, C.c_int, c_fp, c_fp, c_stream]),
     "vsom_fill": (C.c_int, [c_fp, C.c_long, C.c_float, c_stream]),
     "vsom_scaled_mul": (C.c_int, [c_fp, c_fp, c_fp, C.c_long, c_fp, C.c_float, c_stream]),
     "vsom_som_weighted_loss": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_float, c_fp, c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_int,

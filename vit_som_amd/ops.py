@@ -1263,6 +1263,162 @@ def som_batch_update(sums, counts, grid_positions, sigma, W_out, normalize=False
     return W_out
 
 
+# ---------------------------------------------------------------- linear probe (linear_probe.py)
+PROBE_MAX_CLASSES = 256                                          # csrc/linear_probe.hip: PROBE_MAX_C
+PROBE_MAX_STEPS = 16                                             # the line search's ladder
+LBFGS_MAX_MEMORY = 16
+# the L-BFGS state record (state[:16]): indices
+LBFGS_ALPHA0, LBFGS_GTP, LBFGS_GG, LBFGS_GMAX, LBFGS_COUNT, LBFGS_SKIPPED, LBFGS_ACCEPTED, LBFGS_SLOT, LBFGS_HEAD = range(9)
+PROBE_STEP, PROBE_LS_STATUS, PROBE_F, PROBE_J = 12, 13, 14, 15
+LBFGS_RECORD = 16
+
+
+def _probe_labels(y, N):
+    assert y.dtype == torch.int64 and y.is_cuda and y.dim() == 1 and y.is_contiguous() and y.numel() == N, \
+        "y must be a contiguous int64 device vector of N"
+    return y
+
+
+def _probe_f64(t, n, name):
+    """An optional contiguous fp64 device tensor of n elements."""
+    if t is not None:
+        assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.numel() == n, \
+            f"{name} must be a contiguous float64 device tensor of {n} elements"
+    return t
+
+
+def probe_parts(N, C) -> int:
+    """Doubles of scratch probe_residual / probe_linesearch take: host arithmetic."""
+    return int(lib.vsom_probe_parts(int(N), int(C)))
+
+
+def probe_fold(A, invstd, B, W=None, pen=None):
+    """B f32 [C, D] = A o invstd (A fp64 [C, D], invstd fp64 [D]; one rounding); with W fp64 [C, D] and pen fp64 [3] also
+    pen = (W.W, W.A, A.A)."""
+    assert A.dim() == 2, "A must be [C, D]"
+    C, D = A.shape
+    _probe_f64(A, C * D, "A"); _probe_f64(invstd, D, "invstd")
+    _f32(B, "B")
+    assert B.dim() == 2 and tuple(B.shape) == (C, D), "B must be [C, D]"
+    assert (W is None) == (pen is None), "W and pen go together"
+    _probe_f64(W, C * D, "W"); _probe_f64(pen, 3, "pen")
+    n_part = int(lib.vsom_probe_fold_parts(C, D)) if W is not None else 0
+    part = scratch(8 * n_part, A.device)
+    check(lib.vsom_probe_fold(ptr(A), ptr(invstd), C, D, ptr(B), _rows(B), ptr(W), ptr(pen), ptr(part), part.numel() // 8, stream()),
+          "vsom_probe_fold")
+    return B
+
+
+def probe_residual(Z, b, y, R, loss, gb, status, pred=None, prob=None):
+    """R f32 [N, C] = softmax(Z + b) - onehot(y), loss fp64 [1] = the summed cross-entropy, gb fp64 [C] = the column sums of
+    R; pred int64 [N] and prob fp64 [N, C] optionally; status int32 [1] (zeroed by the caller) counts labels outside [0, C)."""
+    N, C, ldz = _kmeans_x(Z)
+    _f32(R, "R")
+    assert R.dim() == 2 and tuple(R.shape) == (N, C), "R must be [N, C]"
+    _probe_f64(b, C, "b"); _probe_f64(loss, 1, "loss"); _probe_f64(gb, C, "gb"); _probe_f64(prob, N * C, "prob")
+    assert loss is not None and gb is not None
+    _probe_labels(y, N)
+    if pred is not None:
+        _probe_labels(pred, N)
+    assert status.dtype == torch.int32 and status.is_cuda and status.numel() == 1
+    part = scratch(8 * probe_parts(N, C), Z.device)
+    check(lib.vsom_probe_residual(ptr(Z), ldz, N, C, ptr(b), ptr(y), ptr(R), _rows(R), ptr(loss), ptr(gb), ptr(pred), ptr(prob),
+                                  ptr(status), ptr(part), part.numel() // 8, stream()), "vsom_probe_residual")
+    return R
+
+
+def probe_linesearch(Z, Zp, b, pb, y, alpha0, nsteps, phi):
+    """phi fp64 [nsteps]: the summed cross-entropy at Z + a_j Zp, b + a_j pb for a_j = alpha0 2^-j (alpha0 fp64 [1] on the
+    device), in one launch."""
+    N, C, ldz = _kmeans_x(Z)
+    _f32(Zp, "Zp")
+    assert Zp.dim() == 2 and tuple(Zp.shape) == (N, C) and _rows(Zp) == ldz, "Zp must have the shape and row stride of Z"
+    assert (b is None) == (pb is None), "b and pb go together"
+    _probe_f64(b, C, "b"); _probe_f64(pb, C, "pb"); _probe_f64(alpha0, 1, "alpha0"); _probe_f64(phi, int(nsteps), "phi")
+    assert alpha0 is not None and phi is not None
+    _probe_labels(y, N)
+    part = scratch(8 * probe_parts(N, C), Z.device)
+    check(lib.vsom_probe_linesearch(ptr(Z), ptr(Zp), ldz, N, C, ptr(b), ptr(pb), ptr(y), ptr(alpha0), int(nsteps), ptr(phi), ptr(part),
+                                    part.numel() // 8, stream()), "vsom_probe_linesearch")
+    return phi
+
+
+def probe_step(phi, alpha0, f0, pen, gtp, lam, c1, Z, Zp, theta, p, s_new, rec):
+    """The Armijo choice from the ladder phi, then Z += alpha Zp, theta += alpha p, s_new = alpha p; rec[12:16] =
+    (alpha, status, F(alpha), j).  alpha0, f0, gtp fp64 [1], pen fp64 [3], rec fp64 [>= 16]: all on the device."""
+    N, C, ldz = _kmeans_x(Z)
+    _f32(Zp, "Zp")
+    assert Zp.dim() == 2 and tuple(Zp.shape) == (N, C) and _rows(Zp) == ldz, "Zp must have the shape and row stride of Z"
+    n = theta.numel()
+    for t, k, name in ((phi, phi.numel(), "phi"), (alpha0, 1, "alpha0"), (f0, 1, "f0"), (pen, 3, "pen"), (gtp, 1, "gtp"),
+                       (theta, n, "theta"), (p, n, "p"), (s_new, n, "s_new")):
+        assert t is not None
+        _probe_f64(t, k, name)
+    assert rec.dtype == torch.float64 and rec.is_cuda and rec.is_contiguous() and rec.numel() >= LBFGS_RECORD
+    check(lib.vsom_probe_step(ptr(phi), phi.numel(), ptr(alpha0), ptr(f0), ptr(pen), ptr(gtp), float(lam), float(c1), ptr(Z), ptr(Zp),
+                              ldz, N, C, ptr(theta), ptr(p), ptr(s_new), n, ptr(rec), stream()), "vsom_probe_step")
+    return rec
+
+
+def probe_gradient(Zt, invstd, theta, gb, N, lam, g, g_prev=None, y_new=None):
+    """g fp64 [n] = (Zt o invstd) / N + lam W, then gb / N when theta holds an intercept (n = C D + C); y_new = g - g_prev."""
+    C, D, ldz = _kmeans_x(Zt)
+    n = theta.numel()
+    assert n in (C * D, C * D + C), "theta must hold C D or C D + C elements"
+    intercept = n > C * D
+    _probe_f64(invstd, D, "invstd"); _probe_f64(theta, n, "theta"); _probe_f64(g, n, "g")
+    _probe_f64(gb, C, "gb"); _probe_f64(g_prev, n, "g_prev"); _probe_f64(y_new, n, "y_new")
+    assert (g_prev is None) == (y_new is None), "g_prev and y_new go together"
+    assert gb is not None or not intercept, "an intercept needs gb"
+    check(lib.vsom_probe_gradient(ptr(Zt), ldz, ptr(invstd), ptr(theta), ptr(gb), C, D, int(intercept), int(N), float(lam), ptr(g_prev),
+                                  ptr(g), ptr(y_new), stream()), "vsom_probe_gradient")
+    return g
+
+
+def lbfgs_state(m, device):
+    """A zeroed state of the L-BFGS pieces for memory m: the record, the Gram matrix and the coefficients."""
+    n = int(lib.vsom_lbfgs_state_doubles(int(m)))
+    if n <= 0:
+        raise ValueError(f"L-BFGS memory must be between 1 and {LBFGS_MAX_MEMORY}, got {m}")
+    return torch.zeros(n, dtype=torch.float64, device=device)
+
+
+def _lbfgs_args(S, Y, g, state):
+    assert S.dim() == 2 and S.shape == Y.shape, "S and Y must be [m, n]"
+    m, n = S.shape
+    _probe_f64(S, m * n, "S"); _probe_f64(Y, m * n, "Y"); _probe_f64(g, n, "g")
+    _probe_f64(state, int(lib.vsom_lbfgs_state_doubles(m)), "state")
+    return m, n
+
+
+def lbfgs_dots(S, Y, g, s_new, y_new, state, dots):
+    """dots fp64 [3 (2 m + 3) + 1]: the products of (s_new, y_new, g) with every vector held, and max |g|, in one pass.
+    s_new = y_new = None: there is no new pair."""
+    m, n = _lbfgs_args(S, Y, g, state)
+    assert (s_new is None) == (y_new is None), "s_new and y_new go together"
+    _probe_f64(s_new, n, "s_new"); _probe_f64(y_new, n, "y_new"); _probe_f64(dots, 3 * (2 * m + 3) + 1, "dots")
+    part = scratch(8 * int(lib.vsom_lbfgs_parts(n, m)), g.device)
+    check(lib.vsom_lbfgs_dots(ptr(S), ptr(Y), ptr(g), ptr(s_new), ptr(y_new), n, m, int(s_new is not None), ptr(state), ptr(dots),
+                              ptr(part), part.numel() // 8, stream()), "vsom_lbfgs_dots")
+    return dots
+
+
+def lbfgs_coeff(dots, m, has_new, state):
+    """Takes the new pair in (or skips it), then the two-loop recursion on coefficients; has_new=False empties the history."""
+    _probe_f64(dots, 3 * (2 * m + 3) + 1, "dots"); _probe_f64(state, int(lib.vsom_lbfgs_state_doubles(m)), "state")
+    check(lib.vsom_lbfgs_coeff(ptr(dots), int(m), int(bool(has_new)), ptr(state), stream()), "vsom_lbfgs_coeff")
+    return state
+
+
+def lbfgs_combine(S, Y, g, s_new, y_new, state, p):
+    """p fp64 [n] = the direction; an accepted pair is copied into its ring slot of S and Y first."""
+    m, n = _lbfgs_args(S, Y, g, state)
+    _probe_f64(s_new, n, "s_new"); _probe_f64(y_new, n, "y_new"); _probe_f64(p, n, "p")
+    check(lib.vsom_lbfgs_combine(ptr(S), ptr(Y), ptr(g), ptr(s_new), ptr(y_new), n, m, ptr(state), ptr(p), stream()),
+          "vsom_lbfgs_combine")
+    return p
+
+
 # ---------------------------------------------------------------- data-parallel exchange (RCCL)
 COMM_ID_BYTES = 128
 

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 import yaml
 
-from .evaluation import (evaluate_classification, evaluate_clustering, evaluate_embedding_quality, evaluate_knn,
+from .evaluation import (evaluate_classification, evaluate_clustering, evaluate_embedding_quality, evaluate_knn, evaluate_linear_probe,
                          evaluate_map_quality, evaluate_silhouette, evaluate_latent_spectrum, fit_som_batch,
                          init_som_from_data)
 from .classifier import ViTClassifier
@@ -277,13 +277,16 @@ def main_vit(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, 
 
 
 def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print, map_quality=False,
-         knn_eval=False, embedding_quality=False, silhouette=False, som_init=None, latent_spectrum=False, som_batch_epochs=0):
+         knn_eval=False, embedding_quality=False, silhouette=False, som_init=None, latent_spectrum=False, som_batch_epochs=0,
+         linear_probe=False):
     """train_vit_som.py:27-130; a config with hyperparameters.model_arch == "vit" runs main_vit (train_vit.py) instead.
     model_states_dir defaults to experiments/states/vit_som (experiments/states/vit for the ViT baseline).
     map_quality: after each run's final evaluation also run evaluate_map_quality on the training loader with the model that
     was evaluated, and report quantization_error / topographic_error next to the other metrics (ViT-SOM only).
     knn_eval: likewise run evaluate_knn with that model (bank = the training loader, queries = the test loader) and report
     knn_accuracy.
+    linear_probe: likewise run evaluate_linear_probe with that model (fitted on the training loader's latents, scored on
+    the test loader's) and report linear_probe_accuracy.
     embedding_quality: likewise run evaluate_embedding_quality with that model on the training loader (as map_quality does)
     and report trustworthiness / continuity of the UMAP embedding of its latents.
     silhouette: likewise run evaluate_silhouette with that model on the training loader, the samples clustered by their
@@ -320,6 +323,8 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
         all_metrics.update(quantization_error=[], topographic_error=[])
     if knn_eval:
         all_metrics.update(knn_accuracy=[])
+    if linear_probe:
+        all_metrics.update(linear_probe_accuracy=[])
     if embedding_quality:
         all_metrics.update(trustworthiness=[], continuity=[])
     if silhouette:
@@ -375,6 +380,11 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
             kr = evaluate_knn(evaluated, config, train_loader, test_loader)
             log(f"kNN probe: accuracy {kr.accuracy:.4f} (k={kr.k}, {kr.n_train} training / {kr.n_test} test samples)")
             all_metrics["knn_accuracy"].append(kr.accuracy)
+        if linear_probe:
+            lp = evaluate_linear_probe(evaluated, config, train_loader, test_loader)
+            log(f"Linear probe: accuracy {lp.accuracy:.4f} (train {lp.train_accuracy:.4f}, {lp.n_iter} iterations, "
+                f"{'converged' if lp.converged else 'not converged'}, {lp.n_train} training / {lp.n_test} test samples)")
+            all_metrics["linear_probe_accuracy"].append(lp.accuracy)
         if embedding_quality:
             eq = evaluate_embedding_quality(evaluated, config, train_loader)
             log(f"Embedding quality: trustworthiness {eq.trustworthiness:.4f}, continuity {eq.continuity:.4f} "
@@ -419,6 +429,9 @@ def _parser():
                     help="after each run also report the map's quantization and topographic error on the training set")
     ap.add_argument("--knn-eval", action="store_true",
                     help="after each run also report the k-nearest-neighbour accuracy of the latents (bank: training set, queries: test set)")
+    ap.add_argument("--linear-probe", action="store_true",
+                    help="after each run also report the accuracy of a linear classifier fitted on the frozen latents (fit: training "
+                         "set, scored: test set)")
     ap.add_argument("--embedding-quality", action="store_true",
                     help="after each run also report trustworthiness and continuity of the UMAP embedding of the training set's latents")
     ap.add_argument("--silhouette", action="store_true",
@@ -442,4 +455,4 @@ if __name__ == "__main__":
         loaders = lambda c, r, w: device_loaders(c, r, w, npz=a.data_npz, auto_augment=a.device_randaug)     # noqa: E731
     main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs, make_loaders=loaders, map_quality=a.map_quality,
          knn_eval=a.knn_eval, embedding_quality=a.embedding_quality, silhouette=a.silhouette, som_init=a.som_init,
-         latent_spectrum=a.latent_spectrum, som_batch_epochs=a.som_batch_epochs)
+         latent_spectrum=a.latent_spectrum, som_batch_epochs=a.som_batch_epochs, linear_probe=a.linear_probe)
