@@ -554,6 +554,11 @@ int vsom_umap_transform_layout(const int64_t* knn_idx, const double* weights, co
  * row) pair is summed in one order over D that depends neither on where the rows fall in a tile, nor on Nq, Nb or the
  * chunking, so a bank streamed in any number of pieces, in any order, gives bit for bit the lists of one call over the
  * whole bank.  Nb < k is legal: the unfilled tail stays (+inf, -1).
+ * Bad rows (here, in vsom_umap_knn and in vsom_knn_ranks): a pair with a row that holds a NaN or an infinity, or whose
+ * squared norm (euclidean: squared distance) overflows fp32, has no distance.  It is never listed and never counted: a
+ * bad bank row is in no list, a bad query's list is all (+inf, -1) (vsom_umap_knn: row i at 0, then empty slots), and
+ * every other query's list is bit for bit that of the call with the bad rows deleted; vsom_knn_ranks gives a slot that
+ * names a bad row, and every slot of a bad row, less = tied = -1.  Every listed distance is finite and >= 0.
  * exclude (may be NULL): exclude[i] is a global bank ordinal that query i never receives (leave-one-out when queries
  * and bank are the same set).
  * 1 <= k <= 64 (more: VSOM_EUNSUPPORTED); 1 <= Nq, Nb <= 2^31 - 129; ldq, ldx >= D >= 1; index_base >= 0.  Rows are
@@ -617,8 +622,10 @@ int vsom_silhouette(const float* X, long ldx, long N, int D, int metric, const i
  *   VSOM_KNN_UNIFORM   1;
  *   VSOM_KNN_DISTANCE  sklearn's rule: 1 / d in fp64 from the stored fp32 distance; if any counted neighbour of the
  *                      query is at distance 0 those get 1 and the others 0;
- *   VSOM_KNN_SOFTMAX   exp(-d / temperature) in fp64, temperature > 0 (else VSOM_EINVAL): for cosine the DINO-style
- *                      exp(sim / T) vote up to a common factor, and it cannot overflow.
+ *   VSOM_KNN_SOFTMAX   exp(-(d - d_min) / temperature) in fp64, d_min the query's smallest counted distance and
+ *                      temperature > 0 (else VSOM_EINVAL): the softmax weights up to a common factor per query (for
+ *                      cosine the DINO-style exp(sim / T) vote).  The nearest counted neighbour weighs exactly 1, so
+ *                      the scores neither overflow nor, at euclidean distances of latent width, all underflow to 0.
  * An entry with idx < 0 is skipped; an idx >= n_bank or a label outside [0, n_classes) is skipped and counted in
  * status[0]; a query left without a counted neighbour gets pred = -1 and is counted in status[1] (status int32 [2],
  * zeroed by the caller).  scores [Nq, n_classes] may be NULL.  k <= 64, n_classes <= 1024: else VSOM_EUNSUPPORTED. */

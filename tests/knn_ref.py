@@ -78,13 +78,14 @@ def vote(idx, dist, bank_labels, n_classes, weights, temperature=0.07):
             status[1] += 1
             continue
         any_zero = any(d == 0.0 for _, d in counted)
+        d_min = min(d for _, d in counted)               # softmax: the weights up to the common factor exp(d_min / T)
         for c, d in counted:
             if weights == UNIFORM:
                 w = np.float64(1.0)
             elif weights == DISTANCE:
                 w = np.float64(1.0 if d == 0.0 else 0.0) if any_zero else np.float64(1.0) / d
             else:
-                w = np.exp(-d / T)
+                w = np.exp(-(d - d_min) / T)
             scores[i, c] = scores[i, c] + w
         pred[i] = int(np.argmax(scores[i]))
     return pred, scores, status

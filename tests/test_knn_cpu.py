@@ -66,7 +66,11 @@ def test_vote_rules():
     assert scores[0].tolist() == [1.0, 0.0, 0.0] and pred[0] == 0            # a neighbour at 0 takes the whole vote
     pred, scores, _ = R.vote(idx[:1], dist[:1], labels, 3, R.SOFTMAX, temperature=0.5)
     T = np.float64(np.float32(0.5))
-    assert scores[0, 0] == np.exp(-0.5 / T) and scores[0, 1] == np.exp(-1.0 / T) + np.exp(-2.0 / T) and pred[0] == 0
+    # shifted by the query's smallest valid distance (0.5): the nearest neighbour weighs exactly 1
+    assert scores[0, 0] == 1.0 and scores[0, 1] == np.exp(-0.5 / T) + np.exp(-1.5 / T) and pred[0] == 0
+    far = np.array([[100.0, 100.5, 101.0]], dtype=np.float32)                # exp(-100 / 0.07) underflows; the shift does not
+    pred, scores, _ = R.vote(np.array([[3, 1, 2]]), far, labels, 3, R.SOFTMAX, temperature=0.07)
+    assert scores[0, 2] == 1.0 and 0.0 < scores[0, 1] < 1e-3 and pred[0] == 2
 
 
 # ------------------------------------------------------------------ the C-ABI, host side

@@ -10,6 +10,7 @@ import torch.multiprocessing as mp
 
 import knn_ref as R
 from helpers import golden_params, load_golden
+from knn_checks import lists_against_fp64
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -59,31 +60,7 @@ def test_query_against_fp64(Nq, Nb, D, k, metric):
     idx2, dist2 = _query(Q, X, k, metric, poison=-3)
     torch.cuda.synchronize()
     assert torch.equal(idx, idx2) and torch.equal(dist, dist2)
-    assert ((idx >= 0) & (idx < Nb)).all()
-    assert (dist[:, 1:] >= dist[:, :-1]).all() and torch.isfinite(dist).all()
-    same_d = dist[:, 1:] == dist[:, :-1]
-    assert (~same_d | (idx[:, 1:] > idx[:, :-1])).all()              # equal distances: ascending index
-
-    Qd, Xd = Q.double(), X.double()
-    sqq, sqx = (Qd * Qd).sum(1), (Xd * Xd).sum(1)
-    G = Qd @ Xd.T
-    if metric == "euclidean":
-        ref = (sqq[:, None] + sqx[None, :] - 2.0 * G).clamp_min(0.0)          # squared
-        mine, got = ref.gather(1, idx), dist.double() ** 2
-        assert ((got - mine).abs() <= 1e-5 * (sqq[:, None] + sqx[idx])).all()
-    else:
-        ref = 1.0 - G / (sqq.sqrt()[:, None] * sqx.sqrt()[None, :])
-        mine, got = ref.gather(1, idx), dist.double()
-        assert ((got - mine).abs() <= 1e-5).all()
-    rv, ri = torch.topk(ref, min(k + 1, Nb), largest=False, sorted=True)
-    if metric == "euclidean":
-        sqj = sqx[ri]
-        gap_tol = 1e-5 * (sqq[:, None] + torch.maximum(sqj[:, 1:], sqj[:, :-1]))
-    else:
-        gap_tol = torch.full_like(rv[:, 1:], 1e-5)
-    clear = ((rv[:, 1:] - rv[:, :-1]) > gap_tol).all(dim=1)
-    assert torch.equal(idx[clear], ri[clear, :k])
-    share = float(clear.double().mean())
+    share, _ = lists_against_fp64(idx, dist, Q, X, k, metric)         # knn_checks.py: shared with the edge suite
     print(f"({Nq}, {Nb}, {D}, {k}) {metric}: rows compared index by index {share:.3f}")
     assert share >= (0.25 if (Nq, Nb, D, k) == (130, 257, 1003, 64) else 0.5), share
 

@@ -90,8 +90,16 @@ __device__ __forceinline__ void knn_insert(float& ld, I& li, float cd, I ci, int
 
 // Distance from the dot product and the two squared norms (umap-learn's definitions; cosine of a zero row: 0 against
 // another zero row, 1 against any other row).
+// The bad-row contract: a pair with a row that holds a NaN or an infinity, or whose squared norm overflows fp32, has
+// no distance: NaN, decided BEFORE the clamps (fmaxf(NaN, 0) is 0, which would make such a row everyone's nearest
+// neighbour).  NaN is below, above and equal to nothing, so knn_less never inserts it and the rank pass never counts
+// it; what reads a distance in another way tests d == d.  For finite operands every bit is as without the test.
 __device__ __forceinline__ float knn_distance(float dot, float si, float sj, int metric) {
-    if (metric == VSOM_DIST_EUCLIDEAN) return sqrtf(fmaxf(si + sj - 2.f * dot, 0.f));
+    if (metric == VSOM_DIST_EUCLIDEAN) {
+        const float d2 = si + sj - 2.f * dot;
+        return fabsf(d2) < INFINITY ? sqrtf(fmaxf(d2, 0.f)) : __builtin_nanf("");
+    }
+    if (!(si < INFINITY && sj < INFINITY && fabsf(dot) < INFINITY)) return __builtin_nanf("");
     if (si == 0.f && sj == 0.f) return 0.f;
     if (si == 0.f || sj == 0.f) return 1.f;
     if (dot == si && dot == sj) return 0.f;                          // identical rows
@@ -191,8 +199,10 @@ struct QueryP {
 
 // One workgroup = 128 queries x one chunk of bank columns.  Per 64-column tile: the 128 x 64 block of Q X^T
 // (knn_tile_dots), the distances into LDS, then every wave folds each of its 32 queries' 64 candidates into that
-// query's list (registers: lane j holds entry j).  A column outside the bank, or the one a query excludes, is offered
-// as (+inf, no index): it is never inserted.  At the end the lists go to the chunk's candidate slab.
+// query's list (registers: lane j holds entry j).  A column outside the bank, the one a query excludes, or a pair
+// without a distance (a bad row on either side, see knn_distance) is offered as (+inf, no index): it is never
+// inserted, so a bad bank row is in no list and a bad query's list stays empty.  At the end the lists go to the
+// chunk's candidate slab.
 // SELF: the bank is the queries (both operands and both norms are read through Q's pointers), nothing is excluded, and
 // row i against itself gets distance -1: it sorts before every real distance (>= 0) and the merge writes it out as 0, so
 // row i comes first even when a duplicate of it has a lower index.  What SELF turns off is compiled out.
@@ -255,7 +265,9 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_tile_kernel(const QueryP p) {
             bool ok = gj < Nb;
             // by every lane, never under a run-time branch: a shuffle under `gj < Nb` would read inactive lanes as 0
             if constexpr (!SELF) ok &= gj != __shfl(excl, rr, 64);
-            knn_insert(ld_[rr], li_[rr], ok ? sd[wm0 + rr][lane] : INFINITY, ok ? gj : 0x7fffffff, p.k, lane);
+            const float cd = sd[wm0 + rr][lane];
+            ok &= cd == cd;     // a pair without a distance (knn_distance) is offered like a column outside the bank
+            knn_insert(ld_[rr], li_[rr], ok ? cd : INFINITY, ok ? gj : 0x7fffffff, p.k, lane);
         }
     }
 #pragma unroll
@@ -396,7 +408,8 @@ __device__ __forceinline__ float knn_pair_dot(const float* __restrict__ x, const
 // One thread per slot (i, j): the threshold d(i, nbr[i][j]) exactly as the tile kernel will compute that pair, the
 // neighbour as a row of this launch, and the slot's two counters at their start value.  A slot that is empty (-1),
 // names row i itself or lies outside [0, N) never reads A: threshold NaN (no distance is below or equal to it),
-// neighbour -1, counters -1 for good.
+// neighbour -1, counters -1 for good.  So does a slot whose pair has no distance (a bad row, see knn_distance); and as
+// the tile kernel's distance to a bad row is NaN as well, such a row is counted for no slot of any other row.
 template <bool VEC>
 __global__ __launch_bounds__(256) void knn_rank_threshold_kernel(const float* __restrict__ A, long lda, long N, int D, int k,
                                                                 int metric, const int64_t* __restrict__ nbr,
@@ -413,9 +426,11 @@ __global__ __launch_bounds__(256) void knn_rank_threshold_kernel(const float* __
         return;
     }
     const float dot = knn_pair_dot<VEC>(A + i * lda, A + n * lda, D);
-    out[slot] = {knn_distance(dot, sq[i], sq[n], metric), (int)n};
-    less[slot] = 0;
-    tied[slot] = 0;
+    const float thr = knn_distance(dot, sq[i], sq[n], metric);
+    const bool ok = thr == thr;                                      // a bad row on either side: nothing to count either
+    out[slot] = {thr, ok ? (int)n : -1};
+    less[slot] = ok ? 0 : -1;
+    tied[slot] = ok ? 0 : -1;
 }
 
 struct RankP {
@@ -741,7 +756,7 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void sil_tile_kernel(const SilP p) 
                 if (colok && rowlab[row] >= 0 && gi != gj) {
                     const float si = rowsq[row];
                     d = knn_distance(acc[j][v], si, sj, p.metric);
-                    // knn_distance clamps with fmaxf, which drops a NaN: the norms say whether a row is finite
+                    // a pair without a distance is NaN (knn_distance) and fails d < bound; the norms are tested as well
                     if (!(si < INFINITY && sj < INFINITY && d < bound)) { ++refused; d = 0.f; }
                 }
                 sd[row][col] = d;
@@ -918,7 +933,13 @@ __global__ __launch_bounds__(VOTE_WAVES * 64) void knn_vote_kernel(const VoteP p
         const bool any_zero = __ballot(valid && d == 0.f) != 0;
         w = any_zero ? (d == 0.f ? 1.0 : 0.0) : 1.0 / (double)d;
     } else {
-        w = exp(-(double)d / (double)p.temperature);
+        // exp(-(d - d_min) / T), d_min the query's smallest valid distance: the scores up to the common factor
+        // exp(d_min / T).  Unshifted, euclidean distances of latent width (d > 52 at T = 0.07) underflow every weight
+        // to 0 and the first argmax answers class 0.  The nearest valid neighbour weighs exactly 1.
+        float dmin = valid ? d : INFINITY;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) dmin = fminf(dmin, __shfl_xor(dmin, o, 64));
+        w = exp(-((double)d - (double)dmin) / (double)p.temperature);
     }
     if (!valid) w = 0.0;
     const unsigned long long vmask = __ballot(valid);

@@ -117,9 +117,17 @@ def rank_penalties(A, B, k, metric_a="euclidean", metric_b="euclidean", ties="mi
     dist = torch.empty(N, k + 1, dtype=torch.float32, device=B.device)
     ops.umap_knn(B, k + 1, mb, idx, dist)                    # row i first in its own list, whatever duplicates it has
     nbr = idx[:, 1:].contiguous()
+    n_empty = int((nbr < 0).sum())                           # N > 2 k: a slot is empty only where a pair has no distance
+    if n_empty:
+        raise ValueError(f"{who}: {n_empty} neighbour slots are empty although N={N} exceeds n_neighbors={k}: B holds NaN or "
+                         f"infinity, or a row's squared norm overflows float32")
     less = torch.empty(N, k, dtype=torch.int32, device=A.device)
     tied = torch.empty(N, k, dtype=torch.int32, device=A.device)
     ops.knn_ranks(A, nbr, ma, less, tied)
+    n_unranked = int((less < 0).sum())                       # every slot names another row: -1 only where A has no distance
+    if n_unranked:
+        raise ValueError(f"{who}: {n_unranked} neighbours could not be ranked: A holds NaN or infinity, or a row's squared "
+                         f"norm overflows float32")
     less_h, tied_h = less.cpu().numpy().astype(np.int64), tied.cpu().numpy().astype(np.int64)
     per_row = penalties_from_counts(less_h, tied_h, k, ties)
     total = sum(int(v) for v in (2 * per_row).astype(np.int64)) / 2 if ties == "average" else sum(int(v) for v in per_row)

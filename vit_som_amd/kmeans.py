@@ -13,6 +13,8 @@ Differences from sklearn, all below fp32 rounding on data with margins: distance
 differences (sklearn: |x|^2 - 2 x.c + |c|^2 on mean-centred data), potentials and inertia are fp64 sums, and
 ``center_shift_tot`` is the fp64 sum of the squared shifts.  No sample weights, Elkan, sparse input or mini-batch.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -45,6 +47,16 @@ class _Work:
         self.centers = [torch.empty(k, D, dtype=torch.float32, device=device) for _ in range(2)]
 
 
+def _refuse_non_finite(X, what):
+    """sklearn refuses such input up front; here the kernels have already said so (a row at no finite distance from any
+    centre joins cluster 0 with mind = inf or keeps a NaN potential), and the rows are counted to name them."""
+    sq = torch.empty(X.shape[0], dtype=torch.float32, device=X.device)
+    ops.row_sqnorm(X, sq)
+    n = int((~torch.isfinite(sq)).sum())
+    raise ValueError(f"KMeans: the {what} is not finite: {n} rows of X hold NaN or infinity, or their squared norm "
+                     f"overflows float32")
+
+
 def _kmeans_plusplus(X, n_clusters, rs, n_local_trials=None):
     """_kmeans_plusplus (unit weights) -> (centers [k, D] device tensor, indices np.int64 [k])."""
     N, D = X.shape
@@ -58,6 +70,8 @@ def _kmeans_plusplus(X, n_clusters, rs, n_local_trials=None):
     pots = torch.empty(max(n_local_trials, 1), dtype=torch.float64, device=dev)
     ops.kmeanspp_dist(X, torch.tensor(indices[:1], device=dev), None, closest, pots)
     current_pot = float(pots[0])
+    if not math.isfinite(current_pot):
+        _refuse_non_finite(X, "k-means++ potential")
     closest_h = closest[0].cpu().numpy()
     dist = torch.empty(n_local_trials, N, dtype=torch.float32, device=dev)
     for c in range(1, n_clusters):
@@ -103,6 +117,8 @@ def _lloyd(X, centers_init, max_iter, tol, w):
         ops.kmeans_assign(X, cur, lab_next, lab, w.mind, w.ws)
         ops.kmeans_update(cur, new, N, w.mind, w.counts, w.status, w.ws)
         st = w.status.tolist()                            # the one host read of the iteration
+        if not math.isfinite(st[3]):
+            _refuse_non_finite(X, "inertia")
         if st[2] > 0:                                     # _relocate_empty_clusters_dense
             counts = w.counts.cpu().numpy()
             empty = np.where(counts == 0)[0]

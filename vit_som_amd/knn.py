@@ -13,8 +13,11 @@ The lists order neighbours by (distance, bank ordinal) and every pair's distance
 streamed lists equal the one-piece lists bit for bit, whatever the chunking.
 
 weights: "uniform" (1), "distance" (sklearn's 1 / d; neighbours at distance 0 take the whole vote) or "softmax"
-(exp(-d / temperature): with metric="cosine" the DINO-style exp(sim / T) vote up to a common factor).  Vote ties go to
-the lowest class.  Distances: "cosine" (1 - cos, clamped at 0) or "euclidean", as UMAP's kNN defines them.
+(exp(-d / temperature) up to a common factor per query -- the kernel shifts by the query's smallest distance, so the
+scores cannot underflow together: with metric="cosine" the DINO-style exp(sim / T) vote).  Vote ties go to the lowest
+class.  Distances: "cosine" (1 - cos, clamped at 0) or "euclidean", as UMAP's kNN defines them.  A row with a NaN, an
+infinity or an overflowing squared norm has no distance to anything: as a bank row it is in no list, as a query it gets
+an empty list, the prediction -1, and is counted in the vote's status[1].
 """
 import torch
 

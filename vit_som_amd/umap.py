@@ -401,6 +401,10 @@ class UMAP:
         idx = torch.empty(N, k, dtype=torch.int64, device=dev)
         dist = torch.empty(N, k, dtype=torch.float32, device=dev)
         ops.umap_knn(X, k, METRICS[self.metric], idx, dist)
+        n_empty = int((idx < 0).sum())               # N > k: a slot is empty only where a pair has no distance
+        if n_empty:
+            raise ValueError(f"UMAP: {n_empty} neighbour slots are empty although N={N} exceeds n_neighbors={k}: X holds NaN "
+                             f"or infinity, or a row's squared norm overflows float32")
         self._knn_indices, self._knn_dists = idx.cpu().numpy(), dist.cpu().numpy()
         G, self._sigmas, self._rhos = fuzzy_simplicial_set(self._knn_indices, self._knn_dists, self.set_op_mix_ratio,
                                                            self.local_connectivity)
