@@ -782,6 +782,65 @@ int vsom_lbfgs_coeff(const double* dots, int m, int has_new, double* state, vsom
 int vsom_lbfgs_combine(double* S, double* Y, const double* g, const double* s_new, const double* y_new, long n, int m,
                        const double* state, double* p, vsom_stream_t stream);
 
+/* ------------------------------------------------------------------ t-SNE (tsne.hip)
+ * scikit-learn's TSNE with an exact all-pairs repulsion (vit_som_amd/tsne.py drives it and states the algorithm, DESIGN.md
+ * section 4 has the bounds; no counterpart in the reference).  Two components only: a third changes the degrees of freedom
+ * and with them the kernel of q.  No floating-point atomics; every sum has one fixed order: all outputs are bitwise
+ * reproducible.  Caller-owned fp64 arrays with an element count are sized by a host-only query (0 for a non-positive
+ * size); a count below the query or a null array is VSOM_EWORKSPACE before any launch.
+ *
+ * vsom_tsne_affinities: the conditional P of every row from its neighbour table, sklearn's _binary_search_perplexity in
+ * fp64, rule for rule.  The row's values are knn_dist[i][first .. first + k_eff) (f32, row stride ldk: first = 1 skips the
+ * self slot of vsom_umap_knn); square != 0 squares them first, in f32 with one rounding, as sklearn squares its euclidean
+ * distances (cosine distances are used as they are).  With d_j the fp64 image of those values: beta = 1; at most 100 steps
+ * of  e_j = exp(-d_j beta), S = sum_j e_j (ascending j; S = (double)1e-8f when it is 0), H = log S + beta sum_j d_j (e_j / S);
+ * stop when |H - log (double)(float)perplexity| <= (double)1e-5f; H too large: beta_min = beta and beta doubles while
+ * beta_max is infinite, else the midpoint; H too small: the mirror image with halving.  Outputs: P[i][j] = e_j / S (fp64,
+ * dense [N, k_eff]) and beta[i] at the LAST EVALUATED beta (after 100 steps without a stop: the hundredth).  A row with a
+ * distance that is NaN, infinite or negative, a square that overflows, or (knn_idx given, same layout, nullable) an empty
+ * slot (index < 0) adds one to status[0] (int32, zeroed by the caller) and is not evaluated: its P and beta are not
+ * written.  1 <= k_eff <= 63 (more: VSOM_EUNSUPPORTED), ldk >= first + k_eff. */
+int vsom_tsne_affinities(const float* knn_dist, const int64_t* knn_idx, long ldk, long N, int k_eff, int first, int square,
+                         double perplexity, double* P, double* beta, int32_t* status, vsom_stream_t stream);
+/* vsom_tsne_repulsion: for Y f32 [N, 2] (dense, 16-byte aligned, finite) and every row i, over ALL j != i with
+ * q_ij = 1 / (1 + |y_i - y_j|^2):  rep[i] (fp64 [N, 2]) = sum_j q_ij^2 (y_i - y_j),  sumq[i] (fp64 [N]) = sum_j q_ij, and
+ * zpart[b] (fp64) = the sum of sumq over rows [64 b, 64 b + 64) in ascending row order; Z = sum_i sumq[i] is the sum of
+ * zpart (vsom_tsne_step adds it).  zpart: vsom_tsne_repulsion_parts(N) = ceil(N / 64) doubles.
+ * Tiled all-pairs: a workgroup owns 64 rows and walks the columns in tiles of 1024 staged in LDS; every lane of a wave
+ * reads the same column (broadcast reads).  The pair (i, i) is excluded by index: coincident points are legal and count
+ * with q = 1.  The symmetry (i, j) / (j, i) is not used.  The differences are taken in f32 before squaring; the reciprocal
+ * is v_rcp_f32 (1 ulp).
+ * Order of the sums: the columns are cut into chunks of 64; a chunk's terms are added in f32 in ascending column order;
+ * chunk c belongs to group c mod 16, a group adds its chunks in fp64 in ascending order, the 16 groups are added in fp64
+ * in ascending order.  Error of Z (all terms are positive, so relative errors carry through): a term q is within 8 * 2^-24
+ * of its value (two differences, a sum of two squares, 1 +, a reciprocal of 1 ulp) and an f32 chain of 64 positive terms
+ * within 63 * 2^-24, so every chunk, every sumq[i] and Z are within (71 * 2^-24 + N * 2^-53) relative = 4.3e-6 of the
+ * exact sums, whatever N: the fp64 part at N = 60 000 (3.6e9 terms, 5.6e7 chunks) is 7e-12.  rep's terms have both signs:
+ * its error is bounded by the same factor times sum_j q^2 |y_i - y_j|.
+ * N < 2^31 - 1 (else VSOM_EUNSUPPORTED). */
+long vsom_tsne_repulsion_parts(long N);
+int vsom_tsne_repulsion(const float* Y, long N, double* rep, double* sumq, double* zpart, long n_zpart, vsom_stream_t stream);
+/* vsom_tsne_step: one iteration from the outputs of vsom_tsne_repulsion at Y_in.  The joint P is a symmetric CSR (indptr
+ * int64 [N + 1], indices int64, data FP64, unexaggerated).  For every row i, all in fp64 and from the iteration-start Y_in
+ * (f32 [N, 2]; Y_out must not alias it):
+ *   Z = sum zpart (64 ascending segments, added in ascending order: the same bits in every workgroup)
+ *   attraction_i = sum_e exaggeration p_e q_e (y_i - y_j),  q_e = 1 / (1 + |y_i - y_j|^2) (edge l of the row belongs to lane
+ *                  l mod 16; a lane adds its edges in ascending order, the 16 lanes meet in a butterfly)
+ *   grad_i = 4 (attraction_i - rep[i] / Z)
+ * and per component, with update and gains f32 [N, 2] updated in place (sklearn's rule):
+ *   gains = gains + 0.2f if (double)update * grad < 0 else gains * 0.8f, then max(gains, 0.01f)          (f32)
+ *   update = (float)(momentum (double)update - (learning_rate (double)gains) grad)                       (one rounding)
+ *   Y_out = Y_in + update                                                                               (f32)
+ * record != 0: part[2 w] = the KL over the edges of workgroup w's 16 rows, sum_e P_e log(max(P_e, eps) / max(q_e / Z, eps))
+ * with P_e = exaggeration p_e and eps = 2^-52 as sklearn reports it, part[2 w + 1] = their sum of |grad_i|^2; the caller
+ * adds the vsom_tsne_step_parts(N) / 2 pairs.  record == 0 skips the logarithms and leaves part alone.  An index outside
+ * [0, N) is never dereferenced (its edge is left out).  part: vsom_tsne_step_parts(N) = 2 ceil(N / 16) doubles; zpart as
+ * above.  N < 2^31 - 1. */
+long vsom_tsne_step_parts(long N);
+int vsom_tsne_step(const int64_t* indptr, const int64_t* indices, const double* data, const float* Y_in, float* Y_out,
+                   float* update, float* gains, long N, const double* rep, const double* zpart, long n_zpart, double exaggeration,
+                   double momentum, double learning_rate, int record, double* part, long n_part, vsom_stream_t stream);
+
 /* SOMLayer.som_loss(weights, distances) = mean(weights * distances) for ARBITRARY weights (som_layer.py:137-142):
    loss_sum <- sum_ik weights[i,k] dist[i,k]; with coef/row_dot/col_dot given, also the backward coefficients of
    grad_scale * that sum w.r.t. the distances' inputs (what vsom_som_bwd consumes) -- with weights = an upstream

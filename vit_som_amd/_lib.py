@@ -197,6 +197,13 @@ SIGNATURES = {
     "vsom_lbfgs_dots": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, C.c_long, C.c_int, C.c_int, c_fp, c_fp, c_fp, C.c_long, c_stream]),
     "vsom_lbfgs_coeff": (C.c_int, [c_fp, C.c_int, C.c_int, c_fp, c_stream]),
     "vsom_lbfgs_combine": (C.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, C.c_long, C.c_int, c_fp, c_fp, c_stream]),
+    "vsom_tsne_affinities": (C.c_int, [c_fp, c_fp, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_double, c_fp, c_fp, c_fp,
+                                       c_stream]),
+    "vsom_tsne_repulsion_parts": (C.c_long, [C.c_long]),
+    "vsom_tsne_repulsion": (C.c_int, [c_fp, C.c_long, c_fp, c_fp, c_fp, C.c_long, c_stream]),
+    "vsom_tsne_step_parts": (C.c_long, [C.c_long]),
+    "vsom_tsne_step": (C.c_int, [c_fp] * 7 + [C.c_long, c_fp, c_fp, C.c_long, C.c_double, C.c_double, C.c_double, C.c_int, c_fp,
+                                               C.c_long, c_stream]),
     "vsom_fill": (C.c_int, [c_fp, C.c_long, C.c_float, c_stream]),
     "vsom_scaled_mul": (C.c_int, [c_fp, c_fp, c_fp, C.c_long, c_fp, C.c_float, c_stream]),
     "vsom_som_weighted_loss": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_float, c_fp, c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_int,

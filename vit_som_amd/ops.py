@@ -1419,6 +1419,75 @@ def lbfgs_combine(S, Y, g, s_new, y_new, state, p):
     return p
 
 
+# ---------------------------------------------------------------- t-SNE (tsne.py)
+TSNE_MAX_K = 63                                                  # csrc/tsne.hip (AFF_MAX_K): the search's 64 less the row itself
+
+
+def tsne_repulsion_parts(N) -> int:
+    """Doubles of zpart at N rows (one per block of 64 rows): host arithmetic."""
+    return int(lib.vsom_tsne_repulsion_parts(int(N)))
+
+
+def tsne_step_parts(N) -> int:
+    """Doubles of the step's record at N rows (KL and |grad|^2 per block of 16 rows): host arithmetic."""
+    return int(lib.vsom_tsne_step_parts(int(N)))
+
+
+def tsne_affinities(knn_dist, perplexity, P, beta, status, knn_idx=None, first=1, square=True):
+    """P fp64 [N, k_eff] and beta fp64 [N]: the conditional affinities of columns [first, first + k_eff) of knn_dist f32
+    [N, k] at this perplexity; status int32 [1] (zeroed by the caller) counts the rows refused, which are not written."""
+    _f32(knn_dist, "knn_dist")
+    assert knn_dist.dim() == 2, "knn_dist must be [N, k]"
+    N, ldk = knn_dist.shape[0], _rows(knn_dist)
+    assert P.dim() == 2 and P.shape[0] == N, "P must be [N, k_eff]"
+    k_eff = P.shape[1]
+    _pca_f64(P, (N, k_eff), "P"); _pca_f64(beta, (N,), "beta")
+    assert first >= 0 and first + k_eff <= knn_dist.shape[1], "columns [first, first + k_eff) must lie inside knn_dist"
+    if knn_idx is not None:
+        assert knn_idx.dtype == torch.int64 and knn_idx.is_cuda and knn_idx.shape == knn_dist.shape \
+            and knn_idx.stride() == knn_dist.stride(), "knn_idx must be an int64 device tensor laid out as knn_dist"
+    assert status.dtype == torch.int32 and status.is_cuda and status.numel() == 1
+    check(lib.vsom_tsne_affinities(ptr(knn_dist), ptr(knn_idx), ldk, N, k_eff, int(first), int(bool(square)), float(perplexity),
+                                   ptr(P), ptr(beta), ptr(status), stream()), "vsom_tsne_affinities")
+    return P, beta
+
+
+def _tsne_y(Y, name):
+    _f32(Y, name)
+    assert Y.dim() == 2 and Y.shape[1] == 2 and Y.is_contiguous(), f"{name} must be a contiguous [N, 2]"
+    return Y.shape[0]
+
+
+def tsne_repulsion(Y, rep, sumq, zpart):
+    """rep fp64 [N, 2] = sum_j q^2 (y_i - y_j), sumq fp64 [N] = sum_j q over all j != i, q = 1 / (1 + |y_i - y_j|^2), and
+    zpart fp64 [>= tsne_repulsion_parts(N)]: the sums of sumq over blocks of 64 rows (their sum is Z)."""
+    N = _tsne_y(Y, "Y")
+    _pca_f64(rep, (N, 2), "rep"); _pca_f64(sumq, (N,), "sumq")
+    assert zpart.dtype == torch.float64 and zpart.is_cuda and zpart.dim() == 1 and zpart.is_contiguous()
+    check(lib.vsom_tsne_repulsion(ptr(Y), N, ptr(rep), ptr(sumq), ptr(zpart), zpart.numel(), stream()), "vsom_tsne_repulsion")
+    return rep, sumq, zpart
+
+
+def tsne_step(indptr, indices, data, Y_in, Y_out, update, gains, rep, zpart, exaggeration, momentum, learning_rate, part,
+              record=False):
+    """One iteration: Y_out from Y_in, update and gains (f32 [N, 2]) in place, from tsne_repulsion's rep and zpart at Y_in
+    and the joint P (CSR: int64, int64, fp64).  record: part fp64 [>= tsne_step_parts(N)] receives the (KL, |grad|^2)
+    pairs of the row blocks; add them."""
+    N = _tsne_y(Y_in, "Y_in")
+    for t, name in ((Y_out, "Y_out"), (update, "update"), (gains, "gains")):
+        assert _tsne_y(t, name) == N, f"{name} must be [N, 2]"
+    assert indptr.dtype == indices.dtype == torch.int64 and indptr.is_cuda and indices.is_cuda
+    assert indptr.is_contiguous() and indices.is_contiguous() and indptr.numel() == N + 1
+    assert data.dtype == torch.float64 and data.is_cuda and data.is_contiguous() and data.numel() == indices.numel()
+    _pca_f64(rep, (N, 2), "rep")
+    for t in (zpart, part):
+        assert t.dtype == torch.float64 and t.is_cuda and t.dim() == 1 and t.is_contiguous()
+    check(lib.vsom_tsne_step(ptr(indptr), ptr(indices), ptr(data), ptr(Y_in), ptr(Y_out), ptr(update), ptr(gains), N, ptr(rep),
+                             ptr(zpart), zpart.numel(), float(exaggeration), float(momentum), float(learning_rate),
+                             int(bool(record)), ptr(part), part.numel(), stream()), "vsom_tsne_step")
+    return Y_out
+
+
 # ---------------------------------------------------------------- data-parallel exchange (RCCL)
 COMM_ID_BYTES = 128
 

@@ -29,7 +29,7 @@ import yaml
 
 from .evaluation import (evaluate_classification, evaluate_clustering, evaluate_embedding_quality, evaluate_knn, evaluate_linear_probe,
                          evaluate_map_quality, evaluate_silhouette, evaluate_latent_spectrum, fit_som_batch,
-                         init_som_from_data)
+                         evaluate_tsne_quality, init_som_from_data)
 from .classifier import ViTClassifier
 from .model import ViTSOM
 
@@ -278,7 +278,7 @@ def main_vit(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, 
 
 def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print, map_quality=False,
          knn_eval=False, embedding_quality=False, silhouette=False, som_init=None, latent_spectrum=False, som_batch_epochs=0,
-         linear_probe=False):
+         linear_probe=False, tsne_quality=False):
     """train_vit_som.py:27-130; a config with hyperparameters.model_arch == "vit" runs main_vit (train_vit.py) instead.
     model_states_dir defaults to experiments/states/vit_som (experiments/states/vit for the ViT baseline).
     map_quality: after each run's final evaluation also run evaluate_map_quality on the training loader with the model that
@@ -289,6 +289,8 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
     the test loader's) and report linear_probe_accuracy.
     embedding_quality: likewise run evaluate_embedding_quality with that model on the training loader (as map_quality does)
     and report trustworthiness / continuity of the UMAP embedding of its latents.
+    tsne_quality: likewise run evaluate_tsne_quality with that model on the training loader and report tsne_trustworthiness
+    and tsne_kl of the t-SNE embedding of its latents.
     silhouette: likewise run evaluate_silhouette with that model on the training loader, the samples clustered by their
     BMU, and report silhouette_bmu (NaN, with the reason logged, when fewer than two units or every sample alone won).
     som_init: "pca" or "sample": before the first step of each run start the SOM's prototypes from the training loader's
@@ -327,6 +329,8 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
         all_metrics.update(linear_probe_accuracy=[])
     if embedding_quality:
         all_metrics.update(trustworthiness=[], continuity=[])
+    if tsne_quality:
+        all_metrics.update(tsne_trustworthiness=[], tsne_kl=[])
     if silhouette:
         all_metrics.update(silhouette_bmu=[])
     if latent_spectrum:
@@ -391,6 +395,12 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
                 f"(k={eq.n_neighbors}, {eq.n_samples} samples)")
             all_metrics["trustworthiness"].append(eq.trustworthiness)
             all_metrics["continuity"].append(eq.continuity)
+        if tsne_quality:
+            tq = evaluate_tsne_quality(evaluated, config, train_loader)
+            log(f"t-SNE quality: trustworthiness {tq.trustworthiness:.4f}, continuity {tq.continuity:.4f}, KL {tq.kl_divergence:.4f} "
+                f"(k={tq.n_neighbors}, {tq.n_samples} samples)")
+            all_metrics["tsne_trustworthiness"].append(tq.trustworthiness)
+            all_metrics["tsne_kl"].append(tq.kl_divergence)
         if silhouette:
             try:
                 sr = evaluate_silhouette(evaluated, config, train_loader, clusters="bmu")
@@ -434,6 +444,8 @@ def _parser():
                          "set, scored: test set)")
     ap.add_argument("--embedding-quality", action="store_true",
                     help="after each run also report trustworthiness and continuity of the UMAP embedding of the training set's latents")
+    ap.add_argument("--tsne-quality", action="store_true",
+                    help="after each run also report trustworthiness and KL divergence of the t-SNE embedding of the training set's latents")
     ap.add_argument("--silhouette", action="store_true",
                     help="after each run also report the silhouette coefficient of the training set's latents clustered by their BMU")
     ap.add_argument("--som-init", choices=("pca", "sample"), default=None,
@@ -455,4 +467,5 @@ if __name__ == "__main__":
         loaders = lambda c, r, w: device_loaders(c, r, w, npz=a.data_npz, auto_augment=a.device_randaug)     # noqa: E731
     main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs, make_loaders=loaders, map_quality=a.map_quality,
          knn_eval=a.knn_eval, embedding_quality=a.embedding_quality, silhouette=a.silhouette, som_init=a.som_init,
-         latent_spectrum=a.latent_spectrum, som_batch_epochs=a.som_batch_epochs, linear_probe=a.linear_probe)
+         latent_spectrum=a.latent_spectrum, som_batch_epochs=a.som_batch_epochs, linear_probe=a.linear_probe,
+         tsne_quality=a.tsne_quality)
