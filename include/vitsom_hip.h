@@ -998,6 +998,54 @@ int vsom_augment_batch_ragged(const unsigned char* data, size_t data_bytes, cons
                               const float* mean, const float* std, uint64_t seed, int epoch, void* scratch, size_t scratch_bytes,
                               float* out, unsigned char* out_u8, vsom_stream_t stream);
 
+/* ------------------------------------------------------------------ Gaussian mixtures (gmm.hip)
+ * The steps of sklearn.mixture.GaussianMixture (covariance_type "diag" and "spherical") that touch the data;
+ * vit_som_amd/gmm.py drives them, DESIGN.md section 4 has the numerical form; no counterpart in the reference.  X is
+ * f32 [N, D] with row stride ldx (any alignment, any D: 16-byte loads when D % 4 == 0, ldx % 4 == 0 and the pointers are
+ * 16-byte aligned, element loads otherwise).  means and prec (the precisions 1 / covariance; a spherical value repeated over
+ * d) are dense f32 [K, D]; logc is fp64 [K], c_k = log w_k + sum_d log prec_kd / 2 - D log(2 pi) / 2.  Limits of every
+ * entry: N, D, K >= 1 (else VSOM_EINVAL), K <= 1024 (else VSOM_EUNSUPPORTED), ldx >= D, ldr >= K (else VSOM_EINVAL).
+ * Scratch is a TYPED array of doubles with an element count, sized by the host-only query vsom_gmm_parts(N, D, K, which)
+ * (0 for a non-positive size or K > 1024); a count below the query or a null array is VSOM_EWORKSPACE before any launch.
+ * No floating-point atomics; every sum has one fixed order: all outputs are bitwise reproducible. */
+#define VSOM_GMM_ESTEP 0
+#define VSOM_GMM_MSTEP 1 /* vsom_gmm_mstep and vsom_gmm_params: one array, handed from the first to the second */
+#define VSOM_GMM_SET 2
+long vsom_gmm_parts(long N, int D, int K, int which);
+/* Rows of one M-step slab (the last may be shorter): the split is a function of the shape alone. */
+long vsom_gmm_slab_rows(long N, int D, int K);
+/* vsom_gmm_estep: the DIRECT form.  m_ik = sum_d (x_id - mu_kd)^2 prec_kd with f32 terms; the terms of a 4-column piece
+ * (one column in the element path) are added in f32, the pieces of a lane in fp64 in column order, the 64 lanes by an
+ * fp64 butterfly.  log p_ik = c_k - m_ik / 2 (fp64); log_prob_norm[i] (fp64 [N]) = the max-shifted fp64 log-sum-exp over
+ * k; resp[i][k] (f32, row stride ldr; NULLABLE) = exp(log p_ik - log_prob_norm_i) rounded once; labels[i] (int64,
+ * NULLABLE) = the first argmax of log p_ik, ties to the lowest k.  A row whose log_prob_norm is not finite (a NaN or an
+ * infinity in X) is REFUSED: counted, its log_prob_norm and resp written as NaN, its label as -1.  part[g] / part[G + g]
+ * receive workgroup g's sum of log_prob_norm over its accepted rows (wave by wave, rows ascending) and its refused rows;
+ * estat (fp64 [2]) = their sums in g order.  The rest of part stages log p.  part: vsom_gmm_parts(.., VSOM_GMM_ESTEP). */
+int vsom_gmm_estep(const float* X, long ldx, long N, int D, const float* means, const float* prec, const double* logc, int K,
+                   float* resp, long ldr, double* log_prob_norm, int64_t* labels, double* estat, double* part, long n_part,
+                   vsom_stream_t stream);
+/* vsom_gmm_mstep: the partial sums of the M-step SHIFTED at means_old (f32 [K, D]: the previous means; the column means
+ * repeated for the first M-step of a fit), per slab of vsom_gmm_slab_rows rows: nk_k = sum_i r_ik, S1_kd = sum_i r_ik e,
+ * S2_kd = sum_i r_ik e^2 with e = x_id - means_old_kd, everything in fp64 (e and r e are exact), rows ascending. */
+int vsom_gmm_mstep(const float* X, long ldx, long N, int D, const float* resp, long ldr, const float* means_old, int K,
+                   double* part, long n_part, vsom_stream_t stream);
+/* vsom_gmm_params: from the array vsom_gmm_mstep filled (it is also this entry's scratch), slabs added in slab order in
+ * fp64: nk_k += 10 eps(fp64); a = S1 / nk; means (f32 [K, D], not means_old) = means_old + a; cov = S2 / nk - a^2 +
+ * reg_covar (fp64 [K, D]; spherical != 0: fp64 [K], the mean over d in ascending d); prec = 1 / cov (f32 [K, D]);
+ * weights (fp64 [K]) = nk / n_norm, or nk / sum_k nk (ascending k) when n_norm == 0; logc as above.  record (fp64 [8]):
+ * [0] estat[0] / N, the lower bound of the E-step that made resp (NaN when estat is NULL), [1] the smallest nk, [2] the
+ * smallest covariance, [3] the covariances that are <= 0 or not finite, [4] estat[1], the refused rows, [5] the weights'
+ * divisor, [6..7] zero.  A component without responsibility keeps its mean (a = 0) and gets cov = reg_covar. */
+int vsom_gmm_params(double* part, long n_part, long N, int D, int K, const float* means_old, double reg_covar, int spherical,
+                    long n_norm, const double* estat, float* means, double* cov, float* prec, double* weights, double* logc,
+                    double* record, vsom_stream_t stream);
+/* vsom_gmm_set_params: prec, logc and record[2..3] from GIVEN weights (fp64 [K]) and covariances (fp64 [K, D] or, spherical,
+ * [K]): what the E-step needs after an initialisation override, a warm start or a fit.  part: vsom_gmm_parts(1, D, K,
+ * VSOM_GMM_SET) doubles. */
+int vsom_gmm_set_params(const double* weights, const double* cov, int D, int K, int spherical, float* prec, double* logc,
+                        double* record, double* part, long n_part, vsom_stream_t stream);
+
 /* ------------------------------------------------------------------ small utilities */
 int vsom_fill(float* p, long n, float value, vsom_stream_t stream);
 /* out[0] = ca * a[0] + cb * b[0]: the step's total loss from its two device-side sums (vit_som.py:93,98); `counter`

@@ -204,6 +204,14 @@ SIGNATURES = {
     "vsom_tsne_step_parts": (C.c_long, [C.c_long]),
     "vsom_tsne_step": (C.c_int, [c_fp] * 7 + [C.c_long, c_fp, c_fp, C.c_long, C.c_double, C.c_double, C.c_double, C.c_int, c_fp,
                                                C.c_long, c_stream]),
+    "vsom_gmm_parts": (C.c_long, [C.c_long, C.c_int, C.c_int, C.c_int]),
+    "vsom_gmm_slab_rows": (C.c_long, [C.c_long, C.c_int, C.c_int]),
+    "vsom_gmm_estep": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, c_fp, c_fp, C.c_int, c_fp, C.c_long, c_fp, c_fp, c_fp, c_fp,
+                                 C.c_long, c_stream]),
+    "vsom_gmm_mstep": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, C.c_long, c_fp, C.c_int, c_fp, C.c_long, c_stream]),
+    "vsom_gmm_params": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, C.c_int, c_fp, C.c_double, C.c_int, C.c_long, c_fp, c_fp, c_fp,
+                                  c_fp, c_fp, c_fp, c_fp, c_stream]),
+    "vsom_gmm_set_params": (C.c_int, [c_fp, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_long, c_stream]),
     "vsom_fill": (C.c_int, [c_fp, C.c_long, C.c_float, c_stream]),
     "vsom_scaled_mul": (C.c_int, [c_fp, c_fp, c_fp, C.c_long, c_fp, C.c_float, c_stream]),
     "vsom_som_weighted_loss": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_float, c_fp, c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_int,

@@ -20,7 +20,7 @@ returns the whole set's result; figures are drawn by rank 0):
   latent                               visualize_umap_map, evaluate_embedding_quality (embedding_quality.py),
                                        visualize_pca_map (pca.py), evaluate_knn (knn.py), evaluate_linear_probe
                                        (defined in linear_probe.py next to its estimator, reachable from here),
-                                       evaluate_tsne_quality (tsne.py, likewise)
+                                       evaluate_tsne_quality (tsne.py, likewise), evaluate_gmm (gmm.py, likewise)
   SOM input and BMU                    evaluate_silhouette / visualize_silhouette_map (silhouette.py),
                                        evaluate_latent_spectrum, init_som_from_data, fit_som_batch (SOMLayer.fit_batch)
   the prototypes only, no data         visualize_decoded_prototypes / decoded_prototype_canvas / decode_prototype
@@ -38,6 +38,7 @@ from .embedding_quality import EmbeddingQuality, embedding_quality, subset_score
 from .kmeans import KMeans
 from .knn import KNNClassifier
 from .linear_probe import LinearProbeReport, evaluate_linear_probe, linear_probe_report  # noqa: F401  (the entry lives with its estimator)
+from .gmm import GMMReport, evaluate_gmm  # noqa: F401  (the entry lives with its estimator)
 from .tsne import TSNEQualityReport, evaluate_tsne_quality, visualize_tsne_progression  # noqa: F401  (the entries live with their estimator)
 from .plots import _draw_grid, _draw_map, _pyplot, _save_scatter, _umap_scatter, draw_decoded_prototypes, draw_label_heatmap  # noqa: F401
 from .silhouette import cluster_silhouette

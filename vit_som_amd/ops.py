@@ -1488,6 +1488,104 @@ def tsne_step(indptr, indices, data, Y_in, Y_out, update, gains, rep, zpart, exa
     return Y_out
 
 
+# ---------------------------------------------------------------- Gaussian mixtures (gmm.py)
+GMM_MAX_K = 1024                                                 # csrc/gmm.hip: GM_MAX_K
+GMM_ESTEP, GMM_MSTEP, GMM_SET = 0, 1, 2                          # `which` of vsom_gmm_parts
+GMM_RECORD = 8                                                   # doubles of the status record
+GMM_LOWER_BOUND, GMM_MIN_NK, GMM_MIN_COV, GMM_BAD_COV, GMM_REFUSED = 0, 1, 2, 3, 4
+
+
+def gmm_parts(N, D, K, which) -> int:
+    """Doubles of scratch gmm_estep (GMM_ESTEP), gmm_mstep + gmm_params (GMM_MSTEP) and gmm_set_params (GMM_SET) take: host
+    arithmetic, 0 for an empty shape."""
+    return int(lib.vsom_gmm_parts(int(N), int(D), int(K), int(which)))
+
+
+def gmm_slab_rows(N, D, K) -> int:
+    """Rows of one M-step slab at this shape: host arithmetic."""
+    return int(lib.vsom_gmm_slab_rows(int(N), int(D), int(K)))
+
+
+def gmm_scratch(N, D, K, which, device):
+    """A float64 view of exactly gmm_parts(...) doubles of the shared scratch."""
+    n = gmm_parts(N, D, K, which)
+    return scratch(8 * n, device)[:8 * n].view(torch.float64)
+
+
+def _gmm_kd(means, prec, D):
+    _f32(means, "means"); _f32(prec, "prec")
+    assert means.dim() == 2 and means.shape[1] == D and means.is_contiguous(), "means must be a contiguous [K, D]"
+    assert prec.shape == means.shape and prec.is_contiguous(), "prec must be a contiguous [K, D]"
+    return means.shape[0]
+
+
+def gmm_estep(X, means, prec, logc, resp, log_prob_norm, labels, estat, part=None):
+    """log_prob_norm fp64 [N], resp f32 [N, K] (None: not wanted), labels int64 [N] (None likewise) of the mixture (means,
+    prec f32 [K, D], logc fp64 [K]) in the direct form; estat fp64 [2] = (sum of log_prob_norm over the accepted rows, rows
+    refused for a NaN or an infinity: theirs are NaN / -1)."""
+    N, D, ldx = _kmeans_x(X)
+    K = _gmm_kd(means, prec, D)
+    _pca_f64(logc, (K,), "logc"); _pca_f64(log_prob_norm, (N,), "log_prob_norm"); _pca_f64(estat, (2,), "estat")
+    ldr = K
+    if resp is not None:
+        _f32(resp, "resp")
+        assert resp.dim() == 2 and tuple(resp.shape) == (N, K), "resp must be [N, K]"
+        ldr = _rows(resp)
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.is_cuda and labels.is_contiguous() and labels.numel() == N
+    part = gmm_scratch(N, D, K, GMM_ESTEP, X.device) if part is None else part
+    check(lib.vsom_gmm_estep(ptr(X), ldx, N, D, ptr(means), ptr(prec), ptr(logc), K, ptr(resp), ldr, ptr(log_prob_norm),
+                             ptr(labels), ptr(estat), ptr(part), part.numel(), stream()), "vsom_gmm_estep")
+    return log_prob_norm
+
+
+def gmm_mstep(X, resp, means_old, part):
+    """The M-step's per-slab partial sums (nk, S1, S2 shifted at means_old f32 [K, D]) into part, fp64
+    [>= gmm_parts(N, D, K, GMM_MSTEP)]; gmm_params turns them into parameters."""
+    N, D, ldx = _kmeans_x(X)
+    _f32(resp, "resp"); _f32(means_old, "means_old")
+    assert means_old.dim() == 2 and means_old.shape[1] == D and means_old.is_contiguous()
+    K = means_old.shape[0]
+    assert resp.dim() == 2 and tuple(resp.shape) == (N, K), "resp must be [N, K]"
+    assert part.dtype == torch.float64 and part.is_cuda and part.dim() == 1 and part.is_contiguous()
+    check(lib.vsom_gmm_mstep(ptr(X), ldx, N, D, ptr(resp), _rows(resp), ptr(means_old), K, ptr(part), part.numel(), stream()),
+          "vsom_gmm_mstep")
+    return part
+
+
+def gmm_params(part, N, means_old, reg_covar, spherical, n_norm, estat, means, cov, prec, weights, logc, record):
+    """New means f32 [K, D], cov fp64 ([K, D]; spherical: [K]), prec f32 [K, D], weights and logc fp64 [K] from gmm_mstep's
+    part; weights = nk / n_norm, or nk / sum(nk) when n_norm == 0.  record fp64 [GMM_RECORD]: the lower bound estat[0] / N
+    (estat None: NaN), the smallest nk, the smallest covariance, the covariances <= 0 or not finite, the refused rows."""
+    K, D = means_old.shape
+    _gmm_kd(means, prec, D)
+    _f32(means_old, "means_old")
+    assert means_old.is_contiguous() and means.shape[0] == K
+    _pca_f64(cov, (K,) if spherical else (K, D), "cov")
+    _pca_f64(weights, (K,), "weights"); _pca_f64(logc, (K,), "logc"); _pca_f64(record, (GMM_RECORD,), "record")
+    if estat is not None:
+        _pca_f64(estat, (2,), "estat")
+    assert part.dtype == torch.float64 and part.is_cuda and part.dim() == 1 and part.is_contiguous()
+    check(lib.vsom_gmm_params(ptr(part), part.numel(), int(N), D, K, ptr(means_old), float(reg_covar), int(bool(spherical)),
+                              int(n_norm), ptr(estat), ptr(means), ptr(cov), ptr(prec), ptr(weights), ptr(logc), ptr(record),
+                              stream()), "vsom_gmm_params")
+    return record
+
+
+def gmm_set_params(weights, cov, D, spherical, prec, logc, record, part=None):
+    """prec f32 [K, D], logc fp64 [K] and record[GMM_MIN_COV], record[GMM_BAD_COV] from given weights fp64 [K] and
+    covariances fp64 ([K, D]; spherical: [K])."""
+    K = weights.numel()
+    _pca_f64(weights, (K,), "weights"); _pca_f64(cov, (K,) if spherical else (K, D), "cov")
+    _f32(prec, "prec")
+    assert tuple(prec.shape) == (K, D) and prec.is_contiguous(), "prec must be a contiguous [K, D]"
+    _pca_f64(logc, (K,), "logc"); _pca_f64(record, (GMM_RECORD,), "record")
+    part = gmm_scratch(1, D, K, GMM_SET, weights.device) if part is None else part
+    check(lib.vsom_gmm_set_params(ptr(weights), ptr(cov), int(D), K, int(bool(spherical)), ptr(prec), ptr(logc), ptr(record),
+                                  ptr(part), part.numel(), stream()), "vsom_gmm_set_params")
+    return prec, logc
+
+
 # ---------------------------------------------------------------- data-parallel exchange (RCCL)
 COMM_ID_BYTES = 128
 

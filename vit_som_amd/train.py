@@ -29,7 +29,7 @@ import yaml
 
 from .evaluation import (evaluate_classification, evaluate_clustering, evaluate_embedding_quality, evaluate_knn, evaluate_linear_probe,
                          evaluate_map_quality, evaluate_silhouette, evaluate_latent_spectrum, fit_som_batch,
-                         evaluate_tsne_quality, init_som_from_data)
+                         evaluate_gmm, evaluate_tsne_quality, init_som_from_data)
 from .classifier import ViTClassifier
 from .model import ViTSOM
 
@@ -278,7 +278,7 @@ def main_vit(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, 
 
 def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print, map_quality=False,
          knn_eval=False, embedding_quality=False, silhouette=False, som_init=None, latent_spectrum=False, som_batch_epochs=0,
-         linear_probe=False, tsne_quality=False):
+         linear_probe=False, tsne_quality=False, gmm_eval=False):
     """train_vit_som.py:27-130; a config with hyperparameters.model_arch == "vit" runs main_vit (train_vit.py) instead.
     model_states_dir defaults to experiments/states/vit_som (experiments/states/vit for the ViT baseline).
     map_quality: after each run's final evaluation also run evaluate_map_quality on the training loader with the model that
@@ -291,6 +291,8 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
     and report trustworthiness / continuity of the UMAP embedding of its latents.
     tsne_quality: likewise run evaluate_tsne_quality with that model on the training loader and report tsne_trustworthiness
     and tsne_kl of the t-SNE embedding of its latents.
+    gmm_eval: likewise run evaluate_gmm with that model on the training loader (a diagonal Gaussian mixture of its latents,
+    data.num_classes components) and report gmm_purity, gmm_nmi and gmm_bic.
     silhouette: likewise run evaluate_silhouette with that model on the training loader, the samples clustered by their
     BMU, and report silhouette_bmu (NaN, with the reason logged, when fewer than two units or every sample alone won).
     som_init: "pca" or "sample": before the first step of each run start the SOM's prototypes from the training loader's
@@ -331,6 +333,8 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
         all_metrics.update(trustworthiness=[], continuity=[])
     if tsne_quality:
         all_metrics.update(tsne_trustworthiness=[], tsne_kl=[])
+    if gmm_eval:
+        all_metrics.update(gmm_purity=[], gmm_nmi=[], gmm_bic=[])
     if silhouette:
         all_metrics.update(silhouette_bmu=[])
     if latent_spectrum:
@@ -401,6 +405,13 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
                 f"(k={tq.n_neighbors}, {tq.n_samples} samples)")
             all_metrics["tsne_trustworthiness"].append(tq.trustworthiness)
             all_metrics["tsne_kl"].append(tq.kl_divergence)
+        if gmm_eval:
+            gr = evaluate_gmm(evaluated, config, train_loader)
+            log(f"Gaussian mixture: purity {gr.purity:.4f}, NMI {gr.nmi:.4f}, BIC {gr.bic:.1f}, mean log-likelihood "
+                f"{gr.log_likelihood:.3f} ({gr.n_components} components, {gr.n_iter} iterations, {gr.n_samples} samples)")
+            all_metrics["gmm_purity"].append(gr.purity)
+            all_metrics["gmm_nmi"].append(gr.nmi)
+            all_metrics["gmm_bic"].append(gr.bic)
         if silhouette:
             try:
                 sr = evaluate_silhouette(evaluated, config, train_loader, clusters="bmu")
@@ -446,6 +457,8 @@ def _parser():
                     help="after each run also report trustworthiness and continuity of the UMAP embedding of the training set's latents")
     ap.add_argument("--tsne-quality", action="store_true",
                     help="after each run also report trustworthiness and KL divergence of the t-SNE embedding of the training set's latents")
+    ap.add_argument("--gmm-eval", action="store_true",
+                    help="after each run also report purity, NMI and BIC of a diagonal Gaussian mixture fitted on the training set's latents")
     ap.add_argument("--silhouette", action="store_true",
                     help="after each run also report the silhouette coefficient of the training set's latents clustered by their BMU")
     ap.add_argument("--som-init", choices=("pca", "sample"), default=None,
@@ -468,4 +481,4 @@ if __name__ == "__main__":
     main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs, make_loaders=loaders, map_quality=a.map_quality,
          knn_eval=a.knn_eval, embedding_quality=a.embedding_quality, silhouette=a.silhouette, som_init=a.som_init,
          latent_spectrum=a.latent_spectrum, som_batch_epochs=a.som_batch_epochs, linear_probe=a.linear_probe,
-         tsne_quality=a.tsne_quality)
+         tsne_quality=a.tsne_quality, gmm_eval=a.gmm_eval)
