@@ -26,9 +26,9 @@ MAX_UNCLEAR = 0.01                               # and at most this share of the
 
 # (N, D, K) of the kernel tests: one row; fewer rows than a wave's block; odd D; a K chunk tail (7 = 8 - 1); D one past
 # the 128-column segment with two K chunks; many chunks and more than one workgroup; the latent width (six LDS tiles);
-# the widest K.
+# the widest K; element loads with two LDS tiles and two K chunks.
 SHAPES = [(1, 1, 1), (63, 5, 2), (257, 37, 3), (1001, 128, 7), (1000, 129, 16), (2000, 784, 100), (300, 12288, 10),
-          (130, 10, 1024)]
+          (130, 10, 1024), (40, 2101, 9)]
 # (seed, n, d, k, cluster_std, offset, covariance_type) of the whole-fit tests
 FIXTURES = [(0, 3000, 20, 5, 4.0, 0.0, "diag"), (2, 1500, 37, 3, 3.0, 0.0, "spherical"), (3, 600, 3072, 4, 8.0, 50.0, "diag")]
 TOL = 1e-3

@@ -62,6 +62,18 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }       // workspace sections
 
+// The canonical split of n items into about `want` pieces: `per` items to a piece (a multiple of `granule`), and the
+// `count` pieces that then hold items -- count <= want, and no piece is empty.  Workspace sizes and grids hang on it, so
+// a size query and the launch it sizes read the same Split.
+struct Split { long per; int count; };
+inline Split even_split(long n, long want, long granule = 1) {
+    Split s;
+    s.per = (n + want - 1) / want;
+    s.per = (s.per + granule - 1) / granule * granule;
+    s.count = (int)((n + s.per - 1) / s.per);
+    return s;
+}
+
 // ---------------------------------------------------------------- device helpers
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -77,6 +89,33 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+
+// Fixed-order fp64 reductions over a workgroup of THREADS threads (a power of two), sh[THREADS] in LDS: a tree of halving
+// strides; every thread gets the result, and sh is free again on return.
+template <int THREADS>
+__device__ double block_sum_f64(double v, double* sh) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = THREADS / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+template <int THREADS>
+__device__ double block_min_f64(double v, double* sh) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = THREADS / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] = fmin(sh[threadIdx.x], sh[threadIdx.x + s]);
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
 }
 
 // Order-preserving map from fp32 bits to uint32: negative values (sign set) are flipped whole, so -1e-7 < -0.0 < +0.0 < 1e-30.

@@ -10,7 +10,7 @@
 // No floating-point atomics anywhere: every sum has one fixed order, so a fit is bitwise reproducible.
 #include <float.h>
 
-#include "common.h"
+#include "row_tile.h"
 
 namespace vsom {
 namespace {
@@ -37,7 +37,7 @@ inline long gm_estep_parts(long N, int K) { return (long)gm_groups(N) * (2 + (lo
 
 // ---- M-step split: row slabs, a function of the shape alone.  One slab holds [K][2][D] + [K] doubles; as many slabs as keep
 // about 1024 workgroups in flight, fewer when they would pass 128 MiB (large K * D) or hold under 32 rows each.
-inline int gm_slabs(long N, int D, int K) {
+inline Split gm_slabs(long N, int D, int K) {
     const size_t per = ((size_t)K * (2 * (size_t)D + 1)) * 8;
     long s = (long)(GM_SLAB_BUDGET / per);
     const long want = (1024 + cdiv(D, GM_MT) - 1) / cdiv(D, GM_MT);
@@ -46,40 +46,31 @@ inline int gm_slabs(long N, int D, int K) {
     const long need = (N + 31) / 32;
     if (s > need) s = need;
     if (s < 1) s = 1;
-    const long rps = (N + s - 1) / s;
-    return (int)((N + rps - 1) / rps);           // every slab holds rows
+    return even_split(N, s);                     // every slab holds rows
 }
 // scratch of the M-step and of the parameter pass: slabs S1 / S2 [S][K][2][D], nk [S][K], the diag covariances [K][D]
 // (what spherical averages), per-component records [K][4]
 inline long gm_mstep_parts(long N, int D, int K) {
-    return (long)gm_slabs(N, D, K) * K * (2 * (long)D + 1) + (long)K * D + (long)K * 4;
+    return (long)gm_slabs(N, D, K).count * K * (2 * (long)D + 1) + (long)K * D + (long)K * 4;
 }
 inline long gm_set_parts(int K) { return (long)K * 4; }
 
-template <int VEC>
-struct GVec;
-template <>
-struct GVec<4> {
-    typedef f32x4 T;
-    static __device__ __forceinline__ T load(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-    static __device__ __forceinline__ void store(float* p, T v) { *reinterpret_cast<f32x4*>(p) = v; }
-    static __device__ __forceinline__ T zero() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-    // sum over the piece's four columns of (x - mu)^2 p: f32 terms, one f32 chain (a segment of 4 columns)
-    static __device__ __forceinline__ float maha(T x, T mu, T pr) {
-        const T e = x - mu;
+// a piece's Mahalanobis terms against planes (means, precisions): the sum over its columns of (x - mu)^2 p in f32, one f32
+// chain (a segment of at most 4 columns), widened once for the fp64 sum over pieces
+struct Maha {
+    static constexpr int PLANES = 2;
+    typedef double Acc;
+    static __device__ __forceinline__ double term(f32x4 x, const f32x4 (&mp)[2]) {
+        const f32x4 e = x - mp[0], pr = mp[1];
         float s = (e.x * e.x) * pr.x;
         s = fmaf(e.y * e.y, pr.y, s);
         s = fmaf(e.z * e.z, pr.z, s);
-        return fmaf(e.w * e.w, pr.w, s);
+        return (double)fmaf(e.w * e.w, pr.w, s);
     }
-};
-template <>
-struct GVec<1> {
-    typedef float T;
-    static __device__ __forceinline__ T load(const float* p) { return *p; }
-    static __device__ __forceinline__ void store(float* p, T v) { *p = v; }
-    static __device__ __forceinline__ T zero() { return 0.f; }
-    static __device__ __forceinline__ float maha(T x, T mu, T pr) { const float e = x - mu; return (e * e) * pr; }
+    static __device__ __forceinline__ double term(float x, const float (&mp)[2]) {
+        const float e = x - mp[0];
+        return (double)((e * e) * mp[1]);
+    }
 };
 
 struct EstepP {
@@ -99,30 +90,26 @@ struct EstepP {
 };
 
 // One workgroup's contiguous row range, 32 rows at a time.
-//  (1) Mahalanobis terms: wave w owns rows 4w..4w+3 of the step, lane l the VEC-wide column pieces l*VEC + 64*VEC*m.  Means
-//      and precisions are staged through LDS in [KC][dt] tiles; each value read from LDS feeds 4 rows.  A piece's VEC terms
+//  (1) Mahalanobis terms: row_tile_pass (row_tile.h) with Maha, wave w on rows 4w..4w+3 of the step.  A piece's VEC terms
 //      are added in f32 (a segment of at most 4 columns), the pieces of a lane in fp64 in column order, the 64 lanes by a
 //      fp64 butterfly (the same value on every lane).  log p_ik = c_k - m_ik / 2 goes to the workgroup's staging rows.
 //  (2) per row, by its wave: first argmax, max-shifted fp64 log-sum-exp (lane l takes k = l, l + 64, ..., then the
 //      butterfly), resp = exp(log p - log_prob_norm) rounded once to f32.
 template <int VEC>
 __global__ __launch_bounds__(GM_THREADS) void gmm_estep_kernel(EstepP p) {
-    typedef GVec<VEC> V;
-    typedef typename V::T vT;
     constexpr int KC = GM_KC;
     extern __shared__ __attribute__((aligned(16))) float lds_g[];     // [KC][dt] means, [KC][dt] precisions
     __shared__ double s_sum[GM_WAVES];
     __shared__ int s_bad[GM_WAVES];
-    float* l_mu = lds_g;
-    float* l_pr = lds_g + (size_t)KC * p.dt;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int D = p.D, K = p.K;
     const long r0 = (long)blockIdx.x * p.rows_per_group;
     const long r1 = min(p.N, r0 + p.rows_per_group);
     double* stage = p.part + 2 * (size_t)p.G + (size_t)blockIdx.x * GM_GROUP * K;
-    const int nchunks = (K + KC - 1) / KC, ntiles = (D + p.dt - 1) / p.dt;
-    const bool resident = nchunks == 1 && ntiles == 1;               // parameters staged once for the whole range
+    const float* const planes[2] = {p.mu, p.prec};
+    const int nchunks = (K + KC - 1) / KC;
+    const bool resident = nchunks == 1 && D <= p.dt;                 // parameters staged once for the whole range
     double wsum = 0.0;
     int wbad = 0;
 
@@ -135,36 +122,8 @@ __global__ __launch_bounds__(GM_THREADS) void gmm_estep_kernel(EstepP p) {
             for (int r = 0; r < GM_RB; ++r)
 #pragma unroll
                 for (int j = 0; j < KC; ++j) acc[r][j] = 0.0;
-            for (int t = 0; t < ntiles; ++t) {
-                const int d0 = t * p.dt, dn = min(p.dt, D - d0);
-                if (!resident || base == r0) {
-                    __syncthreads();
-                    for (int e = tid * VEC; e < KC * p.dt; e += GM_THREADS * VEC) {
-                        const int j = e / p.dt, d = e - j * p.dt;
-                        vT m = V::zero(), q = V::zero();
-                        if (j < kc && d < dn) {
-                            m = V::load(p.mu + (size_t)(j0 + j) * D + d0 + d);
-                            q = V::load(p.prec + (size_t)(j0 + j) * D + d0 + d);
-                        }
-                        V::store(l_mu + e, m);
-                        V::store(l_pr + e, q);
-                    }
-                    __syncthreads();
-                }
-                for (int d = lane * VEC; d < dn; d += 64 * VEC) {
-                    vT xv[GM_RB];
-#pragma unroll
-                    for (int r = 0; r < GM_RB; ++r)
-                        xv[r] = (rw + r < r1) ? V::load(p.X + (rw + r) * p.ldx + d0 + d) : V::zero();
-#pragma unroll
-                    for (int j = 0; j < KC; ++j) {
-                        const vT mv = V::load(l_mu + j * p.dt + d);
-                        const vT qv = V::load(l_pr + j * p.dt + d);
-#pragma unroll
-                        for (int r = 0; r < GM_RB; ++r) acc[r][j] += (double)V::maha(xv[r], mv, qv);
-                    }
-                }
-            }
+            row_tile_pass<GM_THREADS, GM_RB, KC, VEC, Maha>(p.X, p.ldx, rw, r1, D, planes, j0, kc, lds_g, p.dt,
+                                                            !resident || base == r0, acc);
 #pragma unroll
             for (int r = 0; r < GM_RB; ++r)
 #pragma unroll
@@ -275,29 +234,6 @@ __global__ __launch_bounds__(GM_MT) void gmm_mstep_kernel(const float* __restric
         }
 }
 
-__device__ double gm_block_sum(double v, double* sh) {               // fixed-order tree over 256 threads
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = GM_MT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-__device__ double gm_block_min(double v, double* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = GM_MT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] = fmin(sh[threadIdx.x], sh[threadIdx.x + s]);
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 // sklearn _estimate_gaussian_parameters / _estimate_gaussian_covariances_diag about the shift mu_old, slabs in slab order:
 //   nk = sum_s nk_s + 10 eps,  a = S1 / nk,  mean = mu_old + a,  cov = S2 / nk - a^2 + reg_covar
 __global__ __launch_bounds__(GM_MT) void gmm_reduce_kernel(const double* __restrict__ slabs, const double* __restrict__ nks, int S,
@@ -366,9 +302,9 @@ __global__ __launch_bounds__(GM_MT) void gmm_component_kernel(const double* __re
             mn = (c < mn || c != c) ? c : mn;
             bad += b ? 1.0 : 0.0;
         }
-        hl = gm_block_sum(hl, sh);
-        mn = gm_block_min(mn, sh);
-        bad = gm_block_sum(bad, sh);
+        hl = block_sum_f64<GM_MT>(hl, sh);
+        mn = block_min_f64<GM_MT>(mn, sh);
+        bad = block_sum_f64<GM_MT>(bad, sh);
     }
     if (threadIdx.x == 0) { kst[(size_t)k * 4 + 1] = hl; kst[(size_t)k * 4 + 2] = mn; kst[(size_t)k * 4 + 3] = bad; }
 }
@@ -412,20 +348,8 @@ __global__ __launch_bounds__(GM_MT) void gmm_finish_kernel(const double* __restr
 
 template <int VEC>
 int launch_estep(const EstepP& p, hipStream_t stream) {
-    const size_t lds = (size_t)2 * GM_KC * p.dt * 4;
-    static const int attr_rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(gmm_estep_kernel<VEC>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, GM_LDS);
-    VSOM_REQUIRE(attr_rc == 0, VSOM_EUNSUPPORTED, "gmm_estep: cannot reserve %d bytes of LDS", GM_LDS);
-    VSOM_LAUNCH((gmm_estep_kernel<VEC>), dim3(p.G), dim3(GM_THREADS), lds, stream, p);
-    return launch_status("gmm_estep_kernel");
-}
-
-// parameter tile width: the largest multiple of 64*VEC with 2*KC*dt floats in GM_LDS, not wider than D needs
-inline int gm_tile(int VEC, int D) {
-    const int unit = 64 * VEC;
-    int dt = (GM_LDS / (2 * GM_KC * 4)) / unit * unit;
-    const int need = cdiv(D, unit) * unit;
-    return dt < need ? dt : need;
+    return row_tile_launch<EstepP, gmm_estep_kernel<VEC>>(p, p.G, GM_THREADS, (size_t)2 * GM_KC * p.dt * 4, GM_LDS,
+                                                          "gmm_estep_kernel", stream);
 }
 
 int launch_tail(const double* cov, int D, int K, long N, long n_norm, int spherical, const double* weights_in, const double* estat,
@@ -455,7 +379,7 @@ long vsom_gmm_parts(long N, int D, int K, int which) {
 long vsom_gmm_slab_rows(long N, int D, int K) {
     using namespace vsom;
     if (N < 1 || D < 1 || K < 1 || K > GM_MAX_K) return 0;
-    return cdiv(N, gm_slabs(N, D, K));
+    return gm_slabs(N, D, K).per;
 }
 
 int vsom_gmm_estep(const float* X, long ldx, long N, int D, const float* means, const float* prec, const double* logc, int K,
@@ -471,11 +395,11 @@ int vsom_gmm_estep(const float* X, long ldx, long N, int D, const float* means, 
     EstepP p = {};
     p.X = X; p.ldx = ldx; p.N = N; p.D = D; p.K = K; p.mu = means; p.prec = prec; p.logc = logc;
     p.resp = resp; p.ldr = ldr; p.lpn = log_prob_norm; p.labels = labels; p.part = part;
-    const int G0 = gm_groups(N);
-    p.rows_per_group = cdiv(N, G0);
-    p.G = cdiv(N, p.rows_per_group);              // every workgroup gets rows; p.G <= G0, so the staging rows fit
+    const Split rows = even_split(N, gm_groups(N));
+    p.rows_per_group = rows.per;
+    p.G = rows.count;                             // every workgroup gets rows; at most gm_groups(N), so the staging rows fit
     const bool vec = D % 4 == 0 && ldx % 4 == 0 && aligned16(X) && aligned16(means) && aligned16(prec);
-    p.dt = gm_tile(vec ? 4 : 1, D);
+    p.dt = row_tile_width(GM_LDS, Maha::PLANES, GM_KC, vec ? 4 : 1, D);
     const int rc = vec ? launch_estep<4>(p, stream) : launch_estep<1>(p, stream);
     if (rc != VSOM_OK) return rc;
     VSOM_LAUNCH(gmm_estat_kernel, dim3(1), dim3(64), 0, stream, (const double*)part, p.G, estat);
@@ -491,10 +415,10 @@ int vsom_gmm_mstep(const float* X, long ldx, long N, int D, const float* resp, l
     VSOM_REQUIRE(K <= GM_MAX_K, VSOM_EUNSUPPORTED, "gmm_mstep: K=%d > %d", K, GM_MAX_K);
     VSOM_REQUIRE(part && n_part >= gm_mstep_parts(N, D, K), VSOM_EWORKSPACE, "gmm_mstep: part holds %ld doubles < %ld (too small)",
                  part ? n_part : 0L, gm_mstep_parts(N, D, K));
-    const int S = gm_slabs(N, D, K);
-    double* nks = part + (size_t)S * K * 2 * D;
-    VSOM_LAUNCH(gmm_mstep_kernel, dim3(cdiv(D, GM_MT), S), dim3(GM_MT), 0, stream, X, ldx, N, D, K, resp, ldr, means_old, part, nks,
-                (long)cdiv(N, S));
+    const Split slabs = gm_slabs(N, D, K);
+    double* nks = part + (size_t)slabs.count * K * 2 * D;
+    VSOM_LAUNCH(gmm_mstep_kernel, dim3(cdiv(D, GM_MT), slabs.count), dim3(GM_MT), 0, stream, X, ldx, N, D, K, resp, ldr, means_old,
+                part, nks, slabs.per);
     return launch_status("gmm_mstep_kernel");
 }
 
@@ -508,7 +432,7 @@ int vsom_gmm_params(double* part, long n_part, long N, int D, int K, const float
     VSOM_REQUIRE(means_old != means, VSOM_EINVAL, "gmm_params: means must not alias means_old");
     VSOM_REQUIRE(part && n_part >= gm_mstep_parts(N, D, K), VSOM_EWORKSPACE, "gmm_params: part holds %ld doubles < %ld (too small)",
                  part ? n_part : 0L, gm_mstep_parts(N, D, K));
-    const int S = gm_slabs(N, D, K);
+    const int S = gm_slabs(N, D, K).count;
     const double* nks = part + (size_t)S * K * 2 * D;
     double* covd_scratch = part + (size_t)S * K * (2 * (size_t)D + 1);
     double* kst = covd_scratch + (size_t)K * D;

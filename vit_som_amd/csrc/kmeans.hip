@@ -9,7 +9,7 @@
 //   vsom_kmeans_colvar     mean(var(X, axis=0)) of _tolerance.
 //
 // No floating-point atomics anywhere: every sum has one fixed order, so a fit is bitwise reproducible.
-#include "common.h"
+#include "row_tile.h"
 
 namespace vsom {
 namespace {
@@ -49,7 +49,8 @@ struct KmWs {
     float* sums;
     double* part;
     int* amax;
-    int G;
+    long rows_per_group;    // rows of a workgroup of the assign pass (not rounded to 32)
+    int G;                  // workgroups the assign pass runs: every one of them gets rows
     size_t bytes;
 };
 
@@ -58,11 +59,14 @@ inline int km_shift_blocks(int D, int k) { const int b = cdiv((long)k * D, KM_RE
 
 inline KmWs km_layout(void* ws, long N, int D, int k) {
     KmWs w = {};
-    w.G = km_groups(N, D, k);
-    size_t slab = align256((size_t)w.G * k * D * 4);
+    const int G0 = km_groups(N, D, k);          // sizes the sections; the canonical split runs G <= G0 workgroups
+    const Split rows = even_split(N, G0);
+    w.rows_per_group = rows.per;
+    w.G = rows.count;
+    size_t slab = align256((size_t)G0 * k * D * 4);
     const size_t colvar = align256((size_t)KM_COLVAR_CHUNKS * 2 * D * 8);
     if (colvar > slab) slab = colvar;
-    const size_t cnt = align256((size_t)w.G * k * 4), chg = align256((size_t)w.G * 4);
+    const size_t cnt = align256((size_t)G0 * k * 4), chg = align256((size_t)G0 * 4);
     const size_t sums = align256((size_t)k * D * 4), part = align256((size_t)km_shift_blocks(D, k) * 8);
     char* p = static_cast<char*>(ws);
     w.slabs = reinterpret_cast<float*>(p);
@@ -91,37 +95,23 @@ struct AssignP {
     int dt;         // centre D-tile (multiple of 4 * 64 in the vector path, of 64 in the scalar path)
 };
 
-template <int VEC>
-struct Vec;
-template <>
-struct Vec<4> {
-    typedef f32x4 T;
-    static __device__ __forceinline__ T load(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-    static __device__ __forceinline__ T load_nt(const float* p) { return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p)); }
-    static __device__ __forceinline__ void store(float* p, T v) { *reinterpret_cast<f32x4*>(p) = v; }
-    static __device__ __forceinline__ T zero() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-    static __device__ __forceinline__ float sqdist(T a, T b) {
-        const T e = a - b;
+// a piece's squared distance to a centre: f32, one fma chain over the piece's columns
+struct SqDist {
+    static constexpr int PLANES = 1;
+    typedef float Acc;
+    static __device__ __forceinline__ float term(f32x4 x, const f32x4 (&c)[1]) {
+        const f32x4 e = x - c[0];
         float s = e.x * e.x;
         s = fmaf(e.y, e.y, s);
         s = fmaf(e.z, e.z, s);
         return fmaf(e.w, e.w, s);
     }
-};
-template <>
-struct Vec<1> {
-    typedef float T;
-    static __device__ __forceinline__ T load(const float* p) { return *p; }
-    static __device__ __forceinline__ T load_nt(const float* p) { return __builtin_nontemporal_load(p); }
-    static __device__ __forceinline__ void store(float* p, T v) { *p = v; }
-    static __device__ __forceinline__ T zero() { return 0.f; }
-    static __device__ __forceinline__ float sqdist(T a, T b) { const float e = a - b; return e * e; }
+    static __device__ __forceinline__ float term(float x, const float (&c)[1]) { const float e = x - c[0]; return e * e; }
 };
 
 // sklearn lloyd_iter_chunked_dense (_k_means_lloyd.pyx) for one workgroup's contiguous row range, 32 rows at a time:
-//  (1) distances: wave w owns rows 4w..4w+3 of the step; lane l the VEC-wide column pieces l*VEC + 64*VEC*m.  Centres
-//      are staged through LDS in [KC][dt] tiles, each value read from LDS feeds 4 rows.  Per (row, centre) the lane sums
-//      its pieces in column order, then a butterfly sums the 64 lanes (same value on every lane); labels = first argmin.
+//  (1) distances: row_tile_pass (row_tile.h) with SqDist, wave w on rows 4w..4w+3 of the step.  Per (row, centre) the lane
+//      sums its pieces in column order, then a butterfly sums the 64 lanes (same value on every lane); labels = first argmin.
 //  (2) partial M-step: the 32 rows are read again (non-temporally: their last use) and added into
 //      this workgroup's slab, thread t owning the pieces t*VEC + 512*VEC*m, rows in (label, row) order, one
 //      read-modify-write of the slab per label present in the step.  Slab rows never touched are zeroed at the end.
@@ -142,8 +132,9 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_assign_kernel(AssignP p) {
     float* slab = p.slabs + (size_t)blockIdx.x * k * D;
     for (int j = tid; j < k; j += KM_THREADS) { s_cnt[j] = 0; s_seen[j] = 0; }
     if (tid == 0) s_changed = 0;
-    const int nchunks = (k + KC - 1) / KC, ntiles = (D + p.dt - 1) / p.dt;
-    const bool resident = nchunks == 1 && ntiles == 1;              // centres staged once for the whole range
+    const float* const centres[1] = {p.C};
+    const int nchunks = (k + KC - 1) / KC;
+    const bool resident = nchunks == 1 && D <= p.dt;                // centres staged once for the whole range
     __syncthreads();
 
     for (long base = r0; base < r1; base += KM_GROUP) {
@@ -159,31 +150,8 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_assign_kernel(AssignP p) {
             for (int r = 0; r < KM_RB; ++r)
 #pragma unroll
                 for (int j = 0; j < KC; ++j) acc[r][j] = 0.f;
-            for (int t = 0; t < ntiles; ++t) {
-                const int d0 = t * p.dt, dn = min(p.dt, D - d0);
-                if (!resident || base == r0) {
-                    __syncthreads();
-                    for (int e = tid * VEC; e < KC * p.dt; e += KM_THREADS * VEC) {
-                        const int j = e / p.dt, d = e - j * p.dt;
-                        vT v = V::zero();
-                        if (j < kc && d < dn) v = V::load(p.C + (size_t)(j0 + j) * D + d0 + d);
-                        V::store(lds_c + e, v);
-                    }
-                    __syncthreads();
-                }
-                for (int d = lane * VEC; d < dn; d += 64 * VEC) {
-                    vT xv[KM_RB];
-#pragma unroll
-                    for (int r = 0; r < KM_RB; ++r)
-                        xv[r] = (rw + r < r1) ? V::load(p.X + (rw + r) * p.ldx + d0 + d) : V::zero();
-#pragma unroll
-                    for (int j = 0; j < KC; ++j) {
-                        const vT cv = V::load(lds_c + j * p.dt + d);
-#pragma unroll
-                        for (int r = 0; r < KM_RB; ++r) acc[r][j] += V::sqdist(xv[r], cv);
-                    }
-                }
-            }
+            row_tile_pass<KM_THREADS, KM_RB, KC, VEC, SqDist>(p.X, p.ldx, rw, r1, D, centres, j0, kc, lds_c, p.dt,
+                                                              !resident || base == r0, acc);
 #pragma unroll
             for (int r = 0; r < KM_RB; ++r)
 #pragma unroll
@@ -263,19 +231,6 @@ __device__ int first_argmax(const int64_t* counts, int k) {      // np.argmax
     return a;
 }
 
-// fixed-order block reductions (256 threads)
-__device__ double block_sum_f64(double v, double* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = KM_RED_THREADS / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 // status[0] = changed labels, status[2] = empty clusters, status[3] = inertia = sum(mind) (fp64, fixed order);
 // counts[j] = sum_g cnt[g][j]
 __global__ __launch_bounds__(KM_RED_THREADS) void kmeans_counts_kernel(const int* __restrict__ cnt, const int* __restrict__ chg,
@@ -285,10 +240,10 @@ __global__ __launch_bounds__(KM_RED_THREADS) void kmeans_counts_kernel(const int
     __shared__ double sh[KM_RED_THREADS];
     double in = 0.0;
     for (long i = threadIdx.x; i < N; i += KM_RED_THREADS) in += (double)mind[i];
-    in = block_sum_f64(in, sh);
+    in = block_sum_f64<KM_RED_THREADS>(in, sh);
     double ch = 0.0;
     for (int g = threadIdx.x; g < G; g += KM_RED_THREADS) ch += (double)chg[g];
-    ch = block_sum_f64(ch, sh);
+    ch = block_sum_f64<KM_RED_THREADS>(ch, sh);
     double empty = 0.0;
     for (int j = threadIdx.x; j < k; j += KM_RED_THREADS) {
         long c = 0;
@@ -296,7 +251,7 @@ __global__ __launch_bounds__(KM_RED_THREADS) void kmeans_counts_kernel(const int
         counts[j] = c;
         empty += c == 0 ? 1.0 : 0.0;
     }
-    empty = block_sum_f64(empty, sh);                  // (its barriers make every counts[j] visible to thread 0)
+    empty = block_sum_f64<KM_RED_THREADS>(empty, sh);  // (its barriers make every counts[j] visible to thread 0)
     if (threadIdx.x == 0) {
         status[0] = ch; status[2] = empty; status[3] = in;
         *amax = first_argmax(counts, k);
@@ -340,7 +295,7 @@ __global__ __launch_bounds__(KM_RED_THREADS) void kmeans_centres_kernel(const fl
         const double df = (double)v - (double)o;
         sh2 += df * df;
     }
-    sh2 = block_sum_f64(sh2, sh);
+    sh2 = block_sum_f64<KM_RED_THREADS>(sh2, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = sh2;
 }
 
@@ -349,7 +304,7 @@ __global__ __launch_bounds__(KM_RED_THREADS) void kmeans_shift_kernel(const doub
     __shared__ double sh[KM_RED_THREADS];
     double s = 0.0;
     for (int i = threadIdx.x; i < P; i += KM_RED_THREADS) s += part[i];
-    s = block_sum_f64(s, sh);
+    s = block_sum_f64<KM_RED_THREADS>(s, sh);
     if (threadIdx.x == 0) status[1] = s;
 }
 
@@ -374,7 +329,7 @@ __global__ __launch_bounds__(KM_RED_THREADS) void kmeans_relocate_kernel(const f
     }
     double empty = 0.0;
     for (int j = threadIdx.x; j < k; j += KM_RED_THREADS) empty += counts[j] == 0 ? 1.0 : 0.0;
-    empty = block_sum_f64(empty, sh);
+    empty = block_sum_f64<KM_RED_THREADS>(empty, sh);
     if (threadIdx.x == 0) { status[2] = empty; *amax = first_argmax(counts, k); }
 }
 
@@ -402,7 +357,7 @@ __global__ __launch_bounds__(KM_RED_THREADS) void kmeanspp_pot_kernel(const floa
     const float* d = dist + (size_t)blockIdx.x * N;
     double s = 0.0;
     for (long i = threadIdx.x; i < N; i += KM_RED_THREADS) s += (double)d[i];
-    s = block_sum_f64(s, sh);
+    s = block_sum_f64<KM_RED_THREADS>(s, sh);
     if (threadIdx.x == 0) pots[blockIdx.x] = s;
 }
 
@@ -430,26 +385,14 @@ __global__ __launch_bounds__(KM_RED_THREADS) void kmeans_colvar_kernel(const dou
         const double m = s / (double)N;
         acc += fmax(q / (double)N - m * m, 0.0);
     }
-    acc = block_sum_f64(acc, sh);
+    acc = block_sum_f64<KM_RED_THREADS>(acc, sh);
     if (threadIdx.x == 0) out[0] = acc / (double)D;
 }
 
 template <int KC, int VEC>
 int launch_assign(const AssignP& p, int G, hipStream_t stream) {
-    const size_t lds = (size_t)KC * p.dt * 4 + (size_t)2 * p.k * 4;
-    static const int attr_rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kmeans_assign_kernel<KC, VEC>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, KM_LDS + 2 * KM_MAX_K * 4);
-    VSOM_REQUIRE(attr_rc == 0, VSOM_EUNSUPPORTED, "kmeans_assign: cannot reserve %d bytes of LDS", KM_LDS);
-    VSOM_LAUNCH((kmeans_assign_kernel<KC, VEC>), dim3(G), dim3(KM_THREADS), lds, stream, p);
-    return launch_status("kmeans_assign_kernel");
-}
-
-// centre tile width: the largest multiple of 64*VEC with KC*dt floats in KM_LDS, not wider than D needs
-inline int km_tile(int KC, int VEC, int D) {
-    const int unit = 64 * VEC;
-    int dt = (KM_LDS / (KC * 4)) / unit * unit;
-    const int need = cdiv(D, unit) * unit;
-    return dt < need ? dt : need;
+    return row_tile_launch<AssignP, kmeans_assign_kernel<KC, VEC>>(p, G, KM_THREADS, (size_t)KC * p.dt * 4 + (size_t)2 * p.k * 4,
+                                                                   KM_LDS + 2 * KM_MAX_K * 4, "kmeans_assign_kernel", stream);
 }
 
 }  // namespace
@@ -476,20 +419,19 @@ int vsom_kmeans_assign(const float* X, long ldx, long N, int D, const float* cen
     p.X = X; p.ldx = ldx; p.N = N; p.D = D; p.k = k; p.C = centers;
     p.labels = labels; p.prev = prev_labels; p.mind = mind;
     p.slabs = w.slabs; p.cnt = w.cnt; p.chg = w.chg;
-    p.rows_per_group = cdiv(N, w.G);            // every one of the G workgroups gets rows (not rounded to 32)
-    const int G = cdiv(N, p.rows_per_group);
+    p.rows_per_group = w.rows_per_group;
     const bool vec = D % 4 == 0 && ldx % 4 == 0 && aligned16(X) && aligned16(centers);
     const int KC = k <= 4 ? 4 : k <= 8 ? 8 : k <= 12 ? 12 : 16;
-    p.dt = km_tile(KC, vec ? 4 : 1, D);
+    p.dt = row_tile_width(KM_LDS, 1, KC, vec ? 4 : 1, D);
     switch (KC * 2 + (vec ? 1 : 0)) {
-        case 9: return launch_assign<4, 4>(p, G, stream);
-        case 8: return launch_assign<4, 1>(p, G, stream);
-        case 17: return launch_assign<8, 4>(p, G, stream);
-        case 16: return launch_assign<8, 1>(p, G, stream);
-        case 25: return launch_assign<12, 4>(p, G, stream);
-        case 24: return launch_assign<12, 1>(p, G, stream);
-        case 33: return launch_assign<16, 4>(p, G, stream);
-        default: return launch_assign<16, 1>(p, G, stream);
+        case 9: return launch_assign<4, 4>(p, w.G, stream);
+        case 8: return launch_assign<4, 1>(p, w.G, stream);
+        case 17: return launch_assign<8, 4>(p, w.G, stream);
+        case 16: return launch_assign<8, 1>(p, w.G, stream);
+        case 25: return launch_assign<12, 4>(p, w.G, stream);
+        case 24: return launch_assign<12, 1>(p, w.G, stream);
+        case 33: return launch_assign<16, 4>(p, w.G, stream);
+        default: return launch_assign<16, 1>(p, w.G, stream);
     }
 }
 
@@ -502,12 +444,10 @@ int vsom_kmeans_update(const float* centers_old, float* centers_new, long N, int
     VSOM_REQUIRE(ws && aligned16(ws) && ws_bytes >= vsom_kmeans_workspace_bytes(N, D, k), VSOM_EWORKSPACE,
                  "kmeans_update: workspace too small or misaligned");
     const KmWs w = km_layout(ws, N, D, k);
-    const long rpg = cdiv(N, w.G);
-    const int G = cdiv(N, rpg);                  // the workgroups vsom_kmeans_assign ran
     const int P = km_shift_blocks(D, k);
-    VSOM_LAUNCH(kmeans_counts_kernel, dim3(1), dim3(KM_RED_THREADS), 0, stream, w.cnt, w.chg, G, k, mind, N, counts, w.amax,
+    VSOM_LAUNCH(kmeans_counts_kernel, dim3(1), dim3(KM_RED_THREADS), 0, stream, w.cnt, w.chg, w.G, k, mind, N, counts, w.amax,
                 status);
-    VSOM_LAUNCH(kmeans_centres_kernel, dim3(P), dim3(KM_RED_THREADS), 0, stream, w.slabs, G, k, D, w.sums, counts, w.amax, centers_old,
+    VSOM_LAUNCH(kmeans_centres_kernel, dim3(P), dim3(KM_RED_THREADS), 0, stream, w.slabs, w.G, k, D, w.sums, counts, w.amax, centers_old,
                 centers_new, w.part);
     VSOM_LAUNCH(kmeans_shift_kernel, dim3(1), dim3(KM_RED_THREADS), 0, stream, w.part, P, status);
     return launch_status("kmeans_update");

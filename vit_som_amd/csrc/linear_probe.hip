@@ -45,22 +45,20 @@ RowPlan row_plan(long N, int C) {
     long nb = (N + 4L * p.slots - 1) / (4L * p.slots);          // four rows to a slot at least
     if (nb > PROBE_MAX_BLOCKS) nb = PROBE_MAX_BLOCKS;
     if (nb < 1) nb = 1;
-    p.rows_per = (N + nb - 1) / nb;
-    p.rows_per = (p.rows_per + p.slots - 1) / p.slots * p.slots;
-    p.nblk = (int)((N + p.rows_per - 1) / p.rows_per);
+    const Split rows = even_split(N, nb, p.slots);              // whole slots to a block
+    p.rows_per = rows.per;
+    p.nblk = rows.count;
     return p;
 }
 
 struct VecPlan { int nblk; long chunks_per; };
 VecPlan vec_plan(long n, int max_blocks) {
     VecPlan p;
-    const long chunks = (n + LB_CHUNK - 1) / LB_CHUNK;
-    long nb = chunks < max_blocks ? chunks : max_blocks;
-    if (nb < 1) nb = 1;
-    p.chunks_per = (chunks + nb - 1) / nb;
-    if (p.chunks_per < 1) p.chunks_per = 1;
-    p.nblk = (int)((chunks + p.chunks_per - 1) / p.chunks_per);
-    if (p.nblk < 1) p.nblk = 1;
+    long chunks = (n + LB_CHUNK - 1) / LB_CHUNK;
+    if (chunks < 1) chunks = 1;                                 // an empty vector still gets its one block
+    const Split s = even_split(chunks, chunks < max_blocks ? chunks : max_blocks);
+    p.chunks_per = s.per;
+    p.nblk = s.count;
     return p;
 }
 

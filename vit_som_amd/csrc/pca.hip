@@ -45,8 +45,9 @@ PcaPlan pca_plan(long N, int D, int l, int which) {
     if (s > PCA_MAX_SPLITS) s = PCA_MAX_SPLITS;
     if (s > p.ktiles) s = p.ktiles;
     if (s < 1) s = 1;
-    p.per = cdiv(p.ktiles, s);
-    p.splits = cdiv(p.ktiles, p.per);        // canonical: every split owns at least one k-tile
+    const Split ks = even_split(p.ktiles, s);  // every split owns at least one k-tile
+    p.per = (int)ks.per;
+    p.splits = ks.count;
     return p;
 }
 
@@ -58,8 +59,9 @@ CsPlan cs_plan(long N, int D) {
     const long most = (N + CS_MIN_ROWS - 1) / CS_MIN_ROWS;
     if (s > most) s = most;
     if (s < 1) s = 1;
-    p.rows_per = (N + s - 1) / s;
-    p.splits = (int)((N + p.rows_per - 1) / p.rows_per);
+    const Split rows = even_split(N, s);
+    p.rows_per = rows.per;
+    p.splits = rows.count;
     return p;
 }
 
