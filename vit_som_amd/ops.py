@@ -1,8 +1,17 @@
 """Tensor-level wrappers over the C-ABI (one per entry point of include/vitsom_hip.h).
 
-Every wrapper validates device / dtype / inner-stride, passes raw device pointers, row strides
-and torch's current HIP stream, and raises ``VsomError`` on a non-zero status.  Nothing here
-computes: there is no eager fallback.
+Every wrapper passes raw device pointers, row strides and torch's current HIP stream, and raises
+``VsomError`` on a non-zero status.  Nothing here computes: there is no eager fallback.
+
+This module is the only place that can tell a device pointer from a host pointer.  The training
+step's wrappers (above the `evaluation` banner) check device, dtype and inner stride of their
+matrices with ``_f32`` and the rest with ``assert``: the model owns every buffer it hands them.  The
+evaluation wrappers (from that banner to the RCCL section) take tensors from callers: every tensor
+whose address crosses into the library is checked there for device, dtype, layout and size by
+``_matrix`` / ``_dense`` / ``_buffer``, None passes only where the docstring says optional, and a
+refusal is a ``ValueError`` naming the argument, raised before anything is launched, ``python -O``
+or not.  A buffer whose element count goes to the entry (a workspace, ``zpart``, ``part``) is sized
+by the entry, which refuses a short one before it launches.
 """
 from contextlib import contextmanager
 from typing import Optional
@@ -84,6 +93,69 @@ def _f32(t: torch.Tensor, name: str, inner_contig: bool = True):
 
 def _rows(t: torch.Tensor) -> int:
     return t.stride(0) if t.dim() == 2 and t.shape[0] > 1 else t.shape[-1]
+
+
+# The argument checks of the evaluation wrappers (everything below the `evaluation` banner): each tensor whose address goes
+# to the library passes one of _matrix / _dense / _buffer first.  They raise ValueError, so they hold under `python -O`.
+_Tensor, _I32, _I64, _F32, _F64, _U8 = torch.Tensor, torch.int32, torch.int64, torch.float32, torch.float64, torch.uint8
+
+
+def _device(t, name, dtype):
+    """Refuses what is not a tensor, not on the device or not of `dtype` (None: any): the first half of every refusal
+    below, which test everything in one expression first because a loop of an estimator calls them every iteration."""
+    if not isinstance(t, _Tensor):
+        raise ValueError(f"{name}: expected a tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise ValueError(f"{name}: expected a HIP device tensor (vit_som_amd has no CPU path)")
+    if dtype is not None and t.dtype != dtype:
+        raise ValueError(f"{name}: expected {str(dtype)[6:]}, got {t.dtype}")
+
+
+def _matrix(t, name, rows=None, cols=None, optional=False):
+    """A row matrix: float32 on the device, 2-D, innermost stride 1, any row stride (a padded or guarded view passes), with
+    `rows` / `cols` rows and columns where given -> (rows, cols, row stride); (0, 0, 0) for an optional None."""
+    if t is None and optional:
+        return 0, 0, 0
+    if isinstance(t, _Tensor) and t.is_cuda and t.dtype == _F32 and t.dim() == 2:
+        r, c = t.shape
+        if (t.stride(1) == 1 or not t.numel()) and (rows is None or rows == r) and (cols is None or cols == c):
+            return r, c, (t.stride(0) if r > 1 else c)
+    _device(t, name, _F32)
+    raise ValueError(f"{name}: expected a [{'any' if rows is None else rows}, {'any' if cols is None else cols}] matrix with "
+                     f"innermost stride 1, got shape {tuple(t.shape)} with strides {t.stride()}")
+
+
+def _dense(t, name, dtype, shape, optional=False):
+    """A dense tensor: `dtype` on the device, contiguous (a storage offset is fine), of exactly `shape`: a tuple, None in it
+    for an extent the tensor itself sets, or an int for that many elements in any shape.  -> t."""
+    if t is None and optional:
+        return t
+    if isinstance(t, _Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous():
+        if isinstance(shape, int):
+            if t.numel() == shape:
+                return t
+        elif t.shape == shape:
+            return t
+        elif t.dim() == len(shape):
+            for want, got in zip(shape, t.shape):
+                if want is not None and want != got:
+                    break
+            else:
+                return t
+    _device(t, name, dtype)
+    want = f"{shape} elements" if isinstance(shape, int) else f"shape {shape}"
+    raise ValueError(f"{name}: expected a contiguous tensor of {want}, got shape {tuple(t.shape)} with strides {t.stride()}")
+
+
+def _buffer(t, name, dtype, n=0, optional=False):
+    """A buffer: `dtype` (None: any) on the device, contiguous, at least n elements (a longer one passes).  -> t."""
+    if t is None and optional:
+        return t
+    if isinstance(t, _Tensor) and t.is_cuda and (dtype is None or t.dtype == dtype) and t.is_contiguous() and t.numel() >= n:
+        return t
+    _device(t, name, dtype)
+    raise ValueError(f"{name}: expected a contiguous buffer of at least {n} elements, got shape {tuple(t.shape)} with strides "
+                     f"{t.stride()}")
 
 
 # ---------------------------------------------------------------- linear
@@ -676,73 +748,71 @@ def reduce_slabs(slabs, out):
 
 # ---------------------------------------------------------------- evaluation
 def contingency(a, b, table, bad):
-    """table[a[i], b[i]] += 1 (int64 device tensors; table is [na, nb] int64, accumulated)."""
-    assert a.dtype == torch.int64 and b.dtype == torch.int64 and table.dtype == torch.int64 and bad.dtype == torch.int32
-    assert a.is_cuda and a.is_contiguous() and b.is_contiguous() and table.is_contiguous() and a.numel() == b.numel()
-    na, nb = table.shape
-    check(lib.vsom_contingency(ptr(a), ptr(b), a.numel(), na, nb, ptr(table), ptr(bad), stream()), "vsom_contingency")
+    """table[a[i], b[i]] += 1 (a, b: contiguous int64 device tensors of one size; table is [na, nb] int64, accumulated;
+    bad int32 [1] counts the pairs outside it)."""
+    n = _buffer(a, "a", _I64).numel()
+    _dense(b, "b", _I64, n)
+    na, nb = _dense(table, "table", _I64, (None, None)).shape
+    _dense(bad, "bad", _I32, 1)
+    check(lib.vsom_contingency(ptr(a), ptr(b), n, na, nb, ptr(table), ptr(bad), stream()), "vsom_contingency")
     return table
 
 
 def argmax_rows(x, out):
-    rows, cols = x.shape
-    _f32(x, "x")
-    assert out.dtype == torch.int64
-    check(lib.vsom_argmax_rows(ptr(x), _rows(x), rows, cols, ptr(out), stream()), "vsom_argmax_rows")
+    """out int64 [rows] = the first argmax of every row of x f32 [rows, cols] (any row stride)."""
+    rows, cols, ldx = _matrix(x, "x")
+    _dense(out, "out", _I64, rows)
+    check(lib.vsom_argmax_rows(ptr(x), ldx, rows, cols, ptr(out), stream()), "vsom_argmax_rows")
     return out
 
 
 def proto_mosaic(pred, n, p, C, k0, map_size, images=None, canvas=None, gap=1):
     """Decoder output `pred` [chunk * (n + 1), p*p*C] -> images[k0 : k0 + chunk] ([K, C, S, S] float32) and / or the cells
-    k0 .. k0 + chunk - 1 of the uint8 RGB `canvas` of the rows x cols map (see vsom_proto_mosaic)."""
-    _f32(pred, "pred")
+    k0 .. k0 + chunk - 1 of the uint8 RGB `canvas` of the rows x cols map (see vsom_proto_mosaic); both optional."""
     rows, cols = int(map_size[0]), int(map_size[1])
     K, pd = rows * cols, p * p * C
-    assert pred.is_contiguous() and pred.dim() == 2 and pred.shape[1] == pd and pred.shape[0] % (n + 1) == 0
+    _dense(pred, "pred", _F32, (None, pd))
+    if pred.shape[0] % (n + 1):
+        raise ValueError(f"pred: {pred.shape[0]} rows are not a whole number of images of {n} + 1 rows")
     chunk, S = pred.shape[0] // (n + 1), int(round(n ** 0.5)) * p
-    if images is not None:
-        _f32(images, "images")
-        assert images.is_contiguous() and tuple(images.shape) == (K, C, S, S)
-    if canvas is not None:
-        assert canvas.is_cuda and canvas.dtype == torch.uint8 and canvas.is_contiguous()
-        assert tuple(canvas.shape) ==(rows * S + (rows - 1) * gap, cols * S + (cols - 1) * gap, 3)
+    _dense(images, "images", _F32, (K, C, S, S), optional=True)
+    _dense(canvas, "canvas", _U8, (rows * S + (rows - 1) * gap, cols * S + (cols - 1) * gap, 3), optional=True)
     check(lib.vsom_proto_mosaic(ptr(pred), chunk, int(n), int(p), int(C), ptr(images), ptr(canvas), int(k0), K, rows, cols,
                                 int(gap), stream()), "vsom_proto_mosaic")
 
 
 def last_label(bmu, label, first_ordinal, cells, bad):
-    """cells[bmu[i]] = max(cells[bmu[i]], (first_ordinal + i + 1) << 32 | label[i]) (cells: [K] int64, zeroed by the caller)."""
-    assert bmu.dtype == torch.int64 and label.dtype == torch.int64 and cells.dtype == torch.int64 and bad.dtype == torch.int32
-    assert bmu.is_cuda and bmu.is_contiguous() and label.is_contiguous() and cells.is_contiguous() and bmu.numel() == label.numel()
-    check(lib.vsom_last_label(ptr(bmu), ptr(label), bmu.numel(), int(first_ordinal), cells.numel(), ptr(cells), ptr(bad),
+    """cells[bmu[i]] = max(cells[bmu[i]], (first_ordinal + i + 1) << 32 | label[i]) (bmu, label: contiguous int64 of one
+    size; cells: [K] int64, zeroed by the caller; bad int32 [1])."""
+    n = _buffer(bmu, "bmu", _I64).numel()
+    _dense(label, "label", _I64, n)
+    _buffer(cells, "cells", _I64)
+    _dense(bad, "bad", _I32, 1)
+    check(lib.vsom_last_label(ptr(bmu), ptr(label), n, int(first_ordinal), cells.numel(), ptr(cells), ptr(bad),
                               stream()), "vsom_last_label")
     return cells
 
 
 def map_stats(dist, bmu, grid_positions, adj_r2, first_ordinal, hits, qe_fix, te, nearest, bad, second=None):
-    """One batch folded into the map-quality accumulators (see vsom_map_stats): hits / qe_fix [K] and te [1] int64 zeroed by
-    the caller, nearest [K] int64 set to -1 (all-ones), bad [1] int32; `second` [B] int64 receives the runner-up units."""
-    _f32(dist, "dist")
-    _f32(grid_positions, "grid_positions")
-    B, K = dist.shape
-    assert dist.is_contiguous() and grid_positions.is_contiguous() and tuple(grid_positions.shape) == (K, 2)
-    assert bmu.dtype == torch.int64 and bmu.is_contiguous() and bmu.numel() == B
-    for t, n in ((hits, K), (qe_fix, K), (te, 1), (nearest, K)):
-        assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and t.numel() == n
-    assert bad.dtype == torch.int32 and bad.numel() == 1
-    if second is not None:
-        assert second.dtype == torch.int64 and second.is_contiguous() and second.numel() == B
+    """One batch folded into the map-quality accumulators (see vsom_map_stats): dist f32 [B, K] contiguous, bmu int64 [B],
+    hits / qe_fix [K] and te [1] int64 zeroed by the caller, nearest [K] int64 set to -1 (all-ones), bad [1] int32;
+    `second` [B] int64 (optional) receives the runner-up units."""
+    B, K = _dense(dist, "dist", _F32, (None, None)).shape
+    _dense(grid_positions, "grid_positions", _F32, (K, 2))
+    _dense(bmu, "bmu", _I64, B)
+    _dense(hits, "hits", _I64, K); _dense(qe_fix, "qe_fix", _I64, K); _dense(te, "te", _I64, 1); _dense(nearest, "nearest", _I64, K)
+    _dense(bad, "bad", _I32, 1)
+    _dense(second, "second", _I64, B, optional=True)
     check(lib.vsom_map_stats(ptr(dist), ptr(bmu), B, K, ptr(grid_positions), float(adj_r2), int(first_ordinal), ptr(hits),
                              ptr(qe_fix), ptr(te), ptr(nearest), ptr(bad), ptr(second), stream()), "vsom_map_stats")
 
 
 def umatrix(W, grid_positions, adj_r2, distance):
-    """-> (u [K] f32, nbr_idx [K, 8] int32, nbr_dist [K, 8] f32) on the device (see vsom_umatrix).  The status word is read
-    here, after the launch: a unit with more than 8 units within adj_r2 raises VsomError (VSOM_EUNSUPPORTED)."""
-    _f32(W, "W")
-    _f32(grid_positions, "grid_positions")
-    K, L = W.shape
-    assert W.is_contiguous() and grid_positions.is_contiguous() and tuple(grid_positions.shape) == (K, 2)
+    """-> (u [K] f32, nbr_idx [K, 8] int32, nbr_dist [K, 8] f32) on the device (see vsom_umatrix) of W f32 [K, L] contiguous
+    and grid_positions f32 [K, 2].  The status word is read here, after the launch: a unit with more than 8 units within
+    adj_r2 raises VsomError (VSOM_EUNSUPPORTED)."""
+    K, L = _dense(W, "W", _F32, (None, None)).shape
+    _dense(grid_positions, "grid_positions", _F32, (K, 2))
     u = torch.empty(K, dtype=torch.float32, device=W.device)
     nbr_idx = torch.empty(K, 8, dtype=torch.int32, device=W.device)
     nbr_dist = torch.empty(K, 8, dtype=torch.float32, device=W.device)
@@ -759,34 +829,31 @@ def umatrix(W, grid_positions, adj_r2, distance):
 AUGMENT_PARAMS = 16
 
 
+def _crops(scale, log_ratio, scale2, log_ratio2):
+    """The crop-box arguments of the two plan entries; scale2 = None: one crop."""
+    s2, l2 = (scale2, log_ratio2) if scale2 is not None else ((0.0, 0.0), (0.0, 0.0))
+    return (float(scale[0]), float(scale[1]), float(log_ratio[0]), float(log_ratio[1]), int(scale2 is not None), float(s2[0]),
+            float(s2[1]), float(l2[0]), float(l2[1]))
+
+
 def augment_plan(index, params, N, H, S, scale, log_ratio, scale2, log_ratio2, flip_p, erase_p, seed, epoch):
-    """params[b] <- the augmentation plan of row index[b] of a data set of N rows in `epoch` (see vsom_augment_plan);
-    scale2 = None: one crop."""
-    assert index.is_cuda and index.dtype == torch.int64 and index.is_contiguous() and index.dim() == 1
-    assert params.is_cuda and params.dtype == torch.int32 and params.is_contiguous()
-    assert params.dim() == 2 and params.shape[0] >= index.numel() and params.shape[1] == AUGMENT_PARAMS
-    two = scale2 is not None
-    s2, l2 = (scale2, log_ratio2) if two else ((0.0, 0.0), (0.0, 0.0))
-    check(lib.vsom_augment_plan(ptr(index), int(N), index.numel(), int(H), int(S), float(scale[0]), float(scale[1]), float(log_ratio[0]),
-                                float(log_ratio[1]), int(two), float(s2[0]), float(s2[1]), float(l2[0]), float(l2[1]),
+    """params[b] <- the augmentation plan of row index[b] (int64 [B]) of a data set of N rows in `epoch` (see
+    vsom_augment_plan); params int32 [>= B, AUGMENT_PARAMS] (a longer buffer passes); scale2 = None: one crop."""
+    B = _dense(index, "index", _I64, (None,)).numel()
+    _buffer(params, "params", _I32, B * AUGMENT_PARAMS)
+    check(lib.vsom_augment_plan(ptr(index), int(N), B, int(H), int(S), *_crops(scale, log_ratio, scale2, log_ratio2),
                                 float(flip_p), float(erase_p), int(seed), int(epoch), ptr(params), stream()), "vsom_augment_plan")
     return params
 
 
 def augment_batch(src, index, params, out, S, R, off, mean, std, seed, epoch, out_u8=None):
     """out[b] <- the transformed row index[b] of the uint8 set `src` [N, C, H, W] (see vsom_augment_batch); params = None: the
-    whole image, no flip, no erase."""
-    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 4
-    assert index.is_cuda and index.dtype == torch.int64 and index.is_contiguous() and index.dim() == 1
-    N, C, H, W = src.shape
-    B = index.numel()
-    _f32(out, "out"), _f32(mean, "mean"), _f32(std, "std")
-    assert out.is_contiguous() and out.numel() >= B * C * S * S and mean.numel() == C and std.numel() == C
-    if params is not None:
-        assert params.is_cuda and params.dtype == torch.int32 and params.is_contiguous()
-        assert params.shape[0] >= B and params.shape[1] == AUGMENT_PARAMS
-    if out_u8 is not None:
-        assert out_u8.is_cuda and out_u8.dtype == torch.uint8 and out_u8.is_contiguous() and out_u8.numel() >= B * C * S * S
+    whole image, no flip, no erase; out_u8 optional.  out, out_u8 and params may be longer than the batch needs."""
+    N, C, H, W = _dense(src, "src", _U8, (None,) * 4).shape
+    B = _dense(index, "index", _I64, (None,)).numel()
+    _buffer(params, "params", _I32, B * AUGMENT_PARAMS, optional=True)
+    _buffer(out, "out", _F32, B * C * S * S); _buffer(out_u8, "out_u8", _U8, B * C * S * S, optional=True)
+    _dense(mean, "mean", _F32, C); _dense(std, "std", _F32, C)
     check(lib.vsom_augment_batch(ptr(src), N, C, H, W, ptr(index), ptr(params), B, int(S), int(R), int(off), ptr(mean), ptr(std),
                                  int(seed), int(epoch), ptr(out), ptr(out_u8), stream()), "vsom_augment_batch")
     return out
@@ -797,32 +864,29 @@ RANDAUG_PARAMS = 72
 
 def _pack_fill(fill):
     fill = tuple(int(v) for v in fill) + (0,) * (3 - len(fill))
-    assert len(fill) == 3 and all(0 <= v <= 255 for v in fill)
+    if len(fill) != 3 or not all(0 <= v <= 255 for v in fill):
+        raise ValueError(f"fill: expected up to three levels in [0, 255], got {fill}")
     return fill[0] | fill[1] << 8 | fill[2] << 16
 
 
 def randaug_plan(index, ra, N, S, randaug_n, autoaugment, flip1_p, fill_tv, fill_timm, seed, epoch):
-    """ra[b] <- the RandAugment / rand-m9 record of row index[b] in `epoch` (see vsom_randaug_plan); fills: one level per channel."""
-    assert index.is_cuda and index.dtype == torch.int64 and index.is_contiguous() and index.dim() == 1
-    assert ra.is_cuda and ra.dtype == torch.int32 and ra.is_contiguous()
-    assert ra.dim() == 2 and ra.shape[0] >= index.numel() and ra.shape[1] == RANDAUG_PARAMS
-    check(lib.vsom_randaug_plan(ptr(index), int(N), index.numel(), int(S), int(randaug_n), int(bool(autoaugment)), float(flip1_p),
+    """ra[b] <- the RandAugment / rand-m9 record of row index[b] in `epoch` (see vsom_randaug_plan); ra int32
+    [>= B, RANDAUG_PARAMS] (a longer buffer passes); fills: one level per channel."""
+    B = _dense(index, "index", _I64, (None,)).numel()
+    _buffer(ra, "ra", _I32, B * RANDAUG_PARAMS)
+    check(lib.vsom_randaug_plan(ptr(index), int(N), B, int(S), int(randaug_n), int(bool(autoaugment)), float(flip1_p),
                                 _pack_fill(fill_tv), _pack_fill(fill_timm), int(seed), int(epoch), ptr(ra), stream()), "vsom_randaug_plan")
     return ra
 
 
 def augment_batch_ra(src, index, params, ra, out, S, mean, std, seed, epoch, out_u8=None):
-    """out[b] <- the training transform of row index[b] with the op slots of `ra` between the crops (see vsom_augment_batch_ra)."""
-    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 4
-    assert index.is_cuda and index.dtype == torch.int64 and index.is_contiguous() and index.dim() == 1
-    N, C, H, W = src.shape
-    B = index.numel()
-    _f32(out, "out"), _f32(mean, "mean"), _f32(std, "std")
-    assert out.is_contiguous() and out.numel() >= B * C * S * S and mean.numel() == C and std.numel() == C
-    for t, width in ((params, AUGMENT_PARAMS), (ra, RANDAUG_PARAMS)):
-        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.shape[0] >= B and t.shape[1] == width
-    if out_u8 is not None:
-        assert out_u8.is_cuda and out_u8.dtype == torch.uint8 and out_u8.is_contiguous() and out_u8.numel() >= B * C * S * S
+    """out[b] <- the training transform of row index[b] with the op slots of `ra` between the crops (see vsom_augment_batch_ra);
+    params and ra are both needed, out_u8 is optional."""
+    N, C, H, W = _dense(src, "src", _U8, (None,) * 4).shape
+    B = _dense(index, "index", _I64, (None,)).numel()
+    _buffer(params, "params", _I32, B * AUGMENT_PARAMS); _buffer(ra, "ra", _I32, B * RANDAUG_PARAMS)
+    _buffer(out, "out", _F32, B * C * S * S); _buffer(out_u8, "out_u8", _U8, B * C * S * S, optional=True)
+    _dense(mean, "mean", _F32, C); _dense(std, "std", _F32, C)
     check(lib.vsom_augment_batch_ra(ptr(src), N, C, H, W, ptr(index), ptr(params), ptr(ra), B, int(S), ptr(mean), ptr(std), int(seed),
                                     int(epoch), ptr(out), ptr(out_u8), stream()), "vsom_augment_batch_ra")
     return out
@@ -830,16 +894,13 @@ def augment_batch_ra(src, index, params, ra, out, S, mean, std, seed, epoch, out
 
 # ---------------------------------------------------------------- data pipeline, image sets of varying size
 def augment_plan_ragged(index, shapes, params, S, scale, log_ratio, scale2, log_ratio2, flip_p, erase_p, seed, epoch):
-    """augment_plan with box 1 drawn on each sample's own (H_n, W_n) = shapes[index[b]] (see vsom_augment_plan_ragged)."""
-    assert index.is_cuda and index.dtype == torch.int64 and index.is_contiguous() and index.dim() == 1
-    assert shapes.is_cuda and shapes.dtype == torch.int32 and shapes.is_contiguous() and shapes.dim() == 2 and shapes.shape[1] == 2
-    assert params.is_cuda and params.dtype == torch.int32 and params.is_contiguous()
-    assert params.dim() == 2 and params.shape[0] >= index.numel() and params.shape[1] == AUGMENT_PARAMS
-    two = scale2 is not None
-    s2, l2 = (scale2, log_ratio2) if two else ((0.0, 0.0), (0.0, 0.0))
-    check(lib.vsom_augment_plan_ragged(ptr(index), ptr(shapes), shapes.shape[0], index.numel(), int(S), float(scale[0]), float(scale[1]),
-                                       float(log_ratio[0]), float(log_ratio[1]), int(two), float(s2[0]), float(s2[1]), float(l2[0]),
-                                       float(l2[1]), float(flip_p), float(erase_p), int(seed), int(epoch), ptr(params), stream()),
+    """augment_plan with box 1 drawn on each sample's own (H_n, W_n) = shapes[index[b]], shapes int32 [N, 2] (see
+    vsom_augment_plan_ragged)."""
+    B = _dense(index, "index", _I64, (None,)).numel()
+    _dense(shapes, "shapes", _I32, (None, 2))
+    _buffer(params, "params", _I32, B * AUGMENT_PARAMS)
+    check(lib.vsom_augment_plan_ragged(ptr(index), ptr(shapes), shapes.shape[0], B, int(S), *_crops(scale, log_ratio, scale2, log_ratio2),
+                                       float(flip_p), float(erase_p), int(seed), int(epoch), ptr(params), stream()),
           "vsom_augment_plan_ragged")
     return params
 
@@ -850,22 +911,17 @@ def augment_ragged_scratch_bytes(B: int, C: int, S: int) -> int:
 
 def augment_batch_ragged(data, offsets, shapes, C, max_h, max_w, index, params, out, S, R, mean, std, seed, epoch, scratch=None,
                          out_u8=None):
-    """out[b] <- the transformed image index[b] of the ragged uint8 set (data, offsets, shapes) (see vsom_augment_batch_ragged);
-    params = None: the evaluation transform Resize(R) -> CenterCrop(S); otherwise `scratch` (uint8,
-    augment_ragged_scratch_bytes(B, C, S)) holds the image between the two crops."""
-    assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous() and data.dim() == 1
-    assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.dim() == 1
-    assert shapes.is_cuda and shapes.dtype == torch.int32 and shapes.is_contiguous() and tuple(shapes.shape) == (offsets.numel(), 2)
-    assert index.is_cuda and index.dtype == torch.int64 and index.is_contiguous() and index.dim() == 1
-    N, B = offsets.numel(), index.numel()
-    _f32(out, "out"), _f32(mean, "mean"), _f32(std, "std")
-    assert out.is_contiguous() and out.numel() >= B * C * S * S and mean.numel() == C and std.numel() == C
-    if params is not None:
-        assert params.is_cuda and params.dtype == torch.int32 and params.is_contiguous()
-        assert params.shape[0] >= B and params.shape[1] == AUGMENT_PARAMS
-        assert scratch is not None and scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous()
-    if out_u8 is not None:
-        assert out_u8.is_cuda and out_u8.dtype == torch.uint8 and out_u8.is_contiguous() and out_u8.numel() >= B * C * S * S
+    """out[b] <- the transformed image index[b] of the ragged uint8 set (data [bytes], offsets int64 [N], shapes int32 [N, 2])
+    (see vsom_augment_batch_ragged); params = None: the evaluation transform Resize(R) -> CenterCrop(S), and `scratch` is
+    optional; otherwise `scratch` (uint8, augment_ragged_scratch_bytes(B, C, S); the entry checks its size) holds the image
+    between the two crops.  out_u8 optional."""
+    _dense(data, "data", _U8, (None,))
+    N = _dense(offsets, "offsets", _I64, (None,)).numel()
+    _dense(shapes, "shapes", _I32, (N, 2))
+    B = _dense(index, "index", _I64, (None,)).numel()
+    _buffer(params, "params", _I32, B * AUGMENT_PARAMS, optional=True); _buffer(scratch, "scratch", _U8, optional=params is None)
+    _buffer(out, "out", _F32, B * C * S * S); _buffer(out_u8, "out_u8", _U8, B * C * S * S, optional=True)
+    _dense(mean, "mean", _F32, C); _dense(std, "std", _F32, C)
     check(lib.vsom_augment_batch_ragged(ptr(data), data.numel(), ptr(offsets), ptr(shapes), N, int(C), int(max_h), int(max_w),
                                         ptr(index), ptr(params), B, int(S), int(R), ptr(mean), ptr(std), int(seed), int(epoch),
                                         ptr(scratch), 0 if scratch is None else scratch.numel(), ptr(out), ptr(out_u8), stream()),
@@ -878,54 +934,55 @@ def kmeans_workspace_bytes(N: int, D: int, k: int) -> int:
     return lib.vsom_kmeans_workspace_bytes(N, D, k)
 
 
-def _kmeans_x(X):
-    _f32(X, "X")
-    assert X.dim() == 2, "X must be [N, D]"
-    return X.shape[0], X.shape[1], _rows(X)
-
-
 def kmeans_assign(X, centers, labels, prev_labels, mind, ws):
-    """One Lloyd E-step + partial M-step: labels / mind written, cluster partials into ws."""
-    N, D, ldx = _kmeans_x(X)
-    _f32(centers, "centers"); _f32(mind, "mind")
-    assert centers.is_contiguous() and centers.shape[1] == D and labels.dtype == torch.int64 and prev_labels.dtype == torch.int64
-    assert labels.numel() == N and prev_labels.numel() == N and mind.numel() == N
-    check(lib.vsom_kmeans_assign(ptr(X), ldx, N, D, ptr(centers), centers.shape[0], ptr(labels), ptr(prev_labels), ptr(mind),
-                                 ptr(ws), ws.numel() * ws.element_size(), stream()), "vsom_kmeans_assign")
+    """One Lloyd E-step + partial M-step on X f32 [N, D] (any row stride) and centers f32 [k, D]: labels int64 [N] (from
+    prev_labels, likewise) and mind f32 [N] written, cluster partials into ws (kmeans_workspace_bytes(N, D, k) bytes)."""
+    N, D, ldx = _matrix(X, "X")
+    k = _dense(centers, "centers", _F32, (None, D)).shape[0]
+    _dense(labels, "labels", _I64, N); _dense(prev_labels, "prev_labels", _I64, N); _dense(mind, "mind", _F32, N)
+    _buffer(ws, "ws", None)
+    check(lib.vsom_kmeans_assign(ptr(X), ldx, N, D, ptr(centers), k, ptr(labels), ptr(prev_labels), ptr(mind), ptr(ws),
+                                 ws.numel() * ws.element_size(), stream()), "vsom_kmeans_assign")
 
 
 def kmeans_update(centers_old, centers_new, N, mind, counts, status, ws):
-    """centers_new, counts [k] int64 and status [4] fp64 = (changed, center_shift_tot, empty, inertia)."""
-    k, D = centers_old.shape
-    assert centers_new.is_contiguous() and centers_old.is_contiguous() and counts.dtype == torch.int64 and status.dtype == torch.float64
+    """centers_new f32 [k, D], counts [k] int64 and status [4] fp64 = (changed, center_shift_tot, empty, inertia) from
+    centers_old, mind f32 [N] and the ws kmeans_assign left."""
+    k, D = _dense(centers_old, "centers_old", _F32, (None, None)).shape
+    _dense(centers_new, "centers_new", _F32, (k, D)); _dense(mind, "mind", _F32, int(N))
+    _dense(counts, "counts", _I64, k); _dense(status, "status", _F64, 4); _buffer(ws, "ws", None)
     check(lib.vsom_kmeans_update(ptr(centers_old), ptr(centers_new), N, D, k, ptr(mind), ptr(counts), ptr(status), ptr(ws),
                                  ws.numel() * ws.element_size(), stream()), "vsom_kmeans_update")
 
 
 def kmeans_relocate(X, labels, moves, centers_old, centers_new, counts, status, ws):
-    """Apply the empty-cluster moves (int64 [m, 2] device tensor of (cluster, sample)) in order, then the centres again."""
-    N, D, ldx = _kmeans_x(X)
-    k = centers_old.shape[0]
-    assert moves.dtype == torch.int64 and moves.is_contiguous() and moves.is_cuda
+    """Apply the empty-cluster moves (int64 [m, 2] device tensor of (cluster, sample)) in order, then the centres again
+    (labels int64 [N], centres f32 [k, D], counts int64 [k], status fp64 [4] as in kmeans_update)."""
+    N, D, ldx = _matrix(X, "X")
+    k = _dense(centers_old, "centers_old", _F32, (None, D)).shape[0]
+    _dense(centers_new, "centers_new", _F32, (k, D)); _dense(labels, "labels", _I64, N)
+    _dense(moves, "moves", _I64, (None, 2)); _dense(counts, "counts", _I64, k); _dense(status, "status", _F64, 4)
+    _buffer(ws, "ws", None)
     check(lib.vsom_kmeans_relocate(ptr(X), ldx, N, D, k, ptr(labels), ptr(moves), moves.shape[0], ptr(centers_old),
                                    ptr(centers_new), ptr(counts), ptr(status), ptr(ws), ws.numel() * ws.element_size(),
                                    stream()), "vsom_kmeans_relocate")
 
 
 def kmeanspp_dist(X, candidates, closest, dist, pots):
-    """dist [T, N] = min(closest, squared distance to each candidate row); pots [T] fp64 = row sums of dist."""
-    N, D, ldx = _kmeans_x(X)
-    T = candidates.numel()
-    assert candidates.dtype == torch.int64 and candidates.is_cuda and dist.shape == (T, N) and dist.is_contiguous()
-    assert pots.dtype == torch.float64 and pots.numel() >= T
+    """dist f32 [T, N] = min(closest, squared distance to each candidate row) for candidates int64 [T]; closest f32 [N] is
+    optional (None: no minimum); pots fp64 [>= T] = row sums of dist."""
+    N, D, ldx = _matrix(X, "X")
+    T = _buffer(candidates, "candidates", _I64).numel()
+    _dense(closest, "closest", _F32, N, optional=True)
+    _dense(dist, "dist", _F32, (T, N)); _buffer(pots, "pots", _F64, T)
     check(lib.vsom_kmeanspp_dist(ptr(X), ldx, N, D, ptr(candidates), T, ptr(closest), ptr(dist), ptr(pots), stream()),
           "vsom_kmeanspp_dist")
 
 
 def kmeans_colvar(X, k, out, ws):
-    """out[0] = mean(var(X, axis=0)) in fp64."""
-    N, D, ldx = _kmeans_x(X)
-    assert out.dtype == torch.float64
+    """out fp64 [1] = mean(var(X, axis=0)) in fp64; ws as for kmeans_assign."""
+    N, D, ldx = _matrix(X, "X")
+    _dense(out, "out", _F64, 1); _buffer(ws, "ws", None)
     check(lib.vsom_kmeans_colvar(ptr(X), ldx, N, D, k, ptr(out), ptr(ws), ws.numel() * ws.element_size(), stream()),
           "vsom_kmeans_colvar")
 
@@ -937,10 +994,8 @@ UMAP_MAX_K = 64                                                  # csrc/knn.hip 
 def umap_knn(X, k, metric, knn_idx, knn_dist):
     """knn_idx int64 [N, k] / knn_dist f32 [N, k]: the exact k nearest rows of X (row itself first), ascending by
     (distance, index); metric DIST_EUCLIDEAN or DIST_COSINE."""
-    N, D, ldx = _kmeans_x(X)
-    assert knn_idx.dtype == torch.int64 and knn_idx.is_contiguous() and knn_idx.shape == (N, k)
-    _f32(knn_dist, "knn_dist")
-    assert knn_dist.is_contiguous() and knn_dist.shape == (N, k)
+    N, D, ldx = _matrix(X, "X")
+    _dense(knn_idx, "knn_idx", _I64, (N, k)); _dense(knn_dist, "knn_dist", _F32, (N, k))
     ws = scratch(lib.vsom_umap_knn_workspace_bytes(N, k), X.device)
     check(lib.vsom_umap_knn(ptr(X), ldx, N, D, int(k), int(metric), ptr(knn_idx), ptr(knn_dist), ptr(ws), ws.numel(),
                             stream()), "vsom_umap_knn")
@@ -953,14 +1008,13 @@ def umap_neg_sample(seed, epoch, edge, p, N) -> int:
 
 
 def umap_epoch(indptr, indices, eps, next_s, eps_neg, next_neg, Y_in, Y_out, a, b, gamma, alpha, epoch, seed):
-    """One synchronous layout epoch: Y_out from Y_in; next_s / next_neg (fp64 per edge) updated in place."""
-    N, dim = Y_in.shape
-    _f32(Y_in, "Y_in"); _f32(Y_out, "Y_out")
-    assert Y_in.is_contiguous() and Y_out.is_contiguous() and Y_out.shape == (N, dim)
-    assert indptr.dtype == indices.dtype == torch.int64 and indptr.numel() == N + 1
-    nnz = indices.numel()
-    for t in (eps, next_s, eps_neg, next_neg):
-        assert t.dtype == torch.float64 and t.is_contiguous() and t.numel() == nnz and t.is_cuda
+    """One synchronous layout epoch: Y_out from Y_in (f32 [N, dim]) over the CSR graph (indptr int64 [N + 1], indices int64
+    [nnz]); eps, next_s, eps_neg, next_neg fp64 [nnz], next_s / next_neg updated in place."""
+    N, dim = _dense(Y_in, "Y_in", _F32, (None, None)).shape
+    _dense(Y_out, "Y_out", _F32, (N, dim)); _dense(indptr, "indptr", _I64, N + 1)
+    nnz = _buffer(indices, "indices", _I64).numel()
+    _dense(eps, "eps", _F64, nnz); _dense(next_s, "next_s", _F64, nnz)
+    _dense(eps_neg, "eps_neg", _F64, nnz); _dense(next_neg, "next_neg", _F64, nnz)
     check(lib.vsom_umap_epoch(ptr(indptr), ptr(indices), ptr(eps), ptr(next_s), ptr(eps_neg), ptr(next_neg), ptr(Y_in),
                               ptr(Y_out), N, dim, float(a), float(b), float(gamma), float(alpha), int(epoch), int(seed),
                               stream()), "vsom_umap_epoch")
@@ -983,16 +1037,11 @@ def umap_transform_layout(knn_idx, weights, eps, Y_train, Y, a, b, gamma, initia
                           negative_sample_rate, seed, status, ws):
     """Epochs [epoch_begin, epoch_end) of the transform layout of Y [M, dim] against the fixed Y_train [N, dim] in one launch
     (epoch_begin == 0 writes the weighted-mean init first); knn_idx int64 / weights fp64 / eps fp64 [M, k]; status int32 [1]
-    (zeroed by the caller) counts refused edges; ws from umap_transform_workspace(M, k)."""
-    M, k = knn_idx.shape
-    N, dim = Y_train.shape
-    _f32(Y_train, "Y_train"); _f32(Y, "Y")
-    assert Y_train.is_contiguous() and Y.is_contiguous() and Y.shape == (M, dim)
-    assert knn_idx.dtype == torch.int64 and knn_idx.is_contiguous() and knn_idx.is_cuda
-    for t in (weights, eps):
-        assert t.dtype == torch.float64 and t.is_contiguous() and t.shape == (M, k) and t.is_cuda
-    assert status.dtype == torch.int32 and status.numel() == 1 and status.is_cuda
-    assert ws.dtype == torch.uint8 and ws.is_cuda and ws.is_contiguous()
+    (zeroed by the caller) counts refused edges; ws uint8 from umap_transform_workspace(M, k) (the entry checks its size)."""
+    M, k = _dense(knn_idx, "knn_idx", _I64, (None, None)).shape
+    N, dim = _dense(Y_train, "Y_train", _F32, (None, None)).shape
+    _dense(Y, "Y", _F32, (M, dim)); _dense(weights, "weights", _F64, (M, k)); _dense(eps, "eps", _F64, (M, k))
+    _dense(status, "status", _I32, 1); _buffer(ws, "ws", _U8)
     check(lib.vsom_umap_transform_layout(ptr(knn_idx), ptr(weights), ptr(eps), ptr(Y_train), N, ptr(Y), M, k, dim, float(a),
                                          float(b), float(gamma), float(initial_alpha), int(n_epochs), int(epoch_begin),
                                          int(epoch_end), int(negative_sample_rate), int(seed), ptr(status), ptr(ws), ws.numel(),
@@ -1009,15 +1058,10 @@ KNN_UNIFORM, KNN_DISTANCE, KNN_SOFTMAX = 0, 1, 2                 # VSOM_KNN_*
 def knn_query(Q, X, k, metric, idx, dist, index_base=0, accumulate=False, exclude=None):
     """idx int64 [Nq, k] / dist f32 [Nq, k]: the exact k nearest rows of the bank chunk X for every row of Q, as
     index_base + row, ascending by (distance, index); with accumulate the lists already in idx / dist (from other index
-    ranges) are folded with this chunk.  exclude int64 [Nq]: a global bank ordinal each query never receives."""
-    Nq, D, ldq = _kmeans_x(Q)
-    Nb, Db, ldx = _kmeans_x(X)
-    assert Db == D, "Q and X must have the same width"
-    assert idx.dtype == torch.int64 and idx.is_contiguous() and idx.shape == (Nq, k)
-    _f32(dist, "dist")
-    assert dist.is_contiguous() and dist.shape == (Nq, k)
-    if exclude is not None:
-        assert exclude.dtype == torch.int64 and exclude.is_cuda and exclude.is_contiguous() and exclude.numel() == Nq
+    ranges) are folded with this chunk.  exclude int64 [Nq] (optional): a global bank ordinal each query never receives."""
+    Nq, D, ldq = _matrix(Q, "Q")
+    Nb, _, ldx = _matrix(X, "X", cols=D)
+    _dense(idx, "idx", _I64, (Nq, k)); _dense(dist, "dist", _F32, (Nq, k)); _dense(exclude, "exclude", _I64, Nq, optional=True)
     ws = scratch(lib.vsom_knn_query_workspace_bytes(Nq, Nb, k), Q.device)
     check(lib.vsom_knn_query(ptr(Q), ldq, Nq, ptr(X), ldx, Nb, D, int(k), int(metric), int(index_base), int(bool(accumulate)),
                              ptr(exclude), ptr(idx), ptr(dist), ptr(ws), ws.numel(), stream()), "vsom_knn_query")
@@ -1030,11 +1074,9 @@ def knn_ranks(A, nbr, metric, less, tied):
     of umap_knn (same contraction, same order); -1 in both for an empty slot and for n == i.  An index outside [0, N) other
     than -1 is refused HERE, on the host (one device reduction and one synchronisation): the C entry has no status word
     and would treat it as an empty slot."""
-    N, D, lda = _kmeans_x(A)
-    assert nbr.dtype == torch.int64 and nbr.is_cuda and nbr.is_contiguous() and nbr.dim() == 2 and nbr.shape[0] == N
-    k = nbr.shape[1]
-    for t in (less, tied):
-        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.shape == (N, k)
+    N, D, lda = _matrix(A, "A")
+    k = _dense(nbr, "nbr", _I64, (N, None)).shape[1]
+    _dense(less, "less", _I32, (N, k)); _dense(tied, "tied", _I32, (N, k))
     n_bad = int(((nbr < -1) | (nbr >= N)).sum())
     if n_bad:
         raise ValueError(f"knn_ranks: {n_bad} neighbour indices outside [0, {N}) (-1 marks an empty slot)")
@@ -1061,12 +1103,12 @@ def silhouette(X, labels, metric, n_clusters, ws=None, details=True):
     """Silhouette coefficient of the rows of X [N, D] (f32) under labels int64 [N] in [0, n_clusters) -> Silhouette:
     sil f64 [N], a / b f64 [N] and nearest int64 [N] (None without `details`), counts int64 [C], cluster_mean f64 [C],
     score f64 [1], status (host ints: rows with a label out of range, refused distances, non-empty clusters, singleton
-    clusters) and, with a workspace from silhouette_workspace, sums int64 [N, C]: the fixed-point distance sums.
-    One synchronisation, to read status.  A NaN or infinite input (status[1] != 0) raises ValueError; a label outside the
-    range does not: that row gets NaN, counts for nothing and is reported in status[0]."""
-    N, D, ldx = _kmeans_x(X)
+    clusters) and, with a workspace (optional, uint8) from silhouette_workspace, sums int64 [N, C]: the fixed-point distance
+    sums.  One synchronisation, to read status.  A NaN or infinite input (status[1] != 0) raises ValueError; a label outside
+    the range does not: that row gets NaN, counts for nothing and is reported in status[0]."""
+    N, D, ldx = _matrix(X, "X")
     C = int(n_clusters)
-    assert labels.dtype == torch.int64 and labels.is_cuda and labels.is_contiguous() and labels.shape == (N,)
+    _dense(labels, "labels", _I64, (N,))
     dev = X.device
     r = Silhouette()
     f64 = lambda n: torch.empty(n, dtype=torch.float64, device=dev)      # noqa: E731
@@ -1078,7 +1120,7 @@ def silhouette(X, labels, metric, n_clusters, ws=None, details=True):
     need = lib.vsom_silhouette_workspace_bytes(N, C)
     own = ws is not None
     if own:
-        assert ws.dtype == torch.uint8 and ws.is_cuda and ws.is_contiguous()
+        _buffer(ws, "ws", _U8, need)
     else:
         ws = scratch(need, dev)
     check(lib.vsom_silhouette(ptr(X), ldx, N, D, int(metric), ptr(labels), C, ptr(r.sil), ptr(r.a), ptr(r.b), ptr(r.nearest),
@@ -1093,18 +1135,13 @@ def silhouette(X, labels, metric, n_clusters, ws=None, details=True):
 
 
 def knn_vote(idx, dist, bank_labels, n_classes, weights, temperature, pred, status, scores=None):
-    """pred int64 [Nq] = first argmax of the fp64 class scores of each query's neighbour list (weights KNN_UNIFORM /
-    KNN_DISTANCE / KNN_SOFTMAX); scores fp64 [Nq, n_classes] optionally; status int32 [2] (zeroed by the caller) counts
-    refused neighbours and queries left without one (pred -1)."""
-    Nq, k = idx.shape
-    assert idx.dtype == torch.int64 and idx.is_cuda and idx.is_contiguous()
-    _f32(dist, "dist")
-    assert dist.is_contiguous() and dist.shape == (Nq, k)
-    assert bank_labels.dtype == torch.int64 and bank_labels.is_cuda and bank_labels.is_contiguous()
-    assert pred.dtype == torch.int64 and pred.is_contiguous() and pred.numel() == Nq
-    assert status.dtype == torch.int32 and status.numel() == 2 and status.is_cuda
-    if scores is not None:
-        assert scores.dtype == torch.float64 and scores.is_contiguous() and scores.shape == (Nq, n_classes)
+    """pred int64 [Nq] = first argmax of the fp64 class scores of each query's neighbour list (idx int64 / dist f32 [Nq, k],
+    bank_labels int64 [n_bank]; weights KNN_UNIFORM / KNN_DISTANCE / KNN_SOFTMAX); scores fp64 [Nq, n_classes] optionally;
+    status int32 [2] (zeroed by the caller) counts refused neighbours and queries left without one (pred -1)."""
+    Nq, k = _dense(idx, "idx", _I64, (None, None)).shape
+    _dense(dist, "dist", _F32, (Nq, k)); _buffer(bank_labels, "bank_labels", _I64)
+    _dense(pred, "pred", _I64, Nq); _dense(status, "status", _I32, 2)
+    _dense(scores, "scores", _F64, (Nq, int(n_classes)), optional=True)
     check(lib.vsom_knn_vote(ptr(idx), ptr(dist), Nq, k, ptr(bank_labels), bank_labels.numel(), int(n_classes), int(weights),
                             float(temperature), ptr(pred), ptr(scores), ptr(status), stream()), "vsom_knn_vote")
     return pred
@@ -1115,20 +1152,6 @@ PCA_MAX_WIDTH = 256                                              # csrc/pca.hip:
 PCA_PROJECT, PCA_BACKPROJECT = 0, 1                              # `which` of vsom_pca_slabs
 
 
-def _pca_vec(t, n, name):
-    """An optional contiguous f32 device vector of n elements (mean [D], scale [l])."""
-    if t is not None:
-        _f32(t, name)
-        assert t.dim() == 1 and t.numel() == n and t.is_contiguous(), f"{name} must be a contiguous vector of {n}"
-    return t
-
-
-def _pca_f64(t, shape, name):
-    assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == tuple(shape), \
-        f"{name} must be a contiguous float64 device tensor of shape {tuple(shape)}"
-    return t
-
-
 def pca_slabs(N, D, l, which) -> int:
     """Floats of slab space pca_project (which = PCA_PROJECT) / pca_backproject (PCA_BACKPROJECT) take: host arithmetic."""
     return int(lib.vsom_pca_slabs(int(N), int(D), int(l), int(which)))
@@ -1136,10 +1159,10 @@ def pca_slabs(N, D, l, which) -> int:
 
 def pca_colstats(X, mean=None, var=None):
     """(mean f32 [D], var f64 [D]) of the columns of X [N, D]: fp64 sums in a fixed order, the mean rounded once, the
-    unbiased variance about that rounded mean."""
-    N, D, ldx = _kmeans_x(X)
-    mean = torch.empty(D, dtype=torch.float32, device=X.device) if mean is None else _pca_vec(mean, D, "mean")
-    var = torch.empty(D, dtype=torch.float64, device=X.device) if var is None else _pca_f64(var, (D,), "var")
+    unbiased variance about that rounded mean.  mean / var optional: allocated here when None."""
+    N, D, ldx = _matrix(X, "X")
+    mean = torch.empty(D, dtype=torch.float32, device=X.device) if mean is None else _dense(mean, "mean", _F32, (D,))
+    var = torch.empty(D, dtype=torch.float64, device=X.device) if var is None else _dense(var, "var", _F64, (D,))
     n_part = int(lib.vsom_pca_colstats_parts(N, D))
     part = scratch(8 * n_part, X.device)
     check(lib.vsom_pca_colstats(ptr(X), ldx, N, D, ptr(mean), ptr(var), ptr(part), part.numel() // 8, stream()), "vsom_pca_colstats")
@@ -1147,90 +1170,75 @@ def pca_colstats(X, mean=None, var=None):
 
 
 def pca_project(X, mean, B, scale, Y):
-    """Y [N, l] = (X - mean) B^T diag(scale); mean [D] and scale [l] optional."""
-    N, D, ldx = _kmeans_x(X)
-    _f32(B, "B"); _f32(Y, "Y")
-    assert B.dim() == 2 and B.shape[1] == D, "B must be [l, D]"
-    l = B.shape[0]
-    assert Y.dim() == 2 and Y.shape == (N, l), "Y must be [N, l]"
-    _pca_vec(mean, D, "mean"); _pca_vec(scale, l, "scale")
+    """Y [N, l] = (X - mean) B^T diag(scale); X [N, D], B [l, D] and Y with any row stride; mean [D] and scale [l] optional."""
+    N, D, ldx = _matrix(X, "X")
+    l, _, ldb = _matrix(B, "B", cols=D)
+    _, _, ldy = _matrix(Y, "Y", N, l)
+    _dense(mean, "mean", _F32, (D,), optional=True); _dense(scale, "scale", _F32, (l,), optional=True)
     slabs = scratch(4 * pca_slabs(N, D, l, PCA_PROJECT), X.device)
-    check(lib.vsom_pca_project(ptr(X), ldx, N, D, ptr(mean), ptr(B), _rows(B), l, ptr(scale), ptr(Y), _rows(Y), ptr(slabs),
+    check(lib.vsom_pca_project(ptr(X), ldx, N, D, ptr(mean), ptr(B), ldb, l, ptr(scale), ptr(Y), ldy, ptr(slabs),
                                slabs.numel() // 4, stream()), "vsom_pca_project")
     return Y
 
 
 def pca_backproject(Y, X, mean, Zt):
-    """Zt [l, D] = Y^T (X - mean); Y [N, l], mean [D] optional."""
-    N, D, ldx = _kmeans_x(X)
-    _f32(Y, "Y"); _f32(Zt, "Zt")
-    assert Y.dim() == 2 and Y.shape[0] == N, "Y must be [N, l]"
-    l = Y.shape[1]
-    assert Zt.dim() == 2 and Zt.shape == (l, D), "Zt must be [l, D]"
-    _pca_vec(mean, D, "mean")
+    """Zt [l, D] = Y^T (X - mean); Y [N, l], X [N, D] and Zt with any row stride; mean [D] optional."""
+    N, D, ldx = _matrix(X, "X")
+    _, l, ldy = _matrix(Y, "Y", rows=N)
+    _, _, ldz = _matrix(Zt, "Zt", l, D)
+    _dense(mean, "mean", _F32, (D,), optional=True)
     slabs = scratch(4 * pca_slabs(N, D, l, PCA_BACKPROJECT), X.device)
-    check(lib.vsom_pca_backproject(ptr(Y), _rows(Y), ptr(X), ldx, N, D, ptr(mean), l, ptr(Zt), _rows(Zt), ptr(slabs),
+    check(lib.vsom_pca_backproject(ptr(Y), ldy, ptr(X), ldx, N, D, ptr(mean), l, ptr(Zt), ldz, ptr(slabs),
                                    slabs.numel() // 4, stream()), "vsom_pca_backproject")
     return Zt
 
 
 def pca_gram(Zt, G, B=None, H=None):
-    """G f64 [l, l] = Zt Zt^T and, with B [l, D] and H f64 [l, l], H = B Zt^T: fp64 products and sums."""
-    l, D, ldz = _kmeans_x(Zt)
-    _pca_f64(G, (l, l), "G")
-    assert (B is None) == (H is None), "B and H go together"
-    if B is not None:
-        _f32(B, "B")
-        assert B.dim() == 2 and B.shape == (l, D), "B must have the shape of Zt"
-        _pca_f64(H, (l, l), "H")
-    check(lib.vsom_pca_gram(ptr(Zt), ldz, ptr(B), _rows(B) if B is not None else 0, l, D, ptr(G), ptr(H), stream()), "vsom_pca_gram")
+    """G f64 [l, l] = Zt Zt^T and, with B [l, D] and H f64 [l, l] (optional, together), H = B Zt^T: fp64 products and sums."""
+    l, D, ldz = _matrix(Zt, "Zt")
+    _dense(G, "G", _F64, (l, l))
+    if (B is None) != (H is None):
+        raise ValueError("B and H go together")
+    _, _, ldb = _matrix(B, "B", l, D, optional=True)
+    _dense(H, "H", _F64, (l, l), optional=True)
+    check(lib.vsom_pca_gram(ptr(Zt), ldz, ptr(B), ldb, l, D, ptr(G), ptr(H), stream()), "vsom_pca_gram")
     return G, H
 
 
 def pca_rotate(T, Zt, Bout):
     """Bout [l_out, D] = T Zt, T f64 [l_out, l_in] on the device: fp64 accumulation, one rounding.  Bout may not overlap Zt."""
-    l_in, D, ldz = _kmeans_x(Zt)
-    assert T.dim() == 2 and T.shape[1] == l_in, "T must be [l_out, l_in]"
-    l_out = T.shape[0]
-    _pca_f64(T, (l_out, l_in), "T")
-    _f32(Bout, "Bout")
-    assert Bout.dim() == 2 and Bout.shape == (l_out, D), "Bout must be [l_out, D]"
-    check(lib.vsom_pca_rotate(ptr(T), l_out, l_in, ptr(Zt), ldz, D, ptr(Bout), _rows(Bout), stream()), "vsom_pca_rotate")
+    l_in, D, ldz = _matrix(Zt, "Zt")
+    l_out = _dense(T, "T", _F64, (None, l_in)).shape[0]
+    _, _, ldo = _matrix(Bout, "Bout", l_out, D)
+    check(lib.vsom_pca_rotate(ptr(T), l_out, l_in, ptr(Zt), ldz, D, ptr(Bout), ldo, stream()), "vsom_pca_rotate")
     return Bout
 
 
 def pca_reconstruct(Y, scale, B, mean, Xout):
-    """Xout [M, D] = (Y diag(scale)) B + mean; Y [M, l], B [l, D], scale [l] and mean [D] optional."""
-    M, l, ldy = _kmeans_x(Y)
-    _f32(B, "B"); _f32(Xout, "Xout")
-    assert B.dim() == 2 and B.shape[0] == l, "B must be [l, D]"
-    D = B.shape[1]
-    assert Xout.dim() == 2 and Xout.shape == (M, D), "Xout must be [M, D]"
-    _pca_vec(scale, l, "scale"); _pca_vec(mean, D, "mean")
-    check(lib.vsom_pca_reconstruct(ptr(Y), ldy, M, l, ptr(scale), ptr(B), _rows(B), D, ptr(mean), ptr(Xout), _rows(Xout), stream()),
+    """Xout [M, D] = (Y diag(scale)) B + mean; Y [M, l], B [l, D], Xout with any row stride; scale [l] and mean [D] optional."""
+    M, l, ldy = _matrix(Y, "Y")
+    _, D, ldb = _matrix(B, "B", rows=l)
+    _, _, ldo = _matrix(Xout, "Xout", M, D)
+    _dense(scale, "scale", _F32, (l,), optional=True); _dense(mean, "mean", _F32, (D,), optional=True)
+    check(lib.vsom_pca_reconstruct(ptr(Y), ldy, M, l, ptr(scale), ptr(B), ldb, D, ptr(mean), ptr(Xout), ldo, stream()),
           "vsom_pca_reconstruct")
     return Xout
 
 
 # ---------------------------------------------------------------- Kohonen's batch map (SOMLayer.fit_batch)
 def som_batch_accumulate(X, bmu, sums, counts, inv_norm=None, accumulate=False, bad=None):
-    """counts [K] int64 = rows per unit, sums [K, D] float64 = per unit the sum of its rows of X [N, D] (times inv_norm [N]
-    when given), every (unit, column) one fp64 chain in ascending row index (see vsom_som_batch_accumulate).  accumulate=True
-    continues from what sums / counts hold: a row set cut into several calls gives the same bits as one call.
-    bad: an int32 [1] device counter of BMUs outside [0, K) the caller zeroes and reads later; None: checked here (one
-    host read) and raised as VsomError."""
-    N, D, ldx = _kmeans_x(X)
-    K = counts.numel()
-    assert bmu.dtype == torch.int64 and bmu.is_cuda and bmu.dim() == 1 and bmu.is_contiguous() and bmu.numel() == N, \
-        "bmu must be a contiguous int64 device vector of N"
-    _pca_f64(sums, (K, D), "sums")
-    assert counts.dtype == torch.int64 and counts.is_cuda and counts.dim() == 1 and counts.is_contiguous(), \
-        "counts must be a contiguous int64 device vector"
-    _pca_vec(inv_norm, N, "inv_norm")
+    """counts [K] int64 = rows per unit, sums [K, D] float64 = per unit the sum of its rows of X [N, D] (times inv_norm f32
+    [N] when given) under bmu int64 [N], every (unit, column) one fp64 chain in ascending row index (see
+    vsom_som_batch_accumulate).  accumulate=True continues from what sums / counts hold: a row set cut into several calls
+    gives the same bits as one call.  bad: an int32 [1] device counter of BMUs outside [0, K) the caller zeroes and reads
+    later; None: checked here (one host read) and raised as VsomError."""
+    N, D, ldx = _matrix(X, "X")
+    K = _dense(counts, "counts", _I64, (None,)).numel()
+    _dense(bmu, "bmu", _I64, (N,)); _dense(sums, "sums", _F64, (K, D)); _dense(inv_norm, "inv_norm", _F32, (N,), optional=True)
     own = bad is None
     if own:
         bad = torch.zeros(1, dtype=torch.int32, device=X.device)
-    assert bad.dtype == torch.int32 and bad.is_cuda and bad.numel() == 1
+    _dense(bad, "bad", _I32, 1)
     order = torch.sort(bmu, stable=True).indices              # the rows of a unit, ascending: what fixes every chain's order
     n_seg = int(lib.vsom_som_batch_accumulate_parts(K))
     seg = scratch(8 * n_seg, X.device)
@@ -1245,21 +1253,17 @@ def som_batch_accumulate(X, bmu, sums, counts, inv_norm=None, accumulate=False, 
 
 
 def som_batch_update(sums, counts, grid_positions, sigma, W_out, normalize=False):
-    """W_out [K, D] f32 = the batch-map update at radius sigma from sums [K, D] float64 and counts [K] int64 (see
-    vsom_som_batch_update); normalize=True L2-normalises every row afterwards (the cosine map)."""
-    K = counts.numel()
-    assert sums.dim() == 2, "sums must be [K, D]"
-    D = sums.shape[1]
-    _pca_f64(sums, (K, D), "sums")
-    assert counts.dtype == torch.int64 and counts.is_cuda and counts.dim() == 1 and counts.is_contiguous(), \
-        "counts must be a contiguous int64 device vector"
-    _f32(grid_positions, "grid_positions"); _f32(W_out, "W_out")
-    assert grid_positions.is_contiguous() and tuple(grid_positions.shape) == (K, 2), "grid_positions must be [K, 2]"
-    assert W_out.dim() == 2 and tuple(W_out.shape) == (K, D), "W_out must be [K, D]"
+    """W_out [K, D] f32 (any row stride) = the batch-map update at radius sigma from sums [K, D] float64, counts [K] int64
+    and grid_positions f32 [K, 2] (see vsom_som_batch_update); normalize=True L2-normalises every row afterwards (the
+    cosine map)."""
+    K = _dense(counts, "counts", _I64, (None,)).numel()
+    D = _dense(sums, "sums", _F64, (K, None)).shape[1]
+    _dense(grid_positions, "grid_positions", _F32, (K, 2))
+    _, _, ldw = _matrix(W_out, "W_out", K, D)
     n_part = int(lib.vsom_som_batch_update_parts(K))
     part = scratch(8 * n_part, sums.device)
     check(lib.vsom_som_batch_update(ptr(sums), ptr(counts), ptr(grid_positions), K, D, float(sigma), int(bool(normalize)), ptr(W_out),
-                                    _rows(W_out), ptr(part), part.numel() // 8, stream()), "vsom_som_batch_update")
+                                    ldw, ptr(part), part.numel() // 8, stream()), "vsom_som_batch_update")
     return W_out
 
 
@@ -1273,70 +1277,52 @@ PROBE_STEP, PROBE_LS_STATUS, PROBE_F, PROBE_J = 12, 13, 14, 15
 LBFGS_RECORD = 16
 
 
-def _probe_labels(y, N):
-    assert y.dtype == torch.int64 and y.is_cuda and y.dim() == 1 and y.is_contiguous() and y.numel() == N, \
-        "y must be a contiguous int64 device vector of N"
-    return y
-
-
-def _probe_f64(t, n, name):
-    """An optional contiguous fp64 device tensor of n elements."""
-    if t is not None:
-        assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.numel() == n, \
-            f"{name} must be a contiguous float64 device tensor of {n} elements"
-    return t
-
-
 def probe_parts(N, C) -> int:
     """Doubles of scratch probe_residual / probe_linesearch take: host arithmetic."""
     return int(lib.vsom_probe_parts(int(N), int(C)))
 
 
 def probe_fold(A, invstd, B, W=None, pen=None):
-    """B f32 [C, D] = A o invstd (A fp64 [C, D], invstd fp64 [D]; one rounding); with W fp64 [C, D] and pen fp64 [3] also
-    pen = (W.W, W.A, A.A)."""
-    assert A.dim() == 2, "A must be [C, D]"
-    C, D = A.shape
-    _probe_f64(A, C * D, "A"); _probe_f64(invstd, D, "invstd")
-    _f32(B, "B")
-    assert B.dim() == 2 and tuple(B.shape) == (C, D), "B must be [C, D]"
-    assert (W is None) == (pen is None), "W and pen go together"
-    _probe_f64(W, C * D, "W"); _probe_f64(pen, 3, "pen")
+    """B f32 [C, D] (any row stride) = A o invstd (A fp64 [C, D], invstd fp64 [D]; one rounding); with W fp64 [C, D] and pen
+    fp64 [3] (optional, together) also pen = (W.W, W.A, A.A)."""
+    C, D = _dense(A, "A", _F64, (None, None)).shape
+    _dense(invstd, "invstd", _F64, D)
+    _, _, ldb = _matrix(B, "B", C, D)
+    if (W is None) != (pen is None):
+        raise ValueError("W and pen go together")
+    _dense(W, "W", _F64, C * D, optional=True); _dense(pen, "pen", _F64, 3, optional=True)
     n_part = int(lib.vsom_probe_fold_parts(C, D)) if W is not None else 0
     part = scratch(8 * n_part, A.device)
-    check(lib.vsom_probe_fold(ptr(A), ptr(invstd), C, D, ptr(B), _rows(B), ptr(W), ptr(pen), ptr(part), part.numel() // 8, stream()),
+    check(lib.vsom_probe_fold(ptr(A), ptr(invstd), C, D, ptr(B), ldb, ptr(W), ptr(pen), ptr(part), part.numel() // 8, stream()),
           "vsom_probe_fold")
     return B
 
 
 def probe_residual(Z, b, y, R, loss, gb, status, pred=None, prob=None):
-    """R f32 [N, C] = softmax(Z + b) - onehot(y), loss fp64 [1] = the summed cross-entropy, gb fp64 [C] = the column sums of
-    R; pred int64 [N] and prob fp64 [N, C] optionally; status int32 [1] (zeroed by the caller) counts labels outside [0, C)."""
-    N, C, ldz = _kmeans_x(Z)
-    _f32(R, "R")
-    assert R.dim() == 2 and tuple(R.shape) == (N, C), "R must be [N, C]"
-    _probe_f64(b, C, "b"); _probe_f64(loss, 1, "loss"); _probe_f64(gb, C, "gb"); _probe_f64(prob, N * C, "prob")
-    assert loss is not None and gb is not None
-    _probe_labels(y, N)
-    if pred is not None:
-        _probe_labels(pred, N)
-    assert status.dtype == torch.int32 and status.is_cuda and status.numel() == 1
+    """R f32 [N, C] = softmax(Z + b) - onehot(y) (Z, R with any row stride; b fp64 [C] optional: no intercept; y int64 [N]),
+    loss fp64 [1] = the summed cross-entropy, gb fp64 [C] = the column sums of R; pred int64 [N] and prob fp64 [N, C]
+    optionally; status int32 [1] (zeroed by the caller) counts labels outside [0, C)."""
+    N, C, ldz = _matrix(Z, "Z")
+    _, _, ldr = _matrix(R, "R", N, C)
+    _dense(b, "b", _F64, C, optional=True); _dense(loss, "loss", _F64, 1); _dense(gb, "gb", _F64, C)
+    _dense(y, "y", _I64, (N,)); _dense(pred, "pred", _I64, (N,), optional=True); _dense(prob, "prob", _F64, N * C, optional=True)
+    _dense(status, "status", _I32, 1)
     part = scratch(8 * probe_parts(N, C), Z.device)
-    check(lib.vsom_probe_residual(ptr(Z), ldz, N, C, ptr(b), ptr(y), ptr(R), _rows(R), ptr(loss), ptr(gb), ptr(pred), ptr(prob),
+    check(lib.vsom_probe_residual(ptr(Z), ldz, N, C, ptr(b), ptr(y), ptr(R), ldr, ptr(loss), ptr(gb), ptr(pred), ptr(prob),
                                   ptr(status), ptr(part), part.numel() // 8, stream()), "vsom_probe_residual")
     return R
 
 
 def probe_linesearch(Z, Zp, b, pb, y, alpha0, nsteps, phi):
     """phi fp64 [nsteps]: the summed cross-entropy at Z + a_j Zp, b + a_j pb for a_j = alpha0 2^-j (alpha0 fp64 [1] on the
-    device), in one launch."""
-    N, C, ldz = _kmeans_x(Z)
-    _f32(Zp, "Zp")
-    assert Zp.dim() == 2 and tuple(Zp.shape) == (N, C) and _rows(Zp) == ldz, "Zp must have the shape and row stride of Z"
-    assert (b is None) == (pb is None), "b and pb go together"
-    _probe_f64(b, C, "b"); _probe_f64(pb, C, "pb"); _probe_f64(alpha0, 1, "alpha0"); _probe_f64(phi, int(nsteps), "phi")
-    assert alpha0 is not None and phi is not None
-    _probe_labels(y, N)
+    device), in one launch; Zp has the shape and row stride of Z; b and pb (fp64 [C]) optional, together."""
+    N, C, ldz = _matrix(Z, "Z")
+    if _matrix(Zp, "Zp", N, C)[2] != ldz:
+        raise ValueError("Zp must have the shape and row stride of Z")
+    if (b is None) != (pb is None):
+        raise ValueError("b and pb go together")
+    _dense(b, "b", _F64, C, optional=True); _dense(pb, "pb", _F64, C, optional=True)
+    _dense(alpha0, "alpha0", _F64, 1); _dense(phi, "phi", _F64, int(nsteps)); _dense(y, "y", _I64, (N,))
     part = scratch(8 * probe_parts(N, C), Z.device)
     check(lib.vsom_probe_linesearch(ptr(Z), ptr(Zp), ldz, N, C, ptr(b), ptr(pb), ptr(y), ptr(alpha0), int(nsteps), ptr(phi), ptr(part),
                                     part.numel() // 8, stream()), "vsom_probe_linesearch")
@@ -1345,31 +1331,33 @@ def probe_linesearch(Z, Zp, b, pb, y, alpha0, nsteps, phi):
 
 def probe_step(phi, alpha0, f0, pen, gtp, lam, c1, Z, Zp, theta, p, s_new, rec):
     """The Armijo choice from the ladder phi, then Z += alpha Zp, theta += alpha p, s_new = alpha p; rec[12:16] =
-    (alpha, status, F(alpha), j).  alpha0, f0, gtp fp64 [1], pen fp64 [3], rec fp64 [>= 16]: all on the device."""
-    N, C, ldz = _kmeans_x(Z)
-    _f32(Zp, "Zp")
-    assert Zp.dim() == 2 and tuple(Zp.shape) == (N, C) and _rows(Zp) == ldz, "Zp must have the shape and row stride of Z"
-    n = theta.numel()
-    for t, k, name in ((phi, phi.numel(), "phi"), (alpha0, 1, "alpha0"), (f0, 1, "f0"), (pen, 3, "pen"), (gtp, 1, "gtp"),
-                       (theta, n, "theta"), (p, n, "p"), (s_new, n, "s_new")):
-        assert t is not None
-        _probe_f64(t, k, name)
-    assert rec.dtype == torch.float64 and rec.is_cuda and rec.is_contiguous() and rec.numel() >= LBFGS_RECORD
-    check(lib.vsom_probe_step(ptr(phi), phi.numel(), ptr(alpha0), ptr(f0), ptr(pen), ptr(gtp), float(lam), float(c1), ptr(Z), ptr(Zp),
+    (alpha, status, F(alpha), j).  alpha0, f0, gtp fp64 [1], pen fp64 [3], theta, p, s_new fp64 [n], rec fp64 [>= 16]: all
+    on the device."""
+    N, C, ldz = _matrix(Z, "Z")
+    if _matrix(Zp, "Zp", N, C)[2] != ldz:
+        raise ValueError("Zp must have the shape and row stride of Z")
+    nsteps, n = _buffer(phi, "phi", _F64).numel(), _buffer(theta, "theta", _F64).numel()
+    _dense(alpha0, "alpha0", _F64, 1); _dense(f0, "f0", _F64, 1); _dense(pen, "pen", _F64, 3); _dense(gtp, "gtp", _F64, 1)
+    _dense(p, "p", _F64, n); _dense(s_new, "s_new", _F64, n); _buffer(rec, "rec", _F64, LBFGS_RECORD)
+    check(lib.vsom_probe_step(ptr(phi), nsteps, ptr(alpha0), ptr(f0), ptr(pen), ptr(gtp), float(lam), float(c1), ptr(Z), ptr(Zp),
                               ldz, N, C, ptr(theta), ptr(p), ptr(s_new), n, ptr(rec), stream()), "vsom_probe_step")
     return rec
 
 
 def probe_gradient(Zt, invstd, theta, gb, N, lam, g, g_prev=None, y_new=None):
-    """g fp64 [n] = (Zt o invstd) / N + lam W, then gb / N when theta holds an intercept (n = C D + C); y_new = g - g_prev."""
-    C, D, ldz = _kmeans_x(Zt)
-    n = theta.numel()
-    assert n in (C * D, C * D + C), "theta must hold C D or C D + C elements"
+    """g fp64 [n] = (Zt o invstd) / N + lam W, then gb / N when theta holds an intercept (n = C D + C; gb fp64 [C] is optional
+    without one); y_new = g - g_prev (optional, together)."""
+    C, D, ldz = _matrix(Zt, "Zt")
+    n = _buffer(theta, "theta", _F64).numel()
+    if n not in (C * D, C * D + C):
+        raise ValueError("theta must hold C D or C D + C elements")
     intercept = n > C * D
-    _probe_f64(invstd, D, "invstd"); _probe_f64(theta, n, "theta"); _probe_f64(g, n, "g")
-    _probe_f64(gb, C, "gb"); _probe_f64(g_prev, n, "g_prev"); _probe_f64(y_new, n, "y_new")
-    assert (g_prev is None) == (y_new is None), "g_prev and y_new go together"
-    assert gb is not None or not intercept, "an intercept needs gb"
+    if (g_prev is None) != (y_new is None):
+        raise ValueError("g_prev and y_new go together")
+    if intercept and gb is None:
+        raise ValueError("gb: an intercept needs gb")
+    _dense(invstd, "invstd", _F64, D); _dense(g, "g", _F64, n); _dense(gb, "gb", _F64, C, optional=True)
+    _dense(g_prev, "g_prev", _F64, n, optional=True); _dense(y_new, "y_new", _F64, n, optional=True)
     check(lib.vsom_probe_gradient(ptr(Zt), ldz, ptr(invstd), ptr(theta), ptr(gb), C, D, int(intercept), int(N), float(lam), ptr(g_prev),
                                   ptr(g), ptr(y_new), stream()), "vsom_probe_gradient")
     return g
@@ -1383,20 +1371,15 @@ def lbfgs_state(m, device):
     return torch.zeros(n, dtype=torch.float64, device=device)
 
 
-def _lbfgs_args(S, Y, g, state):
-    assert S.dim() == 2 and S.shape == Y.shape, "S and Y must be [m, n]"
-    m, n = S.shape
-    _probe_f64(S, m * n, "S"); _probe_f64(Y, m * n, "Y"); _probe_f64(g, n, "g")
-    _probe_f64(state, int(lib.vsom_lbfgs_state_doubles(m)), "state")
-    return m, n
-
-
 def lbfgs_dots(S, Y, g, s_new, y_new, state, dots):
-    """dots fp64 [3 (2 m + 3) + 1]: the products of (s_new, y_new, g) with every vector held, and max |g|, in one pass.
-    s_new = y_new = None: there is no new pair."""
-    m, n = _lbfgs_args(S, Y, g, state)
-    assert (s_new is None) == (y_new is None), "s_new and y_new go together"
-    _probe_f64(s_new, n, "s_new"); _probe_f64(y_new, n, "y_new"); _probe_f64(dots, 3 * (2 * m + 3) + 1, "dots")
+    """dots fp64 [3 (2 m + 3) + 1]: the products of (s_new, y_new, g) with every vector held (S, Y fp64 [m, n]; g fp64 [n];
+    state from lbfgs_state(m)), and max |g|, in one pass.  s_new = y_new = None: there is no new pair."""
+    m, n = _dense(S, "S", _F64, (None, None)).shape
+    _dense(Y, "Y", _F64, (m, n)); _dense(g, "g", _F64, n); _dense(state, "state", _F64, int(lib.vsom_lbfgs_state_doubles(m)))
+    if (s_new is None) != (y_new is None):
+        raise ValueError("s_new and y_new go together")
+    _dense(s_new, "s_new", _F64, n, optional=True); _dense(y_new, "y_new", _F64, n, optional=True)
+    _dense(dots, "dots", _F64, 3 * (2 * m + 3) + 1)
     part = scratch(8 * int(lib.vsom_lbfgs_parts(n, m)), g.device)
     check(lib.vsom_lbfgs_dots(ptr(S), ptr(Y), ptr(g), ptr(s_new), ptr(y_new), n, m, int(s_new is not None), ptr(state), ptr(dots),
                               ptr(part), part.numel() // 8, stream()), "vsom_lbfgs_dots")
@@ -1405,15 +1388,16 @@ def lbfgs_dots(S, Y, g, s_new, y_new, state, dots):
 
 def lbfgs_coeff(dots, m, has_new, state):
     """Takes the new pair in (or skips it), then the two-loop recursion on coefficients; has_new=False empties the history."""
-    _probe_f64(dots, 3 * (2 * m + 3) + 1, "dots"); _probe_f64(state, int(lib.vsom_lbfgs_state_doubles(m)), "state")
+    _dense(dots, "dots", _F64, 3 * (2 * m + 3) + 1); _dense(state, "state", _F64, int(lib.vsom_lbfgs_state_doubles(m)))
     check(lib.vsom_lbfgs_coeff(ptr(dots), int(m), int(bool(has_new)), ptr(state), stream()), "vsom_lbfgs_coeff")
     return state
 
 
 def lbfgs_combine(S, Y, g, s_new, y_new, state, p):
-    """p fp64 [n] = the direction; an accepted pair is copied into its ring slot of S and Y first."""
-    m, n = _lbfgs_args(S, Y, g, state)
-    _probe_f64(s_new, n, "s_new"); _probe_f64(y_new, n, "y_new"); _probe_f64(p, n, "p")
+    """p fp64 [n] = the direction; an accepted pair (s_new, y_new fp64 [n]) is copied into its ring slot of S and Y first."""
+    m, n = _dense(S, "S", _F64, (None, None)).shape
+    _dense(Y, "Y", _F64, (m, n)); _dense(g, "g", _F64, n); _dense(state, "state", _F64, int(lib.vsom_lbfgs_state_doubles(m)))
+    _dense(s_new, "s_new", _F64, n); _dense(y_new, "y_new", _F64, n); _dense(p, "p", _F64, n)
     check(lib.vsom_lbfgs_combine(ptr(S), ptr(Y), ptr(g), ptr(s_new), ptr(y_new), n, m, ptr(state), ptr(p), stream()),
           "vsom_lbfgs_combine")
     return p
@@ -1435,53 +1419,42 @@ def tsne_step_parts(N) -> int:
 
 def tsne_affinities(knn_dist, perplexity, P, beta, status, knn_idx=None, first=1, square=True):
     """P fp64 [N, k_eff] and beta fp64 [N]: the conditional affinities of columns [first, first + k_eff) of knn_dist f32
-    [N, k] at this perplexity; status int32 [1] (zeroed by the caller) counts the rows refused, which are not written."""
-    _f32(knn_dist, "knn_dist")
-    assert knn_dist.dim() == 2, "knn_dist must be [N, k]"
-    N, ldk = knn_dist.shape[0], _rows(knn_dist)
-    assert P.dim() == 2 and P.shape[0] == N, "P must be [N, k_eff]"
-    k_eff = P.shape[1]
-    _pca_f64(P, (N, k_eff), "P"); _pca_f64(beta, (N,), "beta")
-    assert first >= 0 and first + k_eff <= knn_dist.shape[1], "columns [first, first + k_eff) must lie inside knn_dist"
+    [N, k] (any row stride) at this perplexity; status int32 [1] (zeroed by the caller) counts the rows refused, which are
+    not written.  knn_idx (optional): int64, laid out as knn_dist; a row with an empty slot in it is refused too."""
+    N, k, ldk = _matrix(knn_dist, "knn_dist")
+    k_eff = _dense(P, "P", _F64, (N, None)).shape[1]
+    _dense(beta, "beta", _F64, (N,)); _dense(status, "status", _I32, 1)
+    if first < 0 or first + k_eff > k:
+        raise ValueError("columns [first, first + k_eff) must lie inside knn_dist")
     if knn_idx is not None:
-        assert knn_idx.dtype == torch.int64 and knn_idx.is_cuda and knn_idx.shape == knn_dist.shape \
-            and knn_idx.stride() == knn_dist.stride(), "knn_idx must be an int64 device tensor laid out as knn_dist"
-    assert status.dtype == torch.int32 and status.is_cuda and status.numel() == 1
+        _device(knn_idx, "knn_idx", _I64)
+        if knn_idx.shape != knn_dist.shape or knn_idx.stride() != knn_dist.stride():
+            raise ValueError("knn_idx must be an int64 device tensor laid out as knn_dist")
     check(lib.vsom_tsne_affinities(ptr(knn_dist), ptr(knn_idx), ldk, N, k_eff, int(first), int(bool(square)), float(perplexity),
                                    ptr(P), ptr(beta), ptr(status), stream()), "vsom_tsne_affinities")
     return P, beta
 
 
-def _tsne_y(Y, name):
-    _f32(Y, name)
-    assert Y.dim() == 2 and Y.shape[1] == 2 and Y.is_contiguous(), f"{name} must be a contiguous [N, 2]"
-    return Y.shape[0]
-
-
 def tsne_repulsion(Y, rep, sumq, zpart):
-    """rep fp64 [N, 2] = sum_j q^2 (y_i - y_j), sumq fp64 [N] = sum_j q over all j != i, q = 1 / (1 + |y_i - y_j|^2), and
-    zpart fp64 [>= tsne_repulsion_parts(N)]: the sums of sumq over blocks of 64 rows (their sum is Z)."""
-    N = _tsne_y(Y, "Y")
-    _pca_f64(rep, (N, 2), "rep"); _pca_f64(sumq, (N,), "sumq")
-    assert zpart.dtype == torch.float64 and zpart.is_cuda and zpart.dim() == 1 and zpart.is_contiguous()
+    """rep fp64 [N, 2] = sum_j q^2 (y_i - y_j), sumq fp64 [N] = sum_j q over all j != i, q = 1 / (1 + |y_i - y_j|^2) for Y f32
+    [N, 2] contiguous, and zpart fp64 [>= tsne_repulsion_parts(N)] (the entry checks its size): the sums of sumq over blocks
+    of 64 rows (their sum is Z)."""
+    N = _dense(Y, "Y", _F32, (None, 2)).shape[0]
+    _dense(rep, "rep", _F64, (N, 2)); _dense(sumq, "sumq", _F64, (N,)); _buffer(zpart, "zpart", _F64)
     check(lib.vsom_tsne_repulsion(ptr(Y), N, ptr(rep), ptr(sumq), ptr(zpart), zpart.numel(), stream()), "vsom_tsne_repulsion")
     return rep, sumq, zpart
 
 
 def tsne_step(indptr, indices, data, Y_in, Y_out, update, gains, rep, zpart, exaggeration, momentum, learning_rate, part,
               record=False):
-    """One iteration: Y_out from Y_in, update and gains (f32 [N, 2]) in place, from tsne_repulsion's rep and zpart at Y_in
-    and the joint P (CSR: int64, int64, fp64).  record: part fp64 [>= tsne_step_parts(N)] receives the (KL, |grad|^2)
-    pairs of the row blocks; add them."""
-    N = _tsne_y(Y_in, "Y_in")
-    for t, name in ((Y_out, "Y_out"), (update, "update"), (gains, "gains")):
-        assert _tsne_y(t, name) == N, f"{name} must be [N, 2]"
-    assert indptr.dtype == indices.dtype == torch.int64 and indptr.is_cuda and indices.is_cuda
-    assert indptr.is_contiguous() and indices.is_contiguous() and indptr.numel() == N + 1
-    assert data.dtype == torch.float64 and data.is_cuda and data.is_contiguous() and data.numel() == indices.numel()
-    _pca_f64(rep, (N, 2), "rep")
-    for t in (zpart, part):
-        assert t.dtype == torch.float64 and t.is_cuda and t.dim() == 1 and t.is_contiguous()
+    """One iteration: Y_out from Y_in, update and gains (f32 [N, 2] contiguous) in place, from tsne_repulsion's rep and zpart
+    at Y_in and the joint P (CSR: indptr int64 [N + 1], indices int64 [nnz], data fp64 [nnz]).  record: part fp64
+    [>= tsne_step_parts(N)] receives the (KL, |grad|^2) pairs of the row blocks; add them.  The entry checks the sizes of
+    zpart and part."""
+    N = _dense(Y_in, "Y_in", _F32, (None, 2)).shape[0]
+    _dense(Y_out, "Y_out", _F32, (N, 2)); _dense(update, "update", _F32, (N, 2)); _dense(gains, "gains", _F32, (N, 2))
+    _dense(indptr, "indptr", _I64, N + 1); _dense(data, "data", _F64, _buffer(indices, "indices", _I64).numel())
+    _dense(rep, "rep", _F64, (N, 2)); _buffer(zpart, "zpart", _F64); _buffer(part, "part", _F64)
     check(lib.vsom_tsne_step(ptr(indptr), ptr(indices), ptr(data), ptr(Y_in), ptr(Y_out), ptr(update), ptr(gains), N, ptr(rep),
                              ptr(zpart), zpart.numel(), float(exaggeration), float(momentum), float(learning_rate),
                              int(bool(record)), ptr(part), part.numel(), stream()), "vsom_tsne_step")
@@ -1512,43 +1485,32 @@ def gmm_scratch(N, D, K, which, device):
     return scratch(8 * n, device)[:8 * n].view(torch.float64)
 
 
-def _gmm_kd(means, prec, D):
-    _f32(means, "means"); _f32(prec, "prec")
-    assert means.dim() == 2 and means.shape[1] == D and means.is_contiguous(), "means must be a contiguous [K, D]"
-    assert prec.shape == means.shape and prec.is_contiguous(), "prec must be a contiguous [K, D]"
-    return means.shape[0]
-
-
 def gmm_estep(X, means, prec, logc, resp, log_prob_norm, labels, estat, part=None):
-    """log_prob_norm fp64 [N], resp f32 [N, K] (None: not wanted), labels int64 [N] (None likewise) of the mixture (means,
-    prec f32 [K, D], logc fp64 [K]) in the direct form; estat fp64 [2] = (sum of log_prob_norm over the accepted rows, rows
-    refused for a NaN or an infinity: theirs are NaN / -1)."""
-    N, D, ldx = _kmeans_x(X)
-    K = _gmm_kd(means, prec, D)
-    _pca_f64(logc, (K,), "logc"); _pca_f64(log_prob_norm, (N,), "log_prob_norm"); _pca_f64(estat, (2,), "estat")
-    ldr = K
-    if resp is not None:
-        _f32(resp, "resp")
-        assert resp.dim() == 2 and tuple(resp.shape) == (N, K), "resp must be [N, K]"
-        ldr = _rows(resp)
-    if labels is not None:
-        assert labels.dtype == torch.int64 and labels.is_cuda and labels.is_contiguous() and labels.numel() == N
-    part = gmm_scratch(N, D, K, GMM_ESTEP, X.device) if part is None else part
+    """log_prob_norm fp64 [N], resp f32 [N, K] (any row stride; None: not wanted), labels int64 [N] (None likewise) of the
+    mixture (means, prec f32 [K, D] contiguous, logc fp64 [K]) in the direct form; estat fp64 [2] = (sum of log_prob_norm
+    over the accepted rows, rows refused for a NaN or an infinity: theirs are NaN / -1).  part (optional): fp64, at least
+    gmm_parts(N, D, K, GMM_ESTEP) doubles (the entry checks its size); None: the shared scratch."""
+    N, D, ldx = _matrix(X, "X")
+    K = _dense(means, "means", _F32, (None, D)).shape[0]
+    _dense(prec, "prec", _F32, (K, D)); _dense(logc, "logc", _F64, (K,))
+    _dense(log_prob_norm, "log_prob_norm", _F64, (N,)); _dense(estat, "estat", _F64, (2,))
+    ldr = _matrix(resp, "resp", N, K, optional=True)[2] or K
+    _dense(labels, "labels", _I64, N, optional=True)
+    part = gmm_scratch(N, D, K, GMM_ESTEP, X.device) if part is None else _buffer(part, "part", _F64)
     check(lib.vsom_gmm_estep(ptr(X), ldx, N, D, ptr(means), ptr(prec), ptr(logc), K, ptr(resp), ldr, ptr(log_prob_norm),
                              ptr(labels), ptr(estat), ptr(part), part.numel(), stream()), "vsom_gmm_estep")
     return log_prob_norm
 
 
 def gmm_mstep(X, resp, means_old, part):
-    """The M-step's per-slab partial sums (nk, S1, S2 shifted at means_old f32 [K, D]) into part, fp64
-    [>= gmm_parts(N, D, K, GMM_MSTEP)]; gmm_params turns them into parameters."""
-    N, D, ldx = _kmeans_x(X)
-    _f32(resp, "resp"); _f32(means_old, "means_old")
-    assert means_old.dim() == 2 and means_old.shape[1] == D and means_old.is_contiguous()
-    K = means_old.shape[0]
-    assert resp.dim() == 2 and tuple(resp.shape) == (N, K), "resp must be [N, K]"
-    assert part.dtype == torch.float64 and part.is_cuda and part.dim() == 1 and part.is_contiguous()
-    check(lib.vsom_gmm_mstep(ptr(X), ldx, N, D, ptr(resp), _rows(resp), ptr(means_old), K, ptr(part), part.numel(), stream()),
+    """The M-step's per-slab partial sums (nk, S1, S2 shifted at means_old f32 [K, D]) of X [N, D] under resp f32 [N, K]
+    (both with any row stride) into part, fp64 [>= gmm_parts(N, D, K, GMM_MSTEP)] (the entry checks its size); gmm_params
+    turns them into parameters."""
+    N, D, ldx = _matrix(X, "X")
+    K = _dense(means_old, "means_old", _F32, (None, D)).shape[0]
+    _, _, ldr = _matrix(resp, "resp", N, K)
+    _buffer(part, "part", _F64)
+    check(lib.vsom_gmm_mstep(ptr(X), ldx, N, D, ptr(resp), ldr, ptr(means_old), K, ptr(part), part.numel(), stream()),
           "vsom_gmm_mstep")
     return part
 
@@ -1556,16 +1518,13 @@ def gmm_mstep(X, resp, means_old, part):
 def gmm_params(part, N, means_old, reg_covar, spherical, n_norm, estat, means, cov, prec, weights, logc, record):
     """New means f32 [K, D], cov fp64 ([K, D]; spherical: [K]), prec f32 [K, D], weights and logc fp64 [K] from gmm_mstep's
     part; weights = nk / n_norm, or nk / sum(nk) when n_norm == 0.  record fp64 [GMM_RECORD]: the lower bound estat[0] / N
-    (estat None: NaN), the smallest nk, the smallest covariance, the covariances <= 0 or not finite, the refused rows."""
-    K, D = means_old.shape
-    _gmm_kd(means, prec, D)
-    _f32(means_old, "means_old")
-    assert means_old.is_contiguous() and means.shape[0] == K
-    _pca_f64(cov, (K,) if spherical else (K, D), "cov")
-    _pca_f64(weights, (K,), "weights"); _pca_f64(logc, (K,), "logc"); _pca_f64(record, (GMM_RECORD,), "record")
-    if estat is not None:
-        _pca_f64(estat, (2,), "estat")
-    assert part.dtype == torch.float64 and part.is_cuda and part.dim() == 1 and part.is_contiguous()
+    (estat fp64 [2], optional; None: NaN), the smallest nk, the smallest covariance, the covariances <= 0 or not finite, the
+    refused rows."""
+    K, D = _dense(means_old, "means_old", _F32, (None, None)).shape
+    _dense(means, "means", _F32, (K, D)); _dense(prec, "prec", _F32, (K, D))
+    _dense(cov, "cov", _F64, (K,) if spherical else (K, D))
+    _dense(weights, "weights", _F64, (K,)); _dense(logc, "logc", _F64, (K,)); _dense(record, "record", _F64, (GMM_RECORD,))
+    _dense(estat, "estat", _F64, (2,), optional=True); _buffer(part, "part", _F64)
     check(lib.vsom_gmm_params(ptr(part), part.numel(), int(N), D, K, ptr(means_old), float(reg_covar), int(bool(spherical)),
                               int(n_norm), ptr(estat), ptr(means), ptr(cov), ptr(prec), ptr(weights), ptr(logc), ptr(record),
                               stream()), "vsom_gmm_params")
@@ -1574,13 +1533,12 @@ def gmm_params(part, N, means_old, reg_covar, spherical, n_norm, estat, means, c
 
 def gmm_set_params(weights, cov, D, spherical, prec, logc, record, part=None):
     """prec f32 [K, D], logc fp64 [K] and record[GMM_MIN_COV], record[GMM_BAD_COV] from given weights fp64 [K] and
-    covariances fp64 ([K, D]; spherical: [K])."""
-    K = weights.numel()
-    _pca_f64(weights, (K,), "weights"); _pca_f64(cov, (K,) if spherical else (K, D), "cov")
-    _f32(prec, "prec")
-    assert tuple(prec.shape) == (K, D) and prec.is_contiguous(), "prec must be a contiguous [K, D]"
-    _pca_f64(logc, (K,), "logc"); _pca_f64(record, (GMM_RECORD,), "record")
-    part = gmm_scratch(1, D, K, GMM_SET, weights.device) if part is None else part
+    covariances fp64 ([K, D]; spherical: [K]).  part (optional): fp64, at least gmm_parts(1, D, K, GMM_SET) doubles (the
+    entry checks its size); None: the shared scratch."""
+    K = _dense(weights, "weights", _F64, (None,)).numel()
+    _dense(cov, "cov", _F64, (K,) if spherical else (K, D))
+    _dense(prec, "prec", _F32, (K, D)); _dense(logc, "logc", _F64, (K,)); _dense(record, "record", _F64, (GMM_RECORD,))
+    part = gmm_scratch(1, D, K, GMM_SET, weights.device) if part is None else _buffer(part, "part", _F64)
     check(lib.vsom_gmm_set_params(ptr(weights), ptr(cov), int(D), K, int(bool(spherical)), ptr(prec), ptr(logc), ptr(record),
                                   ptr(part), part.numel(), stream()), "vsom_gmm_set_params")
     return prec, logc
