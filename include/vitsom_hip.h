@@ -1067,6 +1067,46 @@ int vsom_scale_by(float* p, long n, const float* scale_dev, vsom_stream_t stream
 int vsom_reduce_slabs(const float* slabs, long stride, int nslabs, float* out, long n,
                       vsom_stream_t stream);
 
+/* ------------------------------------------------------------------ agglomerative clustering (agglomerative.hip)
+ * The two parts of sklearn.cluster.AgglomerativeClustering / scipy.cluster.hierarchy.linkage that cost time;
+ * vit_som_amd/agglomerative.py drives them and cuts the tree, DESIGN.md section 4 has the algorithm; no counterpart in the
+ * reference.  Limits of every entry: 1 <= N <= 16 384 (more: VSOM_EUNSUPPORTED with the bound in the message; the fp64
+ * matrix is then 2 GiB).  No floating-point atomics, no cooperative launch, no loop that waits for another workgroup: all
+ * outputs are bitwise reproducible.
+ *
+ * The workspace, vsom_agglo_workspace_bytes(N, connectivity) bytes (0 for N outside the limits), 8-byte aligned, holds at
+ * byte 0 the fp64 [N, N] matrix (dense, row stride N), at byte (8 N^2 rounded up to 256) the [N, N] byte adjacency when
+ * connectivity != 0, then the slots' state.  The caller fills the matrix (vsom_agglo_distances with out = the workspace,
+ * ldo = N, or a matrix of its own) and the adjacency (symmetric, 0 / 1) before vsom_agglo_merge, which overwrites both. */
+#define VSOM_AGGLO_EUCLIDEAN 0
+#define VSOM_AGGLO_MANHATTAN 1
+#define VSOM_AGGLO_COSINE 2
+#define VSOM_AGGLO_WARD 0
+#define VSOM_AGGLO_AVERAGE 1
+#define VSOM_AGGLO_COMPLETE 2
+#define VSOM_AGGLO_SINGLE 3
+long vsom_agglo_workspace_bytes(long N, int connectivity);
+/* vsom_agglo_distances: out[i, j] (fp64, row stride ldo >= N) for all i, j in the DIRECT form, every difference, product
+ * and sum in fp64 on the f32 values of X [N, D] (row stride ldx; 16-byte loads when D % 4 == 0, ldx % 4 == 0 and X is
+ * 16-byte aligned, element loads otherwise), columns ascending: euclidean sum_d (x - y)^2 (squared != 0) or its
+ * correctly rounded square root; manhattan sum_d |x - y|; cosine max(0, 1 - x.y / sqrt(|x|^2 |y|^2)).  out[i, j] and
+ * out[j, i] are the same bits, the diagonal is 0, identical rows are at exactly 0.  status (int32 [2], cleared here):
+ * [0] the values of X that are NaN or infinite, [1] the rows of zero length (cosine: their distances are written as 1). */
+int vsom_agglo_distances(const float* X, long ldx, long N, int D, int metric, int squared, double* out, long ldo, int* status,
+                         vsom_stream_t stream);
+/* vsom_agglo_merge: the generic greedy algorithm with a nearest-neighbour array on the workspace's matrix (SQUARED
+ * euclidean distances for VSOM_AGGLO_WARD), N >= 2 (else VSOM_EINVAL).  Step s = 0 .. N - 2 merges the pair of active,
+ * adjacent slots (a < b) that is least under the total order (distance, a, b); children[2 s], children[2 s + 1] (int32)
+ * are the two clusters' ids in scipy's numbering (rows 0 .. N - 1, the cluster of step s is N + s), the smaller first;
+ * distances[s] (fp64) is the pair's distance (its square root for Ward).  The merged cluster takes slot b; row and column
+ * b follow the Lance-Williams update in fp64 without contraction; with connectivity != 0 the adjacency rows are OR-ed and
+ * only adjacent clusters merge, at the FULL linkage distance over all their members.  3 (N - 1) + 2 launches are enqueued;
+ * nothing is read back.  A step that finds no adjacent pair writes children -1, -1 and a NaN distance.  status (int32
+ * [4]): [0] such steps (the graph's components less one), [1] slots other than b whose nearest neighbour was searched
+ * again, [2] steps with such a slot, [3] zero.  ws too small or NULL: VSOM_EWORKSPACE; not 8-byte aligned: VSOM_EALIGN. */
+int vsom_agglo_merge(void* ws, long ws_size, long N, int linkage, int connectivity, int* children, double* distances, int* status,
+                     vsom_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -212,6 +212,9 @@ SIGNATURES = {
     "vsom_gmm_params": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, C.c_int, c_fp, C.c_double, C.c_int, C.c_long, c_fp, c_fp, c_fp,
                                   c_fp, c_fp, c_fp, c_fp, c_stream]),
     "vsom_gmm_set_params": (C.c_int, [c_fp, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_long, c_stream]),
+    "vsom_agglo_workspace_bytes": (C.c_long, [C.c_long, C.c_int]),
+    "vsom_agglo_distances": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, c_fp, C.c_long, c_fp, c_stream]),
+    "vsom_agglo_merge": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_stream]),
     "vsom_fill": (C.c_int, [c_fp, C.c_long, C.c_float, c_stream]),
     "vsom_scaled_mul": (C.c_int, [c_fp, c_fp, c_fp, C.c_long, c_fp, C.c_float, c_stream]),
     "vsom_som_weighted_loss": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_float, c_fp, c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_int,

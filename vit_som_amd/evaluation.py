@@ -11,7 +11,9 @@ Scaffolding, each written once:
 
 Entries, by what they read from the model (every entry runs with grad mode off; with model.world_size > 1 every rank
 returns the whole set's result; figures are drawn by rank 0):
-  predict(), images for every arch     evaluate_clustering (BMUs -> `vsom_contingency`), evaluate_classification (logits)
+  predict(), images for every arch     evaluate_clustering (BMUs -> `vsom_contingency`), evaluate_classification (logits),
+                                       evaluate_map_clusters (the BMU's cluster of units; defined in agglomerative.py next
+                                       to its estimator, reachable from here)
   predict(), the arch's own shape      visualize_label_heatmap (`vsom_last_label`), evaluate_map_quality / visualize_hit_map
                                        (the SOM layer's buffers -> `vsom_map_stats`)
   k-means feature, model(x)[1]         evaluate_kmeans (kmeans.py)
@@ -24,7 +26,8 @@ returns the whole set's result; figures are drawn by rank 0):
   SOM input and BMU                    evaluate_silhouette / visualize_silhouette_map (silhouette.py),
                                        evaluate_latent_spectrum, init_som_from_data, fit_som_batch (SOMLayer.fit_batch)
   the prototypes only, no data         visualize_decoded_prototypes / decoded_prototype_canvas / decode_prototype
-                                       (`vsom_proto_mosaic`), umatrix / visualize_umatrix (`vsom_umatrix`), map_neighbourhood
+                                       (`vsom_proto_mosaic`), umatrix / visualize_umatrix (`vsom_umatrix`), map_neighbourhood,
+                                       visualize_map_clusters (agglomerative.py)
 Host arithmetic on a table: purity_from_table, nmi_from_table, classification_from_table, calculate_purity."""
 import os
 import time
@@ -39,6 +42,7 @@ from .kmeans import KMeans
 from .knn import KNNClassifier
 from .linear_probe import LinearProbeReport, evaluate_linear_probe, linear_probe_report  # noqa: F401  (the entry lives with its estimator)
 from .gmm import GMMReport, evaluate_gmm  # noqa: F401  (the entry lives with its estimator)
+from .agglomerative import MapClustersReport, evaluate_map_clusters, visualize_map_clusters  # noqa: F401  (likewise)
 from .tsne import TSNEQualityReport, evaluate_tsne_quality, visualize_tsne_progression  # noqa: F401  (the entries live with their estimator)
 from .plots import _draw_grid, _draw_map, _pyplot, _save_scatter, _umap_scatter, draw_decoded_prototypes, draw_label_heatmap  # noqa: F401
 from .silhouette import cluster_silhouette

@@ -11,7 +11,8 @@ whose address crosses into the library is checked there for device, dtype, layou
 ``_matrix`` / ``_dense`` / ``_buffer``, None passes only where the docstring says optional, and a
 refusal is a ``ValueError`` naming the argument, raised before anything is launched, ``python -O``
 or not.  A buffer whose element count goes to the entry (a workspace, ``zpart``, ``part``) is sized
-by the entry, which refuses a short one before it launches.
+by the entry, which refuses a short one before it launches.  The agglomerative-clustering wrappers at
+the end of the module are evaluation wrappers under the same contract.
 """
 from contextlib import contextmanager
 from typing import Optional
@@ -1632,3 +1633,56 @@ def tape_segment_ops(tape: int, segment: int) -> int:
 
 def tape_destroy(tape: int):
     check(lib.vsom_tape_destroy(int(tape)), "vsom_tape_destroy")
+
+
+# ---------------------------------------------------------------- agglomerative clustering (agglomerative.py)
+# Evaluation wrappers like those between the `evaluation` banner and the RCCL section, under the same contract: every tensor
+# passes _matrix / _dense / _buffer before its address goes to the library, and a refusal is a ValueError.
+AGGLO_MAX_N = 16384                                              # csrc/agglomerative.hip: AG_MAX_N
+AGGLO_EUCLIDEAN, AGGLO_MANHATTAN, AGGLO_COSINE = 0, 1, 2
+AGGLO_WARD, AGGLO_AVERAGE, AGGLO_COMPLETE, AGGLO_SINGLE = 0, 1, 2, 3
+AGGLO_STATUS = 4                                                 # int32 words of agglo_merge's status
+AGGLO_MISSING, AGGLO_RESCANNED, AGGLO_RESCAN_STEPS = 0, 1, 2
+
+
+def agglo_workspace_bytes(N, connectivity) -> int:
+    """Bytes of agglo_merge's workspace: host arithmetic, 0 for N < 1 or N > AGGLO_MAX_N."""
+    return int(lib.vsom_agglo_workspace_bytes(int(N), int(bool(connectivity))))
+
+
+def agglo_matrix(ws, N):
+    """The fp64 [N, N] matrix at the head of an agglo_merge workspace, as a view."""
+    _buffer(ws, "ws", _U8, 8 * N * N)
+    return ws[:8 * N * N].view(torch.float64).view(N, N)
+
+
+def agglo_adjacency(ws, N):
+    """The uint8 [N, N] adjacency of an agglo_merge workspace sized with connectivity, as a view."""
+    at = (8 * N * N + 255) // 256 * 256
+    _buffer(ws, "ws", _U8, at + N * N)
+    return ws[at:at + N * N].view(N, N)
+
+
+def agglo_distances(X, metric, squared, out, status):
+    """out fp64 [N, N] contiguous = the distances between the rows of X f32 [N, D] (any row stride) in the direct form, all
+    arithmetic in fp64: AGGLO_EUCLIDEAN (squared: the sum of squares, else its root), AGGLO_MANHATTAN, AGGLO_COSINE.
+    Symmetric bit for bit, zero diagonal.  status int32 [2]: the values that are not finite, the zero rows (cosine)."""
+    N, D, ldx = _matrix(X, "X")
+    _dense(out, "out", _F64, (N, N)); _dense(status, "status", _I32, (2,))
+    check(lib.vsom_agglo_distances(ptr(X), ldx, N, D, int(metric), int(bool(squared)), ptr(out), N, ptr(status), stream()),
+          "vsom_agglo_distances")
+    return out
+
+
+def agglo_merge(ws, N, linkage, connectivity, children, distances, status):
+    """The N - 1 merges of the matrix (and, connectivity: the adjacency) that ws holds -- uint8, at least
+    agglo_workspace_bytes(N, connectivity) bytes (the entry checks its size), both overwritten -> children int32 [N - 1, 2]
+    in scipy's numbering, distances fp64 [N - 1], status int32 [AGGLO_STATUS]: steps that found no adjacent pair, slots
+    searched again, steps with such a slot.  Everything is enqueued; nothing is read back."""
+    N = int(N)
+    _buffer(ws, "ws", _U8)
+    _dense(children, "children", _I32, (max(N - 1, 0), 2)); _dense(distances, "distances", _F64, (max(N - 1, 0),))
+    _dense(status, "status", _I32, (AGGLO_STATUS,))
+    check(lib.vsom_agglo_merge(ptr(ws), ws.numel(), N, int(linkage), int(bool(connectivity)), ptr(children), ptr(distances),
+                               ptr(status), stream()), "vsom_agglo_merge")
+    return children, distances

@@ -348,6 +348,16 @@ class SOMLayer(_Base):
         distances^2 are 1, 2, 4, ... (2.25 takes the 8 around a cell), hexagonal ones 1, 3, ... (1.5 takes the 6)."""
         return {"square": 2.25, "hexa": 1.5}[self.topology]
 
+    def grid_connectivity(self) -> torch.Tensor:
+        """bool [K, K] on the prototypes' device: unit u touches unit v on the grid (grid_positions within
+        adjacency_radius2(), the 8 around a cell of a square map, the 6 of a hexagonal one); symmetric, empty diagonal.  What
+        AgglomerativeClustering(connectivity=...) takes to keep every cluster of units one region of the map."""
+        pos = self.grid_positions.to(self.prototypes.device).double()
+        d2 = ((pos[:, None, :] - pos[None, :, :]) ** 2).sum(dim=-1)
+        near = d2 <= self.adjacency_radius2()
+        near.fill_diagonal_(False)
+        return near
+
     def _buffers_for(self, B: int, device) -> _Acts:
         s = self._bufs.get(B)
         if s is not None and s.device == device:
