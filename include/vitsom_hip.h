@@ -193,7 +193,8 @@ int vsom_layernorm_bwd_finish_many(const int64_t* jobs_dev, int first, int count
  * deterministic).  _partial leaves the partials in `part` for vsom_layernorm_bwd_finish_many (same job format, nblk =
  * part_bytes_query / (8 K)).  Supported (vsom_linear_bwd_input_ln_supported != 0): the split-bf16 GEMM modes, K = 192 or
  * 96, enough row tiles for the column reducer; otherwise VSOM_EUNSUPPORTED and the caller takes the two-launch path.
- * Pointers 16-byte aligned, lddy % 4 == 0, X / resid / dX dense [M, K]. */
+ * vsom_linear_bwd_input_ln and vsom_linear_bwd_input_ln_partial alike: dY, Wt, X, gamma, resid and dX 16-byte aligned,
+ * lddy % 4 == 0 and N % 4 == 0 (VSOM_EALIGN otherwise: there is no element-wise form); X / resid / dX dense [M, K]. */
 int vsom_linear_bwd_input_ln_supported(int M, int N, int K);
 size_t vsom_linear_bwd_input_ln_partial_bytes(int M, int K);
 int vsom_linear_bwd_input_ln(const float* dY, long lddy, const float* Wt, int M, int N, int K, const float* X,
@@ -206,10 +207,12 @@ int vsom_linear_bwd_input_ln_partial(const float* dY, long lddy, const float* Wt
 /* ------------------------------------------------------------------ multi-head attention */
 /* out[B,N,H*hd] = softmax(q k^T * hd^-0.5) v, qkv laid out [B,N,3,H,hd] (the qkv Linear's
  * output, vit.py:30-37; dropout p=0).  lse[B,H,N] = log-sum-exp of the scaled scores (saved for
- * the backward, which recomputes the probabilities). */
+ * the backward, which recomputes the probabilities).  hd = 16, 32 or 64 (the 16-byte path): qkv and out 16-byte aligned,
+ * else VSOM_EALIGN; hd <= 8 (element loads): any alignment. */
 int vsom_attention_fwd(const float* qkv, float* out, float* lse, int B, int N, int H, int hd,
                        vsom_stream_t stream);
-/* dqkv[B,N,3,H,hd] from dout[B,N,H*hd] (autograd of the above). delta_ws: [B,H,N] floats. */
+/* dqkv[B,N,3,H,hd] from dout[B,N,H*hd] (autograd of the above). delta_ws: [B,H,N] floats.  hd = 16, 32 or 64: qkv, out,
+ * dout and dqkv 16-byte aligned, else VSOM_EALIGN; hd <= 8: any alignment. */
 int vsom_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse,
                        float* dqkv, float* delta_ws, int B, int N, int H, int hd,
                        vsom_stream_t stream);
@@ -231,7 +234,8 @@ int vsom_set_attention_fused(int fused);
  * (bitwise reproducible).  q / kv / o 16-byte aligned. */
 int vsom_attention_q1_fwd(const float* q, const float* kv, float* o, float* lse, int B, int N, int H, int hd,
                           vsom_stream_t stream);
-/* dq[B,E] and dkv[B*N,2E] from dout[B,E] (autograd of the above); each (image, head) owns its rows of dkv. */
+/* dq[B,E] and dkv[B*N,2E] from dout[B,E] (autograd of the above); each (image, head) owns its rows of dkv.  dout / o / q /
+ * kv / dkv 16-byte aligned (VSOM_EALIGN otherwise, as for q / kv / o above). */
 int vsom_attention_q1_bwd(const float* dout, const float* o, const float* lse, const float* q, const float* kv, float* dq,
                           float* dkv, int B, int N, int H, int hd, vsom_stream_t stream);
 /* dst[r, 0:cols] += src[r, 0:cols] for r < rows (row strides lds / ldd in floats): the CLS rows' residual gradient. */
@@ -327,7 +331,8 @@ int vsom_cross_entropy_ls(const float* logits, const int64_t* y, float smoothing
 /* One decoupled-weight-decay Adam step over a flat fp32 arena (torch.optim.AdamW semantics,
  * vit_som.py:146-151).  wd_per_chunk[i] is the weight decay of elements [256 i, 256 i + 256);
  * adamw=0 selects torch.optim.Adam (L2 in the gradient).  g is multiplied by grad_scale first
- * (1/world_size after a sum all-reduce). */
+ * (1/world_size after a sum all-reduce).  n a multiple of 256; p, g, m and v 16-byte aligned (VSOM_EALIGN otherwise:
+ * the arena is walked 16 bytes at a time and has no element-wise form). */
 int vsom_adamw_step(float* p, const float* g, float* m, float* v, const float* wd_per_chunk, long n,
                     float lr, float beta1, float beta2, float eps, int step, float grad_scale,
                     int adamw, vsom_stream_t stream);
@@ -855,7 +860,10 @@ int vsom_som_weighted_loss(const float* dist, const float* weights, const float*
    the normalised dot| <= 3 * 2^-16) + the squared row norms of X and W; stage 2 = inv_nx / inv_nw
    (1 / max(|row|, 1e-12)), dist, and bmu = first argmin after every prototype within 2e-4 of the approximate
    minimum has been re-ranked with an exact (fp64-accumulated) dot product, whose distance also replaces the
-   approximate one in dist: bmu == argmin(dist) exactly.  K <= 2048; rows 16-byte aligned. */
+   approximate one in dist: bmu == argmin(dist) exactly.  K <= 2048; rows 16-byte aligned: X and W 16-byte aligned, L and
+   ldx multiples of 4.  vsom_bmu_cosine_x3_dots answers VSOM_EALIGN to anything else (the caller then runs the exact form);
+   vsom_bmu_cosine_x3_finalize, whose re-rank reads the rows of X and W 16 bytes at a time, answers VSOM_EALIGN to a
+   misaligned X or W and VSOM_EINVAL to an L or ldx that stage 1 would have refused. */
 size_t vsom_bmu_cosine_x3_workspace_bytes(int B, int K, int L);
 int vsom_bmu_cosine_x3_dots(const float* X, long ldx, const float* W, int B, int K, int L, void* ws, size_t ws_bytes,
                             vsom_stream_t stream);
@@ -871,11 +879,16 @@ int vsom_bmu_cosine_x3_finalize(const float* X, long ldx, const float* W, const 
    rows' squared-norm partials.  The caller owns validity: a plane buffer describes the operand as it was when written.
    Covered shapes: vsom_bmu_cosine_x3_planes_supported (B >= 192, L % 8 == 0, K <= 2048, images < 2 GB); slabs, and
    therefore dist / bmu, are those of vsom_bmu_cosine_x3_dots bit for bit (norms: last-bit differences).
+   Alignment: vsom_bmu_planes_from wants src 16-byte aligned and ld % 4 == 0 (VSOM_EINVAL otherwise) and, like
+   vsom_adamw_step_planes, a 16-byte aligned plane buffer (VSOM_EWORKSPACE); vsom_bmu_cosine_x3_planes_dots refuses a
+   misaligned plane buffer with VSOM_EINVAL; vsom_bmu_cosine_x3_planes_finalize reads the rows of X and W 16 bytes at a time
+   in its re-rank: X and W 16-byte aligned (VSOM_EALIGN), ldx % 4 == 0 (VSOM_EINVAL).
    Same reference lines as above (som_layer.py:119-122, 83-89); the AdamW variant replaces vit_som.py:146-151. */
 size_t vsom_bmu_planes_bytes(int R, int L);
 int vsom_bmu_planes_from(const float* src, long ld, int R, int L, void* planes, size_t planes_bytes, vsom_stream_t stream);
 /* vsom_adamw_step over the arena of n elements (same arguments, bitwise the same update) that also writes the plane
-   buffer of the [R, L] parameter at element offset slice_off (a multiple of 256) from its UPDATED values. */
+   buffer of the [R, L] parameter at element offset slice_off (a multiple of 256) from its UPDATED values.  p, g, m and v
+   16-byte aligned, as for vsom_adamw_step (VSOM_EALIGN). */
 int vsom_adamw_step_planes(float* p, const float* g, float* m, float* v, const float* wd_per_chunk, long n, float lr,
                            float beta1, float beta2, float eps, int step, float grad_scale, int adamw, long slice_off,
                            int R, int L, void* planes, size_t planes_bytes, vsom_stream_t stream);
@@ -890,7 +903,7 @@ int vsom_bmu_cosine_x3_planes_finalize(const float* X, long ldx, const float* W,
 /* Which of the three forms above a caller of the cosine BMU pass should run for B sample rows of stride ldx against K
    prototypes of L elements, under the current GEMM mode ("Which kernel runs": Cosine BMU pass):
    VSOM_BMU_EXACT (vsom_bmu_cosine_*, after the two row-norm passes), VSOM_BMU_X3 (vsom_bmu_cosine_x3_*) or VSOM_BMU_X3_PLANES
-   (vsom_bmu_cosine_x3_planes_*).  flags bit 0: X is 16-byte aligned; bit 1: the caller can supply plane images.  Pure host
+   (vsom_bmu_cosine_x3_planes_*).  flags bit 0: X and W are 16-byte aligned; bit 1: the caller can supply plane images.  Pure host
    arithmetic, the same plan the entry points take their grids and workspace sizes from.  VSOM_EINVAL on a non-positive
    shape. */
 #define VSOM_BMU_EXACT 0
@@ -907,7 +920,8 @@ int vsom_bmu_cosine_form(int B, int K, int L, long ldx, int flags);
  * the rank count.  Boxes: the loop-free RandomResizedCrop draw of tools/utils.py:93-113 (area share U(scale0, scale1),
  * aspect exp(U(log_ratio0, log_ratio1)), Python rounding, clamped to [1, size]), the second on the S x S result of the
  * first; flip: one Bernoulli(flip_p); erase: timm RandomErasing's draw with probability erase_p (ten attempts of
- * area U(0.02, 1/3) S^2, aspect exp(U(log 0.3, log 1/0.3)), accepted when h < S and w < S). */
+ * area U(0.02, 1/3) S^2, aspect exp(U(log 0.3, log 1/0.3)), accepted when h < S and w < S).  params is written a row (64
+ * bytes) at a time and must be 16-byte aligned (VSOM_EALIGN), here and wherever a batch entry below reads it. */
 #define VSOM_AUGMENT_PARAMS 16
 int vsom_augment_plan(const int64_t* index, long N, int B, int H, int S, double scale0, double scale1, double log_ratio0,
                       double log_ratio1, int two_stage, double scale2_0, double scale2_1, double log_ratio2_0,
@@ -922,7 +936,8 @@ int vsom_augment_plan(const int64_t* index, long N, int B, int H, int S, double 
  * transform with R = int(S / 0.875), off = round((R - S) / 2), or identity geometry with R = S = H.  out_u8 (nullable,
  * [B, C, S, S], 4-byte aligned) receives the 8-bit image before normalisation.  mean, std: C floats on the device.
  * S <= 64, S <= R <= 73, H <= 4 S.  An index outside [0, N) is clamped into it, by both entries alike (N = rows of the
- * data set), so plan, noise and pixels still belong to one row; a box outside its image is moved inside. */
+ * data set), so plan, noise and pixels still belong to one row; a box outside its image is moved inside.  out and params
+ * not 16-byte aligned, or out_u8 not 4-byte aligned: VSOM_EALIGN. */
 int vsom_augment_batch(const unsigned char* src, long N, int C, int H, int W, const int64_t* index, const int32_t* params,
                        int B, int S, int R, int off, const float* mean, const float* std, uint64_t seed, int epoch,
                        float* out, unsigned char* out_u8, vsom_stream_t stream);
@@ -950,7 +965,8 @@ int vsom_augment_batch(const unsigned char* src, long N, int C, int H, int W, co
  * Rotate, PosterizeIncreasing, SolarizeIncreasing, SolarizeAdd, Color, Contrast, Brightness, SharpnessIncreasing, ShearX,
  * ShearY, TranslateXRel, TranslateYRel} at m = clamp(N(9, 0.5), 0, 10) (rotate 3 m degrees, shear 0.03 m, translate
  * 0.045 m S px, enhance max(0.1, 1 +- 0.09 m), 4 - int(0.4 m) bits, threshold 256 - int(25.6 m), addend min(128, int(11 m)));
- * BICUBIC, fill fill_timm.  Rotations follow Image.rotate about (S / 2, S / 2).  fill_*: R | G << 8 | B << 16. */
+ * BICUBIC, fill fill_timm.  Rotations follow Image.rotate about (S / 2, S / 2).  fill_*: R | G << 8 | B << 16.  ra not
+ * 16-byte aligned: VSOM_EALIGN. */
 #define VSOM_RANDAUG_PARAMS 72
 int vsom_randaug_plan(const int64_t* index, long N, int B, int S, int randaug_n, int autoaugment, double flip1_p, uint32_t fill_tv,
                       uint32_t fill_timm, uint64_t seed, int epoch, int32_t* ra, vsom_stream_t stream);
@@ -961,7 +977,7 @@ int vsom_randaug_plan(const int64_t* index, long N, int B, int S, int randaug_n,
  * pixel (BICUBIC), ImageEnhance's fp32 blend with its degenerate images, ImageOps' tables.  A slot that is not a record
  * the plan would write is made safe, never refused (the records live on the device): an unknown primitive does nothing, the
  * integer parameter is clamped to 0 .. 256, NaN coefficients become 0 and others are clamped to +-16384, a NaN factor
- * becomes 1. */
+ * becomes 1.  out, params and ra 16-byte aligned, out_u8 4-byte aligned (VSOM_EALIGN otherwise). */
 int vsom_augment_batch_ra(const unsigned char* src, long N, int C, int H, int W, const int64_t* index, const int32_t* params,
                           const int32_t* ra, int B, int S, const float* mean, const float* std, uint64_t seed, int epoch,
                           float* out, unsigned char* out_u8, vsom_stream_t stream);
@@ -972,7 +988,8 @@ int vsom_augment_batch_ra(const unsigned char* src, long N, int C, int H, int W,
  * side (at most 2048).  The transform is vsom_augment_plan's and vsom_augment_batch's -- the same plan row, Philox counters,
  * PIL resampler and output stage -- for outputs up to S = 224 and crops of up to 8 x their output side (33 taps).
  * vsom_augment_plan_ragged: vsom_augment_plan with box 1 drawn on the sample's own H_n x W_n.  On a table whose rows are
- * all (H, H) it writes what vsom_augment_plan(H) writes, bit for bit. */
+ * all (H, H) it writes what vsom_augment_plan(H) writes, bit for bit.  params 16-byte aligned, shapes 4-byte aligned
+ * (VSOM_EALIGN otherwise). */
 int vsom_augment_plan_ragged(const int64_t* index, const int32_t* shapes, long N, int B, int S, double scale0, double scale1,
                              double log_ratio0, double log_ratio1, int two_stage, double scale2_0, double scale2_1,
                              double log_ratio2_0, double log_ratio2_1, double flip_p, double erase_p, uint64_t seed, int epoch,
@@ -989,7 +1006,8 @@ size_t vsom_augment_ragged_scratch_bytes(int B, int C, int S);
  * Every resize is Image.crop(box).resize(size, BICUBIC) byte for byte: horizontal pass first, 8-bit intermediate, taps stop
  * at the box.  On a set whose images are all H x H, H <= 64, out and out_u8 equal vsom_augment_batch's bit for bit.
  * Limits (checked before any launch): S <= 224, R <= 256, C 1 or 3, max_h, max_w <= 2048 and <= 8 S (training) or 8 R
- * (evaluation); data, out, params, scratch 16-byte aligned, out_u8 4-byte aligned.
+ * (evaluation); data, out, params, scratch 16-byte aligned, out_u8 and shapes 4-byte aligned, offsets 8-byte aligned
+ * (VSOM_EALIGN otherwise).
  * Tables on the device cannot be refused, so they are made safe: the index is clamped into [0, N), the shape into
  * [1, max_h] x [1, max_w], the offset so that the image lies inside data[0, data_bytes), every box inside its image.  A bad
  * table reads wrong pixels, never outside the buffer. */

@@ -6,6 +6,8 @@ harness tests itself on the CPU.
 
 The arena of one buffer is  [front guard | payload | back guard]:
 
+* with shift = s the payload starts s elements of its dtype past the 256-byte boundary instead of on it (an operand that is
+  not 16-byte aligned: tests/alignment.py); the elements between the boundary and the payload belong to the front guard;
 * the guards, and the padding columns of a strided payload (ld > shape[-1]), hold the 32-bit word GUARD_WORD.  Read as
   float32 or float64 it is a NaN, read as int32 / int64 it is negative: a kernel that reads past an input's extent and lets
   the value reach a result shows in the comparison of results, a kernel that writes there shows in `check()`;
@@ -48,7 +50,7 @@ def _pattern_arena(nbytes, device):
 class Guarded:
     """Handle of one guarded buffer: `.view` is the tensor to hand to a kernel."""
 
-    def __init__(self, shape, dtype, device, ld=None, front=FRONT_GUARD, back=None, poison=True):
+    def __init__(self, shape, dtype, device, ld=None, front=FRONT_GUARD, back=None, poison=True, shift=0):
         shape = tuple(int(s) for s in shape)
         assert len(shape) >= 1 and all(s >= 0 for s in shape)
         self.shape, self.dtype, self.device = shape, dtype, torch.device(device)
@@ -64,13 +66,15 @@ class Guarded:
         self.nbytes = n_elem * size
         assert front % 4 == 0 and front >= 0
         self.front = front
+        self.shift = int(shift)
+        assert 0 <= self.shift * size < ALIGN, "a shift is a few whole elements"
         self.back = max(BACK_GUARD_MIN, self.nbytes) if back is None else int(back)
-        total = front + self.nbytes + self.back
+        total = front + self.nbytes + self.back + self.shift * size
         self.arena = _pattern_arena(total, device)
-        # the payload starts at the first 256-byte aligned address at or after `front` bytes into the arena
-        self.off = front + (-(self.arena.data_ptr() + front)) % ALIGN
+        # the payload starts `shift` elements past the first 256-byte aligned address at or after `front` bytes into the arena
+        self.off = front + (-(self.arena.data_ptr() + front)) % ALIGN + self.shift * size
         self.view = self._view_of(self.arena)
-        assert self.view.data_ptr() % ALIGN == 0
+        assert self.view.data_ptr() % ALIGN == self.shift * size
         if poison and self.view.numel():
             idt, val = _POISON[dtype]
             self._int_view(self.arena).fill_(val)
@@ -122,15 +126,16 @@ class Guarded:
                                  f"flat index {int(left[0])} (shape {self.shape}, {self.dtype})")
 
 
-def guarded(shape, dtype, device, ld=None, front=FRONT_GUARD, back=None):
-    """-> (view, handle): a poisoned tensor of `shape` (row pitch `ld` when given) between two guard bands."""
-    h = Guarded(shape, dtype, device, ld=ld, front=front, back=back)
+def guarded(shape, dtype, device, ld=None, front=FRONT_GUARD, back=None, shift=0):
+    """-> (view, handle): a poisoned tensor of `shape` (row pitch `ld` when given) between two guard bands, its first
+    element `shift` elements past a 256-byte boundary."""
+    h = Guarded(shape, dtype, device, ld=ld, front=front, back=back, shift=shift)
     return h.view, h
 
 
-def guarded_copy(t, ld=None, front=FRONT_GUARD, back=None):
+def guarded_copy(t, ld=None, front=FRONT_GUARD, back=None, shift=0):
     """-> (view, handle): the values of `t` in a guarded arena of its own (an input: what surrounds it reads as NaN / negative)."""
-    v, h = guarded(t.shape, t.dtype, t.device, ld=ld, front=front, back=back)
+    v, h = guarded(t.shape, t.dtype, t.device, ld=ld, front=front, back=back, shift=shift)
     v.copy_(t)
     return v, h
 

@@ -102,6 +102,62 @@ def test_guarded_copy_keeps_the_values():
     h.check(); h.all_written()
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8])
+@pytest.mark.parametrize("shift", [1, 2, 3])
+def test_a_shifted_payload_starts_off_the_boundary_and_keeps_its_guards(dtype, shift):
+    size = torch.empty(0, dtype=dtype).element_size()
+    v, h = MC.guarded((5, 7), dtype, "cpu", shift=shift)
+    assert v.shape == (5, 7) and v.is_contiguous() and v.data_ptr() % 256 == shift * size and h.shift == shift
+    assert (v.data_ptr() % 16 != 0) == (shift * size % 16 != 0)
+    assert h.off >= h.front + shift * size and h.arena.numel() >= h.off + h.nbytes + h.back
+    h.check()
+    with pytest.raises(AssertionError, match="never written"):
+        h.all_written()
+    v.zero_()
+    h.all_written(); h.check()
+    # the elements between the boundary and the payload are guard: the byte just before the payload, and the boundary itself
+    for back_by in (1, shift * size):
+        h.arena[h.off - back_by] ^= 1
+        with pytest.raises(AssertionError, match=rf"byte offset -{back_by} from the payload start \(the front guard"):
+            h.check()
+        h.arena[h.off - back_by] ^= 1
+    h.arena[h.off + h.nbytes] ^= 1                   # and the first byte past the shifted payload
+    with pytest.raises(AssertionError, match=rf"byte offset {35 * size} from the payload start \(the back guard"):
+        h.check()
+    h.arena[h.off + h.nbytes] ^= 1
+    h.check()
+    if dtype.is_floating_point:                      # what surrounds the payload still reads as NaN
+        assert bool(torch.isnan(h.arena[h.off - size:h.off].view(dtype)).all())
+
+
+@pytest.mark.parametrize("shift", [1, 2])
+def test_a_shifted_payload_with_a_row_pitch(shift):
+    v, h = MC.guarded((4, 6), torch.float32, "cpu", ld=9, shift=shift)
+    assert v.shape == (4, 6) and v.stride() == (9, 1) and v.data_ptr() % 256 == 4 * shift and h.nbytes == (3 * 9 + 6) * 4
+    v.copy_(torch.arange(24.0).view(4, 6))
+    h.check(); h.all_written()
+    flat = h.arena[h.off:h.off + h.nbytes].view(torch.float32)
+    assert bool(torch.isnan(flat[6:9]).all()) and float(flat[9]) == 6.0
+    flat[9 + 6] = 1.0                                # the first padding element of the second row
+    with pytest.raises(AssertionError, match=r"byte offset 60 from the payload start \(a padding column"):
+        h.check()
+    v, h = MC.guarded((4, 6), torch.float32, "cpu", ld=9, shift=shift)
+    v.zero_()
+    keep, _ = MC.guarded((1,), torch.float32, "cpu")
+    v[3, 5] = keep[0]
+    with pytest.raises(AssertionError, match=r"1 of 24 elements were never written, the first at flat index 23"):
+        h.all_written()
+    t = torch.arange(35, dtype=torch.float32).view(5, 7)
+    c, hc = MC.guarded_copy(t, ld=10, shift=shift)
+    assert torch.equal(c, t) and c.stride() == (10, 1) and c.data_ptr() % 16 == 4 * shift
+    hc.check(); hc.all_written()
+
+
+def test_the_default_shift_is_none():
+    v, h = MC.guarded((3, 4), torch.float32, "cpu")
+    assert h.shift == 0 and v.data_ptr() % 256 == 0
+
+
 @pytest.mark.parametrize("fill", MC.FILLS)
 def test_exact_scratch_size_alignment_and_fill(fill):
     es = MC.ExactScratch(fill)

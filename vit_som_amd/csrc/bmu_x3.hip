@@ -731,6 +731,8 @@ int vsom_bmu_cosine_x3_finalize(const float* X, long ldx, const float* W, const 
                                 vsom_stream_t stream) {
     VSOM_REQUIRE(X && W && bmu && inv_nx && inv_nw, VSOM_EINVAL, "bmu_cosine_x3_finalize: null pointer");
     VSOM_REQUIRE(B > 0 && K > 0 && L > 0, VSOM_EINVAL, "bmu_cosine_x3_finalize: bad shape");
+    // the exact re-rank reads whole rows of X and W 16 bytes at a time
+    VSOM_REQUIRE(aligned16(X) && aligned16(W), VSOM_EALIGN, "bmu_cosine_x3_finalize: X and W must be 16-byte aligned");
     const BmuPlan p = x3_plan(B, K, L, ldx, true, false);
     VSOM_REQUIRE(p.x3_status == VSOM_OK, VSOM_EINVAL, "bmu_cosine_x3_finalize: bad shape");
     VSOM_REQUIRE(ws && ws_bytes >= p.ws_bytes, VSOM_EWORKSPACE, "bmu_cosine_x3_finalize: workspace too small");
@@ -757,7 +759,8 @@ static int planes_params(PlanesP& q, int R, int L, void* planes, size_t planes_b
 }
 
 int vsom_bmu_planes_from(const float* src, long ld, int R, int L, void* planes, size_t planes_bytes, vsom_stream_t stream) {
-    VSOM_REQUIRE(src && ld >= L && ld % 4 == 0 && aligned16(src), VSOM_EINVAL, "bmu_planes_from: bad source (ld=%ld)", ld);
+    VSOM_REQUIRE(src && ld >= L && ld % 4 == 0 && aligned16(src), VSOM_EINVAL,
+                 "bmu_planes_from: src must be 16-byte aligned with L <= ld and ld %% 4 == 0 (ld=%ld)", ld);
     PlanesP q = {};
     const int rc = planes_params(q, R, L, planes, planes_bytes, "bmu_planes_from");
     if (rc) return rc;
@@ -830,6 +833,7 @@ int vsom_bmu_cosine_x3_planes_finalize(const float* X, long ldx, const float* W,
                                        int* reranked, int B, int K, int L, vsom_stream_t stream) {
     VSOM_REQUIRE(X && W && xplanes && wplanes && bmu && inv_nx && inv_nw, VSOM_EINVAL, "bmu_cosine_x3_planes_finalize: null pointer");
     VSOM_REQUIRE(B > 0 && K > 0 && L > 0 && ldx >= L, VSOM_EINVAL, "bmu_cosine_x3_planes_finalize: bad shape");
+    VSOM_REQUIRE(aligned16(X) && aligned16(W), VSOM_EALIGN, "bmu_cosine_x3_planes_finalize: X and W must be 16-byte aligned");
     const BmuPlan p = x3_plan(B, K, L, ldx, true, true);
     VSOM_REQUIRE(p.form == VSOM_BMU_X3_PLANES, VSOM_EINVAL, "bmu_cosine_x3_planes_finalize: bad shape");
     VSOM_REQUIRE(ws && ws_bytes >= p.ws_bytes, VSOM_EWORKSPACE, "bmu_cosine_x3_planes_finalize: workspace too small");

@@ -387,7 +387,7 @@ class SOMLayer(_Base):
     def _distances_into(self, x2d, s: _Acts):
         if self._dist_mode == ops.DIST_COSINE:
             W = self.prototypes
-            form = self._bmu_form(x2d.shape[0], x2d.stride(0), x2d.data_ptr() % 16 == 0)
+            form = self._bmu_form(x2d.shape[0], x2d.stride(0), x2d.data_ptr() % 16 == 0 and W.data_ptr() % 16 == 0)
             if form == ops.BMU_X3_PLANES:
                 # norms + reduced-precision contraction + exact re-rank in one pass over X and W, on pre-split operands: the
                 # prototypes' image is kept by the optimizer, the samples' written here
