@@ -1125,6 +1125,55 @@ int vsom_agglo_distances(const float* X, long ldx, long N, int D, int metric, in
 int vsom_agglo_merge(void* ws, long ws_size, long N, int linkage, int connectivity, int* children, double* distances, int* status,
                      vsom_stream_t stream);
 
+/* DBSCAN (Ester et al. 1996; sklearn.cluster.DBSCAN; vit_som_amd/dbscan.py; no counterpart in the reference): the
+ * eps-neighbourhood graph as a bit matrix, the connected components of its core rows, sklearn's labels.  No entry takes a
+ * caller-sized scratch buffer: every buffer is a typed output whose shape follows from N, and each needs only the natural
+ * alignment of its type (hipMalloc and torch give more).  2 <= N <= 131 072 (2 GiB of bits; more: VSOM_EUNSUPPORTED).
+ * No floating-point atomics, every sum in one fixed order: two runs are bitwise equal.
+ *
+ * The bit contract of adj (uint64 [N, W], W = ceil(N / 64), dense):
+ *   bit (j & 63) of adj[i][j >> 6] is set iff rows i and j have a distance and it is <= eps;
+ *   the diagonal is set (a row is in its own neighbourhood, as in sklearn);
+ *   bits of columns >= N are clear;
+ *   a bad row (the contract of vsom_knn_query: a NaN, an infinity, a squared norm that overflows fp32 -- euclidean: a
+ *     squared distance to itself that does) has no bit set anywhere, in its row or its column;
+ *   the matrix is symmetric bit for bit.
+ * Every word is written exactly once (no need to clear adj), by a plain store: the result does not depend on the chunking.
+ *
+ * vsom_dbscan_neighbours: the contraction of vsom_knn_ranks with a thresholding epilogue.  The test is (double)d <= eps
+ * with d bit for bit the fp32 distance of vsom_umap_knn between rows i and j of X [N, D] (row stride ldx >= D >= 1;
+ * VSOM_DIST_EUCLIDEAN, with the root, or VSOM_DIST_COSINE; another metric: VSOM_EUNSUPPORTED) and eps >= 0 the caller's
+ * double.  Rows are loaded 16 bytes per lane when D % 4 == 0, ldx % 4 == 0 and X is 16-byte aligned (the decision of
+ * vsom_knn_ranks), element-wise otherwise: the words are the same bits either way.  Writes sq f32 [N] (the squared
+ * norms in the contraction's order), adj, count int32 [N] (the set bits of row i, its own among them) and status int64
+ * [2]: [0] the bad rows, [1] the set bits of the whole matrix.
+ * vsom_dbscan_threshold: the same contract from a precomputed matrix M [N, N], float32 (is_f64 == 0) or float64, row
+ * stride ldm >= N in elements: the test is (double)M[i][j] <= eps.  A NaN entry clears its bit; the diagonal is set
+ * whatever it holds; the matrix is as symmetric as M is.  status[0] is the number of NaN entries (an integer atomic add),
+ * status[1] the set bits. */
+int vsom_dbscan_neighbours(const float* X, long ldx, long N, int D, int metric, double eps, float* sq, uint64_t* adj,
+                           int32_t* count, int64_t* status, vsom_stream_t stream);
+int vsom_dbscan_threshold(const void* M, long ldm, long N, int is_f64, double eps, uint64_t* adj, int32_t* count, int64_t* status,
+                          vsom_stream_t stream);
+/* The components of the core rows: int32 throughout, atomicMin the only atomic, no grid-wide barrier, no spin-wait.
+ * vsom_dbscan_init: core[i] (uint8 [N]) = count[i] >= min_samples (>= 1); root[i] (int32 [N]) = i for a core row, -1
+ * otherwise.
+ * vsom_dbscan_round: clears changed (int32 [1]), then enqueues `rounds` (1 .. 1024) pairs of a hook step -- one wave per
+ * core row: the least root[j] over the set bits j of its row with core[j], atomicMin-ed into root[i] and into
+ * root[root[i]]; changed is raised when anything moved -- and a pointer-jumping step (roots only ever point to
+ * smaller-or-equal indices, so the chase ends).  The caller repeats the call until changed stays 0.  The fixed point is
+ * unique, every core row's root the smallest core row of its component, so the result does not depend on the races.
+ * vsom_dbscan_finish, at the fixed point: a cluster's number is the rank of its root among the roots, ascending (sklearn's
+ * numbering: it visits the rows in index order); a core row gets its root's number; a row that is not core gets the least
+ * number among its core neighbours (sklearn expands the clusters in label order, so the first to reach a border point
+ * has the smallest label), -1 without one.  Writes labels int64 [N] and record int32 [4]: clusters, core rows, border
+ * rows, noise rows; core is the array vsom_dbscan_init wrote. */
+int vsom_dbscan_init(const int32_t* count, long N, int min_samples, uint8_t* core, int32_t* root, vsom_stream_t stream);
+int vsom_dbscan_round(const uint64_t* adj, long N, const uint8_t* core, int32_t* root, int rounds, int32_t* changed,
+                      vsom_stream_t stream);
+int vsom_dbscan_finish(const uint64_t* adj, long N, const uint8_t* core, const int32_t* root, int64_t* labels, int32_t* record,
+                       vsom_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

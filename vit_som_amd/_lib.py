@@ -215,6 +215,15 @@ SIGNATURES = {
     "vsom_agglo_workspace_bytes": (C.c_long, [C.c_long, C.c_int]),
     "vsom_agglo_distances": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, c_fp, C.c_long, c_fp, c_stream]),
     "vsom_agglo_merge": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_stream]),
+    # DBSCAN (csrc/knn.hip).  adj is the bit matrix uint64 [N, ceil(N / 64)]: bit j & 63 of adj[i][j >> 6] is set iff rows i and
+    # j have a distance <= eps, the diagonal set, the tail bits clear, a bad row empty in row and column, symmetric.  X is
+    # loaded 16 bytes per lane when D % 4 == 0, ldx % 4 == 0 and X is 16-byte aligned, element-wise otherwise (same bits).
+    # No workspace: every buffer is a typed output sized by N, at the natural alignment of its type.
+    "vsom_dbscan_neighbours": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, C.c_int, C.c_double, c_fp, c_fp, c_fp, c_fp, c_stream]),
+    "vsom_dbscan_threshold": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, C.c_double, c_fp, c_fp, c_fp, c_stream]),
+    "vsom_dbscan_init": (C.c_int, [c_fp, C.c_long, C.c_int, c_fp, c_fp, c_stream]),
+    "vsom_dbscan_round": (C.c_int, [c_fp, C.c_long, c_fp, c_fp, C.c_int, c_fp, c_stream]),
+    "vsom_dbscan_finish": (C.c_int, [c_fp, C.c_long, c_fp, c_fp, c_fp, c_fp, c_stream]),
     "vsom_fill": (C.c_int, [c_fp, C.c_long, C.c_float, c_stream]),
     "vsom_scaled_mul": (C.c_int, [c_fp, c_fp, c_fp, C.c_long, c_fp, C.c_float, c_stream]),
     "vsom_som_weighted_loss": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_float, c_fp, c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_int,

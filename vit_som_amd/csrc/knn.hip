@@ -12,6 +12,9 @@
 //                    continuity of an embedding).  Integer atomics only.
 //   vsom_silhouette  the same contraction once more, summing instead of counting: for every row the fixed-point sum of its
 //                    distances to each cluster's members, then the silhouette coefficient.  Integer atomics only.
+//   vsom_dbscan_*    the same contraction a fourth time, thresholding: the eps-neighbourhood graph as a bit matrix, one
+//                    wave64 ballot per word, no atomics; then the connected components of the core rows (int32,
+//                    atomicMin only) and sklearn's DBSCAN labels.  The contract stands at the head of that section.
 //
 // The contract the search entry points keep (the rank pass takes its distances from the same four), written once below:
 //   - the 128 x 64 tile of dot products (knn_tile_dots: the staging, the k-loop and the MFMA order of gemm_f32.h, shared
@@ -431,6 +434,13 @@ __global__ __launch_bounds__(256) void knn_rank_threshold_kernel(const float* __
     out[slot] = {thr, ok ? (int)n : -1};
     less[slot] = ok ? 0 : -1;
     tied[slot] = ok ? 0 : -1;
+}
+
+// The load path of a set contracted with itself (vsom_knn_ranks, vsom_dbscan_neighbours): 16 bytes per lane, or
+// element-wise loads that feed the same values.  One decision for both entries.
+inline bool knn_self_vec(const float* A, long lda, int D) {
+    const bool vec = D % 4 == 0 && lda % 4 == 0 && aligned16(A);
+    return vec;
 }
 
 struct RankP {
@@ -973,6 +983,314 @@ __global__ __launch_bounds__(VOTE_WAVES * 64) void knn_vote_kernel(const VoteP p
     }
 }
 
+// ---------------------------------------------------------------------------------------------- DBSCAN
+// The same contraction of a set with itself a fourth time, thresholding instead of selecting, counting or summing: the
+// eps-neighbourhood graph of DBSCAN (Ester et al. 1996; sklearn.cluster.DBSCAN) as a bit matrix, then the connected
+// components of its core rows and sklearn's labels (vit_som_amd/dbscan.py; no counterpart in the reference).
+//
+// The bit contract (adj u64 [N][W], W = ceil(N / 64)):
+//   - bit (j & 63) of adj[i][j >> 6] is set iff rows i and j have a distance and (double)d <= eps, d bit for bit the fp32
+//     distance of vsom_umap_knn for that pair (euclidean with the root, cosine), eps the caller's double;
+//   - the diagonal is set: a row is in its own neighbourhood, as in sklearn;
+//   - bits of columns >= N are clear;
+//   - a bad row (the contract at knn_distance; decided per row by dbscan_row_ok, so that a row without a distance to
+//     itself has none to anyone) has no bit set anywhere, in its row or in its column, and is counted in status[0];
+//   - a pair's value does not depend on where it falls in a tile and fp32 addition commutes: the matrix is symmetric bit
+//     for bit.
+// The tile kernel walks the 128 x 64 distance tile with lane = column, so one wave64 ballot IS word adj[i][tile].  The column
+// chunks write disjoint words, every word exactly once: nothing is cleared beforehand, nothing is added atomically, and
+// the result does not depend on the chunking.
+//
+// The components are int32 throughout, atomicMin is their only atomic, and nothing waits on another workgroup.
+// root[i] of a core row starts at i and only ever falls, always to a core row of i's own component (a neighbour's root,
+// the root's root).  A hook step that moves nothing has read a state in which root is constant along every edge between
+// core rows, hence over every component; that constant c is a row of the component with root[c] <= c, every root of the
+// component is >= its smallest core row m, and root[m] <= m: so c = m.  The fixed point is unique -- every core row's
+// root is the smallest core row of its component -- and the result does not depend on the races on the way.
+constexpr long DBSCAN_MAX_N = 131072;          // N^2 / 8 = 2 GiB of bits
+constexpr int DBSCAN_ROWS = 4;                 // rows per workgroup of the row-walking kernels (one wave each)
+constexpr int DBSCAN_SCAN = 1024;              // threads of the one-workgroup passes over the rows
+
+// A row that has a distance to itself: its squared norm is finite (euclidean: so is the squared distance 2 s - 2 s).
+__device__ __forceinline__ bool dbscan_row_ok(float s, int metric) {
+    return metric == VSOM_DIST_EUCLIDEAN ? s + s < INFINITY : s < INFINITY;
+}
+
+struct NeighP {
+    KnnOperand A;
+    int D, metric;
+    double eps;
+    const float* sq;
+    unsigned long long* adj;    // [N][ct]
+    int ct, chunks;
+};
+
+// One workgroup = 128 rows x one chunk of column tiles, built like knn_rank_tile_kernel.  Per 64-column tile: the 128 x 64
+// block of A A^T (knn_tile_dots), the distances into LDS -- NaN for a column outside the set and for a pair with a bad
+// row, 0 for a good row against itself -- then every wave ballots (double)d <= eps over each of its 32 rows with
+// lane = column; lane rr keeps row rr's word and stores it as adj[row][tile].  NaN is below nothing: its bit is clear.
+template <bool FAST>
+__global__ __launch_bounds__(KNN_THREADS, 2) void dbscan_tile_kernel(const NeighP p) {
+    constexpr int BM = KNN_BM, BN = KNN_BN;
+    __shared__ __attribute__((aligned(16))) float lds[(BM + BN) * 36];
+    __shared__ float sd[BM][BN + 1];
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int wm0 = wave * 32;
+    const int bm0 = blockIdx.x * BM;
+    const int chunk = blockIdx.y;
+    const int ct0 = (int)((long)chunk * p.ct / p.chunks), ct1 = (int)((long)(chunk + 1) * p.ct / p.chunks);
+    const int N = p.A.rows;
+
+    KnnStage<FAST> st;
+    st.point(p.A, p.A);
+    st.rows_a(p.A, bm0, t);
+
+    for (int ctile = ct0; ctile < ct1; ++ctile) {
+        const int bn0 = ctile * BN;
+        f32x16 acc[2];
+        knn_tile_dots<FAST>(st, p.A, bm0, p.A, bn0, p.D, lds, t, acc);
+
+        // accumulator register v of tile j: row (v & 3) + 8 (v >> 2) + 4h, column 32j + r
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int col = j * 32 + r, gj = bn0 + col;
+            const float sj = gj < N ? p.sq[gj] : __builtin_nanf("");
+            const bool okj = dbscan_row_ok(sj, p.metric);               // false for a column outside the set
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int row = wm0 + (v & 3) + 8 * (v >> 2) + 4 * h, gi = bm0 + row;
+                float d = __builtin_nanf("");
+                if (gi < N && okj) {
+                    const float si = p.sq[gi];
+                    if (dbscan_row_ok(si, p.metric)) d = gi == gj ? 0.f : knn_distance(acc[j][v], si, sj, p.metric);
+                }
+                sd[row][col] = d;
+            }
+        }
+        __syncthreads();        // also: every wave is past its last MFMA read of the LDS tiles before the next tile's stores
+        unsigned long long word = 0;
+#pragma unroll
+        for (int rr = 0; rr < 32; ++rr) {
+            const unsigned long long b = __ballot((double)sd[wm0 + rr][lane] <= p.eps);
+            if (lane == rr) word = b;
+        }
+        const int gi = bm0 + wm0 + lane;
+        if (lane < 32 && gi < N) p.adj[(size_t)gi * p.ct + ctile] = word;
+    }
+}
+
+// One wave per row: count[i] = the set bits of row i (integer adds in the wave, no atomics).
+__global__ __launch_bounds__(DBSCAN_ROWS * 64) void dbscan_count_kernel(const unsigned long long* __restrict__ adj, int N, int W,
+                                                                        int* __restrict__ count) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * DBSCAN_ROWS + (threadIdx.x >> 6);
+    if (i >= N) return;
+    int c = 0;
+    for (int w = lane; w < W; w += 64) c += __popcll(adj[(size_t)i * W + w]);
+#pragma unroll
+    for (int o = 32; o; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (lane == 0) count[i] = c;
+}
+
+// One workgroup: status[0] = the rows without a bit (with_bad: the bad rows -- a good row has its diagonal; else left
+// alone), status[1] = the set bits of the matrix.  Per-thread sums in row order, then thread 0 adds the partial sums in
+// thread order.
+__global__ __launch_bounds__(DBSCAN_SCAN) void dbscan_status_kernel(const int* __restrict__ count, int N, int with_bad,
+                                                                    int64_t* __restrict__ status) {
+    __shared__ long long bits[DBSCAN_SCAN];
+    __shared__ int bad[DBSCAN_SCAN];
+    const int t = threadIdx.x;
+    long long b = 0;
+    int z = 0;
+    for (int i = t; i < N; i += DBSCAN_SCAN) {
+        const int c = count[i];
+        b += c;
+        z += c == 0;
+    }
+    bits[t] = b;
+    bad[t] = z;
+    __syncthreads();
+    if (t == 0) {
+        long long tb = 0, tz = 0;
+        for (int k = 0; k < DBSCAN_SCAN; ++k) { tb += bits[k]; tz += bad[k]; }
+        if (with_bad) status[0] = tz;
+        status[1] = tb;
+    }
+}
+
+// The same bit contract from a precomputed matrix M [N, N] (T float or double, row stride ldm).  One wave per row, lane =
+// column: the ballot of (double)M[i][j] <= eps is word adj[i][j >> 6].  A NaN entry clears its bit and is counted in
+// status[0] (cleared before the launch; an integer atomic, one per row that has any); the diagonal is set whatever it holds.
+template <class T>
+__global__ __launch_bounds__(DBSCAN_ROWS * 64) void dbscan_threshold_kernel(const T* __restrict__ M, long ldm, int N, int W, double eps,
+                                                                            unsigned long long* __restrict__ adj,
+                                                                            int* __restrict__ count,
+                                                                            unsigned long long* __restrict__ status) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * DBSCAN_ROWS + (threadIdx.x >> 6);
+    if (i >= N) return;
+    const T* row = M + (size_t)i * ldm;
+    int c = 0, nans = 0;
+    for (int w = 0; w < W; ++w) {
+        const int j = w * 64 + lane;
+        const double d = j < N ? (double)row[j] : __builtin_nan("");
+        const unsigned long long b = __ballot(j < N && (j == i || d <= eps));
+        nans += __popcll(__ballot(j < N && d != d));
+        c += __popcll(b);
+        if (lane == 0) adj[(size_t)i * W + w] = b;
+    }
+    if (lane == 0) {
+        count[i] = c;
+        if (nans) atomicAdd(&status[0], (unsigned long long)nans);
+    }
+}
+__global__ void dbscan_clear_status_kernel(int64_t* __restrict__ status) { status[threadIdx.x] = 0; }
+
+// core[i] = count[i] >= min_samples; root[i] = i for a core row, -1 otherwise.
+__global__ __launch_bounds__(256) void dbscan_init_kernel(const int* __restrict__ count, int N, int min_samples,
+                                                          unsigned char* __restrict__ core, int* __restrict__ root) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const bool c = count[i] >= min_samples;
+    core[i] = c;
+    root[i] = c ? i : -1;
+}
+
+__global__ void dbscan_clear_changed_kernel(int* __restrict__ changed) { *changed = 0; }
+
+// A root as another workgroup may be lowering it: one relaxed 4-byte load, so a value some atomicMin wrote or the start value.
+__device__ __forceinline__ int dbscan_root(const int* root, int i) { return __atomic_load_n(root + i, __ATOMIC_RELAXED); }
+
+// The hook step, one wave per core row, lane = column: the least root[j] over the set bits j of row i with core[j] (row
+// i's own bit among them), atomicMin-ed into root[i] and into root[root[i]] when it is lower; `changed` is raised when
+// anything moved.  A word without a bit is skipped (the word is wave-uniform).
+__global__ __launch_bounds__(DBSCAN_ROWS * 64) void dbscan_hook_kernel(const unsigned long long* __restrict__ adj, int N, int W,
+                                                                       const unsigned char* __restrict__ core, int* root,
+                                                                       int* __restrict__ changed) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * DBSCAN_ROWS + (threadIdx.x >> 6);
+    if (i >= N || !core[i]) return;
+    int m = 0x7fffffff;
+    for (int w = 0; w < W; ++w) {
+        const unsigned long long word = adj[(size_t)i * W + w];
+        if (!word) continue;
+        const int j = w * 64 + lane;                                 // a set bit has j < N (the tail bits are clear); checked all the same
+        if ((word >> lane & 1) && j < N && core[j]) m = min(m, dbscan_root(root, j));
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) m = min(m, __shfl_xor(m, o, 64));
+    if (lane == 0) {
+        const int r = dbscan_root(root, i);                          // a core row: 0 <= r <= i
+        if (r >= 0 && r < N && m >= 0 && m < r) {
+            atomicMin(&root[i], m);
+            atomicMin(&root[r], m);
+            *changed = 1;
+        }
+    }
+}
+
+// The pointer-jumping step, one thread per core row: root[i] <- the end of the chain root[root[...]].  A root points to a
+// smaller or equal index, so the chase ends.
+__global__ __launch_bounds__(256) void dbscan_jump_kernel(int N, const unsigned char* __restrict__ core, int* root) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N || !core[i]) return;
+    const int r0 = dbscan_root(root, i);
+    if (r0 < 0 || r0 >= N) return;                                   // not what vsom_dbscan_init and the hook step leave: nothing to chase
+    int r = r0;
+    for (int up = dbscan_root(root, r); up >= 0 && up < r; up = dbscan_root(root, r)) r = up;
+    if (r < r0) atomicMin(&root[i], r);
+}
+
+// One workgroup: a cluster's number is the rank of its root (a core row with root[i] == i) among the roots, ascending --
+// sklearn's numbering, which visits the rows in index order.  labels[root] = that rank, every other row -1 for now;
+// record[0] = the clusters, record[1] = the core rows.  Thread t scans rows [t per, (t + 1) per).
+__global__ __launch_bounds__(DBSCAN_SCAN) void dbscan_number_kernel(int N, const unsigned char* __restrict__ core,
+                                                                    const int* __restrict__ root, int64_t* __restrict__ labels,
+                                                                    int* __restrict__ record) {
+    __shared__ int roots[DBSCAN_SCAN];
+    __shared__ int cores[DBSCAN_SCAN];
+    const int t = threadIdx.x;
+    const int per = (N + DBSCAN_SCAN - 1) / DBSCAN_SCAN;
+    const int i0 = min(t * per, N), i1 = min(i0 + per, N);
+    int nr = 0, nc = 0;
+    for (int i = i0; i < i1; ++i) {
+        const bool c = core[i];
+        nc += c;
+        nr += c && root[i] == i;
+    }
+    roots[t] = nr;
+    cores[t] = nc;
+    __syncthreads();
+    if (t == 0) {
+        int sr = 0, sc = 0;
+        for (int k = 0; k < DBSCAN_SCAN; ++k) {
+            const int here = roots[k];
+            roots[k] = sr;
+            sr += here;
+            sc += cores[k];
+        }
+        record[0] = sr;
+        record[1] = sc;
+    }
+    __syncthreads();
+    int next = roots[t];
+    for (int i = i0; i < i1; ++i) labels[i] = core[i] && root[i] == i ? next++ : -1;
+}
+
+// A core row that is not a root takes its root's number (the roots' labels are not written here).
+__global__ __launch_bounds__(256) void dbscan_core_label_kernel(int N, const unsigned char* __restrict__ core,
+                                                                const int* __restrict__ root, int64_t* labels) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N || !core[i]) return;
+    const int r = root[i];
+    if (r != i && r >= 0 && r < N) labels[i] = labels[r];
+}
+
+// One wave per row that is not core, lane = column: the least number among its core neighbours -- sklearn expands the
+// clusters one at a time in label order, so the first to reach a border point is the one with the smallest label -- or -1
+// without a core neighbour.  Reads the labels of core rows only, writes those of the others.
+__global__ __launch_bounds__(DBSCAN_ROWS * 64) void dbscan_border_kernel(const unsigned long long* __restrict__ adj, int N, int W,
+                                                                         const unsigned char* __restrict__ core, int64_t* labels) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * DBSCAN_ROWS + (threadIdx.x >> 6);
+    if (i >= N || core[i]) return;
+    int m = 0x7fffffff;
+    for (int w = 0; w < W; ++w) {
+        const unsigned long long word = adj[(size_t)i * W + w];
+        if (!word) continue;
+        const int j = w * 64 + lane;
+        if ((word >> lane & 1) && j < N && core[j]) m = min(m, (int)labels[j]);
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) m = min(m, __shfl_xor(m, o, 64));
+    if (lane == 0) labels[i] = m == 0x7fffffff ? -1 : m;
+}
+
+// One workgroup: record[2] = the border rows (labelled, not core), record[3] = the noise rows.
+__global__ __launch_bounds__(DBSCAN_SCAN) void dbscan_tally_kernel(int N, const unsigned char* __restrict__ core,
+                                                                   const int64_t* __restrict__ labels, int* __restrict__ record) {
+    __shared__ int border[DBSCAN_SCAN];
+    __shared__ int noise[DBSCAN_SCAN];
+    const int t = threadIdx.x;
+    int nb = 0, nn = 0;
+    for (int i = t; i < N; i += DBSCAN_SCAN) {
+        const bool in = labels[i] >= 0;
+        nb += in && !core[i];
+        nn += !in;
+    }
+    border[t] = nb;
+    noise[t] = nn;
+    __syncthreads();
+    if (t == 0) {
+        int sb = 0, sn = 0;
+        for (int k = 0; k < DBSCAN_SCAN; ++k) { sb += border[k]; sn += noise[k]; }
+        record[2] = sb;
+        record[3] = sn;
+    }
+}
+
 }  // namespace
 }  // namespace vsom
 
@@ -1039,7 +1357,7 @@ int vsom_knn_ranks(const float* A, long lda, long N, int D, int metric, const in
                  "knn_ranks: workspace too small or misaligned");
     const RankWs w = rank_layout(ws, N, k);
     const QueryPlan pl = query_plan(N, N);
-    const bool vec = D % 4 == 0 && lda % 4 == 0 && aligned16(A);
+    const bool vec = knn_self_vec(A, lda, D);
     const size_t ext = (size_t)N * lda * 4;
     VSOM_LAUNCH(knn_sqnorm_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, A, lda, N, D, w.sq);
     const dim3 slots((unsigned)(((size_t)N * k + 255) / 256));
@@ -1122,6 +1440,97 @@ int vsom_knn_vote(const int64_t* idx, const float* dist, long Nq, int k, const i
     p.status = status;
     VSOM_LAUNCH(knn_vote_kernel, dim3(cdiv(Nq, VOTE_WAVES)), dim3(VOTE_WAVES * 64), 0, stream, p);
     return launch_status("knn_vote");
+}
+
+int vsom_dbscan_neighbours(const float* X, long ldx, long N, int D, int metric, double eps, float* sq, uint64_t* adj,
+                           int32_t* count, int64_t* status, vsom_stream_t stream) {
+    using namespace vsom;
+    VSOM_REQUIRE(X && sq && adj && count && status, VSOM_EINVAL, "dbscan_neighbours: null pointer");
+    VSOM_REQUIRE(N >= 2 && D >= 1 && ldx >= D && N <= 0x7fffffffL - KNN_BM, VSOM_EINVAL,
+                 "dbscan_neighbours: bad sizes N=%ld D=%d ldx=%ld", N, D, ldx);
+    VSOM_REQUIRE(eps >= 0.0, VSOM_EINVAL, "dbscan_neighbours: eps=%g must be >= 0", eps);
+    VSOM_REQUIRE(N <= DBSCAN_MAX_N, VSOM_EUNSUPPORTED, "dbscan_neighbours: N=%ld > %ld (the bit matrix would pass 2 GiB)", N,
+                 DBSCAN_MAX_N);
+    VSOM_REQUIRE(metric == VSOM_DIST_EUCLIDEAN || metric == VSOM_DIST_COSINE, VSOM_EUNSUPPORTED,
+                 "dbscan_neighbours: metric %d (euclidean or cosine only)", metric);
+    const QueryPlan pl = query_plan(N, N);
+    const bool vec = knn_self_vec(X, ldx, D);
+    const size_t ext = (size_t)N * ldx * 4;
+    VSOM_LAUNCH(knn_sqnorm_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, X, ldx, N, D, sq);
+    NeighP p = {};
+    p.A = {X, ldx, (int)N, (unsigned)ext, vec};
+    p.D = D; p.metric = metric; p.eps = eps; p.sq = sq; p.adj = reinterpret_cast<unsigned long long*>(adj);
+    p.ct = pl.ct; p.chunks = pl.chunks;
+    const dim3 grid(pl.rb, pl.chunks), block(KNN_THREADS);
+    if (vec && ext < (size_t)OOB - 256) VSOM_LAUNCH(dbscan_tile_kernel<true>, grid, block, 0, stream, p);
+    else VSOM_LAUNCH(dbscan_tile_kernel<false>, grid, block, 0, stream, p);
+    VSOM_LAUNCH(dbscan_count_kernel, dim3(cdiv(N, DBSCAN_ROWS)), dim3(DBSCAN_ROWS * 64), 0, stream,
+                (const unsigned long long*)p.adj, (int)N, pl.ct, count);
+    VSOM_LAUNCH(dbscan_status_kernel, dim3(1), dim3(DBSCAN_SCAN), 0, stream, (const int*)count, (int)N, 1, status);
+    return launch_status("dbscan_neighbours");
+}
+
+int vsom_dbscan_threshold(const void* M, long ldm, long N, int is_f64, double eps, uint64_t* adj, int32_t* count, int64_t* status,
+                          vsom_stream_t stream) {
+    using namespace vsom;
+    VSOM_REQUIRE(M && adj && count && status, VSOM_EINVAL, "dbscan_threshold: null pointer");
+    VSOM_REQUIRE(N >= 2 && ldm >= N, VSOM_EINVAL, "dbscan_threshold: bad sizes N=%ld ldm=%ld", N, ldm);
+    VSOM_REQUIRE(eps >= 0.0, VSOM_EINVAL, "dbscan_threshold: eps=%g must be >= 0", eps);
+    VSOM_REQUIRE(N <= DBSCAN_MAX_N, VSOM_EUNSUPPORTED, "dbscan_threshold: N=%ld > %ld (the bit matrix would pass 2 GiB)", N,
+                 DBSCAN_MAX_N);
+    const int W = cdiv(N, 64);
+    unsigned long long* words = reinterpret_cast<unsigned long long*>(adj);
+    unsigned long long* stat = reinterpret_cast<unsigned long long*>(status);
+    const dim3 grid(cdiv(N, DBSCAN_ROWS)), block(DBSCAN_ROWS * 64);
+    VSOM_LAUNCH(dbscan_clear_status_kernel, dim3(1), dim3(2), 0, stream, status);
+    if (is_f64)
+        VSOM_LAUNCH(dbscan_threshold_kernel<double>, grid, block, 0, stream, static_cast<const double*>(M), ldm, (int)N, W, eps, words,
+                    count, stat);
+    else
+        VSOM_LAUNCH(dbscan_threshold_kernel<float>, grid, block, 0, stream, static_cast<const float*>(M), ldm, (int)N, W, eps, words,
+                    count, stat);
+    VSOM_LAUNCH(dbscan_status_kernel, dim3(1), dim3(DBSCAN_SCAN), 0, stream, (const int*)count, (int)N, 0, status);
+    return launch_status("dbscan_threshold");
+}
+
+int vsom_dbscan_init(const int32_t* count, long N, int min_samples, uint8_t* core, int32_t* root, vsom_stream_t stream) {
+    using namespace vsom;
+    VSOM_REQUIRE(count && core && root, VSOM_EINVAL, "dbscan_init: null pointer");
+    VSOM_REQUIRE(N >= 1 && N <= DBSCAN_MAX_N && min_samples >= 1, VSOM_EINVAL, "dbscan_init: bad sizes N=%ld min_samples=%d", N,
+                 min_samples);
+    VSOM_LAUNCH(dbscan_init_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, count, (int)N, min_samples, core, root);
+    return launch_status("dbscan_init");
+}
+
+int vsom_dbscan_round(const uint64_t* adj, long N, const uint8_t* core, int32_t* root, int rounds, int32_t* changed,
+                      vsom_stream_t stream) {
+    using namespace vsom;
+    VSOM_REQUIRE(adj && core && root && changed, VSOM_EINVAL, "dbscan_round: null pointer");
+    VSOM_REQUIRE(N >= 1 && N <= DBSCAN_MAX_N && rounds >= 1 && rounds <= 1024, VSOM_EINVAL, "dbscan_round: bad sizes N=%ld rounds=%d",
+                 N, rounds);
+    const int W = cdiv(N, 64);
+    const unsigned long long* words = reinterpret_cast<const unsigned long long*>(adj);
+    VSOM_LAUNCH(dbscan_clear_changed_kernel, dim3(1), dim3(1), 0, stream, changed);
+    for (int s = 0; s < rounds; ++s) {
+        VSOM_LAUNCH(dbscan_hook_kernel, dim3(cdiv(N, DBSCAN_ROWS)), dim3(DBSCAN_ROWS * 64), 0, stream, words, (int)N, W, core, root,
+                    changed);
+        VSOM_LAUNCH(dbscan_jump_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, (int)N, core, root);
+    }
+    return launch_status("dbscan_round");
+}
+
+int vsom_dbscan_finish(const uint64_t* adj, long N, const uint8_t* core, const int32_t* root, int64_t* labels, int32_t* record,
+                       vsom_stream_t stream) {
+    using namespace vsom;
+    VSOM_REQUIRE(adj && core && root && labels && record, VSOM_EINVAL, "dbscan_finish: null pointer");
+    VSOM_REQUIRE(N >= 1 && N <= DBSCAN_MAX_N, VSOM_EINVAL, "dbscan_finish: bad sizes N=%ld", N);
+    const int W = cdiv(N, 64);
+    const unsigned long long* words = reinterpret_cast<const unsigned long long*>(adj);
+    VSOM_LAUNCH(dbscan_number_kernel, dim3(1), dim3(DBSCAN_SCAN), 0, stream, (int)N, core, root, labels, record);
+    VSOM_LAUNCH(dbscan_core_label_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, (int)N, core, root, labels);
+    VSOM_LAUNCH(dbscan_border_kernel, dim3(cdiv(N, DBSCAN_ROWS)), dim3(DBSCAN_ROWS * 64), 0, stream, words, (int)N, W, core, labels);
+    VSOM_LAUNCH(dbscan_tally_kernel, dim3(1), dim3(DBSCAN_SCAN), 0, stream, (int)N, core, (const int64_t*)labels, record);
+    return launch_status("dbscan_finish");
 }
 
 }  // extern "C"

@@ -11,8 +11,8 @@ whose address crosses into the library is checked there for device, dtype, layou
 ``_matrix`` / ``_dense`` / ``_buffer``, None passes only where the docstring says optional, and a
 refusal is a ``ValueError`` naming the argument, raised before anything is launched, ``python -O``
 or not.  A buffer whose element count goes to the entry (a workspace, ``zpart``, ``part``) is sized
-by the entry, which refuses a short one before it launches.  The agglomerative-clustering wrappers at
-the end of the module are evaluation wrappers under the same contract.
+by the entry, which refuses a short one before it launches.  The agglomerative-clustering and DBSCAN
+wrappers at the end of the module are evaluation wrappers under the same contract.
 """
 from contextlib import contextmanager
 from typing import Optional
@@ -1686,3 +1686,74 @@ def agglo_merge(ws, N, linkage, connectivity, children, distances, status):
     check(lib.vsom_agglo_merge(ptr(ws), ws.numel(), N, int(linkage), int(bool(connectivity)), ptr(children), ptr(distances),
                                ptr(status), stream()), "vsom_agglo_merge")
     return children, distances
+
+
+# ---------------------------------------------------------------- DBSCAN (dbscan.py)
+# Evaluation wrappers under the contract stated at the agglomerative section: every tensor passes _matrix / _dense / _buffer
+# before its address goes to the library, and a refusal is a ValueError.  No entry takes a workspace: every buffer is a
+# typed output whose shape follows from N.  The bit matrix travels as int64 [N, dbscan_words(N)] (torch has no arithmetic
+# on uint64; the 64 bits are the entry's): bit j & 63 of adj[i, j >> 6] is set iff rows i and j have a distance <= eps.
+DBSCAN_MAX_N = 131072                                            # csrc/knn.hip: DBSCAN_MAX_N, 2 GiB of bits
+DBSCAN_CLUSTERS, DBSCAN_CORE, DBSCAN_BORDER, DBSCAN_NOISE = 0, 1, 2, 3      # the words of dbscan_finish's record
+
+
+def dbscan_words(N) -> int:
+    """64-bit words in a row of the bit matrix of N rows."""
+    return (int(N) + 63) // 64
+
+
+def dbscan_neighbours(X, metric, eps, sq, adj, count, status):
+    """adj int64 [N, dbscan_words(N)] = the eps-neighbourhood graph of the rows of X f32 [N, D] (any row stride) as bits:
+    set iff (double)d <= eps with d the fp32 distance of umap_knn (DIST_EUCLIDEAN or DIST_COSINE), the diagonal set, the
+    tail bits clear, a bad row empty in row and column, symmetric.  sq f32 [N]: the squared norms; count int32 [N]: the
+    set bits of every row; status int64 [2]: the bad rows, the set bits.  All written in full; nothing is read back."""
+    N, D, ldx = _matrix(X, "X")
+    _dense(sq, "sq", _F32, (N,)); _dense(adj, "adj", _I64, (N, dbscan_words(N)))
+    _dense(count, "count", _I32, (N,)); _dense(status, "status", _I64, (2,))
+    check(lib.vsom_dbscan_neighbours(ptr(X), ldx, N, D, int(metric), float(eps), ptr(sq), ptr(adj), ptr(count), ptr(status),
+                                     stream()), "vsom_dbscan_neighbours")
+    return adj, count
+
+
+def dbscan_threshold(M, eps, adj, count, status):
+    """The same bit matrix from precomputed distances M [N, N]: float32 with any row stride, or float64 contiguous (what
+    agglo_distances writes).  A NaN entry clears its bit, the diagonal is set.  status int64 [2]: NaN entries, set bits."""
+    if isinstance(M, _Tensor) and M.dtype == _F64:
+        N = _dense(M, "M", _F64, (None, None)).shape[0]
+        _dense(M, "M", _F64, (N, N))
+        ldm, wide = N, 1
+    else:
+        N, _, ldm = _matrix(M, "M")
+        _matrix(M, "M", N, N)
+        wide = 0
+    _dense(adj, "adj", _I64, (N, dbscan_words(N))); _dense(count, "count", _I32, (N,)); _dense(status, "status", _I64, (2,))
+    check(lib.vsom_dbscan_threshold(ptr(M), ldm, N, wide, float(eps), ptr(adj), ptr(count), ptr(status), stream()),
+          "vsom_dbscan_threshold")
+    return adj, count
+
+
+def dbscan_init(count, min_samples, core, root):
+    """core uint8 [N] = count >= min_samples; root int32 [N] = the row itself for a core row, -1 otherwise."""
+    N = _dense(count, "count", _I32, (None,)).shape[0]
+    _dense(core, "core", _U8, (N,)); _dense(root, "root", _I32, (N,))
+    check(lib.vsom_dbscan_init(ptr(count), N, int(min_samples), ptr(core), ptr(root), stream()), "vsom_dbscan_init")
+    return core, root
+
+
+def dbscan_round(adj, core, root, rounds, changed):
+    """`rounds` pairs of a hook and a pointer-jumping step over root, enqueued; changed int32 [1] is cleared first and
+    raised when a hook moved a root.  Nothing is read back: the caller reads `changed` and repeats until it stays 0."""
+    N = _dense(core, "core", _U8, (None,)).shape[0]
+    _dense(adj, "adj", _I64, (N, dbscan_words(N))); _dense(root, "root", _I32, (N,)); _dense(changed, "changed", _I32, (1,))
+    check(lib.vsom_dbscan_round(ptr(adj), N, ptr(core), ptr(root), int(rounds), ptr(changed), stream()), "vsom_dbscan_round")
+    return changed
+
+
+def dbscan_finish(adj, core, root, labels, record):
+    """At the fixed point of dbscan_round: labels int64 [N] in sklearn's numbering (-1: noise) and record int32 [4]:
+    clusters, core rows, border rows, noise rows (DBSCAN_CLUSTERS ..)."""
+    N = _dense(core, "core", _U8, (None,)).shape[0]
+    _dense(adj, "adj", _I64, (N, dbscan_words(N))); _dense(root, "root", _I32, (N,))
+    _dense(labels, "labels", _I64, (N,)); _dense(record, "record", _I32, (4,))
+    check(lib.vsom_dbscan_finish(ptr(adj), N, ptr(core), ptr(root), ptr(labels), ptr(record), stream()), "vsom_dbscan_finish")
+    return labels, record

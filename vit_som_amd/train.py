@@ -29,7 +29,7 @@ import yaml
 
 from .evaluation import (evaluate_classification, evaluate_clustering, evaluate_embedding_quality, evaluate_knn, evaluate_linear_probe,
                          evaluate_map_quality, evaluate_silhouette, evaluate_latent_spectrum, fit_som_batch,
-                         evaluate_gmm, evaluate_map_clusters, evaluate_tsne_quality, init_som_from_data)
+                         evaluate_gmm, evaluate_map_clusters, evaluate_tsne_quality, init_som_from_data, evaluate_dbscan)
 from .classifier import ViTClassifier
 from .model import ViTSOM
 
@@ -278,7 +278,7 @@ def main_vit(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, 
 
 def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print, map_quality=False,
          knn_eval=False, embedding_quality=False, silhouette=False, som_init=None, latent_spectrum=False, som_batch_epochs=0,
-         linear_probe=False, tsne_quality=False, map_clusters=False, gmm_eval=False):
+         linear_probe=False, tsne_quality=False, map_clusters=False, dbscan_eval=False, gmm_eval=False):
     """train_vit_som.py:27-130; a config with hyperparameters.model_arch == "vit" runs main_vit (train_vit.py) instead.
     model_states_dir defaults to experiments/states/vit_som (experiments/states/vit for the ViT baseline).
     map_quality: after each run's final evaluation also run evaluate_map_quality on the training loader with the model that
@@ -296,6 +296,9 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
     map_clusters: likewise run evaluate_map_clusters with that model on the training loader (the SOM's units merged into
     data.num_classes grid-connected clusters, every sample labelled by its BMU's cluster) and report map_cluster_purity and
     map_cluster_nmi: the map's own clustering at the k that gmm_eval and evaluate_kmeans use.
+    dbscan_eval: likewise run evaluate_dbscan with that model on the training loader (density clusters of the latents the SOM
+    sees, eps from the k-distance curve) and report dbscan_clusters, dbscan_noise, dbscan_purity and dbscan_nmi (the last two
+    over the clustered samples only).
     silhouette: likewise run evaluate_silhouette with that model on the training loader, the samples clustered by their
     BMU, and report silhouette_bmu (NaN, with the reason logged, when fewer than two units or every sample alone won).
     som_init: "pca" or "sample": before the first step of each run start the SOM's prototypes from the training loader's
@@ -340,6 +343,8 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
         all_metrics.update(gmm_purity=[], gmm_nmi=[], gmm_bic=[])
     if map_clusters:
         all_metrics.update(map_cluster_purity=[], map_cluster_nmi=[])
+    if dbscan_eval:
+        all_metrics.update(dbscan_clusters=[], dbscan_noise=[], dbscan_purity=[], dbscan_nmi=[])
     if silhouette:
         all_metrics.update(silhouette_bmu=[])
     if latent_spectrum:
@@ -423,6 +428,14 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
                 f"{mc.linkage} linkage, {mc.metric}, {mc.n_samples} samples)")
             all_metrics["map_cluster_purity"].append(mc.purity)
             all_metrics["map_cluster_nmi"].append(mc.nmi)
+        if dbscan_eval:
+            dr = evaluate_dbscan(evaluated, config, train_loader)
+            log(f"DBSCAN: {dr.n_clusters} clusters, {dr.n_noise} noise rows of {dr.n_samples} (coverage {dr.coverage:.3f}), purity "
+                f"{dr.purity:.4f}, NMI {dr.nmi:.4f} (eps {dr.eps:.6g}, min_samples {dr.min_samples}, {dr.metric})")
+            all_metrics["dbscan_clusters"].append(float(dr.n_clusters))
+            all_metrics["dbscan_noise"].append(float(dr.n_noise))
+            all_metrics["dbscan_purity"].append(dr.purity)
+            all_metrics["dbscan_nmi"].append(dr.nmi)
         if silhouette:
             try:
                 sr = evaluate_silhouette(evaluated, config, train_loader, clusters="bmu")
@@ -473,6 +486,9 @@ def _parser():
     ap.add_argument("--map-clusters", action="store_true",
                     help="after each run also report purity and NMI of the SOM's units merged into data.num_classes grid-connected "
                          "clusters (agglomerative clustering of the prototypes), every sample labelled by its BMU's cluster")
+    ap.add_argument("--dbscan-eval", action="store_true",
+                    help="after each run also report the density clusters (DBSCAN) of the training set's latents: clusters, noise rows, "
+                         "purity and NMI over the clustered samples")
     ap.add_argument("--silhouette", action="store_true",
                     help="after each run also report the silhouette coefficient of the training set's latents clustered by their BMU")
     ap.add_argument("--som-init", choices=("pca", "sample"), default=None,
@@ -495,4 +511,4 @@ if __name__ == "__main__":
     main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs, make_loaders=loaders, map_quality=a.map_quality,
          knn_eval=a.knn_eval, embedding_quality=a.embedding_quality, silhouette=a.silhouette, som_init=a.som_init,
          latent_spectrum=a.latent_spectrum, som_batch_epochs=a.som_batch_epochs, linear_probe=a.linear_probe,
-         tsne_quality=a.tsne_quality, gmm_eval=a.gmm_eval, map_clusters=a.map_clusters)
+         tsne_quality=a.tsne_quality, gmm_eval=a.gmm_eval, map_clusters=a.map_clusters, dbscan_eval=a.dbscan_eval)
