@@ -1174,6 +1174,53 @@ int vsom_dbscan_round(const uint64_t* adj, long N, const uint8_t* core, int32_t*
 int vsom_dbscan_finish(const uint64_t* adj, long N, const uint8_t* core, const int32_t* root, int64_t* labels, int32_t* record,
                        vsom_stream_t stream);
 
+/* Spectral embedding (Belkin and Niyogi 2003; sklearn.manifold.SpectralEmbedding; vit_som_amd/spectral.py; no counterpart
+ * in the reference): the device side of a Chebyshev-filtered subspace iteration (Zhou and Saad 2007) on
+ * M = D^-1/2 A D^-1/2.  A is a symmetric affinity in CSR -- int64 indptr [N + 1] / indices [nnz], fp64 data [nnz], the
+ * convention of vsom_tsne_step -- whose diagonal entries are ignored; d are its row sums, s = d^-1/2.  Everything is fp64.
+ * A block is row-major [N, l] with a row stride in elements, 1 <= l <= 32, 1 <= N <= 131 072 (more: VSOM_EUNSUPPORTED).
+ * Every pointer needs only the natural alignment of its type; no entry has a 16-byte path.  No floating-point atomics, no
+ * grid-wide barrier, no spin-wait: every sum has one order fixed by the operands, two runs are bitwise equal.
+ *
+ * The order of a row's sum: its entries are cut into chunks of 512 in CSR order; a chunk is one fma chain from 0, the
+ * chunks' sums are added in chunk order.  A row of at most 512 entries is one chain.
+ *
+ * vsom_spectral_degrees: d[i] = the sum of row i without its diagonal entry, one chain in CSR order; s[i] = 1 / sqrt(d[i]),
+ * 0 for a row without weight.  heavy (int32 [N]) receives the rows of more than 512 entries, in no particular order.
+ * status (int64 [5], cleared here): [0] rows with d = 0, [1] indices outside [0, N), [2] weights that are negative or not
+ * finite, [3] rows whose indptr pair is not 0 <= indptr[i] <= indptr[i + 1] <= nnz (read as empty), [4] the length of
+ * heavy.  Entries counted in [1] or [2] are left out of the sums.  The caller refuses the matrix when [1..3] are not 0.
+ * vsom_spectral_spmm: Yout = alpha (M Y1 - c Y1) - beta Y0, Y0 may be NULL; all blocks share ld.  Element (i, t) is
+ * s_i * sum_j (a_ij s_j) Y1[j, t] in the order above, j == i and an index outside [0, N) skipped, then
+ * alpha * fma(-c, Y1[i, t], .) and fma(-beta, Y0[i, t], .).  With heavy == NULL one group of lanes walks each row whatever
+ * its length; with the list of vsom_spectral_degrees (all its n_heavy rows) each listed row gets a workgroup of its own:
+ * the same bits.  Yout overlapping Y1 or Y0: VSOM_EINVAL.
+ * vsom_spectral_ws_size: bytes of the workspace of vsom_spectral_gram and vsom_spectral_residual; 0 outside the limits.
+ * The rows are cut into at most `slabs` (1 .. 1024) slabs of a multiple of 64 rows; a slab's sum is one chain over its rows
+ * (residual: eight interleaved chains added in order), the slabs are added in slab order.  The result depends on N, l
+ * and slabs alone.  ws NULL or short: VSOM_EWORKSPACE; not 8-byte aligned: VSOM_EALIGN.
+ * vsom_spectral_gram: G = V^T V and, with W and H, H = V^T W; G and H fp64 [l, l] dense.
+ * vsom_spectral_rotate: Vout [N, l_out] = V [N, l] T, T fp64 [l, l_out] dense on the device, the chain over l in index
+ * order.  Vout overlapping V: VSOM_EINVAL.
+ * vsom_spectral_residual: out[j] = sum_i (W[i, j] - theta[j] V[i, j])^2, from the differences themselves; theta, out fp64 [l].
+ * vsom_spectral_embed: E[i, j] (f32, row stride lde) = sign[j] * (s[i] * V[i, first + j]), one rounding; sign[j] (fp64
+ * [n_out], written) makes the entry of largest |s_i V_ij| positive, the smaller row on a tie (numpy's argmax, as in
+ * sklearn's _deterministic_vector_sign_flip). */
+int vsom_spectral_degrees(const int64_t* indptr, const int64_t* indices, const double* data, long N, long nnz, double* d, double* s,
+                          int32_t* heavy, int64_t* status, vsom_stream_t stream);
+int vsom_spectral_spmm(const int64_t* indptr, const int64_t* indices, const double* data, const double* s, long N, long nnz,
+                       const int32_t* heavy, int n_heavy, const double* Y1, const double* Y0, double* Yout, long ld, int l,
+                       double alpha, double c, double beta, vsom_stream_t stream);
+long vsom_spectral_ws_size(long N, int l, int slabs);
+int vsom_spectral_gram(const double* V, const double* W, long ld, long N, int l, int slabs, double* G, double* H, void* ws, long ws_size,
+                       vsom_stream_t stream);
+int vsom_spectral_rotate(const double* V, long ldv, long N, int l, const double* T, int l_out, double* Vout, long ldo,
+                         vsom_stream_t stream);
+int vsom_spectral_residual(const double* V, const double* W, long ld, long N, int l, const double* theta, int slabs, double* out,
+                           void* ws, long ws_size, vsom_stream_t stream);
+int vsom_spectral_embed(const double* V, long ldv, const double* s, long N, int first, int n_out, float* E, long lde, double* sign,
+                        vsom_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

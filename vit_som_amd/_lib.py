@@ -224,6 +224,15 @@ SIGNATURES = {
     "vsom_dbscan_init": (C.c_int, [c_fp, C.c_long, C.c_int, c_fp, c_fp, c_stream]),
     "vsom_dbscan_round": (C.c_int, [c_fp, C.c_long, c_fp, c_fp, C.c_int, c_fp, c_stream]),
     "vsom_dbscan_finish": (C.c_int, [c_fp, C.c_long, c_fp, c_fp, c_fp, c_fp, c_stream]),
+    # spectral embedding (csrc/spectral.hip): CSR as int64 indptr / indices and fp64 data, fp64 blocks [N, l <= 32]
+    "vsom_spectral_degrees": (C.c_int, [c_fp, c_fp, c_fp, C.c_long, C.c_long, c_fp, c_fp, c_fp, c_fp, c_stream]),
+    "vsom_spectral_spmm": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_long, C.c_long, c_fp, C.c_int, c_fp, c_fp, c_fp, C.c_long, C.c_int,
+                                     C.c_double, C.c_double, C.c_double, c_stream]),
+    "vsom_spectral_ws_size": (C.c_long, [C.c_long, C.c_int, C.c_int]),
+    "vsom_spectral_gram": (C.c_int, [c_fp, c_fp, C.c_long, C.c_long, C.c_int, C.c_int, c_fp, c_fp, c_fp, C.c_long, c_stream]),
+    "vsom_spectral_rotate": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, C.c_int, c_fp, C.c_long, c_stream]),
+    "vsom_spectral_residual": (C.c_int, [c_fp, c_fp, C.c_long, C.c_long, C.c_int, c_fp, C.c_int, c_fp, c_fp, C.c_long, c_stream]),
+    "vsom_spectral_embed": (C.c_int, [c_fp, C.c_long, c_fp, C.c_long, C.c_int, C.c_int, c_fp, C.c_long, c_fp, c_stream]),
     "vsom_fill": (C.c_int, [c_fp, C.c_long, C.c_float, c_stream]),
     "vsom_scaled_mul": (C.c_int, [c_fp, c_fp, c_fp, C.c_long, c_fp, C.c_float, c_stream]),
     "vsom_som_weighted_loss": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_float, c_fp, c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_int,

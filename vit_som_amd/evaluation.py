@@ -46,6 +46,7 @@ from .linear_probe import LinearProbeReport, evaluate_linear_probe, linear_probe
 from .gmm import GMMReport, evaluate_gmm  # noqa: F401  (the entry lives with its estimator)
 from .agglomerative import MapClustersReport, evaluate_map_clusters, visualize_map_clusters  # noqa: F401  (likewise)
 from .dbscan import DBSCANReport, evaluate_dbscan, visualize_dbscan  # noqa: F401  (likewise)
+from .spectral import SpectralReport, evaluate_spectral, visualize_spectral_map  # noqa: F401  (likewise)
 from .tsne import TSNEQualityReport, evaluate_tsne_quality, visualize_tsne_progression  # noqa: F401  (the entries live with their estimator)
 from .plots import _draw_grid, _draw_map, _pyplot, _save_scatter, _umap_scatter, draw_decoded_prototypes, draw_label_heatmap  # noqa: F401
 from .silhouette import cluster_silhouette

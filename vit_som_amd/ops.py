@@ -1757,3 +1757,122 @@ def dbscan_finish(adj, core, root, labels, record):
     _dense(labels, "labels", _I64, (N,)); _dense(record, "record", _I32, (4,))
     check(lib.vsom_dbscan_finish(ptr(adj), N, ptr(core), ptr(root), ptr(labels), ptr(record), stream()), "vsom_dbscan_finish")
     return labels, record
+
+
+# ---------------------------------------------------------------- spectral embedding (spectral.py)
+# Evaluation wrappers under the contract stated at the agglomerative section.  The graph is CSR on the device: int64 indptr
+# [N + 1] and indices [nnz], fp64 data [nnz] (tsne_step's convention).  A block is an fp64 [N, l] tensor with innermost
+# stride 1 and any row stride, l <= SPECTRAL_MAX_WIDTH; the blocks of one call share their row stride.
+SPECTRAL_MAX_N = 131072                                          # csrc/spectral.hip: SP_MAX_N
+SPECTRAL_MAX_WIDTH = 32                                          # SP_MAX_L
+SPECTRAL_CHUNK = 512                                             # SP_CHUNK: the entries of one chain of a row's sum
+SPECTRAL_STATUS = 5                                              # int64 words of spectral_degrees' status
+SPECTRAL_ISOLATED, SPECTRAL_BAD_INDEX, SPECTRAL_BAD_WEIGHT, SPECTRAL_BAD_INDPTR, SPECTRAL_HEAVY = 0, 1, 2, 3, 4
+
+
+def _block(t, name, rows=None, cols=None, ld=None, optional=False):
+    """An fp64 block: on the device, 2-D, innermost stride 1, `rows` x `cols` and of row stride `ld` where given ->
+    (rows, cols, row stride); (0, 0, 0) for an optional None."""
+    if t is None and optional:
+        return 0, 0, 0
+    if isinstance(t, _Tensor) and t.is_cuda and t.dtype == _F64 and t.dim() == 2:
+        r, c = t.shape
+        stride = t.stride(0) if r > 1 else (ld if ld is not None else c)
+        if (t.stride(1) == 1 or not t.numel()) and (rows is None or rows == r) and (cols is None or cols == c) and (
+                ld is None or ld == stride):
+            return r, c, stride
+    _device(t, name, _F64)
+    raise ValueError(f"{name}: expected a [{'any' if rows is None else rows}, {'any' if cols is None else cols}] float64 block with "
+                     f"innermost stride 1{'' if ld is None else f' and row stride {ld}'}, got shape {tuple(t.shape)} with strides "
+                     f"{t.stride()}")
+
+
+def _csr(indptr, indices, data):
+    """-> (N, nnz) of a device CSR triple."""
+    N = _dense(indptr, "indptr", _I64, (None,)).shape[0] - 1
+    nnz = _dense(indices, "indices", _I64, (None,)).shape[0]
+    _dense(data, "data", _F64, (nnz,))
+    if N < 1:
+        raise ValueError(f"indptr: expected at least 2 elements, got {N + 1}")
+    return N, nnz
+
+
+def spectral_degrees(indptr, indices, data, d, s, heavy, status):
+    """d fp64 [N] = the row sums of the CSR matrix without its diagonal, s fp64 [N] = d^-1/2 (0 for a row without weight),
+    heavy int32 [N]: the rows of more than SPECTRAL_CHUNK entries (status[SPECTRAL_HEAVY] of them), status int64
+    [SPECTRAL_STATUS]: isolated rows, indices outside [0, N), weights negative or not finite, bad indptr pairs, long rows."""
+    N, nnz = _csr(indptr, indices, data)
+    _dense(d, "d", _F64, (N,)); _dense(s, "s", _F64, (N,)); _dense(heavy, "heavy", _I32, (N,))
+    _dense(status, "status", _I64, (SPECTRAL_STATUS,))
+    check(lib.vsom_spectral_degrees(ptr(indptr), ptr(indices), ptr(data), N, nnz, ptr(d), ptr(s), ptr(heavy), ptr(status), stream()),
+          "vsom_spectral_degrees")
+    return d, s
+
+
+def spectral_spmm(indptr, indices, data, s, Y1, Y0, out, alpha=1.0, c=0.0, beta=0.0, heavy=None, n_heavy=0):
+    """out = alpha (M Y1 - c Y1) - beta Y0 with M = diag(s) A diag(s), A's diagonal skipped; Y0 may be None.  heavy /
+    n_heavy: the list spectral_degrees wrote, or None (same bits, long rows then occupy one lane group each)."""
+    N, nnz = _csr(indptr, indices, data)
+    _dense(s, "s", _F64, (N,))
+    _, l, ld = _block(Y1, "Y1", N)
+    _block(Y0, "Y0", N, l, ld, optional=True); _block(out, "out", N, l, ld)
+    _buffer(heavy, "heavy", _I32, int(n_heavy), optional=True)
+    check(lib.vsom_spectral_spmm(ptr(indptr), ptr(indices), ptr(data), ptr(s), N, nnz, ptr(heavy), int(n_heavy) if heavy is not None else 0,
+                                 ptr(Y1), ptr(Y0), ptr(out), ld, l, float(alpha), float(c), float(beta), stream()), "vsom_spectral_spmm")
+    return out
+
+
+def spectral_slabs(N) -> int:
+    """The slab count the estimators use: a function of N alone, so that a fit is reproducible."""
+    return max(1, min(512, int(N) // 256))
+
+
+def spectral_ws_size(N, l, slabs) -> int:
+    return int(lib.vsom_spectral_ws_size(int(N), int(l), int(slabs)))
+
+
+def spectral_gram(V, W, G, H, slabs=None):
+    """G fp64 [l, l] = V^T V and, with W and H, H = V^T W: slabs of rows summed in slab order."""
+    N, l, ld = _block(V, "V")
+    _block(W, "W", N, l, ld, optional=True)
+    _dense(G, "G", _F64, (l, l)); _dense(H, "H", _F64, (l, l), optional=True)
+    slabs = spectral_slabs(N) if slabs is None else int(slabs)
+    need = spectral_ws_size(N, l, slabs)
+    ws = scratch(need, V.device)
+    check(lib.vsom_spectral_gram(ptr(V), ptr(W), ld, N, l, slabs, ptr(G), ptr(H), ptr(ws), need, stream()), "vsom_spectral_gram")
+    return G, H
+
+
+def spectral_rotate(V, T, out):
+    """out [N, l_out] = V [N, l] T, T fp64 [l, l_out] dense on the device."""
+    N, l, ldv = _block(V, "V")
+    l_out = _dense(T, "T", _F64, (l, None)).shape[1]
+    _, _, ldo = _block(out, "out", N, l_out)
+    check(lib.vsom_spectral_rotate(ptr(V), ldv, N, l, ptr(T), l_out, ptr(out), ldo, stream()), "vsom_spectral_rotate")
+    return out
+
+
+def spectral_residual(V, W, theta, out, slabs=None):
+    """out fp64 [l] = the squared norms of the columns of W - V diag(theta), from the differences themselves."""
+    N, l, ld = _block(V, "V")
+    _block(W, "W", N, l, ld)
+    _dense(theta, "theta", _F64, (l,)); _dense(out, "out", _F64, (l,))
+    slabs = spectral_slabs(N) if slabs is None else int(slabs)
+    need = spectral_ws_size(N, l, slabs)
+    ws = scratch(need, V.device)
+    check(lib.vsom_spectral_residual(ptr(V), ptr(W), ld, N, l, ptr(theta), slabs, ptr(out), ptr(ws), need, stream()),
+          "vsom_spectral_residual")
+    return out
+
+
+def spectral_embed(V, s, first, E, sign):
+    """E f32 [N, n] = sign[j] * (s[i] * V[i, first + j]), rounded once; sign fp64 [n] (written) makes the entry of largest
+    magnitude of every column positive, the smaller row on a tie."""
+    N, l, ldv = _block(V, "V")
+    _dense(s, "s", _F64, (N,))
+    _, n, lde = _matrix(E, "E", N)
+    _dense(sign, "sign", _F64, (n,))
+    if not 0 <= int(first) <= l - n:
+        raise ValueError(f"first: columns [{first}, {int(first) + n}) are not inside the block's {l}")
+    check(lib.vsom_spectral_embed(ptr(V), ldv, ptr(s), N, int(first), n, ptr(E), lde, ptr(sign), stream()), "vsom_spectral_embed")
+    return E

@@ -29,7 +29,7 @@ import yaml
 
 from .evaluation import (evaluate_classification, evaluate_clustering, evaluate_embedding_quality, evaluate_knn, evaluate_linear_probe,
                          evaluate_map_quality, evaluate_silhouette, evaluate_latent_spectrum, fit_som_batch,
-                         evaluate_gmm, evaluate_map_clusters, evaluate_tsne_quality, init_som_from_data, evaluate_dbscan)
+                         evaluate_gmm, evaluate_map_clusters, evaluate_tsne_quality, init_som_from_data, evaluate_dbscan, evaluate_spectral)
 from .classifier import ViTClassifier
 from .model import ViTSOM
 
@@ -278,7 +278,8 @@ def main_vit(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, 
 
 def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print, map_quality=False,
          knn_eval=False, embedding_quality=False, silhouette=False, som_init=None, latent_spectrum=False, som_batch_epochs=0,
-         linear_probe=False, tsne_quality=False, map_clusters=False, dbscan_eval=False, gmm_eval=False):
+         linear_probe=False, tsne_quality=False, map_clusters=False, dbscan_eval=False, spectral_eval=False,
+         gmm_eval=False):
     """train_vit_som.py:27-130; a config with hyperparameters.model_arch == "vit" runs main_vit (train_vit.py) instead.
     model_states_dir defaults to experiments/states/vit_som (experiments/states/vit for the ViT baseline).
     map_quality: after each run's final evaluation also run evaluate_map_quality on the training loader with the model that
@@ -299,6 +300,9 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
     dbscan_eval: likewise run evaluate_dbscan with that model on the training loader (density clusters of the latents the SOM
     sees, eps from the k-distance curve) and report dbscan_clusters, dbscan_noise, dbscan_purity and dbscan_nmi (the last two
     over the clustered samples only).
+    spectral_eval: likewise run evaluate_spectral with that model on the training loader (spectral clustering of the latents'
+    kNN graph at data.num_classes clusters) and report spectral_purity, spectral_nmi and spectral_eigengap_k, the number of
+    clusters the graph's largest eigengap suggests.
     silhouette: likewise run evaluate_silhouette with that model on the training loader, the samples clustered by their
     BMU, and report silhouette_bmu (NaN, with the reason logged, when fewer than two units or every sample alone won).
     som_init: "pca" or "sample": before the first step of each run start the SOM's prototypes from the training loader's
@@ -345,6 +349,8 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
         all_metrics.update(map_cluster_purity=[], map_cluster_nmi=[])
     if dbscan_eval:
         all_metrics.update(dbscan_clusters=[], dbscan_noise=[], dbscan_purity=[], dbscan_nmi=[])
+    if spectral_eval:
+        all_metrics.update(spectral_purity=[], spectral_nmi=[], spectral_eigengap_k=[])
     if silhouette:
         all_metrics.update(silhouette_bmu=[])
     if latent_spectrum:
@@ -436,6 +442,14 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
             all_metrics["dbscan_noise"].append(float(dr.n_noise))
             all_metrics["dbscan_purity"].append(dr.purity)
             all_metrics["dbscan_nmi"].append(dr.nmi)
+        if spectral_eval:
+            sr = evaluate_spectral(evaluated, config, train_loader)
+            log(f"Spectral clustering: purity {sr.purity:.4f}, NMI {sr.nmi:.4f} at k {sr.n_clusters}; the eigengap suggests k "
+                f"{sr.eigengap_k}; {sr.n_connected_components} graph components, {sr.n_iter} passes ({sr.metric}, "
+                f"{sr.n_neighbors} neighbours)")
+            all_metrics["spectral_purity"].append(sr.purity)
+            all_metrics["spectral_nmi"].append(sr.nmi)
+            all_metrics["spectral_eigengap_k"].append(float(sr.eigengap_k))
         if silhouette:
             try:
                 sr = evaluate_silhouette(evaluated, config, train_loader, clusters="bmu")
@@ -486,6 +500,9 @@ def _parser():
     ap.add_argument("--map-clusters", action="store_true",
                     help="after each run also report purity and NMI of the SOM's units merged into data.num_classes grid-connected "
                          "clusters (agglomerative clustering of the prototypes), every sample labelled by its BMU's cluster")
+    ap.add_argument("--spectral-eval", action="store_true",
+                    help="after each run also report spectral clustering of the training set's latents (kNN graph, data.num_classes "
+                         "clusters): purity, NMI and the number of clusters the largest eigengap suggests")
     ap.add_argument("--dbscan-eval", action="store_true",
                     help="after each run also report the density clusters (DBSCAN) of the training set's latents: clusters, noise rows, "
                          "purity and NMI over the clustered samples")
@@ -511,4 +528,5 @@ if __name__ == "__main__":
     main(load_config(a.config), n_runs=a.runs, max_epochs=a.epochs, make_loaders=loaders, map_quality=a.map_quality,
          knn_eval=a.knn_eval, embedding_quality=a.embedding_quality, silhouette=a.silhouette, som_init=a.som_init,
          latent_spectrum=a.latent_spectrum, som_batch_epochs=a.som_batch_epochs, linear_probe=a.linear_probe,
-         tsne_quality=a.tsne_quality, gmm_eval=a.gmm_eval, map_clusters=a.map_clusters, dbscan_eval=a.dbscan_eval)
+         tsne_quality=a.tsne_quality, gmm_eval=a.gmm_eval, map_clusters=a.map_clusters, dbscan_eval=a.dbscan_eval,
+         spectral_eval=a.spectral_eval)

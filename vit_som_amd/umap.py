@@ -36,6 +36,9 @@ The algorithm (umap-learn 0.5, restated; the departures are marked):
    centroids spectrally) and scaled to half the smallest distance between meta-positions; a component with fewer
    than 2 dim points, or <= dim + 1, is uniform random in that box.  Then x 10 / max|.| plus normal(scale=1e-4)
    noise.  If ARPACK fails: a warning and the random init.  'random': uniform(-10, 10).  An array is taken as given.
+   'spectral_device' (opt-in): on a connected graph the same eigenvectors from the device solver of spectral.py
+   (Chebyshev-filtered subspace iteration in fp64, residual <= 1e-8, a fixed start); with several components the host
+   path above.  'spectral' stays ARPACK and stays the default.
    Then every column is normalised to [0, 10]: 10 (e - min) / (max - min).
    The fit draws from its RandomState in this order: 8 bytes (``bytes(8)``, little-endian) = the 64-bit seed of
    step 8; then the init: the uniform boxes of small components (in component order) and the normal noise
@@ -268,11 +271,15 @@ def _meta_positions(n_comp, labels, dim, centroids):
     return meta / big if big > 0 else meta
 
 
-def spectral_init(G, dim, rs, centroids):
+def spectral_init(G, dim, rs, centroids, device=None):
     """Step 7's 'spectral' layout before the x 10 / max scaling and the noise.  `centroids(labels, n)` -> [n, D]
-    float64 mean input row of every component."""
+    float64 mean input row of every component.  device (init='spectral_device'): a connected graph's eigenvectors come
+    from the device solver of spectral.py instead of ARPACK; several components take the host path either way."""
     n_comp, labels = scipy.sparse.csgraph.connected_components(G, directed=False)
     if n_comp == 1:
+        if device is not None:
+            from .spectral import eigenmap_device
+            return eigenmap_device(G, dim, device)
         return _eigenmap(G, dim)
     meta = _meta_positions(n_comp, labels, dim, centroids)
     out = np.empty((G.shape[0], dim))
@@ -343,8 +350,8 @@ class UMAP:
             raise ValueError(f"UMAP: metric must be one of {sorted(METRICS)}, got {self.metric!r}")
         if self.n_epochs is not None and (not _is_int(self.n_epochs) or self.n_epochs < 1):
             raise ValueError(f"UMAP: n_epochs must be None or a positive integer, got {self.n_epochs!r}")
-        if isinstance(self.init, str) and self.init not in ("spectral", "random"):
-            raise ValueError(f"UMAP: init must be 'spectral', 'random' or an array, got {self.init!r}")
+        if isinstance(self.init, str) and self.init not in ("spectral", "spectral_device", "random"):
+            raise ValueError(f"UMAP: init must be 'spectral', 'spectral_device', 'random' or an array, got {self.init!r}")
         if not self.learning_rate > 0:
             raise ValueError("UMAP: learning_rate must be positive")
         if not (self.min_dist >= 0 and self.spread > 0 and self.min_dist <= self.spread):
@@ -381,7 +388,7 @@ class UMAP:
             emb = rs.uniform(low=-10.0, high=10.0, size=(N, dim))
         else:
             try:
-                emb = spectral_init(G, dim, rs, self._centroids(X))
+                emb = spectral_init(G, dim, rs, self._centroids(X), X.device if self.init == "spectral_device" else None)
             except _ARPACK_FAILURES as e:
                 warnings.warn(f"UMAP: spectral initialisation failed ({e}); falling back to random init")
                 emb = None
