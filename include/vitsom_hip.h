@@ -1174,6 +1174,39 @@ int vsom_dbscan_round(const uint64_t* adj, long N, const uint8_t* core, int32_t*
 int vsom_dbscan_finish(const uint64_t* adj, long N, const uint8_t* core, const int32_t* root, int64_t* labels, int32_t* record,
                        vsom_stream_t stream);
 
+/* HDBSCAN (Campello, Moulavi, Sander 2013; sklearn.cluster.HDBSCAN; vit_som_amd/hdbscan.py; no counterpart in the
+ * reference): the minimum spanning tree of the mutual-reachability graph d_mr(i, j) = max(core[i], core[j], d(i, j)) by
+ * Boruvka rounds, one contraction per round, the graph never held.  Undirected edges are ordered by (w, lo, hi), w the fp32
+ * value of d_mr and lo < hi the rows: the order is strict, the tree unique, and Kruskal under the same order gives the same
+ * N - 1 edges.  No entry takes a caller-sized scratch buffer: every buffer is typed and sized by N, at the natural
+ * alignment of its type.  2 <= N <= 131 072 (more: VSOM_EUNSUPPORTED).  Integer atomics only, no grid-wide barrier, no
+ * spin-wait, every device loop bounded by N: the edge list is bitwise reproducible.
+ *
+ * record (int32 [4]): [0] components left, [1] edges so far, [2] bad rows (matrix: bad entries), [3] rounds merged.
+ * vsom_hdbscan_init: comp[i] (int32 [N]) = i; edges (int32 [N, 3]) = -1; record = (N, 0, 0, 0).
+ * vsom_hdbscan_nearest: best[i] (uint64 [N], written in full) = the least (w, j) over the rows j with comp[j] != comp[i],
+ * packed (fp32 bits of w) << 32 | j, all-ones without one.  d is bit for bit the fp32 distance of vsom_umap_knn between
+ * rows of X [N, D] (row stride ldx >= D >= 1; VSOM_DIST_EUCLIDEAN, with the root, or VSOM_DIST_COSINE; another metric:
+ * VSOM_EUNSUPPORTED); core (f32 [N]) the caller's core distances.  Rows are loaded 16 bytes per lane under the decision of
+ * vsom_knn_ranks, element-wise otherwise: the same bits.  Writes sq f32 [N] (the squared norms) and record[2]: the rows
+ * with a NaN, an infinity, an overflowing norm or a core distance that is not finite; such a row offers and receives nothing.
+ * vsom_hdbscan_nearest_matrix: the same from a precomputed matrix M [N, N], float32 (is_f64 == 0) or float64, row stride
+ * ldm >= N in elements: w = max(core[i], core[j], (float)M[i][j]), the fp32 rounding of the maximum.  An entry off the
+ * diagonal that is not finite as fp32 offers nothing and is counted in record[2].
+ * vsom_hdbscan_merge: per component the least of its rows' candidates under (w, lo, hi) (two integer atomicMin passes);
+ * every component with one hooks onto the component at the other end -- of a mutual pair only the larger label -- and
+ * writes (lo, hi, fp32 bits of w) to edges[label]; the hooks are chased to their roots and comp is relabelled; record[0],
+ * [1] and [3] are updated.  A label is a row of its component; one that hooks is never a label again, so every slot of
+ * edges is written at most once and only the last root's stays -1.  work: int64 [2 N], overwritten.  The caller repeats
+ * nearest + merge until record[0] == 1: at most ceil(log2 N) rounds, since every round at least halves the components. */
+int vsom_hdbscan_init(long N, int32_t* comp, int32_t* edges, int32_t* record, vsom_stream_t stream);
+int vsom_hdbscan_nearest(const float* X, long ldx, long N, int D, int metric, const float* core, const int32_t* comp, float* sq,
+                         uint64_t* best, int32_t* record, vsom_stream_t stream);
+int vsom_hdbscan_nearest_matrix(const void* M, long ldm, long N, int is_f64, const float* core, const int32_t* comp, uint64_t* best,
+                                int32_t* record, vsom_stream_t stream);
+int vsom_hdbscan_merge(const uint64_t* best, long N, int32_t* comp, int32_t* edges, int64_t* work, int32_t* record,
+                       vsom_stream_t stream);
+
 /* Spectral embedding (Belkin and Niyogi 2003; sklearn.manifold.SpectralEmbedding; vit_som_amd/spectral.py; no counterpart
  * in the reference): the device side of a Chebyshev-filtered subspace iteration (Zhou and Saad 2007) on
  * M = D^-1/2 A D^-1/2.  A is a symmetric affinity in CSR -- int64 indptr [N + 1] / indices [nnz], fp64 data [nnz], the

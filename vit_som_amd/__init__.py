@@ -30,6 +30,7 @@ from .linear_probe import LinearProbeReport, LogisticRegression, evaluate_linear
 from .gmm import GaussianMixture, GMMReport, evaluate_gmm  # noqa: F401,E402
 from .agglomerative import AgglomerativeClustering, MapClustersReport, evaluate_map_clusters, visualize_map_clusters  # noqa: F401,E402
 from .dbscan import DBSCAN, DBSCANReport, evaluate_dbscan, k_distances, visualize_dbscan  # noqa: F401,E402
+from .hdbscan import HDBSCAN, HDBSCANReport, evaluate_hdbscan, visualize_hdbscan  # noqa: F401,E402
 from .spectral import SpectralClustering, SpectralEmbedding, SpectralReport, evaluate_spectral, visualize_spectral_map  # noqa: F401,E402
 from .tsne import TSNE, TSNEQualityReport, evaluate_tsne_quality, visualize_tsne_progression  # noqa: F401,E402
 from .data import DeviceDataset, DeviceLoader, DeviceTransform  # noqa: F401,E402

@@ -224,6 +224,11 @@ SIGNATURES = {
     "vsom_dbscan_init": (C.c_int, [c_fp, C.c_long, C.c_int, c_fp, c_fp, c_stream]),
     "vsom_dbscan_round": (C.c_int, [c_fp, C.c_long, c_fp, c_fp, C.c_int, c_fp, c_stream]),
     "vsom_dbscan_finish": (C.c_int, [c_fp, C.c_long, c_fp, c_fp, c_fp, c_fp, c_stream]),
+    # HDBSCAN (csrc/knn.hip): Boruvka rounds over the mutual-reachability graph; typed buffers sized by N, no workspace
+    "vsom_hdbscan_init": (C.c_int, [C.c_long, c_fp, c_fp, c_fp, c_stream]),
+    "vsom_hdbscan_nearest": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_stream]),
+    "vsom_hdbscan_nearest_matrix": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, c_fp, c_fp, c_fp, c_stream]),
+    "vsom_hdbscan_merge": (C.c_int, [c_fp, C.c_long, c_fp, c_fp, c_fp, c_fp, c_stream]),
     # spectral embedding (csrc/spectral.hip): CSR as int64 indptr / indices and fp64 data, fp64 blocks [N, l <= 32]
     "vsom_spectral_degrees": (C.c_int, [c_fp, c_fp, c_fp, C.c_long, C.c_long, c_fp, c_fp, c_fp, c_fp, c_stream]),
     "vsom_spectral_spmm": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_long, C.c_long, c_fp, C.c_int, c_fp, c_fp, c_fp, C.c_long, C.c_int,

@@ -15,6 +15,9 @@
 //   vsom_dbscan_*    the same contraction a fourth time, thresholding: the eps-neighbourhood graph as a bit matrix, one
 //                    wave64 ballot per word, no atomics; then the connected components of the core rows (int32,
 //                    atomicMin only) and sklearn's DBSCAN labels.  The contract stands at the head of that section.
+//   vsom_hdbscan_*   the same contraction a fifth time, once per Boruvka round: every row's least mutual-reachability edge
+//                    out of its component, then the components' hooks -- the minimum spanning tree HDBSCAN reads its
+//                    hierarchy from, under a strict order of the edges.  Integer atomicMin only.
 //
 // The contract the search entry points keep (the rank pass takes its distances from the same four), written once below:
 //   - the 128 x 64 tile of dot products (knn_tile_dots: the staging, the k-loop and the MFMA order of gemm_f32.h, shared
@@ -1291,6 +1294,292 @@ __global__ __launch_bounds__(DBSCAN_SCAN) void dbscan_tally_kernel(int N, const 
     }
 }
 
+// ---------------------------------------------------------------------------------------------- HDBSCAN
+// The same contraction of a set with itself a fifth time, once per Boruvka round: the minimum spanning tree of the mutual
+// reachability graph d_mr(i, j) = max(core_i, core_j, d(i, j)) of HDBSCAN (Campello, Moulavi, Sander 2013;
+// sklearn.cluster.HDBSCAN; vit_som_amd/hdbscan.py; no counterpart in the reference) without ever holding that graph.
+//
+// The order.  Undirected edges are ordered by (w, lo, hi): w the fp32 value of d_mr, lo < hi the two rows.  The order is
+// strict, so the tree is unique, a round -- every component takes its least outgoing edge -- can close no cycle but the
+// mutual pair, and Kruskal under the same order rebuilds the tree edge for edge.  d is bit for bit the fp32 distance of
+// vsom_umap_knn and the same bits seen from (i, j) and from (j, i) (the DBSCAN section's symmetry), fmaxf commutes.
+//
+// A round.  vsom_hdbscan_nearest leaves best[i] = the least (w, j) over the columns j with comp[j] != comp[i], packed
+// as (fp32 bits of w) << 32 | j -- w >= 0, so its bits order as it does -- and all-ones for "none".  For a fixed row
+// (w, j) orders the candidates exactly as (w, lo, hi) does.  vsom_hdbscan_merge takes per component the least of its
+// rows' candidates under the full order in two integer atomicMin passes ((w, lo), then hi among the rows that attain it),
+// hooks every component onto the one at the other end of its edge -- of a mutual pair only the larger label -- chases
+// the hooks to their roots and relabels.  A label is a row of its component with comp[label] == label; a component that
+// hooks emits its edge into edges[label], and that label is never a label again: the slots are disjoint, no counter is
+// needed, and only the last root's slot stays empty.  The hooks are a forest (strict order, mutual pairs broken), so the
+// chase from a label ends after fewer steps than there are components; its loop is bounded by N all the same.
+// Integer atomics only; nothing waits on another workgroup; every value is a minimum under a strict order or a plain
+// store of one: the edge list is bitwise reproducible whatever the chunking and the races.
+constexpr unsigned long long HDB_NONE = ~0ull;
+constexpr int HDB_COMPONENTS = 0, HDB_EDGES = 1, HDB_BAD = 2, HDB_ROUNDS = 3;       // the words of record
+
+__device__ __forceinline__ unsigned long long hdb_key(float w, int j) {
+    return (unsigned long long)(__float_as_uint(w) & 0x7fffffffu) << 32 | (unsigned)j;      // the mask: -0 orders as 0
+}
+
+struct HdbP {
+    KnnOperand A;
+    int D, metric;
+    const float* sq;
+    const float* core;
+    const int* comp;
+    unsigned long long* best;   // [N], all-ones on entry
+    int ct, chunks;
+};
+
+// One workgroup = 128 rows x one chunk of column tiles, built like dbscan_tile_kernel up to the tile of dot products.  The
+// epilogue needs no LDS: a lane of the accumulators holds columns r and 32 + r of 16 rows (register v: row (v & 3) +
+// 8 (v >> 2) + 4h), so lane = column, and it keeps those 16 rows' squared norms, core distances, components and running
+// best (w, j) in registers over the whole chunk.  A lane meets its columns in ascending order, so w < best keeps the
+// lowest column among equals.  At the end of the chunk the 32 lanes of a half fold their keys with an integer minimum
+// and one 64-bit atomicMin per (row, chunk) leaves the workgroup.  A row or column outside the set or without a distance
+// to itself (dbscan_row_ok), a pair of one component -- the diagonal among them -- and a pair without a distance offer nothing.
+template <bool FAST>
+__global__ __launch_bounds__(KNN_THREADS, 2) void hdb_tile_kernel(const HdbP p) {
+    constexpr int BM = KNN_BM, BN = KNN_BN;
+    __shared__ __attribute__((aligned(16))) float lds[(BM + BN) * 36];
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int wm0 = wave * 32;
+    const int bm0 = blockIdx.x * BM;
+    const int chunk = blockIdx.y;
+    const int ct0 = (int)((long)chunk * p.ct / p.chunks), ct1 = (int)((long)(chunk + 1) * p.ct / p.chunks);
+    const int N = p.A.rows;
+
+    float rsq[16], rcore[16], bw[16];
+    int rcomp[16], bj[16];                                           // rcomp -1: a row that offers nothing
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        const int gi = bm0 + wm0 + (v & 3) + 8 * (v >> 2) + 4 * h;
+        const bool in = gi < N;
+        rsq[v] = in ? p.sq[gi] : 0.f;
+        rcore[v] = in ? p.core[gi] : 0.f;
+        rcomp[v] = in && dbscan_row_ok(rsq[v], p.metric) ? p.comp[gi] : -1;
+        bw[v] = INFINITY;
+        bj[v] = 0;
+    }
+
+    KnnStage<FAST> st;
+    st.point(p.A, p.A);
+    st.rows_a(p.A, bm0, t);
+
+    for (int ctile = ct0; ctile < ct1; ++ctile) {
+        const int bn0 = ctile * BN;
+        f32x16 acc[2];
+        knn_tile_dots<FAST>(st, p.A, bm0, p.A, bn0, p.D, lds, t, acc);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            // no LDS staging of the tile's comp / core values: one lane owns one column of the accumulator, so each of the 64
+            // values is loaded by exactly the lane that uses it, once per tile, coalesced
+            const int gj = bn0 + j * 32 + r;
+            const bool in = gj < N;
+            const float sj = in ? p.sq[gj] : 0.f;
+            const float cj = in ? p.core[gj] : 0.f;
+            const int mj = in && dbscan_row_ok(sj, p.metric) ? p.comp[gj] : -1;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const float d = knn_distance(acc[j][v], rsq[v], sj, p.metric);
+                const float w = fmaxf(fmaxf(rcore[v], cj), d);
+                if (rcomp[v] >= 0 && mj >= 0 && mj != rcomp[v] && d == d && w < bw[v]) { bw[v] = w; bj[v] = gj; }
+            }
+        }
+        __syncthreads();        // every wave is past its last MFMA read of the LDS tiles before the next tile's stores
+    }
+
+    unsigned long long mine = HDB_NONE;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        unsigned long long key = bw[v] < INFINITY ? hdb_key(bw[v], bj[v]) : HDB_NONE;
+#pragma unroll
+        for (int o = 16; o; o >>= 1) {
+            const unsigned long long other = __shfl_xor(key, o, 64);    // o < 32: within the half that shares these rows
+            key = other < key ? other : key;
+        }
+        if (r == v) mine = key;
+    }
+    const int gi = bm0 + wm0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+    if (r < 16 && gi < N && mine != HDB_NONE) atomicMin(&p.best[gi], mine);
+}
+
+__global__ __launch_bounds__(256) void hdb_clear_best_kernel(unsigned long long* __restrict__ best, int N) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < N) best[i] = HDB_NONE;
+}
+
+// One workgroup: record[HDB_BAD] = the rows without a distance to themselves or without a finite core distance.
+__global__ __launch_bounds__(DBSCAN_SCAN) void hdb_bad_rows_kernel(const float* __restrict__ sq, const float* __restrict__ core, int N,
+                                                                   int metric, int* __restrict__ record) {
+    __shared__ int bad[DBSCAN_SCAN];
+    const int t = threadIdx.x;
+    int z = 0;
+    for (int i = t; i < N; i += DBSCAN_SCAN) z += !(dbscan_row_ok(sq[i], metric) && fabsf(core[i]) < INFINITY);
+    bad[t] = z;
+    __syncthreads();
+    if (t == 0) {
+        int tz = 0;
+        for (int k = 0; k < DBSCAN_SCAN; ++k) tz += bad[k];
+        record[HDB_BAD] = tz;
+    }
+}
+
+// The same round from a precomputed matrix M [N, N] (T float or double, row stride ldm).  One wave per row, lane = column
+// modulo 64 in ascending order: w = max(core_i, core_j, (float)M[i][j]), which is the fp32 rounding of the maximum since
+// rounding is monotone.  best[i] is a plain store: one wave owns the row.  An entry off the diagonal that is not finite as
+// fp32 offers nothing and is counted in record[HDB_BAD] (cleared before the launch; an integer atomic, one per row that has any).
+template <class T>
+__global__ __launch_bounds__(DBSCAN_ROWS * 64) void hdb_matrix_kernel(const T* __restrict__ M, long ldm, int N,
+                                                                      const float* __restrict__ core, const int* __restrict__ comp,
+                                                                      unsigned long long* __restrict__ best, int* __restrict__ record) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * DBSCAN_ROWS + (threadIdx.x >> 6);
+    if (i >= N) return;
+    const T* row = M + (size_t)i * ldm;
+    const float ci = core[i];
+    const int mi = comp[i];
+    float bw = INFINITY;
+    int bj = 0, bad = 0;
+    for (int j = lane; j < N; j += 64) {
+        const float m = (float)row[j];
+        const bool fin = fabsf(m) < INFINITY;
+        bad += !fin && j != i;
+        const float w = fmaxf(fmaxf(ci, core[j]), m);
+        if (fin && comp[j] != mi && w < bw) { bw = w; bj = j; }
+    }
+    unsigned long long key = bw < INFINITY ? hdb_key(bw, bj) : HDB_NONE;
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        const unsigned long long other = __shfl_xor(key, o, 64);
+        key = other < key ? other : key;
+        bad += __shfl_xor(bad, o, 64);
+    }
+    if (lane == 0) {
+        best[i] = key;
+        if (bad) atomicAdd(&record[HDB_BAD], bad);
+    }
+}
+__global__ void hdb_clear_bad_kernel(int* __restrict__ record) { record[HDB_BAD] = 0; }
+
+// comp[i] = i, edges[i] = (-1, -1, -1), record = (N components, no edge, no bad row, no round).
+__global__ __launch_bounds__(256) void hdb_init_kernel(int N, int* __restrict__ comp, int* __restrict__ edges, int* __restrict__ record) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < N) {
+        comp[i] = i;
+        edges[3 * i] = edges[3 * i + 1] = edges[3 * i + 2] = -1;
+    }
+    if (i < 4) record[i] = i == HDB_COMPONENTS ? N : 0;
+}
+
+// The merge step's arrays, in the caller's work (int64 [2 N]): cbest u64 [N], then (hi, parent) int32 [N] each.
+struct HdbWork {
+    unsigned long long* cbest;
+    int* chi;
+    int* parent;
+};
+inline HdbWork hdb_work(int64_t* work, long N) {
+    HdbWork w;
+    w.cbest = reinterpret_cast<unsigned long long*>(work);
+    w.chi = reinterpret_cast<int*>(work + N);
+    w.parent = w.chi + N;
+    return w;
+}
+
+__global__ __launch_bounds__(256) void hdb_merge_clear_kernel(int N, HdbWork w) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    w.cbest[i] = HDB_NONE;
+    w.chi[i] = 0x7fffffff;
+    w.parent[i] = i;
+}
+
+// Row i's candidate as an undirected edge: false without one (or with a component or a column that is no row index --
+// not what vsom_hdbscan_init and _nearest leave; nothing is then read or written through it).
+__device__ __forceinline__ bool hdb_candidate(const unsigned long long* best, const int* comp, int N, int i, int& c,
+                                              unsigned long long& wlo, int& hi) {
+    const unsigned long long k = best[i];
+    const unsigned j = (unsigned)k;
+    c = comp[i];
+    if (k == HDB_NONE || j >= (unsigned)N || (unsigned)c >= (unsigned)N) return false;
+    const unsigned lo = j < (unsigned)i ? j : (unsigned)i;
+    hi = (int)(j < (unsigned)i ? (unsigned)i : j);
+    wlo = (k & 0xffffffff00000000ull) | lo;
+    return true;
+}
+// cbest[c] = the least (w, lo) over the rows of component c; then chi[c] = the least hi among the rows that attain it.
+__global__ __launch_bounds__(256) void hdb_merge_low_kernel(const unsigned long long* __restrict__ best, const int* __restrict__ comp,
+                                                            int N, HdbWork w) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int c, hi;
+    unsigned long long wlo;
+    if (i < N && hdb_candidate(best, comp, N, i, c, wlo, hi)) atomicMin(&w.cbest[c], wlo);
+}
+__global__ __launch_bounds__(256) void hdb_merge_high_kernel(const unsigned long long* __restrict__ best, const int* __restrict__ comp,
+                                                             int N, HdbWork w) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int c, hi;
+    unsigned long long wlo;
+    if (i < N && hdb_candidate(best, comp, N, i, c, wlo, hi) && wlo == w.cbest[c]) atomicMin(&w.chi[c], hi);
+}
+
+// Label c (comp[c] == c) with an edge hooks onto the component at its other end and emits the edge into edges[c]; of a
+// mutual pair -- both took the same (w, lo, hi) -- only the larger label does.
+__global__ __launch_bounds__(256) void hdb_merge_hook_kernel(const int* __restrict__ comp, int N, HdbWork w, int* __restrict__ edges) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= N || comp[c] != c || w.cbest[c] == HDB_NONE) return;
+    const int lo = (int)(unsigned)w.cbest[c], hi = w.chi[c];
+    if (lo >= N || (unsigned)hi >= (unsigned)N) return;
+    const int o = comp[lo] == c ? comp[hi] : comp[lo];
+    if ((unsigned)o >= (unsigned)N || o == c) return;
+    const bool mutual = w.cbest[o] == w.cbest[c] && w.chi[o] == hi;
+    if (mutual && c < o) return;
+    w.parent[c] = o;
+    edges[3 * c] = lo;
+    edges[3 * c + 1] = hi;
+    edges[3 * c + 2] = (int)(unsigned)(w.cbest[c] >> 32);
+}
+
+// parent[c] <- the root of label c's tree of hooks.  Every value a racing read of parent can return is an ancestor (the
+// hook or the root a finished thread stored), so the chase only ever moves up; the forest is shallower than N.
+__global__ __launch_bounds__(256) void hdb_merge_jump_kernel(const int* __restrict__ comp, int N, int* parent) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= N || comp[c] != c) return;
+    int r = dbscan_root(parent, c);
+    for (int steps = 0; steps < N; ++steps) {
+        const int up = dbscan_root(parent, r);
+        if (up == r) break;
+        r = up;
+    }
+    __atomic_store_n(parent + c, r, __ATOMIC_RELAXED);
+}
+__global__ __launch_bounds__(256) void hdb_merge_relabel_kernel(int N, const int* __restrict__ parent, int* __restrict__ comp) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const int c = comp[i];
+    if ((unsigned)c < (unsigned)N) comp[i] = parent[c];
+}
+
+// One workgroup: record = (the labels left, N less that: the edges so far, ., one round more).
+__global__ __launch_bounds__(DBSCAN_SCAN) void hdb_merge_record_kernel(const int* __restrict__ comp, int N, int* __restrict__ record) {
+    __shared__ int left[DBSCAN_SCAN];
+    const int t = threadIdx.x;
+    int n = 0;
+    for (int i = t; i < N; i += DBSCAN_SCAN) n += comp[i] == i;
+    left[t] = n;
+    __syncthreads();
+    if (t == 0) {
+        int tn = 0;
+        for (int k = 0; k < DBSCAN_SCAN; ++k) tn += left[k];
+        record[HDB_COMPONENTS] = tn;
+        record[HDB_EDGES] = N - tn;
+        record[HDB_ROUNDS] += 1;
+    }
+}
+
 }  // namespace
 }  // namespace vsom
 
@@ -1531,6 +1820,78 @@ int vsom_dbscan_finish(const uint64_t* adj, long N, const uint8_t* core, const i
     VSOM_LAUNCH(dbscan_border_kernel, dim3(cdiv(N, DBSCAN_ROWS)), dim3(DBSCAN_ROWS * 64), 0, stream, words, (int)N, W, core, labels);
     VSOM_LAUNCH(dbscan_tally_kernel, dim3(1), dim3(DBSCAN_SCAN), 0, stream, (int)N, core, (const int64_t*)labels, record);
     return launch_status("dbscan_finish");
+}
+
+int vsom_hdbscan_init(long N, int32_t* comp, int32_t* edges, int32_t* record, vsom_stream_t stream) {
+    using namespace vsom;
+    VSOM_REQUIRE(comp && edges && record, VSOM_EINVAL, "hdbscan_init: null pointer");
+    VSOM_REQUIRE(N >= 2, VSOM_EINVAL, "hdbscan_init: bad sizes N=%ld", N);
+    VSOM_REQUIRE(N <= DBSCAN_MAX_N, VSOM_EUNSUPPORTED, "hdbscan_init: N=%ld > %ld", N, DBSCAN_MAX_N);
+    VSOM_LAUNCH(hdb_init_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, (int)N, comp, edges, record);
+    return launch_status("hdbscan_init");
+}
+
+int vsom_hdbscan_nearest(const float* X, long ldx, long N, int D, int metric, const float* core, const int32_t* comp, float* sq,
+                         uint64_t* best, int32_t* record, vsom_stream_t stream) {
+    using namespace vsom;
+    VSOM_REQUIRE(X && core && comp && sq && best && record, VSOM_EINVAL, "hdbscan_nearest: null pointer");
+    VSOM_REQUIRE(N >= 2 && D >= 1 && ldx >= D, VSOM_EINVAL, "hdbscan_nearest: bad sizes N=%ld D=%d ldx=%ld", N, D, ldx);
+    VSOM_REQUIRE(N <= DBSCAN_MAX_N, VSOM_EUNSUPPORTED, "hdbscan_nearest: N=%ld > %ld", N, DBSCAN_MAX_N);
+    VSOM_REQUIRE(metric == VSOM_DIST_EUCLIDEAN || metric == VSOM_DIST_COSINE, VSOM_EUNSUPPORTED,
+                 "hdbscan_nearest: metric %d (euclidean or cosine only)", metric);
+    const QueryPlan pl = query_plan(N, N);
+    const bool vec = knn_self_vec(X, ldx, D);
+    const size_t ext = (size_t)N * ldx * 4;
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(best);
+    VSOM_LAUNCH(knn_sqnorm_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, X, ldx, N, D, sq);
+    VSOM_LAUNCH(hdb_clear_best_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, keys, (int)N);
+    VSOM_LAUNCH(hdb_bad_rows_kernel, dim3(1), dim3(DBSCAN_SCAN), 0, stream, (const float*)sq, core, (int)N, metric, record);
+    HdbP p = {};
+    p.A = {X, ldx, (int)N, (unsigned)ext, vec};
+    p.D = D; p.metric = metric; p.sq = sq; p.core = core; p.comp = comp; p.best = keys;
+    p.ct = pl.ct; p.chunks = pl.chunks;
+    const dim3 grid(pl.rb, pl.chunks), block(KNN_THREADS);
+    if (vec && ext < (size_t)OOB - 256) VSOM_LAUNCH(hdb_tile_kernel<true>, grid, block, 0, stream, p);
+    else VSOM_LAUNCH(hdb_tile_kernel<false>, grid, block, 0, stream, p);
+    return launch_status("hdbscan_nearest");
+}
+
+int vsom_hdbscan_nearest_matrix(const void* M, long ldm, long N, int is_f64, const float* core, const int32_t* comp, uint64_t* best,
+                                int32_t* record, vsom_stream_t stream) {
+    using namespace vsom;
+    VSOM_REQUIRE(M && core && comp && best && record, VSOM_EINVAL, "hdbscan_nearest_matrix: null pointer");
+    VSOM_REQUIRE(N >= 2 && ldm >= N, VSOM_EINVAL, "hdbscan_nearest_matrix: bad sizes N=%ld ldm=%ld", N, ldm);
+    VSOM_REQUIRE(N <= DBSCAN_MAX_N, VSOM_EUNSUPPORTED, "hdbscan_nearest_matrix: N=%ld > %ld", N, DBSCAN_MAX_N);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(best);
+    const dim3 grid(cdiv(N, DBSCAN_ROWS)), block(DBSCAN_ROWS * 64);
+    VSOM_LAUNCH(hdb_clear_bad_kernel, dim3(1), dim3(1), 0, stream, record);
+    if (is_f64)
+        VSOM_LAUNCH(hdb_matrix_kernel<double>, grid, block, 0, stream, static_cast<const double*>(M), ldm, (int)N, core, comp, keys,
+                    record);
+    else
+        VSOM_LAUNCH(hdb_matrix_kernel<float>, grid, block, 0, stream, static_cast<const float*>(M), ldm, (int)N, core, comp, keys,
+                    record);
+    return launch_status("hdbscan_nearest_matrix");
+}
+
+int vsom_hdbscan_merge(const uint64_t* best, long N, int32_t* comp, int32_t* edges, int64_t* work, int32_t* record,
+                       vsom_stream_t stream) {
+    using namespace vsom;
+    VSOM_REQUIRE(best && comp && edges && work && record, VSOM_EINVAL, "hdbscan_merge: null pointer");
+    VSOM_REQUIRE(N >= 2, VSOM_EINVAL, "hdbscan_merge: bad sizes N=%ld", N);
+    VSOM_REQUIRE(N <= DBSCAN_MAX_N, VSOM_EUNSUPPORTED, "hdbscan_merge: N=%ld > %ld", N, DBSCAN_MAX_N);
+    const unsigned long long* keys = reinterpret_cast<const unsigned long long*>(best);
+    const HdbWork w = hdb_work(work, N);
+    const dim3 grid(cdiv(N, 256)), block(256);
+    const int n = (int)N;
+    VSOM_LAUNCH(hdb_merge_clear_kernel, grid, block, 0, stream, n, w);
+    VSOM_LAUNCH(hdb_merge_low_kernel, grid, block, 0, stream, keys, (const int*)comp, n, w);
+    VSOM_LAUNCH(hdb_merge_high_kernel, grid, block, 0, stream, keys, (const int*)comp, n, w);
+    VSOM_LAUNCH(hdb_merge_hook_kernel, grid, block, 0, stream, (const int*)comp, n, w, edges);
+    VSOM_LAUNCH(hdb_merge_jump_kernel, grid, block, 0, stream, (const int*)comp, n, w.parent);
+    VSOM_LAUNCH(hdb_merge_relabel_kernel, grid, block, 0, stream, n, (const int*)w.parent, comp);
+    VSOM_LAUNCH(hdb_merge_record_kernel, dim3(1), dim3(DBSCAN_SCAN), 0, stream, (const int*)comp, n, record);
+    return launch_status("hdbscan_merge");
 }
 
 }  // extern "C"

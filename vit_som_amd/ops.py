@@ -1876,3 +1876,68 @@ def spectral_embed(V, s, first, E, sign):
         raise ValueError(f"first: columns [{first}, {int(first) + n}) are not inside the block's {l}")
     check(lib.vsom_spectral_embed(ptr(V), ldv, ptr(s), N, int(first), n, ptr(E), lde, ptr(sign), stream()), "vsom_spectral_embed")
     return E
+
+
+# ---------------------------------------------------------------- HDBSCAN (hdbscan.py)
+# Evaluation wrappers under the contract stated at the agglomerative section.  No entry takes a workspace: every buffer is
+# typed and its shape follows from N.  A row's candidate travels as int64 (the 64 bits are the entry's): the fp32 bits of
+# the mutual-reachability distance in the high word, the other row in the low word, -1 (all ones) for none.
+HDBSCAN_MAX_N = DBSCAN_MAX_N                                     # csrc/knn.hip: the limit of the DBSCAN section
+HDBSCAN_COMPONENTS, HDBSCAN_EDGES, HDBSCAN_BAD, HDBSCAN_ROUNDS = 0, 1, 2, 3       # the words of the entries' record
+
+
+def hdbscan_work(N) -> int:
+    """int64 words of hdbscan_merge's work array."""
+    return 2 * int(N)
+
+
+def hdbscan_init(comp, edges, record):
+    """comp int32 [N] = the row itself; edges int32 [N, 3] = -1; record int32 [4] = (N components, 0 edges, 0 bad rows,
+    0 rounds)."""
+    N = _dense(comp, "comp", _I32, (None,)).shape[0]
+    _dense(edges, "edges", _I32, (N, 3)); _dense(record, "record", _I32, (4,))
+    check(lib.vsom_hdbscan_init(N, ptr(comp), ptr(edges), ptr(record), stream()), "vsom_hdbscan_init")
+    return comp, edges
+
+
+def hdbscan_nearest(X, metric, core, comp, sq, best, record):
+    """best int64 [N] = for every row of X f32 [N, D] (any row stride) the least (w, j) over the rows j of another
+    component, w = max(core[i], core[j], d(i, j)) in fp32 with d the distance of umap_knn (DIST_EUCLIDEAN or DIST_COSINE),
+    packed (bits of w) << 32 | j; -1 without one.  core f32 [N], comp int32 [N]; sq f32 [N] receives the squared norms,
+    record[HDBSCAN_BAD] the bad rows.  Nothing is read back."""
+    N, D, ldx = _matrix(X, "X")
+    _dense(core, "core", _F32, (N,)); _dense(comp, "comp", _I32, (N,)); _dense(sq, "sq", _F32, (N,))
+    _dense(best, "best", _I64, (N,)); _dense(record, "record", _I32, (4,))
+    check(lib.vsom_hdbscan_nearest(ptr(X), ldx, N, D, int(metric), ptr(core), ptr(comp), ptr(sq), ptr(best), ptr(record), stream()),
+          "vsom_hdbscan_nearest")
+    return best
+
+
+def hdbscan_nearest_matrix(M, core, comp, best, record):
+    """The same candidates from precomputed distances M [N, N]: float32 with any row stride, or float64 contiguous (what
+    agglo_distances writes).  w is the float32 rounding of max(core[i], core[j], M[i, j]).  An entry off the diagonal that
+    is not finite in float32 offers nothing and is counted in record[HDBSCAN_BAD]."""
+    if isinstance(M, _Tensor) and M.dtype == _F64:
+        N = _dense(M, "M", _F64, (None, None)).shape[0]
+        _dense(M, "M", _F64, (N, N))
+        ldm, wide = N, 1
+    else:
+        N, _, ldm = _matrix(M, "M")
+        _matrix(M, "M", N, N)
+        wide = 0
+    _dense(core, "core", _F32, (N,)); _dense(comp, "comp", _I32, (N,))
+    _dense(best, "best", _I64, (N,)); _dense(record, "record", _I32, (4,))
+    check(lib.vsom_hdbscan_nearest_matrix(ptr(M), ldm, N, wide, ptr(core), ptr(comp), ptr(best), ptr(record), stream()),
+          "vsom_hdbscan_nearest_matrix")
+    return best
+
+
+def hdbscan_merge(best, comp, edges, work, record):
+    """One Boruvka merge from the rows' candidates: every component's least edge under (w, lo, hi) goes to edges[label] as
+    (lo, hi, bits of w), comp is relabelled, record's components, edges and rounds are updated.  work int64
+    [hdbscan_work(N)] is overwritten.  Nothing is read back: the caller reads record and repeats until one component is left."""
+    N = _dense(comp, "comp", _I32, (None,)).shape[0]
+    _dense(best, "best", _I64, (N,)); _dense(edges, "edges", _I32, (N, 3))
+    _dense(work, "work", _I64, (hdbscan_work(N),)); _dense(record, "record", _I32, (4,))
+    check(lib.vsom_hdbscan_merge(ptr(best), N, ptr(comp), ptr(edges), ptr(work), ptr(record), stream()), "vsom_hdbscan_merge")
+    return comp, edges

@@ -29,7 +29,8 @@ import yaml
 
 from .evaluation import (evaluate_classification, evaluate_clustering, evaluate_embedding_quality, evaluate_knn, evaluate_linear_probe,
                          evaluate_map_quality, evaluate_silhouette, evaluate_latent_spectrum, fit_som_batch,
-                         evaluate_gmm, evaluate_map_clusters, evaluate_tsne_quality, init_som_from_data, evaluate_dbscan, evaluate_spectral)
+                         evaluate_gmm, evaluate_map_clusters, evaluate_tsne_quality, init_som_from_data, evaluate_dbscan, evaluate_spectral,
+                         evaluate_hdbscan)
 from .classifier import ViTClassifier
 from .model import ViTSOM
 
@@ -279,7 +280,7 @@ def main_vit(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, 
 def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print, map_quality=False,
          knn_eval=False, embedding_quality=False, silhouette=False, som_init=None, latent_spectrum=False, som_batch_epochs=0,
          linear_probe=False, tsne_quality=False, map_clusters=False, dbscan_eval=False, spectral_eval=False,
-         gmm_eval=False):
+         hdbscan_eval=False, gmm_eval=False):
     """train_vit_som.py:27-130; a config with hyperparameters.model_arch == "vit" runs main_vit (train_vit.py) instead.
     model_states_dir defaults to experiments/states/vit_som (experiments/states/vit for the ViT baseline).
     map_quality: after each run's final evaluation also run evaluate_map_quality on the training loader with the model that
@@ -300,6 +301,9 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
     dbscan_eval: likewise run evaluate_dbscan with that model on the training loader (density clusters of the latents the SOM
     sees, eps from the k-distance curve) and report dbscan_clusters, dbscan_noise, dbscan_purity and dbscan_nmi (the last two
     over the clustered samples only).
+    hdbscan_eval: likewise run evaluate_hdbscan with that model on the training loader (density clusters of those latents
+    without an eps, chosen by their stability) and report hdbscan_clusters, hdbscan_noise, hdbscan_purity and hdbscan_nmi
+    (the last two over the clustered samples only).
     spectral_eval: likewise run evaluate_spectral with that model on the training loader (spectral clustering of the latents'
     kNN graph at data.num_classes clusters) and report spectral_purity, spectral_nmi and spectral_eigengap_k, the number of
     clusters the graph's largest eigengap suggests.
@@ -349,6 +353,8 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
         all_metrics.update(map_cluster_purity=[], map_cluster_nmi=[])
     if dbscan_eval:
         all_metrics.update(dbscan_clusters=[], dbscan_noise=[], dbscan_purity=[], dbscan_nmi=[])
+    if hdbscan_eval:
+        all_metrics.update(hdbscan_clusters=[], hdbscan_noise=[], hdbscan_purity=[], hdbscan_nmi=[])
     if spectral_eval:
         all_metrics.update(spectral_purity=[], spectral_nmi=[], spectral_eigengap_k=[])
     if silhouette:
@@ -442,6 +448,15 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
             all_metrics["dbscan_noise"].append(float(dr.n_noise))
             all_metrics["dbscan_purity"].append(dr.purity)
             all_metrics["dbscan_nmi"].append(dr.nmi)
+        if hdbscan_eval:
+            hr = evaluate_hdbscan(evaluated, config, train_loader)
+            log(f"HDBSCAN: {hr.n_clusters} clusters, {hr.n_noise} noise rows of {hr.n_samples} (coverage {hr.coverage:.3f}), purity "
+                f"{hr.purity:.4f}, NMI {hr.nmi:.4f} (min_cluster_size {hr.min_cluster_size}, min_samples {hr.min_samples}, {hr.metric}, "
+                f"{hr.n_rounds} rounds)")
+            all_metrics["hdbscan_clusters"].append(float(hr.n_clusters))
+            all_metrics["hdbscan_noise"].append(float(hr.n_noise))
+            all_metrics["hdbscan_purity"].append(hr.purity)
+            all_metrics["hdbscan_nmi"].append(hr.nmi)
         if spectral_eval:
             sr = evaluate_spectral(evaluated, config, train_loader)
             log(f"Spectral clustering: purity {sr.purity:.4f}, NMI {sr.nmi:.4f} at k {sr.n_clusters}; the eigengap suggests k "
@@ -506,6 +521,9 @@ def _parser():
     ap.add_argument("--dbscan-eval", action="store_true",
                     help="after each run also report the density clusters (DBSCAN) of the training set's latents: clusters, noise rows, "
                          "purity and NMI over the clustered samples")
+    ap.add_argument("--hdbscan-eval", action="store_true",
+                    help="after each run also report the density clusters without an eps (HDBSCAN) of the training set's latents: "
+                         "clusters, noise rows, purity and NMI over the clustered samples")
     ap.add_argument("--silhouette", action="store_true",
                     help="after each run also report the silhouette coefficient of the training set's latents clustered by their BMU")
     ap.add_argument("--som-init", choices=("pca", "sample"), default=None,
@@ -529,4 +547,4 @@ if __name__ == "__main__":
          knn_eval=a.knn_eval, embedding_quality=a.embedding_quality, silhouette=a.silhouette, som_init=a.som_init,
          latent_spectrum=a.latent_spectrum, som_batch_epochs=a.som_batch_epochs, linear_probe=a.linear_probe,
          tsne_quality=a.tsne_quality, gmm_eval=a.gmm_eval, map_clusters=a.map_clusters, dbscan_eval=a.dbscan_eval,
-         spectral_eval=a.spectral_eval)
+         spectral_eval=a.spectral_eval, hdbscan_eval=a.hdbscan_eval)
