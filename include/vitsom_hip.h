@@ -1254,6 +1254,35 @@ int vsom_spectral_residual(const double* V, const double* W, long ld, long N, in
 int vsom_spectral_embed(const double* V, long ldv, const double* s, long N, int first, int n_out, float* E, long lde, double* sign,
                         vsom_stream_t stream);
 
+/* Attention rollout (Abnar and Zuidema 2020, head fusion as in the vit-explain recipe; vit_som_amd/attention_rollout.py; no
+ * counterpart in the reference): one link of the vector-matrix chain that folds a stack of attention layers into one map
+ * per image.  qkv is a block's saved [B N, 3 H hd] buffer, columns ordered [3][H][hd] as vsom_attention_probs reads it;
+ * v_in, v_out are f32 [B, N] dense.  No N x N matrix is formed anywhere.
+ *
+ *   P_h[i, j] = softmax_j(q_i . k_j / sqrt(hd)), each row normalised by its own scores (the saved lse is not an argument)
+ *   F[i, j]   = the mean (fusion 0), max (1) or min (2) over the heads of P_h[i, j]
+ *   A[i, j]   = (alpha F[i, j] + (1 - alpha) [i == j]) / (alpha sum_j F[i, j] + (1 - alpha)),  0 < alpha <= 1
+ *   v_out[b, j] = sum_i v_in[b, i] A_b[i, j]
+ *
+ * The minimum is taken of log P_h = (s - max) - log(sum) and exponentiated relative to the fused row's largest entry, the
+ * row's scale returning as one factor (with alpha = 1 it cancels and is never formed): where saturated heads disagree
+ * every min_h P_h of a row lies below the smallest float, and only their ratios are needed.
+ * The order of every sum: a score is one fma chain over d ascending from 0, then scaled; a row's maximum and sum are a
+ * lane's keys (j, j + 64, ...) in ascending order, then the wave's xor tree.  The column sum over i is cut into blocks of
+ * 16 rows: inside a block each of four waves adds its four rows in ascending i (fp32 fma), the waves are added in wave
+ * order, and the blocks of a sample are added in block order in fp64 and rounded once.  No atomics, no grid-wide barrier,
+ * no spin-wait; two runs are bitwise equal and a sample's row depends neither on B nor on its place in the batch.
+ *
+ * Plain VALU, 4-byte accesses only: no pointer needs more than the alignment of a float, and no head dim is padded.
+ * Limits: N <= 320 (five chunks of 64 keys) and (N (hd | 1) + 16 hd + 256 ceil(N / 64)) * 4 bytes of LDS <= 160 KiB -- every
+ * project shape (N <= 257, hd <= 64) and any hd >= 1 that fits; otherwise VSOM_EUNSUPPORTED, the message naming N, hd and
+ * the bytes.  A null pointer, a size <= 0, fusion outside {0, 1, 2}, alpha outside (0, 1], or v_out overlapping v_in:
+ * VSOM_EINVAL.  ws NULL or short: VSOM_EWORKSPACE.  All of these before any launch.
+ * vsom_attention_rollout_ws_size: bytes of the workspace (B ceil(N / 16) partial rows of N floats); 0 outside the limits. */
+long vsom_attention_rollout_ws_size(int B, int N, int H, int hd);
+int vsom_attention_rollout_step(const float* qkv, const float* v_in, float* v_out, int B, int N, int H, int hd, int fusion, float alpha,
+                                void* ws, long ws_size, vsom_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

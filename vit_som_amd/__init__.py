@@ -32,5 +32,6 @@ from .agglomerative import AgglomerativeClustering, MapClustersReport, evaluate_
 from .dbscan import DBSCAN, DBSCANReport, evaluate_dbscan, k_distances, visualize_dbscan  # noqa: F401,E402
 from .hdbscan import HDBSCAN, HDBSCANReport, evaluate_hdbscan, visualize_hdbscan  # noqa: F401,E402
 from .spectral import SpectralClustering, SpectralEmbedding, SpectralReport, evaluate_spectral, visualize_spectral_map  # noqa: F401,E402
+from .attention_rollout import AttentionReport, evaluate_attention, visualize_attention_map, visualize_attention_rollout  # noqa: F401,E402
 from .tsne import TSNE, TSNEQualityReport, evaluate_tsne_quality, visualize_tsne_progression  # noqa: F401,E402
 from .data import DeviceDataset, DeviceLoader, DeviceTransform  # noqa: F401,E402

@@ -238,6 +238,10 @@ SIGNATURES = {
     "vsom_spectral_rotate": (C.c_int, [c_fp, C.c_long, C.c_long, C.c_int, c_fp, C.c_int, c_fp, C.c_long, c_stream]),
     "vsom_spectral_residual": (C.c_int, [c_fp, c_fp, C.c_long, C.c_long, C.c_int, c_fp, C.c_int, c_fp, c_fp, C.c_long, c_stream]),
     "vsom_spectral_embed": (C.c_int, [c_fp, C.c_long, c_fp, C.c_long, C.c_int, C.c_int, c_fp, C.c_long, c_fp, c_stream]),
+    # attention rollout (csrc/attention_rollout.hip): one link of the chain, f32 [B, N] in and out
+    "vsom_attention_rollout_ws_size": (C.c_long, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vsom_attention_rollout_step": (C.c_int, [c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_fp, C.c_long,
+                                              c_stream]),
     "vsom_fill": (C.c_int, [c_fp, C.c_long, C.c_float, c_stream]),
     "vsom_scaled_mul": (C.c_int, [c_fp, c_fp, c_fp, C.c_long, c_fp, C.c_float, c_stream]),
     "vsom_som_weighted_loss": (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_float, c_fp, c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_int,

@@ -104,6 +104,11 @@ class ViTClassifier(_ViTOwner):
         evaluation.evaluate_classification reads, the `vit` branch of the reference's evaluation.py:109-110."""
         return None, self._run_forward(x)[2].logits
 
+    def attention_rollout(self, x, query="cls", head_fusion="mean", residual=0.5, start_layer=0):
+        """ViTAutoencoder.attention_rollout of the encoder -> [B, N]: a full encode, whatever hooks.cls_prune says -- the
+        CLS-pruned last block keeps no qkv for all queries."""
+        return self.model.attention_rollout(x, query, head_fusion, residual, start_layer)
+
     @torch.no_grad()
     def _forward_losses(self, x, y, gamma_t=0.0, T=0.0, want_grad=True):
         """Forward + cross-entropy (+ dL/dlogits when want_grad); the mean loss as a 0-dim device tensor (a slot of a

@@ -161,6 +161,11 @@ class DESOM(_ArenaOwner, _Base):
             logits = a.logits.clone()
         return logits, z.clone(), dist, bmu
 
+    def attention_rollout(self, x, *args, **kwargs):
+        """DESOM's encoder is fully connected: there is no attention to roll out.  Always raises ValueError."""
+        raise ValueError("attention_rollout: a DESOM model has no attention layers (its encoder is fully connected); attention "
+                         "rollout needs a vit_som or a vit model")
+
     @torch.no_grad()
     def predict(self, x):
         """Inference fast path for tools/evaluation.py (evaluate_clustering / evaluate_classification read

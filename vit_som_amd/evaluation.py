@@ -25,6 +25,8 @@ returns the whole set's result; figures are drawn by rank 0):
                                        evaluate_tsne_quality (tsne.py, likewise), evaluate_gmm (gmm.py, likewise)
   SOM input                            evaluate_dbscan / visualize_dbscan (defined in dbscan.py next to their estimator,
                                        reachable from here), evaluate_hdbscan / visualize_hdbscan (hdbscan.py, likewise)
+  the encoder's saved qkv              evaluate_attention / visualize_attention_rollout / visualize_attention_map (defined in
+                                       attention_rollout.py next to the chain, reachable from here)
   SOM input and BMU                    evaluate_silhouette / visualize_silhouette_map (silhouette.py),
                                        evaluate_latent_spectrum, init_som_from_data, fit_som_batch (SOMLayer.fit_batch)
   the prototypes only, no data         visualize_decoded_prototypes / decoded_prototype_canvas / decode_prototype
@@ -48,6 +50,7 @@ from .agglomerative import MapClustersReport, evaluate_map_clusters, visualize_m
 from .dbscan import DBSCANReport, evaluate_dbscan, visualize_dbscan  # noqa: F401  (likewise)
 from .hdbscan import HDBSCANReport, evaluate_hdbscan, visualize_hdbscan  # noqa: F401  (likewise)
 from .spectral import SpectralReport, evaluate_spectral, visualize_spectral_map  # noqa: F401  (likewise)
+from .attention_rollout import AttentionReport, evaluate_attention, visualize_attention_map, visualize_attention_rollout  # noqa: F401  (likewise)
 from .tsne import TSNEQualityReport, evaluate_tsne_quality, visualize_tsne_progression  # noqa: F401  (the entries live with their estimator)
 from .plots import _draw_grid, _draw_map, _pyplot, _save_scatter, _umap_scatter, draw_decoded_prototypes, draw_label_heatmap  # noqa: F401
 from .silhouette import cluster_silhouette

@@ -296,6 +296,13 @@ class ViTSOM(_ViTOwner):
             self._log(logs)
         return total.clone()
 
+    def attention_rollout(self, x, query=None, head_fusion="mean", residual=0.5, start_layer=0):
+        """ViTAutoencoder.attention_rollout of the encoder -> [B, N].  query None: what the SOM is fed -- 'patches', or 'cls'
+        when use_reduced is set."""
+        if query is None:
+            query = "cls" if self.use_reduced else "patches"
+        return self.vit.attention_rollout(x, query, head_fusion, residual, start_layer)
+
     def get_latent_representation(self, x):
         """vit_som.py:174-187 (the reference unpacks 4 of 3 values; this returns what it meant)."""
         with torch.no_grad():

@@ -1941,3 +1941,48 @@ def hdbscan_merge(best, comp, edges, work, record):
     _dense(work, "work", _I64, (hdbscan_work(N),)); _dense(record, "record", _I32, (4,))
     check(lib.vsom_hdbscan_merge(ptr(best), N, ptr(comp), ptr(edges), ptr(work), ptr(record), stream()), "vsom_hdbscan_merge")
     return comp, edges
+
+
+# ---------------------------------------------------------------- attention rollout (attention_rollout.py)
+# Evaluation wrappers under the contract stated at the agglomerative section.  qkv is a block's saved [B N, 3 H hd] buffer
+# (columns [3][H][hd]); the state is f32 [B, N].  4-byte accesses only: a qkv view at any float offset is legal input.
+ROLLOUT_FUSIONS = {"mean": 0, "max": 1, "min": 2}                # csrc/attention_rollout.hip: RO_MEAN, RO_MAX, RO_MIN
+ROLLOUT_MAX_N = 320                                              # RO_MAX_CHUNKS * 64
+
+
+def attention_rollout_ws_size(B, N, H, hd) -> int:
+    """Bytes of attention_rollout_step's workspace; 0 for a shape outside the kernel's limits."""
+    return int(lib.vsom_attention_rollout_ws_size(int(B), int(N), int(H), int(hd)))
+
+
+def attention_rollout_step(qkv, v_in, v_out, B, N, H, hd, fusion, alpha):
+    """v_out[b, j] = sum_i v_in[b, i] A_b[i, j], A_b the residual-mixed, head-fused, row-normalised attention matrix of the
+    block whose qkv this is (include/vitsom_hip.h has the formulas and the order of every sum).  fusion is a key of
+    ROLLOUT_FUSIONS or its code; 0 < alpha <= 1.  v_out must not overlap v_in.  No N x N matrix is formed."""
+    B, N, H, hd = int(B), int(N), int(H), int(hd)
+    _dense(qkv, "qkv", _F32, (B * N, 3 * H * hd))
+    _dense(v_in, "v_in", _F32, (B, N)); _dense(v_out, "v_out", _F32, (B, N))
+    code = ROLLOUT_FUSIONS.get(fusion, fusion) if isinstance(fusion, str) else fusion
+    if code not in (0, 1, 2):
+        raise ValueError(f"fusion: expected one of {sorted(ROLLOUT_FUSIONS)} (or 0, 1, 2), got {fusion!r}")
+    need = attention_rollout_ws_size(B, N, H, hd)
+    ws = scratch(need, qkv.device)
+    check(lib.vsom_attention_rollout_step(ptr(qkv), ptr(v_in), ptr(v_out), B, N, H, hd, int(code), float(alpha), ptr(ws), need, stream()),
+          "vsom_attention_rollout_step")
+    return v_out
+
+
+def attention_rollout(qkvs, w, H, hd, fusion="mean", alpha=0.5):
+    """The rollout of the query weights w f32 [B, N] over the blocks whose saved qkv buffers are listed in qkvs, in forward
+    order: the step of the last block first, down to the first of the list.  Two [B, N] buffers take turns; the result is a
+    fresh tensor and w is not written."""
+    qkvs = list(qkvs)
+    if not qkvs:
+        raise ValueError("qkvs: expected at least one block's qkv buffer")
+    B, N = _dense(w, "w", _F32, (None, None)).shape
+    bufs, cur = [None, None], w
+    for k, qkv in enumerate(reversed(qkvs)):
+        if bufs[k & 1] is None:
+            bufs[k & 1] = torch.empty_like(w)
+        cur = attention_rollout_step(qkv, cur, bufs[k & 1], B, N, H, hd, fusion, alpha)
+    return cur

@@ -31,6 +31,7 @@ from .evaluation import (evaluate_classification, evaluate_clustering, evaluate_
                          evaluate_map_quality, evaluate_silhouette, evaluate_latent_spectrum, fit_som_batch,
                          evaluate_gmm, evaluate_map_clusters, evaluate_tsne_quality, init_som_from_data, evaluate_dbscan, evaluate_spectral,
                          evaluate_hdbscan)
+from .attention_rollout import visualize_attention_map, visualize_attention_rollout
 from .classifier import ViTClassifier
 from .model import ViTSOM
 
@@ -280,7 +281,7 @@ def main_vit(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, 
 def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, model_states_dir=None, log=print, map_quality=False,
          knn_eval=False, embedding_quality=False, silhouette=False, som_init=None, latent_spectrum=False, som_batch_epochs=0,
          linear_probe=False, tsne_quality=False, map_clusters=False, dbscan_eval=False, spectral_eval=False,
-         hdbscan_eval=False, gmm_eval=False):
+         hdbscan_eval=False, attention_report=False, gmm_eval=False):
     """train_vit_som.py:27-130; a config with hyperparameters.model_arch == "vit" runs main_vit (train_vit.py) instead.
     model_states_dir defaults to experiments/states/vit_som (experiments/states/vit for the ViT baseline).
     map_quality: after each run's final evaluation also run evaluate_map_quality on the training loader with the model that
@@ -307,6 +308,9 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
     spectral_eval: likewise run evaluate_spectral with that model on the training loader (spectral clustering of the latents'
     kNN graph at data.num_classes clusters) and report spectral_purity, spectral_nmi and spectral_eigengap_k, the number of
     clusters the graph's largest eigengap suggests.
+    attention_report: likewise run attention rollout with that model on the training loader (visualize_attention_map, whose
+    one loader pass is evaluate_attention's, and visualize_attention_rollout), report rollout_entropy and rollout_cls_mass and
+    save the two figures under experiments/plots (a single process only: skipped with a line in the log when world > 1).
     silhouette: likewise run evaluate_silhouette with that model on the training loader, the samples clustered by their
     BMU, and report silhouette_bmu (NaN, with the reason logged, when fewer than two units or every sample alone won).
     som_init: "pca" or "sample": before the first step of each run start the SOM's prototypes from the training loader's
@@ -357,6 +361,8 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
         all_metrics.update(hdbscan_clusters=[], hdbscan_noise=[], hdbscan_purity=[], hdbscan_nmi=[])
     if spectral_eval:
         all_metrics.update(spectral_purity=[], spectral_nmi=[], spectral_eigengap_k=[])
+    if attention_report:
+        all_metrics.update(rollout_entropy=[], rollout_cls_mass=[])
     if silhouette:
         all_metrics.update(silhouette_bmu=[])
     if latent_spectrum:
@@ -465,6 +471,16 @@ def main(config, n_runs=5, max_epochs=None, make_loaders=synthetic_loaders, mode
             all_metrics["spectral_purity"].append(sr.purity)
             all_metrics["spectral_nmi"].append(sr.nmi)
             all_metrics["spectral_eigengap_k"].append(float(sr.eigengap_k))
+        if attention_report:
+            if world > 1:
+                log("Attention rollout: skipped (evaluate_attention runs in a single process only)")
+            else:
+                ar, map_path = visualize_attention_map(evaluated, config, train_loader)
+                _, roll_path = visualize_attention_rollout(evaluated, config, train_loader)
+                log(f"Attention rollout: rollout_entropy {ar.entropy:.4f}, rollout_cls_mass {ar.cls_mass:.4f} ({ar.head_fusion} fusion, "
+                    f"residual {ar.residual:g}, query {ar.query!r}, {ar.n_samples} samples); figures: {map_path}, {roll_path}")
+                all_metrics["rollout_entropy"].append(ar.entropy)
+                all_metrics["rollout_cls_mass"].append(ar.cls_mass)
         if silhouette:
             try:
                 sr = evaluate_silhouette(evaluated, config, train_loader, clusters="bmu")
@@ -521,6 +537,9 @@ def _parser():
     ap.add_argument("--dbscan-eval", action="store_true",
                     help="after each run also report the density clusters (DBSCAN) of the training set's latents: clusters, noise rows, "
                          "purity and NMI over the clustered samples")
+    ap.add_argument("--attention-report", action="store_true",
+                    help="after each run also report attention rollout of the encoder on the training set (rollout_entropy, "
+                         "rollout_cls_mass) and save the per-image overlay and the per-unit / per-class attention maps")
     ap.add_argument("--hdbscan-eval", action="store_true",
                     help="after each run also report the density clusters without an eps (HDBSCAN) of the training set's latents: "
                          "clusters, noise rows, purity and NMI over the clustered samples")
@@ -547,4 +566,4 @@ if __name__ == "__main__":
          knn_eval=a.knn_eval, embedding_quality=a.embedding_quality, silhouette=a.silhouette, som_init=a.som_init,
          latent_spectrum=a.latent_spectrum, som_batch_epochs=a.som_batch_epochs, linear_probe=a.linear_probe,
          tsne_quality=a.tsne_quality, gmm_eval=a.gmm_eval, map_clusters=a.map_clusters, dbscan_eval=a.dbscan_eval,
-         spectral_eval=a.spectral_eval, hdbscan_eval=a.hdbscan_eval)
+         spectral_eval=a.spectral_eval, hdbscan_eval=a.hdbscan_eval, attention_report=a.attention_report)

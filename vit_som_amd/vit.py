@@ -392,6 +392,35 @@ class ViTAutoencoder(nn.Module):
             out.append(probs)
         return out
 
+    # -- attention rollout (attention_rollout.py) -----------------------------------------------------
+    def _rollout(self, a: _Acts, query="cls", head_fusion="mean", residual=0.5, start_layer=0, _check_sign=True):
+        """The rollout [B, N] from the buffers `a` that a full encoder forward has just filled: launches only, no second
+        encoder pass (evaluate_attention calls it right after predict())."""
+        from .attention_rollout import rollout_from_acts
+        return rollout_from_acts(self, a, query, head_fusion, residual, start_layer, "attention_rollout", _check_sign)
+
+    @torch.no_grad()
+    def attention_rollout(self, x, query="cls", head_fusion="mean", residual=0.5, start_layer=0, _check_sign=True):
+        """Attention rollout of the encoder for the images x -> [B, N] float32, each row summing to the query's weight: how much
+        of the query's attention, folded through blocks start_layer .. L - 1 with `residual` of the identity mixed into every
+        block, ends on each input token (column 0 is CLS; patch_map() reshapes the rest to the patch grid).
+        query: 'cls'; 'patches' (1 / n on each patch token, 0 on CLS); an int token index; or a non-negative float tensor of
+        shape [N] or [B, N].  head_fusion: 'mean', 'max' or 'min' over the heads.  residual in [0, 1); start_layer in [0, L).
+        Runs the encoder in full under no_grad, then one kernel pair per block on the saved qkv; no N x N matrix is formed."""
+        from .attention_rollout import check_arguments
+        check_arguments("attention_rollout", head_fusion, residual, start_layer, len(self.blocks))
+        x = self._check_input(x)
+        if not x.is_cuda:
+            raise ValueError("attention_rollout: input must live on the MI355X (there is no CPU path)")
+        a = self._buffers_for(x.shape[0], x.device)
+        self._encode(x, a)
+        return self._rollout(a, query, head_fusion, residual, start_layer, _check_sign)
+
+    def patch_map(self, r):
+        """Columns 1: of a rollout [B, N] as [B, gh, gw] on the patch grid."""
+        from .attention_rollout import patch_map
+        return patch_map(self, r)
+
     def _wants_grad(self, *inputs):
         return torch.is_grad_enabled() and (any(p.requires_grad for _, p in _trainable_order(self))
                                             or any(t.requires_grad for t in inputs))
