@@ -12,12 +12,20 @@
 //                    continuity of an embedding).  Integer atomics only.
 //   vsom_silhouette  the same contraction once more, summing instead of counting: for every row the fixed-point sum of its
 //                    distances to each cluster's members, then the silhouette coefficient.  Integer atomics only.
-//   vsom_dbscan_*    the same contraction a fourth time, thresholding: the eps-neighbourhood graph as a bit matrix, one
+//   vsom_dbscan_*    the same contraction, thresholding: the eps-neighbourhood graph as a bit matrix, one
 //                    wave64 ballot per word, no atomics; then the connected components of the core rows (int32,
 //                    atomicMin only) and sklearn's DBSCAN labels.  The contract stands at the head of that section.
-//   vsom_hdbscan_*   the same contraction a fifth time, once per Boruvka round: every row's least mutual-reachability edge
+//   vsom_hdbscan_*   the same contraction, once per Boruvka round: every row's least mutual-reachability edge
 //                    out of its component, then the components' hooks -- the minimum spanning tree HDBSCAN reads its
 //                    hierarchy from, under a strict order of the edges.  Integer atomicMin only.
+//
+// What the five tile kernels share, written once next to knn_tile_dots: KnnBlock (where a thread stands: its rows, its
+// accumulator column, the chunk's tiles -- the one chunk split and the one register-to-row map), knn_tile_dots (the
+// tile of dot products) and knn_tile_walk (every dot product handed to the kernel's own distance predicate, then the
+// barrier).  The four contractions of a set with itself also share the head of their parameter structs (SelfP) and
+// their launch (knn_self_launch).  A kernel keeps its tile loop, its predicate -- which pairs are NaN, 0, -1 or +inf --
+// and its wave-level epilogue, which is what it is there for.  The next self-contraction writes: a struct deriving from
+// SelfP with its own fields, a kernel<FAST> of that shape, and an entry that fills those fields and calls knn_self_launch.
 //
 // The contract the search entry points keep (the rank pass takes its distances from the same four), written once below:
 //   - the 128 x 64 tile of dot products (knn_tile_dots: the staging, the k-loop and the MFMA order of gemm_f32.h, shared
@@ -122,32 +130,69 @@ using KnnOperand = F32Operand;
 template <bool FAST>
 using KnnStage = F32Stage<true, true, KNN_BM, KNN_BN, FAST>;
 
+// Where one thread stands in a tile kernel's grid (row blocks, chunks) of 256-thread workgroups: its wave owns rows wm0..wm0 +
+// 31 of the block's 128 (from bm0), its lane column r of each 32-column accumulator and the row half h (mfma_tile), and the
+// workgroup the column tiles [ct0, ct1) of the launch's ct.  The one place that spells the chunk split: the chunks are
+// disjoint and cover every tile, which dbscan_tile_kernel relies on -- it writes every word of adj exactly once and
+// clears nothing.  row(v): the block row of accumulator register v, the one statement of mfma_tile's output layout.
+struct KnnBlock {
+    int t, lane, wave, r, h, wm0, bm0, chunk, ct0, ct1;
+    __device__ __forceinline__ KnnBlock(int ct, int chunks)
+        : t(threadIdx.x), lane(t & 63), wave(t >> 6), r(lane & 31), h(lane >> 5), wm0(wave * 32), bm0(blockIdx.x * KNN_BM),
+          chunk(blockIdx.y) {
+        auto first_tile = [&](int c) { return (int)((long)c * ct / chunks); };
+        ct0 = first_tile(chunk); ct1 = first_tile(chunk + 1);
+    }
+    __device__ __forceinline__ int row(int v) const { return wm0 + (v & 3) + 8 * (v >> 2) + 4 * h; }
+};
+
 // acc[j] <- the 128 x 64 block <A[bm0 + .], B[bn0 + .]> over K on the f32 matrix cores: wave w owns rows 32w..32w+31,
-// acc[j] columns 32j..32j+31 (register v of acc[j]: row (v & 3) + 8 (v >> 2) + 4h, column 32j + r).  Operand tiles are
+// acc[j] columns 32j..32j+31 (register v of acc[j]: row KnnBlock::row(v), column 32j + r).  Operand tiles are
 // staged global -> registers -> LDS by the staging, the k-loop and the MFMA order of gemm_f32_kernel, the same code
 // (gemm_f32.h; lds: (128 + 64) * 36 floats).  Every pair's products are summed k-tile by k-tile, 8-group by 8-group,
 // step s = 0..3 with k = kb + s before kb + 4 + s inside the instruction (mfma_tile): one order for every pair.  Rows
 // outside either operand and k >= K contribute exact zeros.  All waves must call it; the caller synchronises before the
-// next call overwrites the LDS tiles.
+// next call overwrites the LDS tiles (knn_tile_walk does).
 template <bool FAST>
-__device__ __forceinline__ void knn_tile_dots(KnnStage<FAST>& st, const KnnOperand& A, int bm0, const KnnOperand& B, int bn0,
-                                              int K, float* lds, int t, f32x16 (&acc)[2]) {
+__device__ __forceinline__ void knn_tile_dots(KnnStage<FAST>& st, const KnnBlock& g, const KnnOperand& A, const KnnOperand& B,
+                                              int bn0, int K, float* lds, f32x16 (&acc)[2]) {
     constexpr int BM = KNN_BM, BN = KNN_BN;
     float* As = lds;
     float* Bs = lds + BM * 36;
-    const int lane = t & 63, wave = t >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int wm0 = wave * 32;
     const int ktiles = (K + 31) >> 5;
-    st.rows_b(B, bn0, t);
-    auto gload = [&](int kt) { st.gload(A, bm0, B, bn0, kt << 5, K, t); };
-    auto lstore = [&]() { st.lstore(As, Bs, t); };
+    st.rows_b(B, bn0, g.t);
+    auto gload = [&](int kt) { st.gload(A, g.bm0, B, bn0, kt << 5, K, g.t); };
+    auto lstore = [&]() { st.lstore(As, Bs, g.t); };
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int v = 0; v < 16; ++v) acc[j][v] = 0.f;
-    auto tile = [&]() { mfma_tile<true, true, BM, BN>(As, Bs, wm0, 0, r, h, reinterpret_cast<f32x16 (&)[1][2]>(acc)); };
+    auto tile = [&]() { mfma_tile<true, true, BM, BN>(As, Bs, g.wm0, 0, g.r, g.h, reinterpret_cast<f32x16 (&)[1][2]>(acc)); };
     F32_KLOOP(true, 0, ktiles, gload, lstore, tile);       // K >= 1: every entry refuses D < 1
+}
+
+// One pair of the tile as its thread holds it: accumulator register v, (row, col) in the block's 128 x 64 tile, (gi, gj) in
+// the two sets.
+struct KnnPair { int v, row, col, gi, gj; };
+
+// The walk over a thread's 32 dot products of the tile at column bn0: column(col, gj) once for each of its two columns
+// (that column's norm, label, ...: whatever the kernel reads per column), then pair(dot, KnnPair, that value) for the 16
+// rows of the column.  The barrier at the end is every tile kernel's: what the pairs stored into LDS (the distances,
+// sd[row][col]) is whole for the wave walks that follow, and every wave is past its last MFMA read of the LDS operand
+// tiles before the next tile's stores.  All waves must call it.
+template <class Column, class Pair>
+__device__ __forceinline__ void knn_tile_walk(const KnnBlock& g, int bn0, const f32x16 (&acc)[2], Column&& column, Pair&& pair) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int col = j * 32 + g.r, gj = bn0 + col;
+        const auto cv = column(col, gj);
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            const int row = g.row(v);
+            pair(acc[j][v], KnnPair{v, row, col, g.bm0 + row, gj}, cv);
+        }
+    }
+    __syncthreads();
 }
 
 // (query row blocks, bank column tiles, chunks): chunks split the bank's columns so that few queries still fill the GPU.
@@ -162,6 +207,8 @@ inline QueryPlan query_plan(long Nq, long Nb) {
     p.chunks = want < 1 ? 1 : (want > p.ct ? p.ct : want);
     return p;
 }
+// The 16-byte buffer loads (FAST) also need the operand's extent under the buffer limit.
+inline bool knn_buffer_extent(size_t bytes) { return bytes < (size_t)OOB - 256; }
 
 // Workspace: sqq f32 [Nq], sqx f32 [Nb], cand_d f32 [chunks][Nq][k], cand_i i32 [chunks][Nq][k], each 256-aligned.  The
 // slabs are sized in whole row blocks (Nq <= rb * 128), by a bound on chunks * rb that grows with Nq -- chunks * rb <=
@@ -218,12 +265,8 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_tile_kernel(const QueryP p) {
     __shared__ __attribute__((aligned(16))) float lds[(BM + BN) * 36];
     __shared__ float sd[BM][BN + 1];
 
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int wm0 = wave * 32;
-    const int bm0 = blockIdx.x * BM;
-    const int chunk = blockIdx.y;
-    const int ct0 = (int)((long)chunk * p.ct / p.chunks), ct1 = (int)((long)(chunk + 1) * p.ct / p.chunks);
+    const KnnBlock g(p.ct, p.chunks);
+    const int lane = g.lane, wm0 = g.wm0, bm0 = g.bm0;
     const KnnOperand& X = SELF ? p.Q : p.X;
     const float* sqx = SELF ? p.sqq : p.sqx;
     const int Nq = p.Q.rows, Nb = X.rows;
@@ -244,27 +287,19 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_tile_kernel(const QueryP p) {
 
     KnnStage<FAST> st;
     st.point(p.Q, X);
-    st.rows_a(p.Q, bm0, t);
+    st.rows_a(p.Q, bm0, g.t);
 
-    for (int ctile = ct0; ctile < ct1; ++ctile) {
+    for (int ctile = g.ct0; ctile < g.ct1; ++ctile) {
         const int bn0 = ctile * BN;
         f32x16 acc[2];
-        knn_tile_dots<FAST>(st, p.Q, bm0, X, bn0, p.D, lds, t, acc);
-
-        // accumulator register v of tile j: row (v & 3) + 8 (v >> 2) + 4h, column 32j + r
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = j * 32 + r, gj = bn0 + col;
-            const float sj = gj < Nb ? sqx[gj] : 0.f;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int row = wm0 + (v & 3) + 8 * (v >> 2) + 4 * h, gi = bm0 + row;
+        knn_tile_dots<FAST>(st, g, p.Q, X, bn0, p.D, lds, acc);
+        knn_tile_walk(
+            g, bn0, acc, [&](int, int gj) { return gj < Nb ? sqx[gj] : 0.f; },
+            [&](float dot, const KnnPair& c, float sj) {
                 float d = INFINITY;
-                if (gi < Nq && gj < Nb) d = SELF && gi == gj ? -1.f : knn_distance(acc[j][v], p.sqq[gi], sj, p.metric);
-                sd[row][col] = d;
-            }
-        }
-        __syncthreads();        // also: every wave is past its last MFMA read of the LDS tiles before the next tile's stores
+                if (c.gi < Nq && c.gj < Nb) d = SELF && c.gi == c.gj ? -1.f : knn_distance(dot, p.sqq[c.gi], sj, p.metric);
+                sd[c.row][c.col] = d;
+            });
         const int gj = bn0 + lane;
 #pragma unroll
         for (int rr = 0; rr < 32; ++rr) {
@@ -280,7 +315,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_tile_kernel(const QueryP p) {
     for (int rr = 0; rr < 32; ++rr) {
         const int gi = bm0 + wm0 + rr;
         if (gi < Nq && lane < p.k) {
-            const size_t o = ((size_t)chunk * Nq + gi) * p.k + lane;
+            const size_t o = ((size_t)g.chunk * Nq + gi) * (unsigned)p.k + lane;        // k >= 1: unsigned, a 32 x 32-bit multiply
             p.cand_d[o] = ld_[rr];
             p.cand_i[o] = li_[rr];
         }
@@ -343,7 +378,7 @@ int knn_search(const char* name, bool self, const float* Q, long ldq, long Nq, c
     p.X = {X, ldx, (int)Nb, (unsigned)xext, xvec};
     p.D = D; p.k = k; p.metric = metric; p.sqq = w.sqq; p.sqx = w.sqx; p.exclude = exclude; p.index_base = index_base;
     p.cand_d = w.cand_d; p.cand_i = w.cand_i; p.ct = pl.ct; p.chunks = pl.chunks;
-    const bool fast = qvec && xvec && qext < (size_t)OOB - 256 && xext < (size_t)OOB - 256;
+    const bool fast = qvec && xvec && knn_buffer_extent(qext) && knn_buffer_extent(xext);
     const dim3 grid(pl.rb, pl.chunks), block(KNN_THREADS);
     if (self) {
         if (fast) VSOM_LAUNCH((knn_tile_kernel<true, true>), grid, block, 0, stream, p);
@@ -446,17 +481,37 @@ inline bool knn_self_vec(const float* A, long lda, int D) {
     return vec;
 }
 
-struct RankP {
+// What every tile kernel over a set contracted with itself reads: the head of its parameter struct.
+struct SelfP {
     KnnOperand A;
-    int D, k, metric;
-    const float* sq;
+    int D, metric;
+    const float* sq;            // [N] squared norms in the contraction's order
+    int ct, chunks;             // query_plan(N, N)
+};
+
+// The launch of a self-contraction's tile kernel, its own parameters already in p: fills the head from the set and its
+// plan and launches TILE_FAST or TILE_GENERIC (the kernel's <true> and <false>) over (row blocks, chunks).  vec is the
+// caller's decision on the pointer and the strides (knn_self_vec, or the entry's own line).  Returns the plan it launched.
+template <class P, void (*TILE_FAST)(P), void (*TILE_GENERIC)(P)>
+QueryPlan knn_self_launch(P p, const float* X, long ld, long N, int D, int metric, const float* sq, bool vec, vsom_stream_t stream) {
+    const QueryPlan pl = query_plan(N, N);
+    const size_t ext = (size_t)N * ld * 4;
+    p.A = {X, ld, (int)N, (unsigned)ext, vec};
+    p.D = D; p.metric = metric; p.sq = sq; p.ct = pl.ct; p.chunks = pl.chunks;
+    const dim3 grid(pl.rb, pl.chunks), block(KNN_THREADS);
+    if (vec && knn_buffer_extent(ext)) VSOM_LAUNCH(TILE_FAST, grid, block, 0, stream, p);
+    else VSOM_LAUNCH(TILE_GENERIC, grid, block, 0, stream, p);
+    return pl;
+}
+
+struct RankP : SelfP {
+    int k;
     const RankSlot* slot;       // [N][k]
     int* less;                  // [N][k], 0 (or -1) on entry
     int* tied;
-    int ct, chunks;
 };
 
-// One workgroup = 128 rows x one chunk of column tiles, built like knn_tile_kernel<., SELF>.  Per 64-column tile: the
+// One workgroup = 128 rows x one chunk of column tiles (KnnBlock), like knn_tile_kernel<., SELF>.  Per 64-column tile: the
 // 128 x 64 block of A A^T (knn_tile_dots), the distances into LDS -- NaN for a column outside the set and for row i
 // against itself, so neither is ever counted -- then every wave walks each of its 32 rows' 64 distances: lane j < k
 // holds slot j's threshold and neighbour, all lanes read the same LDS word (a broadcast), and two integer counters per
@@ -469,12 +524,8 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void knn_rank_tile_kernel(const Ran
     __shared__ __attribute__((aligned(16))) float lds[(BM + BN) * 36];
     __shared__ float sd[BM][BN + 1];
 
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int wm0 = wave * 32;
-    const int bm0 = blockIdx.x * BM;
-    const int chunk = blockIdx.y;
-    const int ct0 = (int)((long)chunk * p.ct / p.chunks), ct1 = (int)((long)(chunk + 1) * p.ct / p.chunks);
+    const KnnBlock g(p.ct, p.chunks);
+    const int lane = g.lane, wm0 = g.wm0, bm0 = g.bm0;
     const int N = p.A.rows;
 
     // lane j < k of the wave holds slot j of each of its 32 rows: the two counters stay in registers over the chunk, the
@@ -488,27 +539,19 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void knn_rank_tile_kernel(const Ran
 
     KnnStage<FAST> st;
     st.point(p.A, p.A);
-    st.rows_a(p.A, bm0, t);
+    st.rows_a(p.A, bm0, g.t);
 
-    for (int ctile = ct0; ctile < ct1; ++ctile) {
+    for (int ctile = g.ct0; ctile < g.ct1; ++ctile) {
         const int bn0 = ctile * BN;
         f32x16 acc[2];
-        knn_tile_dots<FAST>(st, p.A, bm0, p.A, bn0, p.D, lds, t, acc);
-
-        // accumulator register v of tile j: row (v & 3) + 8 (v >> 2) + 4h, column 32j + r
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = j * 32 + r, gj = bn0 + col;
-            const float sj = gj < N ? p.sq[gj] : 0.f;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int row = wm0 + (v & 3) + 8 * (v >> 2) + 4 * h, gi = bm0 + row;
+        knn_tile_dots<FAST>(st, g, p.A, p.A, bn0, p.D, lds, acc);
+        knn_tile_walk(
+            g, bn0, acc, [&](int, int gj) { return gj < N ? p.sq[gj] : 0.f; },
+            [&](float dot, const KnnPair& c, float sj) {
                 float d = __builtin_nanf("");
-                if (gi < N && gj < N && gi != gj) d = knn_distance(acc[j][v], p.sq[gi], sj, p.metric);
-                sd[row][col] = d;
-            }
-        }
-        __syncthreads();        // also: every wave is past its last MFMA read of the LDS tiles before the next tile's stores
+                if (c.gi < N && c.gj < N && c.gi != c.gj) d = knn_distance(dot, p.sq[c.gi], sj, p.metric);
+                sd[c.row][c.col] = d;
+            });
         RankSlot sl_[32];
         int off = lane;
         asm volatile("" : "+v"(off));                                // computed per tile: 32 hoisted addresses cost the occupancy
@@ -670,18 +713,15 @@ __global__ __launch_bounds__(256) void sil_prepare_kernel(const int64_t* __restr
     }
 }
 
-struct SilP {
-    KnnOperand A;
-    int D, metric, C;
-    const float* sq;
+struct SilP : SelfP {
+    int C;
     const int64_t* labels;
     const unsigned* ctrl;
     unsigned long long* S;          // [N][C]
     unsigned long long* status;
-    int ct, chunks;
 };
 
-// One workgroup = 128 rows x one chunk of column tiles, built like knn_rank_tile_kernel.  Per 64-column tile: the labels
+// One workgroup = 128 rows x one chunk of column tiles (KnnBlock).  Per 64-column tile: the labels
 // of its columns into LDS (once; -1 for a column outside the set or the range), the 128 x 64 block of A A^T
 // (knn_tile_dots), the distances into LDS -- 0 for a pair that adds nothing: (i, i), a row or column that is not
 // counted, a distance that is refused -- then every wave walks its 32 rows with lane = column: the distance becomes
@@ -697,12 +737,8 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void sil_tile_kernel(const SilP p) 
     __shared__ int rowlab[BM];
     __shared__ float rowsq[BM];
 
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int wm0 = wave * 32;
-    const int bm0 = blockIdx.x * BM;
-    const int chunk = blockIdx.y;
-    const int ct0 = (int)((long)chunk * p.ct / p.chunks), ct1 = (int)((long)(chunk + 1) * p.ct / p.chunks);
+    const KnnBlock g(p.ct, p.chunks);
+    const int t = g.t, lane = g.lane, wm0 = g.wm0, bm0 = g.bm0;
     const int N = p.A.rows;
 
     const int e = sil_bound_exp(p.ctrl[0], p.metric);
@@ -726,9 +762,9 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void sil_tile_kernel(const SilP p) 
     st.point(p.A, p.A);
     st.rows_a(p.A, bm0, t);      // the row offsets of the 128 A rows: once per workgroup
 
-    for (int ctile = ct0; ctile < ct1; ++ctile) {
+    for (int ctile = g.ct0; ctile < g.ct1; ++ctile) {
         const int bn0 = ctile * BN;
-        const int par = (ctile - ct0) & 1;
+        const int par = (ctile - g.ct0) & 1;
         if (t < BN) {
             const int gj = bn0 + t;
             int l = -1;
@@ -744,11 +780,11 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void sil_tile_kernel(const SilP p) 
             const int len = p.D - k0 < SIL_SEG ? p.D - k0 : SIL_SEG;
             st.point(seg, seg);
             if (k0 == 0) {
-                knn_tile_dots<FAST>(st, seg, bm0, seg, bn0, len, lds, t, acc);  // its barriers publish collab (and rowlab, rowsq)
+                knn_tile_dots<FAST>(st, g, seg, seg, bn0, len, lds, acc);      // its barriers publish collab (and rowlab, rowsq)
             } else {
                 f32x16 part[2];
                 __syncthreads();                                            // every wave is past its reads of the LDS tiles
-                knn_tile_dots<FAST>(st, seg, bm0, seg, bn0, len, lds, t, part);
+                knn_tile_dots<FAST>(st, g, seg, seg, bn0, len, lds, part);
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -756,26 +792,23 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void sil_tile_kernel(const SilP p) 
             }
         }
 
-        // accumulator register v of tile j: row (v & 3) + 8 (v >> 2) + 4h, column 32j + r
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = j * 32 + r, gj = bn0 + col;
-            const bool colok = collab[par][col] >= 0;
-            const float sj = colok ? p.sq[gj] : 0.f;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int row = wm0 + (v & 3) + 8 * (v >> 2) + 4 * h, gi = bm0 + row;
+        struct Column { bool ok; float sq; };
+        knn_tile_walk(
+            g, bn0, acc,
+            [&](int col, int gj) {
+                const bool ok = collab[par][col] >= 0;
+                return Column{ok, ok ? p.sq[gj] : 0.f};
+            },
+            [&](float dot, const KnnPair& c, const Column& cj) {
                 float d = 0.f;
-                if (colok && rowlab[row] >= 0 && gi != gj) {
-                    const float si = rowsq[row];
-                    d = knn_distance(acc[j][v], si, sj, p.metric);
+                if (cj.ok && rowlab[c.row] >= 0 && c.gi != c.gj) {
+                    const float si = rowsq[c.row];
+                    d = knn_distance(dot, si, cj.sq, p.metric);
                     // a pair without a distance is NaN (knn_distance) and fails d < bound; the norms are tested as well
-                    if (!(si < INFINITY && sj < INFINITY && d < bound)) { ++refused; d = 0.f; }
+                    if (!(si < INFINITY && cj.sq < INFINITY && d < bound)) { ++refused; d = 0.f; }
                 }
-                sd[row][col] = d;
-            }
-        }
-        __syncthreads();        // also: every wave is past its last MFMA read of the LDS tiles before the next tile's stores
+                sd[c.row][c.col] = d;
+            });
 
         const int lab = collab[par][lane];
         const int prev = __shfl_up(lab, 1, 64);
@@ -1019,16 +1052,12 @@ __device__ __forceinline__ bool dbscan_row_ok(float s, int metric) {
     return metric == VSOM_DIST_EUCLIDEAN ? s + s < INFINITY : s < INFINITY;
 }
 
-struct NeighP {
-    KnnOperand A;
-    int D, metric;
+struct NeighP : SelfP {
     double eps;
-    const float* sq;
     unsigned long long* adj;    // [N][ct]
-    int ct, chunks;
 };
 
-// One workgroup = 128 rows x one chunk of column tiles, built like knn_rank_tile_kernel.  Per 64-column tile: the 128 x 64
+// One workgroup = 128 rows x one chunk of column tiles (KnnBlock).  Per 64-column tile: the 128 x 64
 // block of A A^T (knn_tile_dots), the distances into LDS -- NaN for a column outside the set and for a pair with a bad
 // row, 0 for a good row against itself -- then every wave ballots (double)d <= eps over each of its 32 rows with
 // lane = column; lane rr keeps row rr's word and stores it as adj[row][tile].  NaN is below nothing: its bit is clear.
@@ -1038,41 +1067,33 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void dbscan_tile_kernel(const Neigh
     __shared__ __attribute__((aligned(16))) float lds[(BM + BN) * 36];
     __shared__ float sd[BM][BN + 1];
 
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int wm0 = wave * 32;
-    const int bm0 = blockIdx.x * BM;
-    const int chunk = blockIdx.y;
-    const int ct0 = (int)((long)chunk * p.ct / p.chunks), ct1 = (int)((long)(chunk + 1) * p.ct / p.chunks);
+    const KnnBlock g(p.ct, p.chunks);
+    const int lane = g.lane, wm0 = g.wm0, bm0 = g.bm0;
     const int N = p.A.rows;
 
     KnnStage<FAST> st;
     st.point(p.A, p.A);
-    st.rows_a(p.A, bm0, t);
+    st.rows_a(p.A, bm0, g.t);
 
-    for (int ctile = ct0; ctile < ct1; ++ctile) {
+    for (int ctile = g.ct0; ctile < g.ct1; ++ctile) {
         const int bn0 = ctile * BN;
         f32x16 acc[2];
-        knn_tile_dots<FAST>(st, p.A, bm0, p.A, bn0, p.D, lds, t, acc);
-
-        // accumulator register v of tile j: row (v & 3) + 8 (v >> 2) + 4h, column 32j + r
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = j * 32 + r, gj = bn0 + col;
-            const float sj = gj < N ? p.sq[gj] : __builtin_nanf("");
-            const bool okj = dbscan_row_ok(sj, p.metric);               // false for a column outside the set
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int row = wm0 + (v & 3) + 8 * (v >> 2) + 4 * h, gi = bm0 + row;
+        knn_tile_dots<FAST>(st, g, p.A, p.A, bn0, p.D, lds, acc);
+        struct Column { float sq; bool ok; };
+        knn_tile_walk(
+            g, bn0, acc,
+            [&](int, int gj) {
+                const float sj = gj < N ? p.sq[gj] : __builtin_nanf("");
+                return Column{sj, dbscan_row_ok(sj, p.metric)};         // not ok: also a column outside the set
+            },
+            [&](float dot, const KnnPair& c, const Column& cj) {
                 float d = __builtin_nanf("");
-                if (gi < N && okj) {
-                    const float si = p.sq[gi];
-                    if (dbscan_row_ok(si, p.metric)) d = gi == gj ? 0.f : knn_distance(acc[j][v], si, sj, p.metric);
+                if (c.gi < N && cj.ok) {
+                    const float si = p.sq[c.gi];
+                    if (dbscan_row_ok(si, p.metric)) d = c.gi == c.gj ? 0.f : knn_distance(dot, si, cj.sq, p.metric);
                 }
-                sd[row][col] = d;
-            }
-        }
-        __syncthreads();        // also: every wave is past its last MFMA read of the LDS tiles before the next tile's stores
+                sd[c.row][c.col] = d;
+            });
         unsigned long long word = 0;
 #pragma unroll
         for (int rr = 0; rr < 32; ++rr) {
@@ -1322,19 +1343,15 @@ __device__ __forceinline__ unsigned long long hdb_key(float w, int j) {
     return (unsigned long long)(__float_as_uint(w) & 0x7fffffffu) << 32 | (unsigned)j;      // the mask: -0 orders as 0
 }
 
-struct HdbP {
-    KnnOperand A;
-    int D, metric;
-    const float* sq;
+struct HdbP : SelfP {
     const float* core;
     const int* comp;
     unsigned long long* best;   // [N], all-ones on entry
-    int ct, chunks;
 };
 
-// One workgroup = 128 rows x one chunk of column tiles, built like dbscan_tile_kernel up to the tile of dot products.  The
-// epilogue needs no LDS: a lane of the accumulators holds columns r and 32 + r of 16 rows (register v: row (v & 3) +
-// 8 (v >> 2) + 4h), so lane = column, and it keeps those 16 rows' squared norms, core distances, components and running
+// One workgroup = 128 rows x one chunk of column tiles (KnnBlock).  The
+// epilogue needs no LDS: a lane of the accumulators holds columns r and 32 + r of 16 rows (register v: KnnBlock::row(v)),
+// so lane = column, and it keeps those 16 rows' squared norms, core distances, components and running
 // best (w, j) in registers over the whole chunk.  A lane meets its columns in ascending order, so w < best keeps the
 // lowest column among equals.  At the end of the chunk the 32 lanes of a half fold their keys with an integer minimum
 // and one 64-bit atomicMin per (row, chunk) leaves the workgroup.  A row or column outside the set or without a distance
@@ -1344,19 +1361,15 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void hdb_tile_kernel(const HdbP p) 
     constexpr int BM = KNN_BM, BN = KNN_BN;
     __shared__ __attribute__((aligned(16))) float lds[(BM + BN) * 36];
 
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int wm0 = wave * 32;
-    const int bm0 = blockIdx.x * BM;
-    const int chunk = blockIdx.y;
-    const int ct0 = (int)((long)chunk * p.ct / p.chunks), ct1 = (int)((long)(chunk + 1) * p.ct / p.chunks);
+    const KnnBlock g(p.ct, p.chunks);
+    const int r = g.r, bm0 = g.bm0;
     const int N = p.A.rows;
 
     float rsq[16], rcore[16], bw[16];
     int rcomp[16], bj[16];                                           // rcomp -1: a row that offers nothing
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
-        const int gi = bm0 + wm0 + (v & 3) + 8 * (v >> 2) + 4 * h;
+        const int gi = bm0 + g.row(v);
         const bool in = gi < N;
         rsq[v] = in ? p.sq[gi] : 0.f;
         rcore[v] = in ? p.core[gi] : 0.f;
@@ -1367,29 +1380,28 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void hdb_tile_kernel(const HdbP p) 
 
     KnnStage<FAST> st;
     st.point(p.A, p.A);
-    st.rows_a(p.A, bm0, t);
+    st.rows_a(p.A, bm0, g.t);
 
-    for (int ctile = ct0; ctile < ct1; ++ctile) {
+    for (int ctile = g.ct0; ctile < g.ct1; ++ctile) {
         const int bn0 = ctile * BN;
         f32x16 acc[2];
-        knn_tile_dots<FAST>(st, p.A, bm0, p.A, bn0, p.D, lds, t, acc);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            // no LDS staging of the tile's comp / core values: one lane owns one column of the accumulator, so each of the 64
-            // values is loaded by exactly the lane that uses it, once per tile, coalesced
-            const int gj = bn0 + j * 32 + r;
-            const bool in = gj < N;
-            const float sj = in ? p.sq[gj] : 0.f;
-            const float cj = in ? p.core[gj] : 0.f;
-            const int mj = in && dbscan_row_ok(sj, p.metric) ? p.comp[gj] : -1;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const float d = knn_distance(acc[j][v], rsq[v], sj, p.metric);
-                const float w = fmaxf(fmaxf(rcore[v], cj), d);
-                if (rcomp[v] >= 0 && mj >= 0 && mj != rcomp[v] && d == d && w < bw[v]) { bw[v] = w; bj[v] = gj; }
-            }
-        }
-        __syncthreads();        // every wave is past its last MFMA read of the LDS tiles before the next tile's stores
+        knn_tile_dots<FAST>(st, g, p.A, p.A, bn0, p.D, lds, acc);
+        // no LDS staging of the tile's comp / core values: one lane owns one column of the accumulator, so each of the 64
+        // values is loaded by exactly the lane that uses it, once per tile, coalesced
+        struct Column { float sq, core; int comp; };
+        knn_tile_walk(
+            g, bn0, acc,
+            [&](int, int gj) {
+                const bool in = gj < N;
+                const float sj = in ? p.sq[gj] : 0.f;
+                return Column{sj, in ? p.core[gj] : 0.f, in && dbscan_row_ok(sj, p.metric) ? p.comp[gj] : -1};
+            },
+            [&](float dot, const KnnPair& c, const Column& cj) {
+                const int v = c.v;
+                const float d = knn_distance(dot, rsq[v], cj.sq, p.metric);
+                const float w = fmaxf(fmaxf(rcore[v], cj.core), d);
+                if (rcomp[v] >= 0 && cj.comp >= 0 && cj.comp != rcomp[v] && d == d && w < bw[v]) { bw[v] = w; bj[v] = c.gj; }
+            });
     }
 
     unsigned long long mine = HDB_NONE;
@@ -1403,7 +1415,7 @@ __global__ __launch_bounds__(KNN_THREADS, 2) void hdb_tile_kernel(const HdbP p) 
         }
         if (r == v) mine = key;
     }
-    const int gi = bm0 + wm0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+    const int gi = bm0 + g.row(r);                                  // lane r < 16 of a half took register r's key
     if (r < 16 && gi < N && mine != HDB_NONE) atomicMin(&p.best[gi], mine);
 }
 
@@ -1645,9 +1657,7 @@ int vsom_knn_ranks(const float* A, long lda, long N, int D, int metric, const in
     VSOM_REQUIRE(ws && aligned16(ws) && ws_bytes >= vsom_knn_ranks_workspace_bytes(N, k), VSOM_EWORKSPACE,
                  "knn_ranks: workspace too small or misaligned");
     const RankWs w = rank_layout(ws, N, k);
-    const QueryPlan pl = query_plan(N, N);
     const bool vec = knn_self_vec(A, lda, D);
-    const size_t ext = (size_t)N * lda * 4;
     VSOM_LAUNCH(knn_sqnorm_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, A, lda, N, D, w.sq);
     const dim3 slots((unsigned)(((size_t)N * k + 255) / 256));
     if (vec)
@@ -1657,12 +1667,8 @@ int vsom_knn_ranks(const float* A, long lda, long N, int D, int metric, const in
         VSOM_LAUNCH(knn_rank_threshold_kernel<false>, slots, dim3(256), 0, stream, A, lda, N, D, k, metric, nbr,
                     (const float*)w.sq, w.slot, less, tied);
     RankP p = {};
-    p.A = {A, lda, (int)N, (unsigned)ext, vec};
-    p.D = D; p.k = k; p.metric = metric; p.sq = w.sq; p.slot = w.slot; p.less = less; p.tied = tied;
-    p.ct = pl.ct; p.chunks = pl.chunks;
-    const dim3 grid(pl.rb, pl.chunks), block(KNN_THREADS);
-    if (vec && ext < (size_t)OOB - 256) VSOM_LAUNCH(knn_rank_tile_kernel<true>, grid, block, 0, stream, p);
-    else VSOM_LAUNCH(knn_rank_tile_kernel<false>, grid, block, 0, stream, p);
+    p.k = k; p.slot = w.slot; p.less = less; p.tied = tied;
+    knn_self_launch<RankP, knn_rank_tile_kernel<true>, knn_rank_tile_kernel<false>>(p, A, lda, N, D, metric, w.sq, vec, stream);
     return launch_status("knn_ranks");
 }
 
@@ -1685,9 +1691,7 @@ int vsom_silhouette(const float* X, long ldx, long N, int D, int metric, const i
     VSOM_REQUIRE(ws && aligned16(ws) && ws_bytes >= vsom_silhouette_workspace_bytes(N, n_clusters), VSOM_EWORKSPACE,
                  "silhouette: workspace too small or misaligned");
     const SilWs w = sil_layout(ws, N, n_clusters);
-    const QueryPlan pl = query_plan(N, N);
     const bool vec = D % 4 == 0 && ldx % 4 == 0 && aligned16(X);
-    const size_t ext = (size_t)N * ldx * 4;
     unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
     unsigned long long* stat = reinterpret_cast<unsigned long long*>(status);
     const size_t clear_blocks = (w.clear_words + 255) / 256;
@@ -1697,12 +1701,8 @@ int vsom_silhouette(const float* X, long ldx, long N, int D, int metric, const i
     VSOM_LAUNCH(sil_prepare_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, labels, (const float*)w.sq, N, n_clusters, cnt, w.ctrl,
                 stat);
     SilP p = {};
-    p.A = {X, ldx, (int)N, (unsigned)ext, vec};
-    p.D = D; p.metric = metric; p.C = n_clusters; p.sq = w.sq; p.labels = labels; p.ctrl = w.ctrl; p.S = w.S; p.status = stat;
-    p.ct = pl.ct; p.chunks = pl.chunks;
-    const dim3 grid(pl.rb, pl.chunks), block(KNN_THREADS);
-    if (vec && ext < (size_t)OOB - 256) VSOM_LAUNCH(sil_tile_kernel<true>, grid, block, 0, stream, p);
-    else VSOM_LAUNCH(sil_tile_kernel<false>, grid, block, 0, stream, p);
+    p.C = n_clusters; p.labels = labels; p.ctrl = w.ctrl; p.S = w.S; p.status = stat;
+    knn_self_launch<SilP, sil_tile_kernel<true>, sil_tile_kernel<false>>(p, X, ldx, N, D, metric, w.sq, vec, stream);
     const SilOut out = {sil, a, b, nearest};
     VSOM_LAUNCH(sil_finish_kernel, dim3(cdiv(N, SIL_ROWS)), dim3(SIL_ROWS * 64), 0, stream, (const unsigned long long*)w.S,
                 (const unsigned long long*)cnt, labels, N, n_clusters, (const unsigned*)w.ctrl, metric, out, w.acc);
@@ -1742,17 +1742,12 @@ int vsom_dbscan_neighbours(const float* X, long ldx, long N, int D, int metric, 
                  DBSCAN_MAX_N);
     VSOM_REQUIRE(metric == VSOM_DIST_EUCLIDEAN || metric == VSOM_DIST_COSINE, VSOM_EUNSUPPORTED,
                  "dbscan_neighbours: metric %d (euclidean or cosine only)", metric);
-    const QueryPlan pl = query_plan(N, N);
     const bool vec = knn_self_vec(X, ldx, D);
-    const size_t ext = (size_t)N * ldx * 4;
     VSOM_LAUNCH(knn_sqnorm_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, X, ldx, N, D, sq);
     NeighP p = {};
-    p.A = {X, ldx, (int)N, (unsigned)ext, vec};
-    p.D = D; p.metric = metric; p.eps = eps; p.sq = sq; p.adj = reinterpret_cast<unsigned long long*>(adj);
-    p.ct = pl.ct; p.chunks = pl.chunks;
-    const dim3 grid(pl.rb, pl.chunks), block(KNN_THREADS);
-    if (vec && ext < (size_t)OOB - 256) VSOM_LAUNCH(dbscan_tile_kernel<true>, grid, block, 0, stream, p);
-    else VSOM_LAUNCH(dbscan_tile_kernel<false>, grid, block, 0, stream, p);
+    p.eps = eps; p.adj = reinterpret_cast<unsigned long long*>(adj);
+    const QueryPlan pl =
+        knn_self_launch<NeighP, dbscan_tile_kernel<true>, dbscan_tile_kernel<false>>(p, X, ldx, N, D, metric, sq, vec, stream);
     VSOM_LAUNCH(dbscan_count_kernel, dim3(cdiv(N, DBSCAN_ROWS)), dim3(DBSCAN_ROWS * 64), 0, stream,
                 (const unsigned long long*)p.adj, (int)N, pl.ct, count);
     VSOM_LAUNCH(dbscan_status_kernel, dim3(1), dim3(DBSCAN_SCAN), 0, stream, (const int*)count, (int)N, 1, status);
@@ -1839,20 +1834,14 @@ int vsom_hdbscan_nearest(const float* X, long ldx, long N, int D, int metric, co
     VSOM_REQUIRE(N <= DBSCAN_MAX_N, VSOM_EUNSUPPORTED, "hdbscan_nearest: N=%ld > %ld", N, DBSCAN_MAX_N);
     VSOM_REQUIRE(metric == VSOM_DIST_EUCLIDEAN || metric == VSOM_DIST_COSINE, VSOM_EUNSUPPORTED,
                  "hdbscan_nearest: metric %d (euclidean or cosine only)", metric);
-    const QueryPlan pl = query_plan(N, N);
     const bool vec = knn_self_vec(X, ldx, D);
-    const size_t ext = (size_t)N * ldx * 4;
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(best);
     VSOM_LAUNCH(knn_sqnorm_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, X, ldx, N, D, sq);
     VSOM_LAUNCH(hdb_clear_best_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, keys, (int)N);
     VSOM_LAUNCH(hdb_bad_rows_kernel, dim3(1), dim3(DBSCAN_SCAN), 0, stream, (const float*)sq, core, (int)N, metric, record);
     HdbP p = {};
-    p.A = {X, ldx, (int)N, (unsigned)ext, vec};
-    p.D = D; p.metric = metric; p.sq = sq; p.core = core; p.comp = comp; p.best = keys;
-    p.ct = pl.ct; p.chunks = pl.chunks;
-    const dim3 grid(pl.rb, pl.chunks), block(KNN_THREADS);
-    if (vec && ext < (size_t)OOB - 256) VSOM_LAUNCH(hdb_tile_kernel<true>, grid, block, 0, stream, p);
-    else VSOM_LAUNCH(hdb_tile_kernel<false>, grid, block, 0, stream, p);
+    p.core = core; p.comp = comp; p.best = keys;
+    knn_self_launch<HdbP, hdb_tile_kernel<true>, hdb_tile_kernel<false>>(p, X, ldx, N, D, metric, sq, vec, stream);
     return launch_status("hdbscan_nearest");
 }
 
