@@ -44,7 +44,13 @@ const char* vsom_last_error_string(void);
 /* ------------------------------------------------------------------ Linear layers
  * (fp32-accurate on the matrix cores: split-bf16 engine by default, exact-f32 MFMA on request -- vsom_set_gemm_mode) */
 /* Y[M,N] = X[M,K] * W[N,K]^T + bias      -- nn.Linear forward: qkv models/vit.py:30,
- * decoder_pred vit.py:234, cls_head models/vit_som.py:77.  bias may be NULL. */
+ * decoder_pred vit.py:234, cls_head models/vit_som.py:77.  bias may be NULL.
+ * Far pitches.  Every `ld` of this header is 64-bit: outputs, residuals and every operand of a kernel without a 16-byte
+ * path are addressed with plain pointers at any pitch.  The two multiplied operands of a GEMM -- here and in
+ * vsom_linear_gelu_fwd, vsom_linear_relu_fwd, vsom_linear_residual_fwd, vsom_linear_bwd_input, vsom_linear_bwd_input_t,
+ * vsom_linear_bwd_weight, vsom_patch_embed_fwd, vsom_som_bwd, vsom_bmu_cosine_dots, vsom_bmu_cosine_fwd and
+ * vsom_bmu_euclid_fwd -- are buffer resources with 32-bit byte offsets on the 16-byte path: operands of 4 GB or more take
+ * the element-wise loads (from 0xFFFF0000 bytes, counted from the base to the end of the last row), without an error. */
 int vsom_linear_fwd(const float* X, long ldx, const float* W, const float* bias, float* Y, long ldy,
                     int M, int N, int K, vsom_stream_t stream);
 
@@ -194,7 +200,9 @@ int vsom_layernorm_bwd_finish_many(const int64_t* jobs_dev, int first, int count
  * part_bytes_query / (8 K)).  Supported (vsom_linear_bwd_input_ln_supported != 0): the split-bf16 GEMM modes, K = 192 or
  * 96, enough row tiles for the column reducer; otherwise VSOM_EUNSUPPORTED and the caller takes the two-launch path.
  * vsom_linear_bwd_input_ln and vsom_linear_bwd_input_ln_partial alike: dY, Wt, X, gamma, resid and dX 16-byte aligned,
- * lddy % 4 == 0 and N % 4 == 0 (VSOM_EALIGN otherwise: there is no element-wise form); X / resid / dX dense [M, K]. */
+ * lddy % 4 == 0 and N % 4 == 0 (VSOM_EALIGN otherwise: there is no element-wise form); X / resid / dX dense [M, K]; dY
+ * (from its base to the end of its last row, at pitch lddy) and X below 4 GB (0xFFFF0000 bytes), VSOM_EUNSUPPORTED
+ * otherwise, for the same reason. */
 int vsom_linear_bwd_input_ln_supported(int M, int N, int K);
 size_t vsom_linear_bwd_input_ln_partial_bytes(int M, int K);
 int vsom_linear_bwd_input_ln(const float* dY, long lddy, const float* Wt, int M, int N, int K, const float* X,
@@ -489,7 +497,7 @@ int vsom_kmeans_colvar(const float* X, long ldx, long N, int D, int k, double* o
  * 1 - <x,y> / (|x| |y|) clamped at 0, 0 when both rows are zero and 1 when exactly one is.  <x,y> is an f32 matrix-core
  * contraction; the squared norms are summed in its order, so identical rows are at distance exactly 0.
  * This is the search of vsom_knn_query with the set as its own bank (one kernel, csrc/knn.hip); only here is row i put
- * first.
+ * first.  Rows are loaded under the conditions of vsom_knn_query: operands of 4 GB or more take the element-wise loads.
  * 1 <= k <= 64, k < N.  Workspace: vsom_umap_knn_workspace_bytes(N, k) (host arithmetic; 0 for a non-positive size): the
  * N squared norms and two candidate slabs (f32 distances, i32 rows) of chunks * rb * 128 * k entries each, rb =
  * ceil(N / 128) row blocks and chunks = min(ceil(N / 64), ceil(2048 / rb)) column chunks, every section rounded up to
@@ -567,7 +575,8 @@ int vsom_umap_transform_layout(const int64_t* knn_idx, const double* weights, co
  * exclude (may be NULL): exclude[i] is a global bank ordinal that query i never receives (leave-one-out when queries
  * and bank are the same set).
  * 1 <= k <= 64 (more: VSOM_EUNSUPPORTED); 1 <= Nq, Nb <= 2^31 - 129; ldq, ldx >= D >= 1; index_base >= 0.  Rows are
- * loaded 16 bytes per lane when D % 4 == 0 and both pointers and strides are 16-byte aligned, element-wise otherwise.
+ * loaded 16 bytes per lane when D % 4 == 0 and both pointers and strides are 16-byte aligned, element-wise otherwise;
+ * operands of 4 GB or more take the element-wise loads too (rows * ld * 4 bytes from 0xFFFFFFF0 - 256, no error).
  * Workspace: vsom_knn_query_workspace_bytes(Nq, Nb, k) (host arithmetic, monotone in each argument; 0 for a
  * non-positive size); too small or NULL: VSOM_EWORKSPACE. */
 size_t vsom_knn_query_workspace_bytes(long Nq, long Nb, int k);
@@ -589,8 +598,9 @@ int vsom_knn_query(const float* Q, long ldq, long Nq, const float* X, long ldx, 
  * empty one (-1, -1); the host wrapper ops.knn_ranks refuses such a table with ValueError before the call.
  * Both outputs are written in full (no need to clear them).  1 <= k <= 64 (more: VSOM_EUNSUPPORTED), 2 <= N <= 2^31 - 129,
  * lda >= D >= 1, metric as vsom_umap_knn; 16-byte row loads under the conditions of vsom_knn_query, element-wise
- * otherwise.  Workspace: vsom_knn_ranks_workspace_bytes(N, k) (host arithmetic; 0 for a non-positive size): the N squared
- * norms, the N k thresholds and the N k neighbours as int32, each rounded up to 256 bytes. */
+ * otherwise (operands of 4 GB or more take the element-wise loads).  Workspace: vsom_knn_ranks_workspace_bytes(N, k)
+ * (host arithmetic; 0 for a non-positive size): the N squared norms, the N k thresholds and the N k neighbours as int32,
+ * each rounded up to 256 bytes. */
 size_t vsom_knn_ranks_workspace_bytes(long N, int k);
 int vsom_knn_ranks(const float* A, long lda, long N, int D, int metric, const int64_t* nbr, int k, int32_t* less, int32_t* tied,
                    void* ws, size_t ws_bytes, vsom_stream_t stream);
@@ -614,9 +624,10 @@ int vsom_knn_ranks(const float* A, long lda, long N, int D, int metric, const in
  * All integer sums: every output is bitwise reproducible and bit for bit independent of the order of the rows and of the
  * launch's chunking.  a, b, nearest and cluster_mean may be NULL; every output given is written in full (no need to clear
  * it).  2 <= N <= 2^22 - 1 (more: VSOM_EUNSUPPORTED -- a row's sum of N values below 2^40 must stay below 2^63),
- * n_clusters >= 1, ldx >= D >= 1, metric VSOM_DIST_COSINE | VSOM_DIST_EUCLIDEAN; 16-byte row loads under the conditions of
- * vsom_knn_query, element-wise otherwise.  Workspace: vsom_silhouette_workspace_bytes(N, n_clusters) (host arithmetic; 0
- * for a non-positive size), 16-byte aligned; its first N * n_clusters uint64 words are S, left there for the caller. */
+ * n_clusters >= 1, ldx >= D >= 1, metric VSOM_DIST_COSINE | VSOM_DIST_EUCLIDEAN; 16-byte row loads under the conditions
+ * of vsom_knn_query, element-wise otherwise (operands of 4 GB or more take the element-wise loads).  Workspace:
+ * vsom_silhouette_workspace_bytes(N, n_clusters) (host arithmetic; 0 for a non-positive size), 16-byte aligned; its first
+ * N * n_clusters uint64 words are S, left there for the caller. */
 size_t vsom_silhouette_workspace_bytes(long N, int n_clusters);
 int vsom_silhouette(const float* X, long ldx, long N, int D, int metric, const int64_t* labels, int n_clusters, double* sil,
                     double* a, double* b, int64_t* nearest, int64_t* counts, double* cluster_mean, double* score,
@@ -664,11 +675,13 @@ long vsom_pca_slabs(long N, int D, int l, int which);
  * matrix cores (v_mfma_f32_32x32x2_f32), both operands k-contiguous; the mean is subtracted from each X tile between the
  * global load and the LDS store, and only from elements inside the matrix.  The reduction over D is split, per-split
  * slabs are added in split order.  16-byte loads when D % 4 == 0 and X, B, mean and their strides are 16-byte aligned,
- * element-wise otherwise. */
+ * element-wise otherwise; operands of 4 GB or more take the element-wise loads (from 0xFFFF0000 bytes, counted from the
+ * base to the end of the last row; no error).  Y is written through a plain pointer at any pitch. */
 int vsom_pca_project(const float* X, long ldx, long N, int D, const float* mean, const float* B, long ldb, int l,
                      const float* scale, float* Y, long ldy, float* slabs, long n_slabs, vsom_stream_t stream);
 /* Zt [l, D] (row stride ldz) = Y^T (X - mean): the other half of a pass; both operands k-strided (the shape of a weight
- * gradient), the reduction over the N rows split the same way.  16-byte loads additionally want ldy % 4 == 0. */
+ * gradient), the reduction over the N rows split the same way.  16-byte loads additionally want ldy % 4 == 0; operands
+ * of 4 GB or more take the element-wise loads, as in vsom_pca_project. */
 int vsom_pca_backproject(const float* Y, long ldy, const float* X, long ldx, long N, int D, const float* mean, int l, float* Zt,
                          long ldz, float* slabs, long n_slabs, vsom_stream_t stream);
 /* G [l, l] = Zt Zt^T and, when B (and H) are given, H [l, l] = B Zt^T: products and sums in fp64, each entry one
@@ -863,7 +876,9 @@ int vsom_som_weighted_loss(const float* dist, const float* weights, const float*
    approximate one in dist: bmu == argmin(dist) exactly.  K <= 2048; rows 16-byte aligned: X and W 16-byte aligned, L and
    ldx multiples of 4.  vsom_bmu_cosine_x3_dots answers VSOM_EALIGN to anything else (the caller then runs the exact form);
    vsom_bmu_cosine_x3_finalize, whose re-rank reads the rows of X and W 16 bytes at a time, answers VSOM_EALIGN to a
-   misaligned X or W and VSOM_EINVAL to an L or ldx that stage 1 would have refused. */
+   misaligned X or W and VSOM_EINVAL to an L or ldx that stage 1 would have refused.  X (from its base to the end of its last
+   row, at pitch ldx) and W below 4 GB (0xFFFF0000 bytes): stage 1 reads them as buffer resources and has no other form;
+   vsom_bmu_cosine_x3_dots and vsom_bmu_cosine_x3_finalize alike answer VSOM_EUNSUPPORTED to a larger operand. */
 size_t vsom_bmu_cosine_x3_workspace_bytes(int B, int K, int L);
 int vsom_bmu_cosine_x3_dots(const float* X, long ldx, const float* W, int B, int K, int L, void* ws, size_t ws_bytes,
                             vsom_stream_t stream);
@@ -882,7 +897,9 @@ int vsom_bmu_cosine_x3_finalize(const float* X, long ldx, const float* W, const 
    Alignment: vsom_bmu_planes_from wants src 16-byte aligned and ld % 4 == 0 (VSOM_EINVAL otherwise) and, like
    vsom_adamw_step_planes, a 16-byte aligned plane buffer (VSOM_EWORKSPACE); vsom_bmu_cosine_x3_planes_dots refuses a
    misaligned plane buffer with VSOM_EINVAL; vsom_bmu_cosine_x3_planes_finalize reads the rows of X and W 16 bytes at a time
-   in its re-rank: X and W 16-byte aligned (VSOM_EALIGN), ldx % 4 == 0 (VSOM_EINVAL).
+   in its re-rank: X and W 16-byte aligned (VSOM_EALIGN), ldx % 4 == 0 (VSOM_EINVAL), and X and W below 4 GB as for
+   vsom_bmu_cosine_x3_finalize (VSOM_EUNSUPPORTED).  An image of 2 GB or more (it is one buffer resource) is refused by
+   every entry that takes a plane buffer with VSOM_EUNSUPPORTED; the pitch of src has no limit (plain pointers).
    Same reference lines as above (som_layer.py:119-122, 83-89); the AdamW variant replaces vit_som.py:146-151. */
 size_t vsom_bmu_planes_bytes(int R, int L);
 int vsom_bmu_planes_from(const float* src, long ld, int R, int L, void* planes, size_t planes_bytes, vsom_stream_t stream);
@@ -1144,9 +1161,9 @@ int vsom_agglo_merge(void* ws, long ws_size, long N, int linkage, int connectivi
  * with d bit for bit the fp32 distance of vsom_umap_knn between rows i and j of X [N, D] (row stride ldx >= D >= 1;
  * VSOM_DIST_EUCLIDEAN, with the root, or VSOM_DIST_COSINE; another metric: VSOM_EUNSUPPORTED) and eps >= 0 the caller's
  * double.  Rows are loaded 16 bytes per lane when D % 4 == 0, ldx % 4 == 0 and X is 16-byte aligned (the decision of
- * vsom_knn_ranks), element-wise otherwise: the words are the same bits either way.  Writes sq f32 [N] (the squared
- * norms in the contraction's order), adj, count int32 [N] (the set bits of row i, its own among them) and status int64
- * [2]: [0] the bad rows, [1] the set bits of the whole matrix.
+ * vsom_knn_ranks: operands of 4 GB or more take the element-wise loads), element-wise otherwise: the words are the same
+ * bits either way.  Writes sq f32 [N] (the squared norms in the contraction's order), adj, count int32 [N] (the set bits
+ * of row i, its own among them) and status int64 [2]: [0] the bad rows, [1] the set bits of the whole matrix.
  * vsom_dbscan_threshold: the same contract from a precomputed matrix M [N, N], float32 (is_f64 == 0) or float64, row
  * stride ldm >= N in elements: the test is (double)M[i][j] <= eps.  A NaN entry clears its bit; the diagonal is set
  * whatever it holds; the matrix is as symmetric as M is.  status[0] is the number of NaN entries (an integer atomic add),
@@ -1188,8 +1205,9 @@ int vsom_dbscan_finish(const uint64_t* adj, long N, const uint8_t* core, const i
  * packed (fp32 bits of w) << 32 | j, all-ones without one.  d is bit for bit the fp32 distance of vsom_umap_knn between
  * rows of X [N, D] (row stride ldx >= D >= 1; VSOM_DIST_EUCLIDEAN, with the root, or VSOM_DIST_COSINE; another metric:
  * VSOM_EUNSUPPORTED); core (f32 [N]) the caller's core distances.  Rows are loaded 16 bytes per lane under the decision of
- * vsom_knn_ranks, element-wise otherwise: the same bits.  Writes sq f32 [N] (the squared norms) and record[2]: the rows
- * with a NaN, an infinity, an overflowing norm or a core distance that is not finite; such a row offers and receives nothing.
+ * vsom_knn_ranks (operands of 4 GB or more take the element-wise loads), element-wise otherwise: the same bits.  Writes sq
+ * f32 [N] (the squared norms) and record[2]: the rows with a NaN, an infinity, an overflowing norm or a core distance that
+ * is not finite; such a row offers and receives nothing.
  * vsom_hdbscan_nearest_matrix: the same from a precomputed matrix M [N, N], float32 (is_f64 == 0) or float64, row stride
  * ldm >= N in elements: w = max(core[i], core[j], (float)M[i][j]), the fp32 rounding of the maximum.  An entry off the
  * diagonal that is not finite as fp32 offers nothing and is counted in record[2].

@@ -44,6 +44,9 @@ vsom_bmu_cosine_x3_planes_finalize alone (the stage before it sees only the plan
 pointers is what keeps a shifted view from the re-rank's 16-byte loads.
 
 Looked at and left out: LEFT_OUT below, each with its reason.
+
+Far pitches -- a last row 2 GiB, 4 GiB or 2^31 elements from the base -- are the subject of tests/far_pitch.py, which reuses
+these rows for every operand marked `ld=True`.
 """
 import functools
 import math

@@ -16,6 +16,9 @@ The arena of one buffer is  [front guard | payload | back guard]:
 
 The back guard is max(1 MiB, payload bytes): 1 MiB is the floor of `ops.scratch`, so an overrun that lands silently inside the
 shared scratch in the rest of the suite lands inside the test's own arena here.  The front guard is 64 KiB.
+
+`guarded_far` is the sibling for row pitches of gigabytes (tests/far_pitch.py): a back guard of 1 MiB, a front guard of the
+caller's choice, and a `check()` that reads the arena in place, piece by piece (GuardedFar below).
 """
 import torch
 
@@ -138,6 +141,162 @@ def guarded_copy(t, ld=None, front=FRONT_GUARD, back=None, shift=0):
     v, h = guarded(t.shape, t.dtype, t.device, ld=ld, front=front, back=back, shift=shift)
     v.copy_(t)
     return v, h
+
+
+FAR_BACK = 1 << 20
+FAR_PIECE = 64 << 20                     # 32-bit words per piece of GuardedFar.check: 256 MiB read, a 64 MiB mask, one count
+
+
+class GuardedFar:
+    """`Guarded` for a 2-D payload whose row pitch is gigabytes (tests/far_pitch.py): [front guard | row 0 | gap | row 1 | ...
+    | back guard], the first element on a 256-byte boundary.  The arena is filled with GUARD_WORD by one fill; only the
+    payload rows are touched afterwards (the poison, or an input's values).  The back guard is 1 MiB, not the payload's
+    extent, and `check()` reads the arena where it lies, FAR_PIECE words at a time: no clone, no copy to the host beyond one
+    count per piece, and a 64 MiB mask as its only temporary (the far-pitch tests allow themselves 1 GiB).
+
+    `front` is at least FRONT_GUARD.  The far-pitch table asks for more: an offset that a kernel truncated to 32 bits lands
+    inside the arena by construction; one it sign-extended from 32 bits lands up to 2 GiB (a byte offset) or up to
+    2^31 elements (an element index) in front of the base, and the front guard is sized to hold it."""
+
+    def __init__(self, rows, cols, dtype, device, ld, front=FRONT_GUARD, poison=True, backing=None):
+        rows, cols, ld, front = int(rows), int(cols), int(ld), int(front)
+        size = _itemsize(dtype)
+        assert rows >= 1 and cols >= 1 and ld >= cols and size in (4, 8), (rows, cols, ld, dtype)
+        assert front >= FRONT_GUARD and front % ALIGN == 0
+        self.shape, self.dtype, self.device = (rows, cols), dtype, torch.device(device)
+        self.rows, self.cols, self.ld, self.size = rows, cols, ld, size
+        self.front, self.back, self.shift = front, FAR_BACK, 0
+        self.nbytes = ((rows - 1) * ld + cols) * size
+        total = front + self.nbytes + self.back
+        n_words = (total + ALIGN + 3) // 4
+        if backing is None:
+            self.words = torch.full((n_words,), GUARD_WORD, dtype=torch.int32, device=device)
+        else:                            # the caller's memory (an int32 tensor it reuses from arena to arena): the same one fill
+            assert backing.dtype == torch.int32 and backing.dim() == 1 and backing.numel() >= n_words and backing.device.type == self.device.type
+            self.words = backing[:n_words]
+            self.words.fill_(GUARD_WORD)
+        self.arena = self.words.view(torch.uint8)
+        self.off = front + (-(self.arena.data_ptr() + front)) % ALIGN
+        self.view = self.arena[self.off:self.off + self.nbytes].view(dtype).as_strided((rows, cols), (ld, 1))
+        assert self.view.data_ptr() % ALIGN == 0
+        if poison:
+            self._int_view().fill_(_POISON[dtype][1])
+
+    def arena_bytes(self):
+        return self.arena.numel()
+
+    def _int_view(self):
+        idt, _ = _POISON[self.dtype]
+        return self.view if idt == self.dtype else self.view.view(idt)
+
+    def _row_words(self, r):
+        """[lo, hi): the 32-bit words of the arena that payload row r occupies."""
+        lo = (self.off + r * self.ld * self.size) // 4
+        return lo, lo + self.cols * self.size // 4
+
+    def _where(self, word):
+        byte = word * 4 - self.off
+        if byte < 0:
+            return byte, "the front guard"
+        if byte >= self.nbytes:
+            return byte, "the back guard"
+        return byte, f"the gap after row {byte // (self.ld * self.size)}"
+
+    def check(self, what="buffer", piece=FAR_PIECE):
+        """Every byte in front of, between and behind the payload rows is as it was made; else names the first damaged byte
+        offset relative to the start of the payload (negative: in the front guard)."""
+        n = self.words.numel()
+        pitch = self.ld * self.size // 4
+        first_row_word = self.off // 4
+        counts, pieces = [], []
+        for s in range(0, n, piece):
+            e = min(n, s + piece)
+            bad = self.words[s:e] != GUARD_WORD
+            # the payload rows that meet [s, e)
+            r0 = max(0, (s - first_row_word - self.cols * self.size // 4) // pitch)
+            for r in range(r0, self.rows):
+                lo, hi = self._row_words(r)
+                if lo >= e:
+                    break
+                if hi > s:
+                    bad[max(lo, s) - s:min(hi, e) - s] = False
+            counts.append(bad.sum())
+            pieces.append(s)
+            del bad
+        counts = torch.stack(counts).cpu()
+        total = int(counts.sum())
+        if total:
+            s = pieces[int(counts.nonzero()[0])]
+            e = min(n, s + piece)
+            bad = self.words[s:e] != GUARD_WORD
+            for r in range(self.rows):
+                lo, hi = self._row_words(r)
+                if hi > s and lo < e:
+                    bad[max(lo, s) - s:min(hi, e) - s] = False
+            word = s + int(bad.nonzero()[0])
+            byte, where = self._where(word)
+            # the damaged word's first differing byte
+            got = self.arena[word * 4:word * 4 + 4].cpu()
+            want = torch.tensor([GUARD_WORD], dtype=torch.int32).view(torch.uint8)
+            byte += int((got != want).nonzero()[0])
+            raise AssertionError(f"{what}: {total} guard words damaged, the first at byte offset {byte} from the payload start "
+                                 f"({where}; payload extent {self.nbytes} bytes, shape {self.shape}, ld {self.ld}, {self.dtype})")
+
+    def all_written(self, what="buffer"):
+        """No element of the payload rows still holds the poison."""
+        _, val = _POISON[self.dtype]
+        left = (self._int_view() == val).reshape(-1).nonzero()
+        if left.numel():
+            i = int(left[0])
+            raise AssertionError(f"{what}: {left.numel()} of {self.rows * self.cols} elements were never written, the first at "
+                                 f"flat index {i} (row {i // self.cols}, column {i % self.cols}; shape {self.shape}, ld {self.ld}, "
+                                 f"{self.dtype})")
+
+    def untouched(self):
+        """Every element of the payload rows still holds the poison (a refused call's outputs)."""
+        return bool((self._int_view() == _POISON[self.dtype][1]).all())
+
+
+class FarColumns:
+    """Columns [c0, c1) of a GuardedFar payload as an operand of their own: blocks that share one `ld` parameter are column
+    slices of one wide matrix, each row [block 0 | block 1 | ...] and then the gap.  `check()` is the arena's (every block
+    of the row is payload, whoever writes it); `all_written()` and `untouched()` look at this block's columns only."""
+
+    def __init__(self, parent, c0, c1):
+        assert 0 <= c0 < c1 <= parent.cols
+        self.parent, self.c0, self.c1 = parent, c0, c1
+        self.view = parent.view[:, c0:c1]
+        self.dtype, self.shape = parent.dtype, (parent.rows, c1 - c0)
+
+    def _int_view(self):
+        return self.parent._int_view()[:, self.c0:self.c1]
+
+    def check(self, what="buffer", piece=FAR_PIECE):
+        self.parent.check(what, piece=piece)
+
+    def all_written(self, what="buffer"):
+        left = (self._int_view() == _POISON[self.dtype][1]).reshape(-1).nonzero()
+        if left.numel():
+            i, cols = int(left[0]), self.c1 - self.c0
+            raise AssertionError(f"{what}: {left.numel()} of {self.parent.rows * cols} elements were never written, the first at "
+                                 f"flat index {i} (row {i // cols}, column {i % cols} of columns [{self.c0}, {self.c1}); ld "
+                                 f"{self.parent.ld}, {self.dtype})")
+
+    def untouched(self):
+        return bool((self._int_view() == _POISON[self.dtype][1]).all())
+
+
+def guarded_far(shape, dtype, device, ld, front=FRONT_GUARD, backing=None):
+    """-> (view, handle): a poisoned [rows, cols] tensor at the far row pitch `ld`."""
+    h = GuardedFar(shape[0], shape[1], dtype, device, ld, front=front, backing=backing)
+    return h.view, h
+
+
+def guarded_far_copy(t, ld, front=FRONT_GUARD, backing=None):
+    """-> (view, handle): the values of the 2-D tensor `t` at the far row pitch `ld`, GUARD_WORD everywhere else."""
+    h = GuardedFar(t.shape[0], t.shape[1], t.dtype, t.device, ld, front=front, poison=False, backing=backing)
+    h.view.copy_(t)
+    return h.view, h
 
 
 class ExactScratch:

@@ -696,6 +696,17 @@ size_t vsom_bmu_cosine_x3_workspace_bytes(int B, int K, int L) {
     return bmu_form_plan(VSOM_BMU_X3, B, K, L).ws_bytes;
 }
 
+// The family's operands are single buffer resources in stage 1 (bmu_x3_kernel): X (to the end of its last row) and W below
+// 4 GB.  Stage 2 reads plain pointers, but finalizes only what a stage 1 of the same operands could have left, so all
+// entries of the family hold to the one rule.
+static long x3_x_bytes(int B, int L, long ldx) { return ((long)(B - 1) * ldx + L) * 4; }
+static long x3_w_bytes(int K, int L) { return (long)K * L * 4; }
+static int x3_operands_fit(const char* who, int B, int K, int L, long ldx) {
+    const long xb = x3_x_bytes(B, L, ldx), wb = x3_w_bytes(K, L);
+    VSOM_REQUIRE(xb < 0xFFFF0000L && wb < 0xFFFF0000L, VSOM_EUNSUPPORTED, "%s: operand larger than 4 GB", who);
+    return VSOM_OK;
+}
+
 // the in-loop form's workspace: slabs, then the squared-norm partials of X and of W
 static void x3_layout(const BmuPlan& p, int B, int K, void* ws, BmuP& g) {
     float* f = static_cast<float*>(ws);
@@ -712,13 +723,12 @@ int vsom_bmu_cosine_x3_dots(const float* X, long ldx, const float* W, int B, int
     VSOM_REQUIRE(p.x3_status != VSOM_EUNSUPPORTED, VSOM_EUNSUPPORTED, "bmu_cosine_x3: more than %d prototypes", BMU_X3_MAX_K);
     VSOM_REQUIRE(p.x3_status == VSOM_OK, VSOM_EALIGN, "bmu_cosine_x3: rows must be 16-byte aligned (L, ldx multiples of 4)");
     VSOM_REQUIRE(ws && ws_bytes >= p.ws_bytes && aligned16(ws), VSOM_EWORKSPACE, "bmu_cosine_x3: workspace too small or misaligned");
-    const long xb = ((long)(B - 1) * ldx + L) * 4, wb = (long)K * L * 4;
-    VSOM_REQUIRE(xb < 0xFFFF0000L && wb < 0xFFFF0000L, VSOM_EUNSUPPORTED, "bmu_cosine_x3: operand larger than 4 GB");
+    if (int rc = x3_operands_fit("bmu_cosine_x3", B, K, L, ldx)) return rc;
     BmuP g = {};
     x3_layout(p, B, K, ws, g);
     g.X = X; g.ldx = ldx; g.W = W; g.B = B; g.K = K; g.L = L;
     g.ktiles_per_split = p.ktiles_per_split;
-    g.x_bytes = (unsigned)xb; g.w_bytes = (unsigned)wb;
+    g.x_bytes = (unsigned)x3_x_bytes(B, L, ldx); g.w_bytes = (unsigned)x3_w_bytes(K, L);
     if (p.tile_m == 256) VSOM_LAUNCH((bmu_x3_kernel<2, 3, 4, 2>), dim3(p.tiles * p.splits), dim3(p.threads), 0, stream, g);
     else VSOM_LAUNCH((bmu_x3_kernel<2, 2, 2, 2>), dim3(p.tiles * p.splits), dim3(p.threads), 0, stream, g);
     return launch_status("bmu_x3_kernel");
@@ -735,6 +745,7 @@ int vsom_bmu_cosine_x3_finalize(const float* X, long ldx, const float* W, const 
     VSOM_REQUIRE(aligned16(X) && aligned16(W), VSOM_EALIGN, "bmu_cosine_x3_finalize: X and W must be 16-byte aligned");
     const BmuPlan p = x3_plan(B, K, L, ldx, true, false);
     VSOM_REQUIRE(p.x3_status == VSOM_OK, VSOM_EINVAL, "bmu_cosine_x3_finalize: bad shape");
+    if (int rc = x3_operands_fit("bmu_cosine_x3_finalize", B, K, L, ldx)) return rc;
     VSOM_REQUIRE(ws && ws_bytes >= p.ws_bytes, VSOM_EWORKSPACE, "bmu_cosine_x3_finalize: workspace too small");
     BmuP g = {};
     x3_layout(p, B, K, const_cast<void*>(ws), g);
@@ -836,6 +847,7 @@ int vsom_bmu_cosine_x3_planes_finalize(const float* X, long ldx, const float* W,
     VSOM_REQUIRE(aligned16(X) && aligned16(W), VSOM_EALIGN, "bmu_cosine_x3_planes_finalize: X and W must be 16-byte aligned");
     const BmuPlan p = x3_plan(B, K, L, ldx, true, true);
     VSOM_REQUIRE(p.form == VSOM_BMU_X3_PLANES, VSOM_EINVAL, "bmu_cosine_x3_planes_finalize: bad shape");
+    if (int rc = x3_operands_fit("bmu_cosine_x3_planes_finalize", B, K, L, ldx)) return rc;
     VSOM_REQUIRE(ws && ws_bytes >= p.ws_bytes, VSOM_EWORKSPACE, "bmu_cosine_x3_planes_finalize: workspace too small");
     const float* xsq = reinterpret_cast<const float*>(static_cast<const char*>(xplanes) + planes_image_bytes(B, L));
     const float* wsq = reinterpret_cast<const float*>(static_cast<const char*>(wplanes) + planes_image_bytes(K, L));
