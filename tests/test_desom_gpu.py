@@ -19,7 +19,6 @@ def build(name):
     missing, unexpected = m.load_state_dict(golden_params(z), strict=False)
     assert not missing and not unexpected, (missing, unexpected)
     m.set_schedule(int(z["n_train"]))
-    m._it = int(z["it"]); m.iteration.fill_(int(z["it"]))
     return m, z, cfg
 
 

@@ -308,9 +308,3 @@ class ViTSOM(_ViTOwner):
         with torch.no_grad():
             cls_token, patches, _ = self.vit(x)
             return cls_token if self.use_reduced else patches.flatten(start_dim=1)
-
-    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
-        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
-        key = prefix + "iteration"
-        if key in state_dict:
-            self._it = int(state_dict[key])

@@ -1,4 +1,5 @@
 """The reference's layer-decay parameter groups and the fused AdamW step over the flat arena."""
+import weakref
 from typing import Dict
 
 import torch
@@ -52,16 +53,27 @@ class FusedAdamW(torch.optim.Optimizer):
         self._model = model
         self._adamw = adamw
         self._step = 0
-        # per-chunk weight decay follows the groups
-        name_of = {id(p): n for n, p in model._named_trainable()}
-        for g in self.param_groups:
+        self._wd_seen = None
+        self._sync_weight_decay()
+
+    def _sync_weight_decay(self):
+        """The kernel reads weight decay per 256-float chunk from arena.wd_chunk; the groups are where it is set -- by the
+        constructor, by load_state_dict, by whoever edits param_groups (torch allows it).  One host-side comparison of the
+        groups' values per call; the chunks are rewritten only when a value (or the arena) has changed."""
+        a = self._model.arena
+        wds = tuple(float(g["weight_decay"]) for g in self.param_groups)
+        if self._wd_seen is not None and self._wd_seen[0]() is a and self._wd_seen[1] == wds:
+            return
+        name_of = {id(p): n for n, p in self._model._named_trainable()}
+        for g, wd in zip(self.param_groups, wds):
             for p in g["params"]:
-                model.arena.set_weight_decay(name_of[id(p)], float(g["weight_decay"]))
-        if model.classification:
+                a.set_weight_decay(name_of[id(p)], wd)
+        if self._model.classification:
             # the reference leaves the decoder without gradients in classification mode, so
             # torch's AdamW never touches it (no decay either) -- SURVEY.md section 5 defect (a)
-            for n in model._decoder_param_names():
-                model.arena.set_weight_decay(n, 0.0)
+            for n in self._model._decoder_param_names():
+                a.set_weight_decay(n, 0.0)
+        self._wd_seen = (weakref.ref(a), wds)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -71,6 +83,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 loss = closure()
         m = self._model
         m.allreduce_gradients()
+        self._sync_weight_decay()
         self._step += 1
         g0 = self.param_groups[0]
         lrs = {float(g["lr"]) for g in self.param_groups}
@@ -138,3 +151,4 @@ class FusedAdamW(torch.optim.Optimizer):
         if len(steps) > 1:
             raise ValueError("FusedAdamW.load_state_dict: parameters carry different step counts")
         self._step = steps.pop() if steps else 0
+        self._sync_weight_decay()

@@ -250,6 +250,14 @@ class _ArenaOwner:
             self._pack(dev)
         return self
 
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        """The host counter `_it` (temperature, gamma ramp) follows a loaded `iteration` buffer, for every model that has one:
+        the reference reads the buffer itself (vit_som.py:84, desom.py:113-118)."""
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        key = prefix + "iteration"
+        if key in state_dict and "iteration" in self._buffers:
+            self._it = int(state_dict[key])
+
     def _G(self, prefix: str):
         return lambda name: self._grad_views[prefix + name]
 

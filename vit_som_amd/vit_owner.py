@@ -268,6 +268,8 @@ class _ViTOwner(_ArenaOwner, _Base):
                 raise ValueError("checkpoint carries no hyper_parameters; pass config=")
         model = cls(config, device=device)
         model.load_state_dict(ckpt["state_dict"])
+        if "iteration" not in model._buffers:
+            model._it = int(ckpt.get("global_step", 0))          # no `iteration` buffer to restore the step count from
         model._loaded_checkpoint = ckpt
         return model
 
